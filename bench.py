@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: hypotheses/s of the differentiable-RANSAC hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One *step* = one pass of the hot path (test mode, ransac.py:55-144, one RANSAC batch) over one batch of synthetic image
@@ -12,7 +12,11 @@ Headline workload = BASELINE.json configs[1] ("c2"): Nister 5-pt, N = 2000 point
 sampler, MSAC; `--pairs` pairs per GPU per step (weak scaling: pairs shard across ranks, no data-path collective --
 SURVEY 8(e)).  Prints ONE JSON line on rank 0.
 
-The other BASELINE configs are measured after the headline region (N = 1 only) and reported under "configs":
+A plain run sets up, pre-conditions and warms up, times EXACTLY --steps steps (`ms_per_step`), and prints the line;
+`--dump-outputs DIR` writes what the last timed step returned (the sampler is rewound before the timed steps, so the same
+arguments give the same outputs).  Everything else is measured with `--full` only: the timed region repeated as 5 segments
+(median reported), the scoring launch's roofline, the informational regions, the CPU baselines and the checks, and, after the
+headline region (N = 1 only), the other BASELINE configs reported under "configs":
   c1  8-point F, 128 points, 64 hypotheses, uniform sampler (256 pairs per step: one pair is launch-bound)
   c3  Stewenius 5-point, 2000 points, 4096 hypotheses, 32 pairs
   c4  rigid SVD, 50 000 points, 2048 hypotheses, one pair
@@ -98,10 +102,10 @@ def parse():
                          "hypotheses).  auto: the train step and the sub-records of the other configs are replayed; the "
                          "headline test-mode region stays eager, because its roofline needs HIP events around the scoring "
                          "launch of every step (it is device-bound either way)")
-    ap.add_argument("--segments", type=int, default=5,
+    ap.add_argument("--segments", type=int, default=None,
                     help="the timed region is repeated as this many segments of EXACTLY --steps steps, each bracketed by a "
                          "barrier + synchronize on both sides; the line reports the median segment (value, ms_per_step, the "
-                         "scoring launch's HIP-event mean) and lists all of them")
+                         "scoring launch's HIP-event mean) and lists all of them.  Default 1, 5 with --full")
     ap.add_argument("--prewarm-s", type=float, default=0.6,
                     help="time-based pre-conditioning before the counted warm-up: the same step is issued until this many "
                          "seconds of wall time have passed (clocks, allocator pools, caches), reported as prewarm_s.  A "
@@ -113,7 +117,17 @@ def parse():
                          "time, so that the HIP-event duration of the scoring kernel in the timed region is its own "
                          "(roofline attribution).  Two batches in flight are always measured after the timed region and "
                          "reported as `two_batches_in_flight`")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the scoring launch's roofline (HIP events in the timed region), "
+                         "the informational regions, the sub-records of the other configs, the CPU baselines and the checks.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, or float64 for f64 and 32/64-bit "
+                         "integer outputs; under 64 MB in all: a larger output is a fixed, seeded sample of its elements)")
+    args = ap.parse_args()
+    if args.segments is None:
+        args.segments = 5 if args.full else 1
+    return args
 
 
 def resolve(args):
@@ -211,6 +225,38 @@ def run_bounded(fn, n, window=32, stride=4):
             stride = 1
         if (i + 1) % stride == 0:
             ev[(i // stride) % window].record(st if own else torch.cuda.current_stream())
+
+
+def rewind_sampler(rn):
+    """Sets the driver's per-call sampler seed back to that of its first call (host counter, and the device counter of
+    device_seeds()).  The pre-conditioning issues as many steps as fit in its wall time, so without this the timed steps would
+    draw different hypotheses from run to run; after it, the same arguments give the same timed steps."""
+    rn.calls = 0
+    if rn._dev_seed is not None:
+        rn._dev_seed.state[1].zero_()
+
+
+DUMP_BUDGET_BYTES = 60 * 2 ** 20   # (npy headers included, the files stay below 64 MB in either unit)
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every tensor of what the last timed step returned, as path/<name>.npy -- float64 for f64 and 32/64-bit
+    integer outputs, float32 for the rest.  Smallest first, each output gets an even share of what is left of DUMP_BUDGET_BYTES:
+    one that fits is written whole, a larger one as that many elements at fixed, seeded flat indices (sorted), written flat."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((k, v) for k, v in out.items() if torch.is_tensor(v)), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = DUMP_BUDGET_BYTES
+    for i, (name, t) in enumerate(items):
+        dt = torch.float64 if t.dtype in (torch.float64, torch.int32, torch.int64) else torch.float32
+        cap = left // (len(items) - i) // (8 if dt == torch.float64 else 4)
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.to(dt).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 K4_EVENT_EVERY = 4   # the scoring launch's HIP-event pair: every 4th step of the timed region (a pair costs the step ~11 us of idle device)
@@ -869,7 +915,8 @@ def main():
     M = w["hyps"] * S
     score_prefix = "dr_rigid_residual_" if w["solver"] == "rigid" else "dr_msac_score_f"
     n_seg = max(1, args.segments)
-    timer = CallTimer((score_prefix,), args.steps * n_seg)
+    # the roofline's HIP-event pairs around the scoring launch (--full only: a plain run times the steps and nothing else)
+    timer = CallTimer((score_prefix,), args.steps * n_seg) if args.full else None
 
     # the training step's collective: one flat bucket = the scores network's gradient (random stand-in of the reference
     # CLNet's size: the network itself is out of scope).  Ranks own different pairs: the per-pair logits gradient continues into
@@ -942,6 +989,7 @@ def main():
         issue_bounded(n_issued, n_issued)
         n_issued += 1
     torch.cuda.synchronize()
+    rewind_sampler(info["rn"])
     # the timed region: n_seg segments of EXACTLY --steps steps, each bracketed by barrier + synchronize on both sides; whole-job
     # rate of a segment = sum of hypotheses over ranks / max elapsed over ranks; the line reports the MEDIAN segment
     seg_elapsed, seg_rate, seg_k4, seg_coll = [], [], [], []
@@ -955,7 +1003,8 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for i in range(args.steps):
-            timer.i = sgi * args.steps + i if i % K4_EVENT_EVERY == 0 else -1
+            if timer is not None:
+                timer.i = sgi * args.steps + i if i % K4_EVENT_EVERY == 0 else -1
             issue_bounded(i, n_issued)
             n_issued += 1
         if bucket is not None:
@@ -965,13 +1014,16 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
-        timer.i = -1
+        if timer is not None:
+            timer.i = -1
         rate, el = sharding.job_throughput(P * w["hyps"] * args.steps, el, dist, dev)
         seg_elapsed.append(el)
         seg_rate.append(rate)
         if bucket is not None and bucket.exposed_events:
             seg_coll.append(sum(a.elapsed_time(b) for a, b in bucket.exposed_events) / len(bucket.exposed_events))
     out = outs[(args.steps - 1) % len(streams)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
     med = sorted(range(n_seg), key=lambda i: seg_elapsed[i])[n_seg // 2]
     elapsed, job_hyps_per_s = seg_elapsed[med], seg_rate[med]
     n_ranks_seen = 1
@@ -980,10 +1032,10 @@ def main():
         dist.all_reduce(one)
         n_ranks_seen = int(one.item())
     # exposed = what the compute stream waited at the optimizer's read (median segment); collective_ms = the same all-reduce
-    # issued BLOCKING on an idle device after the timed region (its own duration, nothing to hide behind)
+    # issued BLOCKING on an idle device after the timed region (its own duration, nothing to hide behind; --full only)
     collective_exposed_ms = sorted(seg_coll)[len(seg_coll) // 2] if seg_coll else (0.0 if world > 1 else None)
-    collective_ms = 0.0 if world > 1 else None
-    if bucket is not None:
+    collective_ms = 0.0 if world > 1 and bucket is None else None
+    if bucket is not None and args.full:
         torch.cuda.synchronize()
         evs = []
         for _ in range(20):
@@ -1009,7 +1061,7 @@ def main():
         # the block sharding.pair_range(P * world, r, world) -- gathered and checked to cover the job's pairs exactly once; and the
         # program order of the overlapped collective on this rank's call trace (step i + 1 enqueued before the wait on bucket i)
         partition, trace_ok = None, None
-        if world > 1:
+        if world > 1 and args.full:
             mine = torch.tensor([rank * P, rank * P + P], dtype=torch.int64, device=dev if args.backend == "nccl" else "cpu")
             got = [torch.empty_like(mine) for _ in range(world)]
             dist.all_gather(got, mine)
@@ -1039,13 +1091,38 @@ def main():
                               if collective_exposed_ms else None,
                               "collective_bytes": 4 * CLNET_PARAMS if world > 1 else 0,
                               "pair_partition": partition, "overlap_trace_ok": trace_ok,
-                              "grad_finite": bool(torch.isfinite(out["grad"]).all())}))
-        timer.close()
+                              "grad_finite": bool(torch.isfinite(out["grad"]).all()) if args.full else None}))
+        if timer is not None:
+            timer.close()
         if dist is not None:
             dist.destroy_process_group()
         return
 
-    # informational second region: the same K steps with two batches in flight on two streams
+    head = {
+        "metric": "hypotheses/sec (and image-pairs/sec) at 2000 pts x 1024 hyps, 1/2/4/8 GPU",
+        "value": job_hyps_per_s,
+        **common,
+        "config": {"workload": f"{w['text']}, test mode, {P} pairs/GPU/step", "baseline_config_index": w["baseline_config"],
+                   "sampler": w["sampler"], "pairs_per_gpu": P, "points": N, "hypotheses_per_pair": B,
+                   "hypotheses_per_pair_per_gpu": w["hyps"], "models_per_pair": B * S, "solver": w["solver"],
+                   "parallelism": (f"hypotheses of the same {P} pair(s) split over {world} GPUs, per-pair winners merged by two "
+                                   "all_gathers per step" if split_h else f"pairs sharded over {world} GPU(s), no collective"),
+                   "streams": len(streams),
+                   "issue": f"{len(streams)} batch(es) in flight, round-robin over {len(streams)} HIP stream(s), "
+                            + ("HIP graph replay" if use_graph else "eager launches"
+                               + (" (HIP events around the scoring launch)" if timer is not None else ""))},
+        "pairs_per_s": (1 if split_h else world) * P * args.steps / elapsed,
+    }
+    if not args.full:
+        if args.profile_kernels and rank == 0 and w["solver"] != "rigid":
+            head["kernel_breakdown_ms"] = kernel_breakdown(w, rn, matches, logits, ops)
+        if rank == 0:
+            print(json.dumps(head))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # --full from here on.  Informational second region: the same K steps with two batches in flight on two streams
     overlap = None
     if world == 1 and args.extras:
         n2 = 1 if len(streams) > 1 else 2
@@ -1148,18 +1225,7 @@ def main():
     inl_frac = None if rigid else float(out["inliers"].float().mean()) / N
 
     result = {
-        "metric": "hypotheses/sec (and image-pairs/sec) at 2000 pts x 1024 hyps, 1/2/4/8 GPU",
-        "value": job_hyps_per_s,
-        **common,
-        "config": {"workload": f"{w['text']}, test mode, {P} pairs/GPU/step", "baseline_config_index": w["baseline_config"],
-                   "sampler": w["sampler"], "pairs_per_gpu": P, "points": N, "hypotheses_per_pair": B,
-                   "hypotheses_per_pair_per_gpu": w["hyps"], "models_per_pair": B * S, "solver": w["solver"],
-                   "parallelism": (f"hypotheses of the same {P} pair(s) split over {world} GPUs, per-pair winners merged by two "
-                                   "all_gathers per step" if split_h else f"pairs sharded over {world} GPU(s), no collective"),
-                   "streams": len(streams),
-                   "issue": f"{len(streams)} batch(es) in flight, round-robin over {len(streams)} HIP stream(s), "
-                            + ("HIP graph replay" if use_graph else "eager launches (HIP events around the scoring launch)")},
-        "pairs_per_s": (1 if split_h else world) * P * args.steps / elapsed,
+        **head,
         "roofline": {"bound": "hbm", "binding_unit": None if rigid else "valu_f32",
                      "bound_note": ("`bound` names the roof `frac` is priced against (BASELINE's target is stated against HBM: the mask "
                                     "stream is the launch's only large transfer); the unit that saturates first is the f32 vector ALU "

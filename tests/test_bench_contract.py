@@ -103,3 +103,39 @@ def test_committed_bench_line_carries_the_contract_fields_and_the_round6_records
     assert f["bytes_formula"] == "P (16 N + 40 M + N)" and f["algorithmic_bytes_per_launch"] == 128 * (16 * 2000 + 40 * 10240 + 2000)
     a = d["k4_all_valid"]
     assert a["all_slots_valid"]["evaluated_slot_fraction"] == 1.0 and a["all_slots_valid"]["hbm_frac"] < r["frac"]
+
+
+def test_plain_run_is_lean_and_full_is_opt_in(monkeypatch):
+    """a plain run times exactly --steps steps (one segment); the repeated segments and everything else come with --full"""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.segments == 1 and a.dump_outputs is None and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.segments == 5 and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--segments", "3"])
+    assert bench.parse().segments == 3
+
+
+def test_dump_outputs_dtypes_budget_and_fixed_sample(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    bench = _bench()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    g = torch.Generator().manual_seed(3)
+    out = {"score": torch.rand(4, generator=g), "model": torch.rand(4, 3, 3, generator=g, dtype=torch.float64),
+           "inliers": torch.arange(4, dtype=torch.int32), "mask": torch.rand(64, 64, generator=g) > 0.5, "iterations": None}
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["inliers.npy", "mask.npy", "model.npy", "score.npy"]
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert a["score"].dtype == np.float32 and np.array_equal(a["score"], out["score"].numpy())
+    assert a["model"].dtype == np.float64 and np.array_equal(a["model"], out["model"].numpy())
+    assert a["inliers"].dtype == np.float64 and np.array_equal(a["inliers"], np.arange(4))
+    # the mask does not fit what is left of the budget: a flat sample of it, the same one in every run
+    assert a["mask"].dtype == np.float32 and a["mask"].ndim == 1 and 0 < a["mask"].size < 64 * 64
+    assert sum(v.nbytes for v in a.values()) <= 4096
+    assert set(np.unique(a["mask"])) <= {0.0, 1.0}
+    assert np.array_equal(a["mask"], np.load(tmp_path / "b" / "mask.npy"))

@@ -63,7 +63,7 @@ def test_bench_plain_launch_two_ranks_on_one_gpu():
     for mode in ("test", "train"):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--gpus-shared",
                             "--steps", "4", "--warmup", "2", "--pairs", "8", "--segments", "3", "--prewarm-s", "0.1",
-                            "--mode", mode, "--no-configs", "--no-cpu-baseline", "--no-extras"],
+                            "--mode", mode, "--full", "--no-configs", "--no-cpu-baseline", "--no-extras"],
                            capture_output=True, text=True, env=env, timeout=240, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-3000:]
         lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -79,6 +79,55 @@ def test_bench_plain_launch_two_ranks_on_one_gpu():
             assert part["total_pairs"] == 16 and part["ranges"] == [[0, 8], [8, 16]] and part["covers_once"] and part["equals_pair_range"]
             assert rec["overlap_trace_ok"] is True
 
+
+
+def _bench_line(*flags, env=None):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *flags], capture_output=True, text=True, env=env,
+                       timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_every_run(tmp_path):
+    """a plain run (no --full) times exactly --steps steps and prints the headline only; --dump-outputs writes what the last
+    timed step returned, and since the sampler is rewound before the timed steps, two runs whose pre-conditioning issued
+    different numbers of steps write the same arrays"""
+    recs = []
+    for tag, pre in (("a", "0.05"), ("b", "0.4")):
+        recs.append(_bench_line("--gpus", "1", "--steps", "5", "--warmup", "2", "--pairs", "8", "--prewarm-s", pre,
+                                "--dump-outputs", str(tmp_path / tag)))
+    for rec in recs:
+        assert rec["steps"] == 5 and rec["n_gpus"] == 1 and rec["unit"] == "hypotheses/s" and rec["dtype"] == "f32"
+        assert rec["segments"]["n"] == 1 and len(rec["segments"]["ms_per_step"]) == 1 and rec["ms_per_step"] > 0
+        assert rec["value"] > 0 and rec["higher_is_better"] is True
+        assert not {"roofline", "configs", "cpu_baseline", "check", "two_batches_in_flight"} & set(rec)
+    assert recs[0]["prewarm_steps"] != recs[1]["prewarm_steps"]
+    files = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert files == sorted(f.name for f in (tmp_path / "b").iterdir())
+    assert {"model.npy", "mask.npy", "score.npy", "inliers.npy"} <= set(files)
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    assert np.load(tmp_path / "a" / "model.npy").shape == (8, 3, 3)
+    assert np.load(tmp_path / "a" / "mask.npy").shape == (8, 2000)
+
+
+def test_bench_plain_two_rank_run_is_lean(tmp_path):
+    """the same lean path with two ranks (gloo, one shared GPU), in both modes: the headline fields, nothing of --full"""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    for mode in ("test", "train"):
+        rec = _bench_line("--gpus", "2", "--backend", "gloo", "--gpus-shared", "--steps", "4", "--warmup", "2", "--pairs", "8",
+                          "--prewarm-s", "0.1", "--mode", mode, "--dump-outputs", str(tmp_path / mode), env=env)
+        assert rec["n_gpus"] == 2 and rec["n_ranks_seen"] == 2 and rec["steps"] == 4 and rec["segments"]["n"] == 1
+        assert rec["ms_per_step"] > 0 and rec["value"] > 0
+        assert "roofline" not in rec
+        if mode == "train":
+            assert rec["collective_ms"] is None and rec["grad_finite"] is None and rec["pair_partition"] is None
+            assert np.load(tmp_path / mode / "grad.npy").shape == (8, 2000)
+        else:
+            assert np.load(tmp_path / mode / "model.npy").shape == (8, 3, 3)
 
 # ---------------------------------------------------------------------------------------------------------------------
 # weighted LSQ refit of F (`-fmat 1 -wei 1 -tr 0`, ransac.py:151-153)
