@@ -45,7 +45,7 @@
 // static shares started in lock step (scratch/ab_k4nt.py); register budgets for 3 / 5 / 6 waves per SIMD instead of 4:
 // 233 / 221 / 343 us; 32- and 128-slot tiles at 128 pairs per launch: 793 / 757 against 692 us.  The matrix-core
 // candidate filter of round 2 (correct, slower: DESIGN 2b) is kept as scratch/k4_filter_kernel.patch.
-#include "dr_common.hpp"
+#include "ransac_device.hpp"
 
 // 0: the empty mask rows of the slots a tile does not evaluate are written by a store-only tail after the model loop (rounds 1-4);
 // 1 / 2: one (up to two) of them per evaluated model INSIDE the model loop of the 16-points-per-lane kernel, so that the store issues
@@ -65,20 +65,6 @@ constexpr int kModelsPerBlock = 32;
 
 template <typename T>
 struct Pt4 { T x1, y1, x2, y2; };
-
-template <typename T>
-__device__ __forceinline__ T sampson_s(const T m[9], T x1, T y1, T x2, T y2, T inv_thr2) {
-  // a = M^T x2 ; b = M x1 (first two) ; r = x1 . a       (msac_score.py:33-39)
-  T a0 = fma(x2, m[0], fma(y2, m[3], m[6]));
-  T a1 = fma(x2, m[1], fma(y2, m[4], m[7]));
-  T a2 = fma(x2, m[2], fma(y2, m[5], m[8]));
-  T b0 = fma(x1, m[0], fma(y1, m[1], m[2]));
-  T b1 = fma(x1, m[3], fma(y1, m[4], m[5]));
-  T r = fma(x1, a0, fma(y1, a1, a2));
-  T jj = fma(a0, a0, fma(a1, a1, fma(b0, b0, b1 * b1)));
-  T d2 = (r * r) * fast_rcp(jj);
-  return fma(d2, inv_thr2, T(-1));  // s = d2/thr2 - 1 ; inlier <=> s < 0 ; soft score = max(-s, 0)
-}
 
 template <typename T, bool kMask>
 __global__ __launch_bounds__(kThreads) void msac_score_kernel(const T *__restrict__ matches,
@@ -732,12 +718,7 @@ __global__ __launch_bounds__(kThreads) void refit_accept_kernel(const T *__restr
       m[q] = cand[((size_t)p * S + c) * 9 + q];
       finite = finite && is_finite(m[q]);
     }
-    T acc = T(0);
-    for (int n = tid; n < N; n += kThreads) {
-      const T *q = matches + ((size_t)p * N + n) * 4;
-      const T sv = sampson_s<T>(m, q[0], q[1], q[2], q[3], inv_thr2);
-      acc += (sv < T(0)) ? -sv : T(0);      // a 0/0 point (NaN) contributes 0, as in the scoring kernel
-    }
+    T acc = msac_partial<T, kThreads>(matches + (size_t)p * N * 4, m, N, inv_thr2);
     acc = wave_sum(acc);
     if (lane == 0) s_part[wv] = acc;
     __syncthreads();
@@ -894,14 +875,9 @@ __global__ __launch_bounds__(kUpdThreads) void ransac_update_kernel(
 #pragma unroll
         for (int q = 0; q < 9; ++q) best_model[(size_t)p * 9 + q] = m[q];
         // adaptive_iteration_number, ransac.py:202-215
-        const double ratio = (double)inl / (double)N;
-        const double rk = pow(ratio, (double)k);
-        const double prob = 1.0 - rk;
-        double nmi = (double)max_iterations;
         // (round 5, measured and dropped: the thread's correspondences requested before the arg-max, twelve scores in flight instead
         //  of four -- 15.9 -> 15.9 / 16.1 us at 128 pairs, 10.1 at one pair; without this f64 pow / log10 tail: 15.1 / 9.2 us)
-        if (!(prob >= 1.0 - eps)) nmi = fmax(0.0, log10(1.0 - confidence) / log10(1.0 - rk + eps));
-        nmi = fmin((double)max_iterations, nmi);
+        const double nmi = adaptive_max_iters(inl, N, k, confidence, eps, max_iterations);
         max_iters[p] = nmi;
         s_mi = nmi;
       }

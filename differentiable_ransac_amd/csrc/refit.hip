@@ -10,11 +10,16 @@
 #include <algorithm>
 #include <cstdlib>
 #include "fivepoint_device.hpp"
+#include "ransac_device.hpp"
 
 namespace dr {
 
 constexpr int kRefT = 256;
 constexpr int kRefitPairFinishMinPairs = 16;   // launches of fewer pairs keep the light final stage (see refit_essential_kernel)
+// dynamic LDS of a refit block: five-point workspace (one slot), gram[81] + red[4] (padded to 96), wave partials [4][45], Jacobi
+// V[81] + (C, S)[9]: 4.6 KB -- with a 162-double slot PER LANE (83 KB) a block left room for only two of the four solver blocks a
+// CU hosts.  The wave-cooperative final stage overlays the solver's workspace, kNisterPairDoubles.
+constexpr int kRefitLdsDoubles = 192 + 96 + 4 * 45 + 81 + 18;   // (the Jacobi's per-index rotation table: C[9], S[9])
 
 __device__ __forceinline__ double block_sum(double v, double *red /* [4] */) {
   v = wave_sum(v);
@@ -77,16 +82,15 @@ __device__ __forceinline__ void gram_accumulate(const T *__restrict__ mt, const 
 // chain anyway) keep the light one-sample form -- 256 registers, 4.6 KB of LDS; same-box A/B of the per-pair loop: 0.208-0.211 ms
 // per pair with it, 0.214-0.217 with the heavy form -- batched calls take the fast one.
 // (register budget of the light form: 256 per lane, waves_per_eu(2, 2), although one wave per pair does the work)
+// One pair, the whole block: the 10 candidates of the five-point solver on the rows mt [N,4] selected by mk (NULL = all) ->
+// models [10,9], valid [10].  Waves 1-3 return after the Gram matrix, wave 0 solves (a caller that goes on puts a barrier behind).
+// lds: the block's dynamic LDS -- [192] five-point workspace, then gram[81] + red[4], wave partials, Jacobi (kRefitLdsDoubles),
+// or the solver's whole workspace with kPairFinish (kmax(kRefitLdsDoubles, kNisterPairDoubles)).
 template <typename T, bool kPairFinish>
-__global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kPairFinish ? 1 : 2, kPairFinish ? 1 : 2))) void refit_essential_kernel(const T *__restrict__ matches,
-                                                                const uint8_t *__restrict__ mask, int N,
-                                                                T *__restrict__ models, uint8_t *__restrict__ valid) {
-  extern __shared__ __align__(16) double lds[];   // [192] five-point workspace, then gram[81] + red[4], wave partials, Jacobi
+__device__ __forceinline__ void refit_essential_pair(const T *__restrict__ mt, const uint8_t *__restrict__ mk, int N, double *lds,
+                                                     T *__restrict__ models, uint8_t *__restrict__ valid) {
   double *gram = lds + 192;   // [0,162): the one five-point workspace slot all lanes share (identical values)
   double *red = gram + 81;
-  const int p = blockIdx.x;
-  const T *mt = matches + (size_t)p * N * 4;
-  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
   const double mu[4] = {0, 0, 0, 0};
   gram_accumulate<false, T>(mt, mk, static_cast<const T *>(nullptr), N, mu, 1.0, 1.0, gram, red);
 #if defined(DR_REFIT_STOP) && DR_REFIT_STOP == 1
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kPairFini
       for (int r = 0; r < 9; ++r) nb[3 - t][r] = ev[t][r];
   }
 #if defined(DR_REFIT_STOP) && DR_REFIT_STOP == 2
-  if (lane == 0) models[(size_t)p * 90] = (T)nb[0][0];
+  if (lane == 0) models[0] = (T)nb[0][0];
   return;
 #endif
   double e[3][3][4];
@@ -123,28 +127,32 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kPairFini
   if constexpr (kPairFinish) {
     // lane pair 0 holds the sample (lane 0 searches |z| <= 1, lane 1 |z| > 1); the other 31 pairs are empty slots of the wave's
     // task queues, which is where the pair's brackets and candidates are worked on side by side.  The block's LDS is reused whole.
-    nister_finish_pair<T>(nb, X, ok, lds, lane, 0, lane < 2, models + (size_t)p * 90, valid + (size_t)p * 10, nullptr);
+    nister_finish_pair<T>(nb, X, ok, lds, lane, 0, lane < 2, models, valid, nullptr);
   } else {
     // like the minimal solver, two lanes share the sample: even lanes search |z| <= 1 and fill the slots from 0 upwards,
     // odd lanes |z| > 1 from 9 downwards (all 32 lane pairs do the same work; lanes 0 and 1 store)
-    nister_finish<T, true>(nb, X, ok, models + (size_t)p * 90, valid + (size_t)p * 10, lane < 2, lane & 1);
+    nister_finish<T, true>(nb, X, ok, models, valid, lane < 2, lane & 1);
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) void refit_fundamental_kernel(const T *__restrict__ matches,
-                                                                  const uint8_t *__restrict__ mask,
-                                                                  const T *__restrict__ weights, int N,
-                                                                  T *__restrict__ models, uint8_t *__restrict__ valid) {
+template <typename T, bool kPairFinish>
+__global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kPairFinish ? 1 : 2, kPairFinish ? 1 : 2))) void refit_essential_kernel(const T *__restrict__ matches,
+                                                                const uint8_t *__restrict__ mask, int N,
+                                                                T *__restrict__ models, uint8_t *__restrict__ valid) {
   extern __shared__ __align__(16) double lds[];
+  const int p = blockIdx.x;
+  refit_essential_pair<T, kPairFinish>(matches + (size_t)p * N * 4, mask ? mask + (size_t)p * N : nullptr, N, lds,
+                                       models + (size_t)p * 90, valid + (size_t)p * 10);
+}
+
+// One pair, the whole block: the (row-weighted when wt != NULL) LSQ 8-point model of the rows mt [N,4] selected by mk (NULL = all)
+// -> model [9], valid [1] (0 below 8 rows or when not finite).  Waves 1-3 return after the Gram matrix, wave 0 solves.
+template <typename T>
+__device__ __forceinline__ void refit_fundamental_pair(const T *__restrict__ mt, const uint8_t *__restrict__ mk,
+                                                       const T *__restrict__ wt, int N, double *lds, T *__restrict__ model,
+                                                       uint8_t *__restrict__ valid) {
   double *gram = lds + 192;   // [0,162): the one five-point workspace slot all lanes share (identical values)
   double *red = gram + 81;
-  const int p = blockIdx.x;
-  const T *mt = matches + (size_t)p * N * 4;
-  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
-  // per-point row weights [P,N] (ransac.py:151-153 hands the estimator `soft_weights[0, inlier_indices]`); the Hartley
-  // normalisation below stays unweighted, as in fundamental_matrix_estimator.py:177-228
-  const T *wt = weights ? weights + (size_t)p * N : nullptr;
   // pass 1: centroid of the selected points
   double s[4] = {0, 0, 0, 0}, cnt = 0;
   for (int n = threadIdx.x; n < N; n += kRefT) {
@@ -199,9 +207,22 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   for (int q = 0; q < 9; ++q) ok = ok && is_finite(F[q]);
   if (lane == 0) {
 #pragma unroll
-    for (int q = 0; q < 9; ++q) models[(size_t)p * 9 + q] = ok ? (T)F[q] : T(q % 4 == 0 ? 1 : 0);
-    valid[p] = ok;
+    for (int q = 0; q < 9; ++q) model[q] = ok ? (T)F[q] : T(q % 4 == 0 ? 1 : 0);
+    valid[0] = ok;
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) void refit_fundamental_kernel(const T *__restrict__ matches,
+                                                                  const uint8_t *__restrict__ mask,
+                                                                  const T *__restrict__ weights, int N,
+                                                                  T *__restrict__ models, uint8_t *__restrict__ valid) {
+  extern __shared__ __align__(16) double lds[];
+  const int p = blockIdx.x;
+  // per-point row weights [P,N] (ransac.py:151-153 hands the estimator `soft_weights[0, inlier_indices]`); the Hartley
+  // normalisation stays unweighted, as in fundamental_matrix_estimator.py:177-228
+  refit_fundamental_pair<T>(matches + (size_t)p * N * 4, mask ? mask + (size_t)p * N : nullptr,
+                            weights ? weights + (size_t)p * N : nullptr, N, lds, models + (size_t)p * 9, valid + p);
 }
 
 // A/B knob (DRANSAC_REFIT_PAIR_MIN): launches of at least this many pairs take the wave-cooperative final stage
@@ -218,9 +239,7 @@ static inline int refit_pair_finish_min_pairs() {
 template <typename T>
 int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *models,
                  uint8_t *valid, hipStream_t st) {
-  // five-point workspace (one slot), gram[81] + red[4] (padded to 96), wave partials [4][45], Jacobi V[81] + (C, S)[9]:
-  // 4.6 KB -- with a 162-double slot PER LANE (83 KB) a block left room for only two of the four solver blocks a CU hosts
-  const size_t smem = sizeof(double) * (192 + 96 + 4 * 45 + 81 + 18);   // (the Jacobi's per-index rotation table: C[9], S[9])
+  const size_t smem = sizeof(double) * kRefitLdsDoubles;
   static bool attr_e = false, attr_p = false, attr_f = false;
   if (fundamental) {
     if (!attr_f) {
@@ -246,6 +265,159 @@ int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const 
     hipLaunchKernelGGL((refit_essential_kernel<T, false>), dim3(P), dim3(kRefT), smem, st, matches, mask, N, models, valid);
   }
   return check_launch("refit_kernel");
+}
+
+
+// ---- K7b local optimisation (RANSAC.localOptimization, ransac.py:217-257, lo = 1 / 2), one 256-thread block per pair, once per
+// device round right behind dr_ransac_update.  A pair whose (best_score, best_model) still equals its snapshot lo_seen[p] (bit
+// for bit: only a replacement by dr_ransac_update changes them, and the snapshot starts as NaN) returns at once.  Otherwise, up
+// to `iters` times: the refit of this file on the best mask (F: LSQ 8-point, unweighted; E: the five-point solver on the
+// selected rows, f64 inside), the MSAC scores of its valid, finite candidates (refit_accept_kernel's rule, first arg-max), and,
+// if that score is >= the best (ransac.py:252: ties are taken), the new best score / model and -- with dr_ransac_update's
+// predicate -- mask and inlier count.  The loop stops early when a refit loses or leaves the mask as it was (the next refit
+// would see the same rows: same model, same outcome).  Then max_iters from the new inlier count (ransac.py:135-142) and the
+// snapshot.  The refit's candidates live in LDS behind the refit workspace.
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+// kMode: 0 = F, 1 = E with the light final stage, 2 = E with the wave-cooperative one (chosen per launch like refit_launch)
+template <typename T, int kMode>
+__global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 1 ? 2 : 1, kMode == 1 ? 2 : 1))) void local_opt_kernel(
+    const T *__restrict__ matches, const T *__restrict__ thr, int N, int iters, int k, double confidence, double eps,
+    int max_iterations, T *__restrict__ best_score, T *__restrict__ best_model, uint8_t *__restrict__ best_mask,
+    int32_t *__restrict__ best_inliers, double *__restrict__ max_iters, T *__restrict__ lo_seen, int32_t *__restrict__ lo_refits) {
+  constexpr bool kF = kMode == 0;
+  constexpr int kS = kF ? 1 : 10;                 // candidates per refit
+  constexpr int kMinRows = kF ? 8 : 5;            // rows the LSQ solve needs
+  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
+  constexpr int kCand = (kWs + 3) & ~3;           // (32-byte aligned)
+  extern __shared__ __align__(16) double lds[];   // [kWs] refit workspace | candidates [kS][9] (T) | their valid flags
+  T *cand = reinterpret_cast<T *>(lds + kCand);
+  uint8_t *cvalid = reinterpret_cast<uint8_t *>(lds + kCand + 90);
+  __shared__ T s_part[kRefT / kWave];
+  __shared__ int s_cnt[kRefT / kWave], s_chg[kRefT / kWave];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const T *mt = matches + (size_t)p * N * 4;
+  uint8_t *mk = best_mask + (size_t)p * N;
+  T *seen = lo_seen + (size_t)p * 10;
+  T bs = best_score[p];
+  T bm[9];
+  bool same = same_bits(bs, seen[0]);
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    bm[q] = best_model[(size_t)p * 9 + q];
+    same = same && same_bits(bm[q], seen[1 + q]);
+  }
+  if (same) return;   // block-uniform: no replacement since the last visit
+  const T t = T(1.5) * thr[p];
+  const T inv_thr2 = T(1) / (t * t);
+  // the current inlier count, from the mask itself
+  int cnt = 0;
+  for (int n = tid; n < N; n += kRefT) cnt += mk[n] != 0;
+  cnt = wave_sum(cnt);
+  if (lane == 0) s_cnt[wv] = cnt;
+  __syncthreads();
+  int inl = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+  const bool run = inl >= kMinRows;
+  int refits = 0;
+  for (int it = 0; run && it < iters && inl >= kMinRows; ++it) {
+    __syncthreads();   // (the previous pass's s_cnt / s_chg have been read; the refit's LDS is free)
+    if constexpr (kF)
+      refit_fundamental_pair<T>(mt, mk, static_cast<const T *>(nullptr), N, lds, cand, cvalid);
+    else
+      refit_essential_pair<T, kMode == 2>(mt, mk, N, lds, cand, cvalid);
+    __syncthreads();
+    ++refits;
+    T cb = -INFINITY;
+    int which = -1;
+    for (int c = 0; c < kS; ++c) {
+      if (!cvalid[c]) continue;   // block-uniform
+      T m[9];
+      bool finite = true;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) {
+        m[q] = cand[c * 9 + q];
+        finite = finite && is_finite(m[q]);
+      }
+      T acc = msac_partial<T, kRefT>(mt, m, N, inv_thr2);
+      acc = wave_sum(acc);
+      if (lane == 0) s_part[wv] = acc;
+      __syncthreads();
+      T sc = T(0);
+      for (int w = 0; w < kRefT / kWave; ++w) sc += s_part[w];   // refit_accept_kernel's order
+      __syncthreads();
+      if (finite && sc > cb) { cb = sc; which = c; }            // strict: the first maximum wins, like torch.argmax
+    }
+    if (which < 0 || !(cb >= bs)) break;                         // ransac.py:252-257
+#pragma unroll
+    for (int q = 0; q < 9; ++q) bm[q] = cand[which * 9 + q];
+    bs = cb;
+    int c2 = 0, chg = 0;
+    for (int n = tid; n < N; n += kRefT) {
+      const T *q = mt + (size_t)n * 4;
+      const uint8_t in = sampson_s<T>(bm, q[0], q[1], q[2], q[3], inv_thr2) < T(0);
+      chg |= in != mk[n];
+      mk[n] = in;
+      c2 += in;
+    }
+    c2 = wave_sum(c2);
+    chg = wave_sum(chg);
+    if (lane == 0) { s_cnt[wv] = c2; s_chg[wv] = chg; }
+    __syncthreads();
+    inl = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    const bool changed = (s_chg[0] | s_chg[1] | s_chg[2] | s_chg[3]) != 0;
+    if (tid == 0) {
+      best_score[p] = bs;
+      best_inliers[p] = inl;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) best_model[(size_t)p * 9 + q] = bm[q];
+    }
+    if (!changed) break;
+  }
+  if (tid == 0) {
+    if (run) max_iters[p] = adaptive_max_iters(inl, N, k, confidence, eps, max_iterations);
+    seen[0] = bs;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) seen[1 + q] = bm[q];
+    if (lo_refits) lo_refits[p] += refits;
+  }
+}
+
+template <typename T, int kMode>
+static void local_opt_go(int P, hipStream_t st, const T *matches, const T *thr, int N, int iters, int k, double confidence,
+                         double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask, int32_t *best_inliers,
+                         double *max_iters, T *lo_seen, int32_t *lo_refits) {
+  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
+  const size_t smem = sizeof(double) * (((kWs + 3) & ~3) + 90 + 2);
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&local_opt_kernel<T, kMode>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    attr = true;
+  }
+  hipLaunchKernelGGL((local_opt_kernel<T, kMode>), dim3(P), dim3(kRefT), smem, st, matches, thr, N, iters, k, confidence, eps,
+                     max_iterations, best_score, best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits);
+}
+
+template <typename T>
+int local_opt_launch(const T *matches, const T *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
+                     double confidence, double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask,
+                     int32_t *best_inliers, double *max_iters, T *lo_seen, int32_t *lo_refits, hipStream_t st) {
+  DR_REQUIRE(matches && thr && best_score && best_model && best_mask && best_inliers && max_iters && lo_seen, "null pointer");
+  DR_REQUIRE(P > 0 && N >= (fundamental ? 8 : 5) && k > 0, "bad sizes");
+  DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");
+  DR_REQUIRE(lo == 1 || lo_iters >= 1, "lo_iters must be at least 1");
+  const int iters = lo == 1 ? 1 : lo_iters;
+  if (fundamental)
+    local_opt_go<T, 0>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
+                       best_inliers, max_iters, lo_seen, lo_refits);
+  else if (P >= refit_pair_finish_min_pairs())
+    local_opt_go<T, 2>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
+                       best_inliers, max_iters, lo_seen, lo_refits);
+  else
+    local_opt_go<T, 1>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
+                       best_inliers, max_iters, lo_seen, lo_refits);
+  return check_launch("local_opt_kernel");
 }
 
 }  // namespace dr
@@ -275,6 +447,19 @@ int dr_refit_fundamental_f64(const double *matches, const uint8_t *mask, const d
   DR_REQUIRE(matches && models && valid, "null pointer");
   DR_REQUIRE(P > 0 && N >= 8, "bad sizes");
   return dr::refit_launch<double>(true, matches, mask, weights, P, N, models, valid, (hipStream_t)stream);
+}
+
+int dr_local_opt_f32(const float *matches, const float *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
+                     double confidence, double eps, int max_iterations, float *best_score, float *best_model, uint8_t *best_mask,
+                     int32_t *best_inliers, double *max_iters, float *lo_seen, int32_t *lo_refits, void *stream) {
+  return dr::local_opt_launch<float>(matches, thr, P, N, fundamental, lo, lo_iters, k, confidence, eps, max_iterations, best_score,
+                                     best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, (hipStream_t)stream);
+}
+int dr_local_opt_f64(const double *matches, const double *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
+                     double confidence, double eps, int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
+                     int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits, void *stream) {
+  return dr::local_opt_launch<double>(matches, thr, P, N, fundamental, lo, lo_iters, k, confidence, eps, max_iterations, best_score,
+                                      best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, (hipStream_t)stream);
 }
 
 }  // extern "C"

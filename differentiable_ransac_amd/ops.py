@@ -150,6 +150,29 @@ def ransac_update(state: RansacState, matches, models, valid, scores, thr, B: in
 
 
 # ------------------------------------------------------------------------------------------ K1 / K1u / K2
+def local_optimize(state: RansacState, matches, thr, fundamental: bool, lo: int, lo_iters: int, k: int,
+                   confidence: float = 0.999, eps: float = 1e-5, max_iterations: Optional[int] = None,
+                   lo_seen: Optional[torch.Tensor] = None, lo_refits: Optional[torch.Tensor] = None) -> None:
+    """K7b (dr_local_opt): local optimisation of ransac.py:217-257 (lo = 1: one LSQ refit on the inliers, lo = 2: up to
+    lo_iters), in place on `state`, for the pairs whose best model dr_ransac_update replaced since the last visit.
+    lo_seen [P,10] (matches' dtype) is the per-call snapshot, filled with NaN before the first round; lo_refits [P] int32
+    (optional) accumulates the refits run per pair.  One launch, no synchronisation."""
+    tensors = (matches, thr, lo_seen, lo_refits, state.best_score, state.best_model, state.best_mask, state.best_inliers,
+               state.max_iters)
+    if any(t is not None and not t.is_cuda for t in tensors):
+        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    P, N, _ = matches.shape
+    if lo_seen is None or lo_seen.shape != (P, 10) or lo_seen.dtype != matches.dtype or not lo_seen.is_contiguous():
+        raise L.DransacError("local_optimize: lo_seen must be a contiguous [P,10] tensor of the matches' dtype")
+    if lo_refits is not None and (lo_refits.shape != (P,) or lo_refits.dtype != torch.int32):
+        raise L.DransacError("local_optimize: lo_refits must be [P] int32")
+    mi = state.max_iterations if max_iterations is None else max_iterations
+    L.call(f"dr_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), c_int(P), c_int(N),
+           c_int(1 if fundamental else 0), c_int(int(lo)), c_int(int(lo_iters)), c_int(int(k)), L.c_double(confidence),
+           L.c_double(eps), c_int(int(mi)), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
+           ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits), stream())
+
+
 class DeviceSeed:
     """The per-call sampler seed of the batched drivers, kept on the device: state = (base, calls) and `next()` launches
     dr_seed_next_n -> a one-word tensor holding base * 0x9E3779B97F4A7C15 + calls (mod 2^64), calls += 1.  The samplers

@@ -49,6 +49,17 @@ def _takes_argument(fn) -> bool:
     return len(params) >= 1
 
 
+def _check_lo(lo, lo_iters):
+    """lo 0 / 1 / 2 (ransac.py:217-257); 3, the inner RANSAC of :258-299, never ran in the reference."""
+    if lo == 3:
+        raise NotImplementedError("lo=3 (inner RANSAC) is out of scope: it never ran in the reference either (its "
+                                  "UniformSampler call raises TypeError, SURVEY Q2)")
+    if lo not in (0, 1, 2):
+        raise ValueError(f"lo must be 0, 1 (one LSQ refit on the inliers) or 2 (iterated refits), got {lo!r}")
+    if int(lo_iters) < 1:
+        raise ValueError(f"lo_iters must be at least 1, got {lo_iters!r}")
+
+
 def _is_gumbel(sampler_id):
     # ids 2 and 3 in the reference; id 1 builds a Gumbel sampler there too but then crashes (Q16): treated as 2
     return sampler_id in (1, 2, 3)
@@ -56,7 +67,12 @@ def _is_gumbel(sampler_id):
 
 class RANSAC(object):
     """Drop-in for the reference's RANSAC (ransac.py:6-200): __call__(matches [N,4], logits [N], K1, K2, gt_model)
-    -> (best_model | {iteration: models}, best_mask, best_score, iterations)."""
+    -> (best_model | {iteration: models}, best_mask, best_score, iterations).
+
+    lo = 1 / 2 (test mode): localOptimization of ransac.py:217-257 after every new best model -- on the device (dr_local_opt)
+    in the fused path, host-side with the plugins otherwise.  With lo > 0 every batch is a device round of its own, so a call
+    replays as one graph when it is at most 8 rounds (`-rbs 1024` / 5000: 5) and runs the eager fused driver otherwise
+    (`-rbs 64`: 79 rounds)."""
 
     def __init__(self, estimator, sampler, scoring, fmat=False, train=False, ransac_batch_size=64, sampler_id=0,
                  weighted=0, threshold=1e-3, confidence=0.999, max_iterations=5000, lo=0, lo_iters=64, eps=1e-5):
@@ -89,14 +105,62 @@ class RANSAC(object):
         self._fast = None
         self._fast_cfg = None
         self._graphs = collections.OrderedDict()
-        if lo:
-            raise NotImplementedError("local optimisation is out of scope (it never ran in the reference either: "
-                                      "lo defaults to 0 and lo=3 raises TypeError, SURVEY Q2)")
+        if lo not in (0, 1, 2):
+            # lo=3, the inner RANSAC of ransac.py:258-299, never ran in the reference (its UniformSampler call raises TypeError)
+            raise NotImplementedError(f"lo={lo!r}: only lo=1 (one LSQ refit on the inliers) and lo=2 (iterated refits) are "
+                                      "implemented; lo=3 (inner RANSAC) never ran in the reference either (SURVEY Q2)")
+        _check_lo(lo, lo_iters)
 
     def adaptive_iteration_number(self, inlier_number, point_number, confidence):
         """ransac.py:202-215, the reference's method form (sample size, eps and the cap come from the object)."""
         return adaptive_iteration_number(inlier_number, point_number, self.estimator.sample_size, confidence, self.eps,
                                          self.max_iterations)
+
+    def _lo_candidates(self, matches, mask):
+        """The LSQ refit of localOptimization (ransac.py:227-242) on the rows `mask` selects -> (models [S,3,3], valid [S] or None),
+        or None when there are too few rows.  This package's estimators solve what dr_local_opt solves: F = the unweighted Hartley
+        8-point (ops.refit_fundamental), E = the five-point solver on the selected rows in f64 (ops.refit_essential; the
+        reference's f32 run of the same solver, Q11).  A third-party estimator goes through its estimate_model."""
+        from .estimators import EssentialMatrixEstimator, EssentialMatrixEstimatorNister, FundamentalMatrixEstimatorNew
+        n = int(mask.sum())
+        if n < (8 if self.fmat else 5):
+            return None
+        if matches.is_cuda and type(self.estimator) is FundamentalMatrixEstimatorNew and self.fmat:
+            F, v = ops.refit_fundamental(matches.unsqueeze(0), mask.unsqueeze(0))
+            return F, v
+        if matches.is_cuda and type(self.estimator) in (EssentialMatrixEstimatorNister, EssentialMatrixEstimator) and not self.fmat:
+            E, v = ops.refit_essential(matches.unsqueeze(0), mask.unsqueeze(0))
+            return E[0], v[0]
+        models = self.estimator.estimate_model(matches[mask].unsqueeze(0))
+        if models is None or models.shape[0] == 0:
+            models = torch.eye(3, device=matches.device, dtype=matches.dtype).unsqueeze(0)   # ransac.py:243-244
+        return models.reshape(-1, 3, 3).to(matches.dtype), None
+
+    def _local_optimization(self, best_score, best_mask, best_model, best_inlier_number, matches, threshold):
+        """localOptimization, ransac.py:217-257 (lo = 1: one refit, lo = 2: up to lo_iters): refit on the inliers, score, keep the
+        result when it scores at least as well (a tie is taken), stop otherwise -- or when the mask did not change (the next
+        refit would see the same rows).  The host-side twin of dr_local_opt (the fused path), for the plugin path."""
+        for _ in range(1 if self.lo == 1 else self.lo_iters):
+            got = self._lo_candidates(matches, best_mask)
+            if got is None:
+                break
+            cand, cvalid = got
+            scores, masks = self.scoring.score(matches, cand, threshold)
+            ok = ~torch.isnan(scores) & torch.isfinite(cand).flatten(1).all(-1)
+            if cvalid is not None:
+                ok = ok & cvalid
+            if not bool(ok.any()):
+                break
+            scores = torch.where(ok, scores, torch.full_like(scores, -float("inf")))
+            b = int(torch.argmax(scores))
+            if not float(scores[b]) >= float(best_score):
+                break
+            changed = bool((masks[b] != best_mask).any())
+            best_score, best_mask, best_model = scores[b], masks[b], cand[b]
+            best_inlier_number = int(torch.sum(best_mask))
+            if not changed:
+                break
+        return best_score, best_mask, best_model, best_inlier_number
 
     # -- one batch: sample -> gather -> solve; returns models [B,S,3,3], valid [B,S], soft weights
     def _hypotheses(self, matches, logits, gumbels=None):
@@ -151,7 +215,7 @@ class RANSAC(object):
     def _make_fast(self, solver, seed=0, super_hypotheses=None):
         drv = BatchedRANSAC(solver, ransac_batch_size=self.ransac_batch_size, train=False, threshold=self.threshold,
                             confidence=self.confidence, max_iterations=self.max_iterations, tau=self.sampler.tau,
-                            weighted=self.weighted, refit=True, eps=self.eps, seed=seed)
+                            weighted=self.weighted, refit=True, eps=self.eps, seed=seed, lo=self.lo, lo_iters=self.lo_iters)
         drv.super_hypotheses = super_hypotheses
         return drv
 
@@ -181,7 +245,7 @@ class RANSAC(object):
         solver = self._fused_solver() if self.fused else None
         if solver is not None and matches.is_cuda:
             cfg = (solver, self.ransac_batch_size, self.threshold, self.confidence, self.max_iterations, self.sampler.tau,
-                   self.weighted, self.eps)
+                   self.weighted, self.eps, self.lo, self.lo_iters)
             cfg = cfg + (self.graph_hypotheses,)
             if self._fast_cfg != cfg:     # public attributes may change between calls (sweeps)
                 self._fast, self._graphs, self._fast_cfg = None, collections.OrderedDict(), cfg
@@ -249,6 +313,9 @@ class RANSAC(object):
                     best_mask = masks[best_idx]
                     best_model = flat[best_idx]
                     best_inlier_number = int(torch.sum(best_mask))
+                    if self.lo:
+                        best_score, best_mask, best_model, best_inlier_number = self._local_optimization(
+                            best_score, best_mask, best_model, best_inlier_number, matches, threshold)
                     max_iters = min(self.max_iterations,
                                     adaptive_iteration_number(best_inlier_number, point_number, self.estimator.sample_size,
                                                               self.confidence, self.eps, self.max_iterations))
@@ -424,7 +491,7 @@ class BatchedRANSAC(object):
 
     def __init__(self, solver="nister", ransac_batch_size=1024, train=False, threshold=0.75, confidence=0.999,
                  max_iterations=5000, tau=1.0, seed=0, weighted=0, keep_masks=False, refit=True, eps=1e-5,
-                 sampling="gumbel", num_samples=None):
+                 sampling="gumbel", num_samples=None, lo=0, lo_iters=64):
         # num_samples: points per sample when it is not the solver's minimal count -- 8 with solver="nister" is the reference's
         # `-sam 3` (8-point Gumbel sampler) feeding the five-point estimator (ransac.py:82-83; nister.py:64-65 runs on all rows)
         # sampling: "gumbel" = the reference's sampler (noise for every point of every hypothesis, top-k);
@@ -434,6 +501,11 @@ class BatchedRANSAC(object):
         # the last point never drawn) for all pairs in one launch; index sets only, logits ignored.
         if sampling not in ("gumbel", "topdown", "uniform"):
             raise ValueError("sampling must be 'gumbel', 'topdown' or 'uniform'")
+        # lo (test mode; ignored in train mode, as in the reference): local optimisation of ransac.py:217-257 after every new best
+        # model -- 1 = one LSQ refit on its inliers, 2 = up to lo_iters of them (ops.local_optimize, one launch per device round)
+        _check_lo(lo, lo_iters)
+        self.lo = int(lo)
+        self.lo_iters = int(lo_iters)
         if sampling in ("topdown", "uniform") and (train or weighted):
             raise ValueError(f"{sampling} sampling yields index sets only: train mode and weighted=1 need the Gumbel sampler")
         self.sampling = sampling
@@ -515,6 +587,10 @@ class BatchedRANSAC(object):
         sh = self.super_hypotheses
         one = [1] * n_batches
         if sh is False or self.train or self.sampling != "gumbel" or self.keep_masks or dtype != torch.float32:
+            return one
+        if self.lo and not self.train:
+            # a local optimisation after sub-batch j changes the score sub-batch j + 1 must beat: dr_ransac_update cannot walk
+            # several batches in one launch exactly, so every batch is a device round with its own local-optimisation launch
             return one
         if self.weighted:
             # weighted rows in the minimal solves (ransac.py:70-74) need the soft weights of every batch, and the weighted refit wants
@@ -690,6 +766,12 @@ class BatchedRANSAC(object):
                                       K2 if use_K else None, dev, dt, seeds=(self._dev_seed, n_batches) if fold else None,
                                       packed=_FOLD_SETUP and self.device_termination and P == 1, race_logits=race_lg)
             self._race_ws = st.race_ws
+            lo_seen = lo_refits = None
+            if self.lo:
+                # the local optimisation's per-pair snapshot of (best_score, best_model) -- NaN: the first replacement is always
+                # seen -- and its refit counters (capturable allocations: a replayed call re-fills them)
+                lo_seen = torch.full((P, 10), float("nan"), device=dev, dtype=dt)
+                lo_refits = torch.zeros(P, device=dev, dtype=torch.int32)
             if draw and not fold:
                 st.seeds = self._dev_seed.next_block(n_batches)
             if pre is not None and plan and P * self.B * plan[0] >= 65536:
@@ -744,8 +826,10 @@ class BatchedRANSAC(object):
                         all_masks = masks
                     ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.k, self.confidence,
                                       self.eps, sub_models=sub_of(r))
+                    if lo_seen is not None:
+                        self._local_opt(st, matches, thr, lo_seen, lo_refits)
                 self._seed_queue = []
-                return self._finish(st, matches, thr, pre, last_w, all_masks)
+                return self._finish(st, matches, thr, pre, last_w, all_masks, lo_refits)
             ahead = None
             if have_round(0):
                 h = self._hypotheses(matches, logits, noise_of(0), R=plan[0])
@@ -775,6 +859,8 @@ class BatchedRANSAC(object):
                 # K6: arg-max, "better?" test, best mask / inlier count and the adaptive stop of ransac.py:135-142, on the device
                 ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.k, self.confidence,
                                   self.eps, sub_models=sub_of(r))
+                if lo_seen is not None:      # (before the read-back below: it sees the bound the local optimisation set)
+                    self._local_opt(st, matches, thr, lo_seen, lo_refits)
                 r += 1
                 if not have_round(r):
                     break
@@ -793,9 +879,13 @@ class BatchedRANSAC(object):
                         t_.record_stream(main)
             if ahead is not None and self._pipe is not None:
                 main.wait_stream(self._pipe)              # dropped speculative work: keep the allocator's stream order simple
-            return self._finish(st, matches, thr, pre, last_w, all_masks)
+            return self._finish(st, matches, thr, pre, last_w, all_masks, lo_refits)
 
-    def _finish(self, st, matches, thr, pre, last_w, all_masks):
+    def _local_opt(self, st, matches, thr, lo_seen, lo_refits):
+        ops.local_optimize(st, matches, thr, self.fmat, self.lo, self.lo_iters, self.k, self.confidence, self.eps,
+                           self.max_iterations, lo_seen, lo_refits)
+
+    def _finish(self, st, matches, thr, pre, last_w, all_masks, lo_refits=None):
         """final refit on the inliers of the best model (ransac.py:148-195) and the result dictionary"""
         self._race_ws = None
         best_score, best_model, best_mask, best_inl, iters = (st.best_score, st.best_model, st.best_mask,
@@ -812,8 +902,11 @@ class BatchedRANSAC(object):
                     cvalid.record_stream(torch.cuda.current_stream())
             # score the candidates and keep the best one where it beats the RANSAC result: one launch, in place
             ops.refit_accept(matches, cand, cvalid, thr, best_score, best_model)
-        return dict(model=best_model, mask=best_mask, score=best_score, iterations=iters, inliers=best_inl,
-                    masks=all_masks, packed=st.packed)
+        out = dict(model=best_model, mask=best_mask, score=best_score, iterations=iters, inliers=best_inl,
+                   masks=all_masks, packed=st.packed)
+        if lo_refits is not None:
+            out["lo_refits"] = lo_refits
+        return out
 
 
 class BatchedRANSAC3D(object):

@@ -438,6 +438,32 @@ int dr_refit_accept_f64(const double *matches, const double *cand, const uint8_t
                         int S, int N, double *best_score, double *best_model, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K7b local optimisation, RANSAC.localOptimization ransac.py:217-257 with lo = 1 (one LSQ refit on the inliers) or
+ *     lo = 2 (up to lo_iters refits), test mode, on the per-pair state of dr_ransac_update, in place.  Meant to be
+ *     enqueued right behind every dr_ransac_update (one launch per device round, no host synchronisation: capturable).
+ *     One cooperative block per pair:
+ *   - lo_seen [P,10] is the caller's snapshot (best_score, best_model) of the last visit, initialised to NaN: a pair whose
+ *     best_score / best_model still equal it bit for bit was not replaced since and is left untouched (whether or not
+ *     its iteration counter has reached max_iters: LO runs before the loop's stop test, ransac.py:122-144);
+ *   - with fewer than 8 (fundamental) / 5 (essential) inliers the pair is left as it is;
+ *   - otherwise, up to 1 (lo = 1) or lo_iters (lo = 2) times: the K7 refit on best_mask (fundamental: unweighted
+ *     Hartley LSQ 8-point; essential: the five-point solver on the selected rows, f64 inside), the MSAC scores at
+ *     1.5 thr of its valid, finite candidates (dr_refit_accept's rule, first arg-max) and, where that score is
+ *     >= best_score (a tie is taken, ransac.py:252), the new best_score / best_model and -- with dr_ransac_update's
+ *     predicate -- best_mask / best_inliers.  The loop stops when a refit loses or leaves the mask unchanged;
+ *   - then max_iters[p] = min(max_iterations, adaptive_iteration_number(best_inliers)) (ransac.py:135-142), the
+ *     snapshot is stored, and lo_refits[p] (NULL = not counted) grows by the number of refits run.
+ * ------------------------------------------------------------------------------------------ */
+int dr_local_opt_f32(const float *matches, const float *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
+                     double confidence, double eps, int max_iterations, float *best_score, float *best_model,
+                     uint8_t *best_mask, int32_t *best_inliers, double *max_iters, float *lo_seen, int32_t *lo_refits,
+                     void *stream);
+int dr_local_opt_f64(const double *matches, const double *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
+                     double confidence, double eps, int max_iterations, double *best_score, double *best_model,
+                     uint8_t *best_mask, int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits,
+                     void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * the training loss right after the path -- MatchLoss (loss.py:107-153) on batch_episym
  * (cv_utils.py:680-695).  sums [P,M] = sum over the points with mask[p,n] != 0 (NULL = all points) of
  * min(ys, 1), ys = (x2^T M x1)^2 (1/((Mx1)_0^2+(Mx1)_1^2+1e-15) + 1/((M^T x2)_0^2+(M^T x2)_1^2+1e-15)).
