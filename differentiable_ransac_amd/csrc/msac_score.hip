@@ -712,12 +712,16 @@ __global__ __launch_bounds__(kThreads) void refit_accept_kernel(const T *__restr
   for (int c = 0; c < S; ++c) {
     if (cvalid && !cvalid[(size_t)p * S + c]) continue;   // block-uniform
     T m[9];
-    bool finite = true;
+    bool finite = true, nonzero = false;
 #pragma unroll
     for (int q = 0; q < 9; ++q) {
       m[q] = cand[((size_t)p * S + c) * 9 + q];
       finite = finite && is_finite(m[q]);
+      nonzero = nonzero || (m[q] != T(0));
     }
+    // an all-zero candidate competes no more than a non-finite one: dr_msac_score gives it a NaN score (the reference's 0/0),
+    // while the sum below would be 0 and could beat a negative best_score
+    finite = finite && nonzero;
     T acc = msac_partial<T, kThreads>(matches + (size_t)p * N * 4, m, N, inv_thr2);
     acc = wave_sum(acc);
     if (lane == 0) s_part[wv] = acc;

@@ -488,6 +488,10 @@ class BatchedRANSAC(object):
     """
 
     _SOLVERS = {"nister": (5, 10), "stewenius": (5, 10), "f8": (8, 1), "f7": (7, 4)}
+    # exponent of the adaptive stop: the reference raises the inlier ratio to its estimator's `sample_size` (ransac.py:204-215), 5 for
+    # the essential estimators and 7 for FundamentalMatrixEstimatorNew (fundamental_matrix_estimator.py:164) -- not the sampler's
+    # points per sample (8 for "f8", and for "nister" with num_samples=8)
+    _STOP_EXPONENT = {"nister": 5, "stewenius": 5, "f8": 7, "f7": 7}
 
     def __init__(self, solver="nister", ransac_batch_size=1024, train=False, threshold=0.75, confidence=0.999,
                  max_iterations=5000, tau=1.0, seed=0, weighted=0, keep_masks=False, refit=True, eps=1e-5,
@@ -519,6 +523,7 @@ class BatchedRANSAC(object):
         self._pipe = None
         self.solver = solver
         self.k, self.S = self._SOLVERS[solver]
+        self.stop_k = self._STOP_EXPONENT[solver]     # (unchanged by num_samples)
         if num_samples is not None and num_samples != self.k:
             if solver not in ("nister", "f8") or not self.k < num_samples <= 8:
                 raise ValueError(f"solver {solver!r} takes {self.k} points per sample (non-minimal samples: 'nister' / 'f8', up to 8)")
@@ -824,7 +829,7 @@ class BatchedRANSAC(object):
                                                    gate=gate)
                     if self.keep_masks:
                         all_masks = masks
-                    ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.k, self.confidence,
+                    ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.stop_k, self.confidence,
                                       self.eps, sub_models=sub_of(r))
                     if lo_seen is not None:
                         self._local_opt(st, matches, thr, lo_seen, lo_refits)
@@ -857,7 +862,7 @@ class BatchedRANSAC(object):
                 if self.keep_masks:
                     all_masks = masks
                 # K6: arg-max, "better?" test, best mask / inlier count and the adaptive stop of ransac.py:135-142, on the device
-                ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.k, self.confidence,
+                ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.stop_k, self.confidence,
                                   self.eps, sub_models=sub_of(r))
                 if lo_seen is not None:      # (before the read-back below: it sees the bound the local optimisation set)
                     self._local_opt(st, matches, thr, lo_seen, lo_refits)
@@ -882,7 +887,7 @@ class BatchedRANSAC(object):
             return self._finish(st, matches, thr, pre, last_w, all_masks, lo_refits)
 
     def _local_opt(self, st, matches, thr, lo_seen, lo_refits):
-        ops.local_optimize(st, matches, thr, self.fmat, self.lo, self.lo_iters, self.k, self.confidence, self.eps,
+        ops.local_optimize(st, matches, thr, self.fmat, self.lo, self.lo_iters, self.stop_k, self.confidence, self.eps,
                            self.max_iterations, lo_seen, lo_refits)
 
     def _finish(self, st, matches, thr, pre, last_w, all_masks, lo_refits=None):

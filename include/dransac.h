@@ -394,6 +394,8 @@ int dr_ransac_init_f64(const double *K1, const double *K2, int k_stride, double 
  *         log10(1-confidence) / log10(1 - (inliers/N)^k + eps))   (computed in f64);
  *     iters[p] += B.
  *   The caller initialises best_score = 0, iters = 0, max_iters = max_iterations (dr_ransac_init does).
+ *   k is the exponent of the stop: the estimator's sample_size (ransac.py:204-215; 5 for E, 7 for the F estimator), which
+ *   is not the sampler's points per sample (8 for the 8-point F sampler and for `num_samples = 8`).
  *   sub_models (round 6): 0 (or >= M) = the M models are one batch of B hypotheses.  0 < sub_models < M: they are ceil(M / sub_models)
  *   consecutive sub-batches of B hypotheses each (at most 512), and the steps above are applied to one sub-batch after the other, IN
  *   ORDER, stopping as the loop of ransac.py:55 does when iters[p] >= max_iters[p]: the state after the launch is the state that loop
@@ -430,8 +432,9 @@ int dr_refit_fundamental_f64(const double *matches, const uint8_t *mask, const d
                              uint8_t *valid, void *stream);
 
 /* K7 acceptance (ransac.py:173-185): MSAC scores of the S refit candidates of every pair (cand [P,S,9], cand_valid [P,S]
- * or NULL); where the best candidate scores strictly higher than best_score[p], best_score[p] and best_model[p] ([P,9])
- * are replaced in place (the best mask is not touched, as in the reference). */
+ * or NULL; non-finite and all-zero candidates do not compete, as their NaN score of dr_msac_score would not); where the
+ * first best candidate scores strictly higher than best_score[p], best_score[p] and best_model[p] ([P,9]) are replaced in
+ * place (the best mask is not touched, as in the reference). */
 int dr_refit_accept_f32(const float *matches, const float *cand, const uint8_t *cand_valid, const float *thr, int P, int S,
                         int N, float *best_score, float *best_model, void *stream);
 int dr_refit_accept_f64(const double *matches, const double *cand, const uint8_t *cand_valid, const double *thr, int P,

@@ -520,7 +520,8 @@ def ransac_test(matches, logits, gumbel_batches, K1, K2, solver: str, threshold:
     at the adaptive bound or when the list is exhausted.
     Returns best_model [3,3], best_mask [N], best_score, iterations."""
     fmat = solver == "f8"
-    k = 8 if fmat else 5
+    k = 8 if fmat else 5              # points per sample
+    ks = 7 if fmat else 5             # exponent of the adaptive stop: the estimator's sample_size (7 for the 8-point F estimator)
     thr = normalized_threshold(threshold, K1, K2, fmat)
     N = matches.shape[0]
     it, best_score, best_mask, best_model = 0, 0.0, None, None
@@ -546,7 +547,7 @@ def ransac_test(matches, logits, gumbel_batches, K1, K2, solver: str, threshold:
         b = int(torch.argmax(scores))
         if float(scores[b]) > best_score or it == 0:
             best_score, best_mask, best_model = float(scores[b]), masks[b], models[b]
-            max_iters = min(max_iterations, adaptive_iteration_number(int(best_mask.sum()), N, k, confidence,
+            max_iters = min(max_iterations, adaptive_iteration_number(int(best_mask.sum()), N, ks, confidence,
                                                                       max_iterations=max_iterations))
         it += B
     if refit:

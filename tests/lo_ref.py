@@ -46,12 +46,12 @@ def ransac_test_lo(matches, logits, gumbel_batches, K1, K2, solver: str, lo: int
                    threshold: float = 0.75, max_iterations: int = 5000, confidence: float = 0.999, tau: float = 1.0,
                    refit: bool = True, num_samples=None, sample_size=None):
     """oracle.cpu_ref.ransac_test (lo = 0) with the local optimisation after every new best model.
-    sample_size: the exponent of the adaptive stop; None = the points per sample, as in oracle.cpu_ref.ransac_test and the
-    device drivers (the reference's 8-point F estimator declares 7, fundamental_matrix_estimator.py:9).
+    sample_size: the exponent of the adaptive stop; None = the estimator's sample_size, as in the reference, oracle.cpu_ref.ransac_test
+    and the device drivers: 7 for the 8-point F estimator, 5 for the five-point one, whatever num_samples is.
     Returns best_model [3,3], best_mask [N], best_score, iterations, refits (total LSQ refits of the local optimisation)."""
     fmat = solver == "f8"
     k = num_samples or (8 if fmat else 5)
-    ks = sample_size or k
+    ks = sample_size or (7 if fmat else 5)
     thr = O.normalized_threshold(threshold, K1, K2, fmat)
     N = matches.shape[0]
     it, best_score, best_mask, best_model = 0, 0.0, None, None

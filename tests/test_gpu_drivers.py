@@ -282,20 +282,25 @@ def test_ransac_init_threshold_and_state(dev, dtype):
 
 def test_dropin_fused_path_equals_plugin_path(dev):
     """RANSAC.__call__ in test mode: the device-resident batched driver (fused=True, the default when the plugins are
-    this package's) and the per-batch plugin path give the same result for the same explicit noise."""
-    g = load_golden("ransac_test_nister")
-    args = (g["matches"].to(dev), g["logits"].to(dev), g["K1"].to(dev), g["K2"].to(dev), None)
-    noise = [x.to(dev) for x in g["gumbels"]]
-    out = {}
-    for fused in (True, False):
-        r = _make("nister", 16, False, 5000)
-        r.fused = fused
-        out[fused] = r(*args, gumbels=noise)
-    (ma, ka, sa, ia), (mb, kb, sb, ib) = out[True], out[False]
-    assert ia == ib
-    assert torch.equal(ka, kb)
-    assert abs(float(sa) - float(sb)) <= 1e-4 * max(1.0, abs(float(sb)))
-    assert (O.canonical(ma.cpu().double()) - O.canonical(mb.cpu().double())).abs().max() < 1e-5
+    this package's) and the per-batch plugin path give the same result for the same explicit noise -- five-point and
+    8-point F (the F noise lengthened past the recorded list, so that both stop on their adaptive bound)."""
+    from differentiable_ransac_amd import synth
+    for name in ("nister", "f8"):
+        g = load_golden(f"ransac_test_{name}")
+        args = (g["matches"].to(dev), g["logits"].to(dev), g["K1"].to(dev), g["K2"].to(dev), None)
+        noise = [x.to(dev) for x in g["gumbels"]]
+        if name == "f8":
+            noise += [x.to(dev) for x in synth.gumbel_noise((48,) + tuple(noise[0].shape), seed=2025)]
+        out = {}
+        for fused in (True, False):
+            r = _make(name, 16, False, 5000)
+            r.fused = fused
+            out[fused] = r(*args, gumbels=noise)
+        (ma, ka, sa, ia), (mb, kb, sb, ib) = out[True], out[False]
+        assert ia == ib, name
+        assert torch.equal(ka, kb), name
+        assert abs(float(sa) - float(sb)) <= 1e-4 * max(1.0, abs(float(sb))), name
+        assert (O.canonical(ma.cpu().double()) - O.canonical(mb.cpu().double())).abs().max() < 1e-5, name
 
 
 def test_batched_topdown_sampling_recovers_the_pose(dev):
