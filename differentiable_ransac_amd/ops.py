@@ -4,12 +4,62 @@ torch stream and returns freshly allocated torch tensors; nothing synchronises.
 """
 from __future__ import annotations
 
+import os as _os
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib as L
 from ._lib import c_int, c_uint64, ptr, stream
+
+# Round 5: the screened register kernel for rows of <= 2048 points (dr_gumbel_topk_gather_f32 with a screen_ws workspace) is built,
+# bit-identical (tests/test_gpu_round5.py) and SLOWER than the unscreened one at the shapes measured -- 199.5 vs 164.1 us at 128
+# pairs x 1024 rows x 2000 points, 57.4 vs 45.2 at 32 pairs, 25.6 vs 18.2 at one pair (scratch/ab_k1_screen.py), in both of its forms
+# (words parked in LDS + one evaluation per lane and round: 200.8; slot-wise wave masks, no parking, no dependent load: 199.5):
+# ~16 of 2000 points pass, but Philox (40 % of the row's instructions) cannot be screened and the unscreened transform is 7 vector
+# instructions per element -- a branch per element slot costs what it saves.  Off unless asked for (screen=True, DRANSAC_SCREEN_SHORT=1).
+SCREEN_SHORT_ROWS = _os.environ.get("DRANSAC_SCREEN_SHORT", "0") == "1"
+
+
+# Round 6: the exponential-race form of the index-only sampler (one logarithm per element; dr_gumbel_topk_gather_f32's race_ws).
+# Same top-k up to the rounding of near-ties; off = the two-logarithm form of rounds 1-5 (A/B runs, tests: DRANSAC_K1_RACE=0).
+K1_RACE = _os.environ.get("DRANSAC_K1_RACE", "1") != "0"
+K1_RACE_SOFT = _os.environ.get("DRANSAC_K1_RACE_SOFT", "1") != "0"   # ... in train mode (SampleGather's fused launch)
+_RACE_MIN = tuple(int(v) for v in _os.environ.get("DRANSAC_K1_RACE_MIN", "32768,32").split(","))   # (rows, pairs) from which it is automatic
+FUSED_SAMPLE_GATHER = _os.environ.get("DRANSAC_FUSED_SAMPLE_GATHER", "1") != "0"   # A/B and tests: off = the two-launch forward / backward of rounds 1-4
+FUSED_MATCH_LOSS = True   # tests / A-B runs: False = the two-pass form of rounds 3-4
+
+
+def _u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """an optional bool tensor as the bytes the C ABI takes"""
+    return None if t is None else t.contiguous().view(torch.uint8)
+
+
+def _u8_ptr(t: Optional[torch.Tensor]):
+    return ptr(_u8(t))
+
+
+def _gate_args(gate):
+    """the (iters, max_iters) pointer pair of a gated entry: gate = RansacState (a later round of a multi-round call, the blocks of
+    terminated pairs return at once) or None"""
+    return (ptr(None), ptr(None)) if gate is None else (ptr(gate.iters), ptr(gate.max_iters))
+
+
+def _dev_seed(seed):
+    if torch.is_tensor(seed):
+        if seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
+            L._reset()      # (may be raised half-way through an argument list: see _lib.ptr)
+            raise L.DransacError("a device seed is a one-element int64 CUDA tensor (DeviceSeed.next())")
+        return True
+    return False
+
+
+def _seed_args(seed):
+    """the (seed by value, seed on the device) argument pair of a sampler entry: an int goes by value, a DeviceSeed.next() tensor
+    by pointer (read when the kernel starts)"""
+    if _dev_seed(seed):
+        return c_uint64(0), ptr(seed)
+    return c_uint64(seed & (2 ** 64 - 1)), ptr(None)
 
 
 def _thr_tensor(threshold, P: int, like: torch.Tensor) -> torch.Tensor:
@@ -35,7 +85,7 @@ def msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, want_mask
     thr = _thr_tensor(threshold, P, matches)
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     masks = torch.empty((P, M, N), device=matches.device, dtype=torch.bool) if want_masks else None
-    v = None if valid is None else valid.contiguous().view(torch.uint8)
+    v = _u8(valid)
     if path not in (0, 1):
         raise L.DransacError("msac_score: path must be 0 or 1 (the general kernels); path 2, the matrix-core candidate filter of "
                              "round 2, was measured slower and left the library (scratch/k4_filter_kernel.patch)")
@@ -43,7 +93,7 @@ def msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, want_mask
         # gate (a later round of a multi-round call): the blocks of terminated pairs (gate = RansacState) return at once, their
         # scores are never looked at (dr_ransac_update skips such pairs)
         L.call("dr_msac_score_f32", ptr(matches), ptr(models), ptr(v), ptr(thr), c_int(P), c_int(M), c_int(N), ptr(scores),
-               ptr(masks), ptr(None if gate is None else gate.iters), ptr(None if gate is None else gate.max_iters), stream())
+               ptr(masks), *_gate_args(gate), stream())
         return scores, masks
     L.call(f"dr_msac_score_{L.suffix(matches.dtype)}", ptr(matches), ptr(models), ptr(v), ptr(thr), c_int(P), c_int(M), c_int(N),
            ptr(scores), ptr(masks), stream())
@@ -62,8 +112,7 @@ def select_best(matches: torch.Tensor, models: torch.Tensor, scores: torch.Tenso
     best_model = torch.empty((P, 3, 3), device=dev, dtype=dt)
     best_mask = torch.empty((P, N), device=dev, dtype=torch.bool)
     inliers = torch.empty((P,), device=dev, dtype=torch.int32)
-    v = None if valid is None else valid.contiguous().view(torch.uint8)
-    L.call(f"dr_select_best_{L.suffix(dt)}", ptr(matches.contiguous()), ptr(models.contiguous()), ptr(v),
+    L.call(f"dr_select_best_{L.suffix(dt)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(scores.contiguous()), ptr(thr), c_int(P), c_int(M), c_int(N), ptr(best_idx), ptr(best_score),
            ptr(best_model), ptr(best_mask), ptr(inliers), stream())
     return best_idx, best_score, best_model, best_mask, inliers
@@ -141,8 +190,7 @@ def ransac_update(state: RansacState, matches, models, valid, scores, thr, B: in
     M = models.shape[1]
     if sub_models and M > sub_models * 512:
         raise L.DransacError("ransac_update: at most 512 sub-batches per launch")
-    v = None if valid is None else valid.contiguous().view(torch.uint8)
-    L.call(f"dr_ransac_update_{L.suffix(matches.dtype)}", ptr(matches), ptr(models.contiguous()), ptr(v),
+    L.call(f"dr_ransac_update_{L.suffix(matches.dtype)}", ptr(matches), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(scores.contiguous()), ptr(thr), c_int(P), c_int(M), c_int(N), c_int(B), c_int(k),
            L.c_double(confidence), L.c_double(eps), c_int(state.max_iterations), ptr(state.best_score),
            ptr(state.best_model), ptr(state.best_mask), ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters),
@@ -204,14 +252,6 @@ class DeviceSeed:
         return [out[i:i + 1] for i in range(n)]
 
 
-def _dev_seed(seed):
-    if torch.is_tensor(seed):
-        if seed.dtype != torch.int64 or seed.numel() != 1 or not seed.is_cuda:
-            raise L.DransacError("a device seed is a one-element int64 CUDA tensor (DeviceSeed.next())")
-        return True
-    return False
-
-
 def gumbel_topk(logits: Optional[torch.Tensor], B: int, k: int, tau: float = 1.0,
                 gumbel: Optional[torch.Tensor] = None, seed: int = 0, N: Optional[int] = None,
                 dense: bool = False, want_noise: bool = False, device=None, dtype=torch.float32, soft: bool = True,
@@ -241,44 +281,24 @@ def gumbel_topk(logits: Optional[torch.Tensor], B: int, k: int, tau: float = 1.0
             and N > 2048 and N % 4 == 0 and k <= 5 and (B >= 64 if screen is None else screen)):
         # long rows, index sets only: the screened one-pass kernel (dr_gumbel_topk_index_f32; same index sets, bit for bit)
         ws = torch.empty(((N + 32) * P,), device=device, dtype=torch.int32)
-        ds = _dev_seed(seed)
-        L.call("dr_gumbel_topk_index_f32", ptr(logits), c_uint64(0 if ds else seed & (2 ** 64 - 1)), ptr(seed if ds else None),
-               L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(ws), stream())
+        L.call("dr_gumbel_topk_index_f32", ptr(logits), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k),
+               ptr(idx), ptr(ws), stream())
         return dict(idx=idx, y_sel=None, lse=None)
     y_sel = torch.empty((P, B, k), device=device, dtype=dtype) if soft else None
     lse = torch.empty((P, B), device=device, dtype=dtype) if soft else None
     y_soft = torch.empty((P, B, N), device=device, dtype=dtype) if dense else None
     ret = torch.empty((P, B, N), device=device, dtype=dtype) if dense else None
     noise = torch.empty((P, B, N), device=device, dtype=dtype) if want_noise else None
-    ds = _dev_seed(seed)
-    if ds and (gumbel is not None or dense or want_noise or logits is None):
+    if _dev_seed(seed) and (gumbel is not None or dense or want_noise or logits is None):
         raise L.DransacError("a device seed serves the in-kernel noise of given logits only (no explicit noise / dense outputs)")
-    L.call(f"dr_gumbel_topk_fwd_{L.suffix(dtype)}", ptr(logits), ptr(gumbel), c_uint64(0 if ds else seed & (2 ** 64 - 1)),
-           ptr(seed if ds else None), L.scalar(dtype, tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(y_sel), ptr(lse),
-           ptr(y_soft), ptr(ret), ptr(noise), stream())
+    L.call(f"dr_gumbel_topk_fwd_{L.suffix(dtype)}", ptr(logits), ptr(gumbel), *_seed_args(seed), L.scalar(dtype, tau), c_int(P),
+           c_int(B), c_int(N), c_int(k), ptr(idx), ptr(y_sel), ptr(lse), ptr(y_soft), ptr(ret), ptr(noise), stream())
     out = dict(idx=idx, y_sel=y_sel, lse=lse)
     if dense:
         out.update(y_soft=y_soft, ret=ret)
     if want_noise:
         out["gumbel"] = noise
     return out
-
-
-import os as _os
-# Round 5: the screened register kernel for rows of <= 2048 points (dr_gumbel_topk_gather_f32 with a screen_ws workspace) is built,
-# bit-identical (tests/test_gpu_round5.py) and SLOWER than the unscreened one at the shapes measured -- 199.5 vs 164.1 us at 128
-# pairs x 1024 rows x 2000 points, 57.4 vs 45.2 at 32 pairs, 25.6 vs 18.2 at one pair (scratch/ab_k1_screen.py), in both of its forms
-# (words parked in LDS + one evaluation per lane and round: 200.8; slot-wise wave masks, no parking, no dependent load: 199.5):
-# ~16 of 2000 points pass, but Philox (40 % of the row's instructions) cannot be screened and the unscreened transform is 7 vector
-# instructions per element -- a branch per element slot costs what it saves.  Off unless asked for (screen=True, DRANSAC_SCREEN_SHORT=1).
-SCREEN_SHORT_ROWS = _os.environ.get("DRANSAC_SCREEN_SHORT", "0") == "1"
-
-
-# Round 6: the exponential-race form of the index-only sampler (one logarithm per element; dr_gumbel_topk_gather_f32's race_ws).
-# Same top-k up to the rounding of near-ties; off = the two-logarithm form of rounds 1-5 (A/B runs, tests: DRANSAC_K1_RACE=0).
-K1_RACE = _os.environ.get("DRANSAC_K1_RACE", "1") != "0"
-K1_RACE_SOFT = _os.environ.get("DRANSAC_K1_RACE_SOFT", "1") != "0"   # ... in train mode (SampleGather's fused launch)
-_RACE_MIN = tuple(int(v) for v in _os.environ.get("DRANSAC_K1_RACE_MIN", "32768,32").split(","))   # (rows, pairs) from which it is automatic
 
 
 def race_form_pays(P: int, B: int, N: int, tau: float) -> bool:
@@ -302,7 +322,6 @@ def gumbel_topk_gather(matches: torch.Tensor, logits: torch.Tensor, B: int, k: i
     P, N = logits.shape
     idx = torch.empty((P, B, k), device=logits.device, dtype=torch.int32)
     samples = torch.empty((P, B, k, 4), device=logits.device, dtype=torch.float32)
-    dev_seed = _dev_seed(seed)
     # round 5: rows of <= 2048 points through the SCREENED register kernel (a workspace of thresholds per point: same index sets)
     want_screen = SCREEN_SHORT_ROWS if screen is None else screen
     ws = (torch.empty((P, N + 32), device=logits.device, dtype=torch.int32)
@@ -311,11 +330,9 @@ def gumbel_topk_gather(matches: torch.Tensor, logits: torch.Tensor, B: int, k: i
     ready = race_ws is not None and ws is None and N <= 2048 and N % 4 == 0 and tau == 1.0
     want_race = not ready and (race_form_pays(P, B, N, tau) if race is None else race) and ws is None and N <= 2048 and N % 4 == 0 and tau == 1.0
     rws = race_ws if ready else (torch.empty((P, N + 32), device=logits.device, dtype=torch.float32) if want_race else None)
-    # (gate: a later round of a multi-round call, terminated pairs are skipped)
-    L.call("dr_gumbel_topk_gather_f32", ptr(logits), ptr(matches), c_uint64(0 if dev_seed else seed & (2 ** 64 - 1)),
-           ptr(seed if dev_seed else None), L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(samples),
-           ptr(ws), ptr(None if gate is None else gate.iters), ptr(None if gate is None else gate.max_iters),
-           c_int(0 if sub >= B else int(sub)), ptr(rws), c_int(1 if ready else 0), stream())
+    L.call("dr_gumbel_topk_gather_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B), c_int(N),
+           c_int(k), ptr(idx), ptr(samples), ptr(ws), *_gate_args(gate), c_int(0 if sub >= B else int(sub)), ptr(rws),
+           c_int(1 if ready else 0), stream())
     return idx, samples
 
 
@@ -331,10 +348,8 @@ def gumbel_topk_bwd(logits, gumbel, seed, tau, idx, lse, a_sel):
                L.c_double(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(lse.contiguous()),
                ptr(a_sel.to(torch.float64).contiguous()), ptr(grad), stream())
         return grad
-    ds = _dev_seed(seed)
-    L.call("dr_gumbel_topk_bwd_f32", ptr(logits.contiguous()), ptr(None if ds else gumbel), c_uint64(0 if ds else seed & (2 ** 64 - 1)),
-           ptr(seed if ds else None), L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(lse),
-           ptr(a_sel.contiguous()), ptr(grad), stream())
+    L.call("dr_gumbel_topk_bwd_f32", ptr(logits.contiguous()), ptr(None if _dev_seed(seed) else gumbel), *_seed_args(seed),
+           L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(lse), ptr(a_sel.contiguous()), ptr(grad), stream())
     return grad
 
 
@@ -353,24 +368,21 @@ def topdown_sample(logits: Optional[torch.Tensor], B: int, k: int, seed: int = 0
         sfx = "f32"
     ws = torch.empty((P, N), device=device, dtype=torch.float64)
     idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
-    ds = _dev_seed(seed)
     if sfx == "f32":
-        L.call("dr_topdown_sample_f32", ptr(logits), c_uint64(0 if ds else seed & (2 ** 64 - 1)), ptr(seed if ds else None), c_int(P),
-               c_int(B), c_int(N), c_int(k), ptr(ws), ptr(idx), stream())
+        L.call("dr_topdown_sample_f32", ptr(logits), *_seed_args(seed), c_int(P), c_int(B), c_int(N), c_int(k), ptr(ws), ptr(idx),
+               stream())
         return idx
-    if ds:
+    if _dev_seed(seed):
         raise L.DransacError("device seeds: f32 logits")
-    L.call("dr_topdown_sample_f64", ptr(logits), c_uint64(seed & (2 ** 64 - 1)), c_int(P), c_int(B), c_int(N), c_int(k),
-           ptr(ws), ptr(idx), stream())
+    L.call("dr_topdown_sample_f64", ptr(logits), _seed_args(seed)[0], c_int(P), c_int(B), c_int(N), c_int(k), ptr(ws), ptr(idx),
+           stream())
     return idx
 
 
 def uniform_sample(P: int, B: int, k: int, N: int, seed: int, device) -> torch.Tensor:
     """K1u: idx [P,B,k] int32 ~ U{0..N-2} (uniform_sampler.py:15-19 semantics)."""
     idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
-    ds = _dev_seed(seed)
-    L.call("dr_uniform_sample", c_uint64(0 if ds else seed & (2 ** 64 - 1)), ptr(seed if ds else None), c_int(P), c_int(B), c_int(k),
-           c_int(N), ptr(idx), stream())
+    L.call("dr_uniform_sample", *_seed_args(seed), c_int(P), c_int(B), c_int(k), c_int(N), ptr(idx), stream())
     return idx
 
 
@@ -396,9 +408,6 @@ def gather_bwd(matches, idx, y_sel, grad_samples, grad_w=None, want_grad_matches
     return a_sel, gm
 
 
-FUSED_SAMPLE_GATHER = _os.environ.get("DRANSAC_FUSED_SAMPLE_GATHER", "1") != "0"   # A/B and tests: off = the two-launch forward / backward of rounds 1-4
-
-
 class SampleGather(torch.autograd.Function):
     """K1+K2 fused at the autograd level: (matches [P,N,c], logits [P,N]) -> samples [P,B,k,c], weights [P,B,k].
 
@@ -422,14 +431,12 @@ class SampleGather(torch.autograd.Function):
                      y_sel=torch.empty((P, B, k), device=logits.device, dtype=torch.float32),
                      lse=torch.empty((P, B), device=logits.device, dtype=torch.float32))
             samples = torch.empty((P, B, k, 4), device=logits.device, dtype=torch.float32)
-            ds = _dev_seed(seed)
             # round 6: the one-logarithm form in train mode too (keys, winners and soft-max statistics from one logarithm and one
             # reciprocal per element), where its weights prologue pays
             rws = (torch.empty((P, N + 32), device=logits.device, dtype=torch.float32)
                    if K1_RACE_SOFT and race_form_pays(P, B, N, tau) else None)
-            L.call("dr_gumbel_topk_gather_soft_f32", ptr(logits), ptr(matches), c_uint64(0 if ds else seed & (2 ** 64 - 1)),
-                   ptr(seed if ds else None), L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(r["idx"]), ptr(r["y_sel"]),
-                   ptr(r["lse"]), ptr(samples), ptr(rws), stream())
+            L.call("dr_gumbel_topk_gather_soft_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B),
+                   c_int(N), c_int(k), ptr(r["idx"]), ptr(r["y_sel"]), ptr(r["lse"]), ptr(samples), ptr(rws), stream())
         else:
             r = gumbel_topk(logits, B, k, tau, gumbel, seed)
             samples = gather(matches, r["idx"], r["y_sel"])
@@ -451,10 +458,9 @@ class SampleGather(torch.autograd.Function):
         if ctx.fused and not ctx.needs_input_grad[0]:
             P, B, k = idx.shape
             gl = torch.empty_like(logits)
-            ds = _dev_seed(seed)
-            L.call("dr_gumbel_topk_gather_bwd_f32", ptr(logits), ptr(matches), c_uint64(0 if ds else seed & (2 ** 64 - 1)),
-                   ptr(seed if ds else None), L.c_float(tau), c_int(P), c_int(B), c_int(logits.shape[1]), c_int(k), ptr(idx), ptr(lse),
-                   ptr(g_samples.contiguous()), ptr(None if g_w is None else g_w.contiguous()), ptr(gl), stream())
+            L.call("dr_gumbel_topk_gather_bwd_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B),
+                   c_int(logits.shape[1]), c_int(k), ptr(idx), ptr(lse), ptr(g_samples.contiguous()),
+                   ptr(None if g_w is None else g_w.contiguous()), ptr(gl), stream())
             return None, gl, None, None, None, None, None
         a_sel, gm = gather_bwd(matches, idx, y_sel, g_samples, g_w, want_grad_matches=ctx.needs_input_grad[0])
         gl = gumbel_topk_bwd(logits, gumbel if has_noise else None, seed, tau, idx, lse, a_sel)
@@ -467,9 +473,21 @@ def _flat_samples(samples: torch.Tensor, c: int):
     return s, s.shape[0], s.shape[1]
 
 
-def solve_nister5(samples: torch.Tensor, weights: Optional[torch.Tensor] = None, path: int = 0):
+def _solver_gate(gate, s: torch.Tensor, n: int):
+    """gate = (RansacState, rows per pair) of solve_nister5 / solve_stewenius5 -> (rows per pair, state), (0, None) without one"""
+    if gate is None:
+        return 0, None
+    if n != 5 or s.dtype != torch.float32:
+        raise L.DransacError("the gated five-point entries take f32 minimal samples")
+    return int(gate[1]), gate[0]
+
+
+def solve_nister5(samples: torch.Tensor, weights: Optional[torch.Tensor] = None, path: int = 0, gate=None):
     """samples [..., n>=5, 4] -> models [..., 10, 3, 3], valid [..., 10] bool (real solutions, ascending root).
-    path (f32 minimal samples only): 0 automatic, 1 lane-pair kernel, 2 two-phase kernel (include/dransac.h)."""
+    path (f32 minimal samples only): 0 automatic, 1 lane-pair kernel, 2 two-phase kernel (include/dransac.h).
+    gate = (RansacState, rows per pair), f32 minimal samples [P,B,5,4] of a later round of a multi-round test-mode call: the blocks
+    of pairs that have terminated (iters >= max_iters) return at once and leave their part of the outputs unwritten --
+    dr_ransac_update never looks at it."""
     s, Bt, n = _flat_samples(samples, 4)
     lead = samples.shape[:-2]
     models = torch.empty((Bt, 10, 3, 3), device=s.device, dtype=s.dtype)
@@ -477,9 +495,10 @@ def solve_nister5(samples: torch.Tensor, weights: Optional[torch.Tensor] = None,
     w = None if weights is None else weights.reshape(Bt, n).to(s.dtype).contiguous()
     if path != 0 and (n != 5 or s.dtype != torch.float32):
         raise L.DransacError("an explicit five-point kernel path exists for f32 minimal samples only")
+    rows, st = _solver_gate(gate, s, n)
     if s.dtype == torch.float32:
-        L.call("dr_solve_nister5_f32", ptr(s), ptr(w), c_int(Bt), c_int(n), ptr(models), ptr(None), ptr(valid), c_int(path), c_int(0),
-               ptr(None), ptr(None), stream())
+        L.call("dr_solve_nister5_f32", ptr(s), ptr(w), c_int(Bt), c_int(n), ptr(models), ptr(None), ptr(valid), c_int(path), c_int(rows),
+               *_gate_args(st), stream())
     else:
         L.call(f"dr_solve_nister5_{L.suffix(s.dtype)}", ptr(s), ptr(w), c_int(Bt), c_int(n), ptr(models), ptr(valid), stream())
     return models.reshape(*lead, 10, 3, 3), valid.reshape(*lead, 10)
@@ -501,20 +520,9 @@ def solve_nister5_hp(samples: torch.Tensor, weights: Optional[torch.Tensor] = No
 
 
 def solve_essential_gated(samples: torch.Tensor, which: str, gate):
-    """A later round of a multi-round test-mode call: samples [P,B,5,4] f32 -> (models [P,B,10,3,3], valid [P,B,10]); the
-    blocks of pairs that have terminated (gate = RansacState: iters >= max_iters) return at once and leave their part of the
-    outputs unwritten -- dr_ransac_update never looks at it (the gate arguments of dr_solve_nister5_f32 / dr_solve_stewenius5_f32)."""
-    P, B = samples.shape[0], samples.shape[1]
-    s = samples.reshape(P * B, 5, 4).contiguous()
-    models = torch.empty((P * B, 10, 3, 3), device=s.device, dtype=torch.float32)
-    valid = torch.empty((P * B, 10), device=s.device, dtype=torch.bool)
-    if which == "nister":
-        L.call("dr_solve_nister5_f32", ptr(s), ptr(None), c_int(P * B), c_int(5), ptr(models), ptr(None), ptr(valid), c_int(0), c_int(B),
-               ptr(gate.iters), ptr(gate.max_iters), stream())
-    else:
-        L.call("dr_solve_stewenius5_f32", ptr(s), c_int(P * B), ptr(models), ptr(valid), c_int(0), c_int(B), ptr(gate.iters),
-               ptr(gate.max_iters), stream())
-    return models.reshape(P, B, 10, 3, 3), valid.reshape(P, B, 10)
+    """A later round of a multi-round test-mode call: samples [P,B,5,4] f32 -> (models [P,B,10,3,3], valid [P,B,10]), the pairs
+    that have terminated (gate = RansacState) skipped: solve_nister5 / solve_stewenius5 with `gate=`."""
+    return (solve_nister5 if which == "nister" else solve_stewenius5)(samples, gate=(gate, samples.shape[1]))
 
 
 def debug_real_roots10(coef: torch.Tensor, method: int = 1):
@@ -528,8 +536,8 @@ def debug_real_roots10(coef: torch.Tensor, method: int = 1):
     return roots, counts
 
 
-def solve_stewenius5(samples: torch.Tensor, path: int = 0):
-    """samples [..., 5, 4] -> models [..., 10, 3, 3], valid [..., 10].  path: as solve_nister5 (f32 only)."""
+def solve_stewenius5(samples: torch.Tensor, path: int = 0, gate=None):
+    """samples [..., 5, 4] -> models [..., 10, 3, 3], valid [..., 10].  path, gate: as solve_nister5 (f32 only)."""
     s, Bt, n = _flat_samples(samples, 4)
     if n != 5:
         raise L.DransacError("the Stewenius solver takes exactly 5 correspondences per sample")
@@ -538,8 +546,9 @@ def solve_stewenius5(samples: torch.Tensor, path: int = 0):
     valid = torch.empty((Bt, 10), device=s.device, dtype=torch.bool)
     if path != 0 and s.dtype != torch.float32:
         raise L.DransacError("an explicit five-point kernel path exists for f32 minimal samples only")
+    rows, st = _solver_gate(gate, s, n)
     if s.dtype == torch.float32:
-        L.call("dr_solve_stewenius5_f32", ptr(s), c_int(Bt), ptr(models), ptr(valid), c_int(path), c_int(0), ptr(None), ptr(None), stream())
+        L.call("dr_solve_stewenius5_f32", ptr(s), c_int(Bt), ptr(models), ptr(valid), c_int(path), c_int(rows), *_gate_args(st), stream())
     else:
         L.call(f"dr_solve_stewenius5_{L.suffix(s.dtype)}", ptr(s), c_int(Bt), ptr(models), ptr(valid), stream())
     return models.reshape(*lead, 10, 3, 3), valid.reshape(*lead, 10)
@@ -565,9 +574,8 @@ def solve_f8_uniform(matches: torch.Tensor, B: int, seed):
     idx = torch.empty((P, B, 8), device=matches.device, dtype=torch.int32)
     models = torch.empty((P, B, 3, 3), device=matches.device, dtype=torch.float32)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    ds = _dev_seed(seed)
-    L.call("dr_solve_f8_uniform_f32", ptr(matches.contiguous()), c_uint64(0 if ds else seed & (2 ** 64 - 1)), ptr(seed if ds else None),
-           c_int(P), c_int(B), c_int(N), ptr(idx), ptr(models), ptr(valid), stream())
+    L.call("dr_solve_f8_uniform_f32", ptr(matches.contiguous()), *_seed_args(seed), c_int(P), c_int(B), c_int(N), ptr(idx),
+           ptr(models), ptr(valid), stream())
     return idx, models, valid
 
 
@@ -650,9 +658,8 @@ def ransac3d_update(pts: torch.Tensor, models: torch.Tensor, valid: Optional[tor
     out_res = torch.empty((P,), device=pts.device, dtype=pts.dtype)
     out_model = torch.empty((P, 4, 4), device=pts.device, dtype=pts.dtype)
     idx = torch.empty((P,), device=pts.device, dtype=torch.int32)
-    v = None if valid is None else valid.contiguous().view(torch.uint8)
     mk = None if best_mask is None else best_mask.view(torch.uint8)
-    L.call(f"dr_ransac3d_update_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()), ptr(v),
+    L.call(f"dr_ransac3d_update_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(res.contiguous()), L.scalar(pts.dtype, threshold), c_int(P), c_int(M), c_int(N),
            ptr(None if best_res is None else best_res.contiguous()), ptr(None if best_model is None else best_model.contiguous()),
            ptr(out_res), ptr(out_model), ptr(mk), ptr(idx), stream())
@@ -665,9 +672,8 @@ def select_closest(models: torch.Tensor, valid: Optional[torch.Tensor], gt: torc
     P, B, S = models.shape[:3]
     chosen = torch.empty((P, B, 3, 3), device=models.device, dtype=models.dtype)
     which = torch.empty((P, B), device=models.device, dtype=torch.int32)
-    v = None if valid is None else valid.contiguous().view(torch.uint8)
     keep = torch.empty((P, B), device=models.device, dtype=torch.bool) if want_keep else None
-    L.call(f"dr_select_closest_{L.suffix(models.dtype)}", ptr(models.contiguous()), ptr(v),
+    L.call(f"dr_select_closest_{L.suffix(models.dtype)}", ptr(models.contiguous()), _u8_ptr(valid),
            ptr(gt.to(models.dtype).contiguous()), c_int(P), c_int(B), c_int(S), ptr(chosen), ptr(which), ptr(keep), stream())
     return (chosen, which, keep) if want_keep else (chosen, which)
 
@@ -678,8 +684,7 @@ def refit_essential(matches: torch.Tensor, mask: Optional[torch.Tensor] = None):
     P, N, _ = matches.shape
     models = torch.empty((P, 10, 3, 3), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, 10), device=matches.device, dtype=torch.bool)
-    mk = None if mask is None else mask.contiguous().view(torch.uint8)
-    L.call(f"dr_refit_essential_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(mk), c_int(P), c_int(N),
+    L.call(f"dr_refit_essential_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask), c_int(P), c_int(N),
            ptr(models), ptr(valid), stream())
     return models, valid
 
@@ -690,9 +695,8 @@ def refit_accept(matches: torch.Tensor, cand: torch.Tensor, cand_valid: Optional
     [P,3,3] IN PLACE where a candidate scores strictly higher (ransac.py:173-185)."""
     P, N, _ = matches.shape
     S = cand.shape[1]
-    cv = None if cand_valid is None else cand_valid.contiguous().view(torch.uint8)
-    L.call(f"dr_refit_accept_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(cand.contiguous()), ptr(cv), ptr(thr),
-           c_int(P), c_int(S), c_int(N), ptr(best_score), ptr(best_model), stream())
+    L.call(f"dr_refit_accept_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(cand.contiguous()), _u8_ptr(cand_valid),
+           ptr(thr), c_int(P), c_int(S), c_int(N), ptr(best_score), ptr(best_model), stream())
 
 
 def refit_fundamental(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
@@ -701,10 +705,9 @@ def refit_fundamental(matches: torch.Tensor, mask: Optional[torch.Tensor] = None
     P, N, _ = matches.shape
     models = torch.empty((P, 3, 3), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
-    mk = None if mask is None else mask.contiguous().view(torch.uint8)
     if weights is not None and weights.shape != (P, N):
         raise L.DransacError("refit weights are [P,N], one per point")
-    L.call(f"dr_refit_fundamental_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(mk),
+    L.call(f"dr_refit_fundamental_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
            ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(models), ptr(valid),
            stream())
     return models, valid
@@ -754,7 +757,7 @@ class _SolveEssential(torch.autograd.Function):
             # `-pr 2 -tr 1`, round 5: f64 samples, models and gradients straight through (dr_solve_nister5_bwd_f64)
             s, Bt, n = _flat_samples(samples, 4)
             gs = torch.empty_like(s)
-            L.call("dr_solve_nister5_bwd_f64", ptr(s), ptr(models.contiguous()), ptr(valid.contiguous().view(torch.uint8)),
+            L.call("dr_solve_nister5_bwd_f64", ptr(s), ptr(models.contiguous()), _u8_ptr(valid),
                    ptr(g_models.to(torch.float64).contiguous()), c_int(Bt), ptr(gs), stream())
             return gs.reshape(samples.shape), None, None
         if f64:
@@ -765,7 +768,7 @@ class _SolveEssential(torch.autograd.Function):
             w = ctx.weights
             gw = None if w is None or not ctx.needs_input_grad[1] else torch.empty((Bt, n), device=s.device, dtype=torch.float64)
             L.call("dr_solve_nister5_nm_bwd_f64", ptr(s), ptr(None if w is None else w.reshape(Bt, n).double().contiguous()),
-                   ptr(models.contiguous()), ptr(valid.contiguous().view(torch.uint8)), ptr(g_models.to(torch.float64).contiguous()),
+                   ptr(models.contiguous()), _u8_ptr(valid), ptr(g_models.to(torch.float64).contiguous()),
                    c_int(Bt), c_int(n), ptr(gs), ptr(gw), stream())
             return gs.reshape(samples.shape), (None if gw is None else gw.reshape(w.shape).to(w.dtype)), None
         s, Bt, n = _flat_samples(samples, 4)
@@ -777,12 +780,12 @@ class _SolveEssential(torch.autograd.Function):
             gw = None if w is None or not ctx.needs_input_grad[1] else torch.empty((Bt, n), device=s.device, dtype=torch.float32)
             L.call("dr_solve_nister5_nm_bwd_f32", ptr(s), ptr(None if w is None else w.reshape(Bt, n).float().contiguous()),
                    ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None),
-                   ptr(valid.contiguous().view(torch.uint8)), ptr(g_models.contiguous()), c_int(Bt), c_int(n), ptr(gs), ptr(gw),
+                   _u8_ptr(valid), ptr(g_models.contiguous()), c_int(Bt), c_int(n), ptr(gs), ptr(gw),
                    stream())
             gs = gs.reshape(samples.shape)
             return (gs.double() if f64 else gs), (None if gw is None else gw.reshape(w.shape).to(w.dtype)), None
         L.call("dr_solve_nister5_bwd_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None),
-               ptr(valid.contiguous().view(torch.uint8)), ptr(g_models.contiguous()), c_int(Bt), ptr(gs), stream())
+               _u8_ptr(valid), ptr(g_models.contiguous()), c_int(Bt), ptr(gs), stream())
         gs = gs.reshape(samples.shape)
         return (gs.double() if f64 else gs), None, None
 
@@ -821,7 +824,7 @@ class _SolveSelectEssential(torch.autograd.Function):
         s, Bt, _ = _flat_samples(samples, 4)
         gs = torch.empty_like(s)
         L.call("dr_solve_nister5_bwd_sel_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous()),
-               ptr(valid.contiguous().view(torch.uint8)), ptr(g_chosen.contiguous()), ptr(which.contiguous()), c_int(Bt),
+               _u8_ptr(valid), ptr(g_chosen.contiguous()), ptr(which.contiguous()), c_int(Bt),
                ptr(gs), stream())
         return gs.reshape(samples.shape), None, None
 
@@ -986,17 +989,23 @@ def select_closest_autograd(models, valid, gt, want_keep: bool = False):
 
 
 # ------------------------------------------------------------------------------------------ MatchLoss residual (8(f) rank 2)
+def _episym_fwd(matches, mask, models, valid):
+    """dr_episym_fwd_f32, the first launch of the three nodes below -> (matches, models: contiguous; mask, valid: as bytes or None;
+    sums [P,M]: every slot is written, an invalid one with 0)"""
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    matches, models = matches.contiguous(), models.contiguous()
+    mk, v = _u8(mask), _u8(valid)
+    sums = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
+    L.call("dr_episym_fwd_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), c_int(P), c_int(M), c_int(N), ptr(sums), stream())
+    return matches, models, mk, v, sums
+
+
 class _EpisymSums(torch.autograd.Function):
     @staticmethod
     def forward(ctx, matches, mask, models, valid):
         ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
-        P, N, _ = matches.shape
-        M = models.shape[1]
-        sums = torch.empty((P, M), device=matches.device, dtype=matches.dtype)   # every slot is written (invalid: 0)
-        mk = None if mask is None else mask.contiguous().view(torch.uint8)
-        v = None if valid is None else valid.contiguous().view(torch.uint8)
-        L.call("dr_episym_fwd_f32", ptr(matches.contiguous()), ptr(mk), ptr(models.contiguous()), ptr(v), c_int(P), c_int(M),
-               c_int(N), ptr(sums), stream())
+        _, _, mk, v, sums = _episym_fwd(matches, mask, models, valid)
         ctx.save_for_backward(matches, models)
         ctx.aux = (mk, v)
         return sums
@@ -1029,14 +1038,8 @@ class _MatchLossPair(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, matches, mask, models, keep):
-        P, N, _ = matches.shape
-        M = models.shape[1]
-        matches, models = matches.contiguous(), models.contiguous()
-        mk = None if mask is None else mask.contiguous().view(torch.uint8)
-        v = None if keep is None else keep.contiguous().view(torch.uint8)
-        sums = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
-        L.call("dr_episym_fwd_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), c_int(P), c_int(M), c_int(N), ptr(sums),
-               stream())
+        matches, models, mk, v, sums = _episym_fwd(matches, mask, models, keep)
+        (P, N, _), M = matches.shape, models.shape[1]
         per_pair = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         coef = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         L.call("dr_match_loss_pair_f32", ptr(sums), ptr(mk), ptr(v), c_int(P), c_int(M), c_int(N), ptr(per_pair), ptr(coef),
@@ -1066,14 +1069,8 @@ class _MatchLossMean(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, matches, mask, models, keep):
-        P, N, _ = matches.shape
-        M = models.shape[1]
-        matches, models = matches.contiguous(), models.contiguous()
-        mk = None if mask is None else mask.contiguous().view(torch.uint8)
-        v = None if keep is None else keep.contiguous().view(torch.uint8)
-        sums = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
-        L.call("dr_episym_fwd_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), c_int(P), c_int(M), c_int(N), ptr(sums),
-               stream())
+        matches, models, mk, v, sums = _episym_fwd(matches, mask, models, keep)
+        (P, N, _), M = matches.shape, models.shape[1]
         per_pair = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         coef = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         mean = torch.empty((), device=matches.device, dtype=matches.dtype)
@@ -1107,8 +1104,7 @@ class _MatchLossFused(torch.autograd.Function):
         P, N, _ = matches.shape
         M = models.shape[1]
         matches, models = matches.contiguous(), models.contiguous()
-        mk = None if mask is None else mask.contiguous().view(torch.uint8)
-        v = None if keep is None else keep.contiguous().view(torch.uint8)
+        mk, v = _u8(mask), _u8(keep)
         dev, dt = matches.device, matches.dtype
         sums = torch.empty((P, M), device=dev, dtype=dt)
         gun = torch.empty((P, M, 3, 3), device=dev, dtype=dt)
@@ -1146,9 +1142,6 @@ def match_loss_mean(matches, mask, models, keep=None):
     if matches.shape[0] > 64:
         return match_loss_per_pair(matches, mask, models, keep).mean()
     return _MatchLossMean.apply(matches, mask, models, keep)
-
-
-FUSED_MATCH_LOSS = True   # tests / A-B runs: False = the two-pass form of rounds 3-4
 
 
 def _match_loss_mean_f64(matches, mask, models, keep, chunk: int = 256):

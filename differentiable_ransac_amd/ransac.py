@@ -10,14 +10,14 @@ from __future__ import annotations
 
 import collections
 import math
+import os as _os
+import types
 from typing import Dict
 
 import torch
 
 from . import ops
 
-
-import os as _os
 _FOLD_SETUP = _os.environ.get("DRANSAC_FOLD_SETUP", "1") != "0"   # A/B: 0 = seed launch and result gather as separate nodes (round 5)
 
 
@@ -106,7 +106,7 @@ class RANSAC(object):
         self._fast_cfg = None
         self._graphs = collections.OrderedDict()
         if lo not in (0, 1, 2):
-            # lo=3, the inner RANSAC of ransac.py:258-299, never ran in the reference (its UniformSampler call raises TypeError)
+            # any other value, not only the 3 _check_lo names, is "not implemented" for the drop-in class (BatchedRANSAC: ValueError)
             raise NotImplementedError(f"lo={lo!r}: only lo=1 (one LSQ refit on the inliers) and lo=2 (iterated refits) are "
                                       "implemented; lo=3 (inner RANSAC) never ran in the reference either (SURVEY Q2)")
         _check_lo(lo, lo_iters)
@@ -478,7 +478,49 @@ class RANSAC3D(object):
         return best_model, residuals, mean_residuals, best_score, iterations
 
 
-class BatchedRANSAC(object):
+class _Seeds(object):
+    """The per-call sampler seeds of a batched driver: call number c of a driver with base seed s draws with the key
+    s * 0x9E3779B97F4A7C15 + c (mod 2^64), from the host formula or, after on_device(), from a counter on the device
+    (ops.DeviceSeed: graph-capturable steps) -- the same sequence either way."""
+
+    def __init__(self, seed):
+        self.seed, self.calls = seed, 0
+        self.dev = None          # ops.DeviceSeed
+        self.ahead = None        # (block, position): seeds drawn ahead for every batch of a call by ONE launch (device_termination)
+
+    def on_device(self, device):
+        self.dev = ops.DeviceSeed(self.seed, device, self.calls)
+
+    def next(self, R=1):
+        """the seed of the next batch.  R > 1: of the next batch of a device round of R batches; the R - 1 batches behind it take the
+        consecutive seeds (consumed here: a batch-by-batch driver with the same base seed draws the same hypotheses)"""
+        first = self.calls
+        self.calls += R
+        if self.dev is None:
+            return (self.seed * 0x9E3779B97F4A7C15 + first) & (2 ** 64 - 1)
+        if self.ahead is not None:
+            blk, pos = self.ahead
+            self.ahead = (blk, pos + R) if pos + R < blk.shape[0] else None
+            return blk[pos:pos + 1]
+        return self.dev.next() if R == 1 else self.dev.next_block(R)[:1]
+
+
+class _SeededDriver(object):
+    """`seed`, `calls` (assignable between calls), `_dev_seed` and device_seeds() of the batched drivers, kept in one _Seeds"""
+    seed = property(lambda self: self._seeds.seed, lambda self, v: setattr(self._seeds, "seed", v))
+    calls = property(lambda self: self._seeds.calls, lambda self, v: setattr(self._seeds, "calls", v))
+    _dev_seed = property(lambda self: self._seeds.dev)
+
+    def device_seeds(self, device):
+        """From the next call on the per-call seed is computed on the device (ops.DeviceSeed) -- the same sequence of seeds,
+        hence the same hypotheses, but nothing about a call depends on a host-side counter any more, so a call with
+        max_iterations <= ransac_batch_size (one round, no read-back) can be captured in a HIP graph and replayed
+        (differentiable_ransac_amd.graphs.GraphedStep)."""
+        self._seeds.on_device(device)
+        return self
+
+
+class BatchedRANSAC(_SeededDriver):
     """The (pair x hypothesis) grid in one go: all P pairs sample, solve, score and select per round with a fixed
     number of launches (K1, K2, K3, K4, K6) and no [B,N] / [M,N] tensor in HBM unless `keep_masks` is set.
 
@@ -534,8 +576,7 @@ class BatchedRANSAC(object):
         self.confidence = confidence
         self.max_iterations = max_iterations
         self.tau = tau
-        self.seed = seed
-        self.calls = 0
+        self._seeds = _Seeds(seed)
         self.weighted = weighted
         self.keep_masks = keep_masks
         self.refit = refit
@@ -544,8 +585,6 @@ class BatchedRANSAC(object):
         self._race_ws = None     # per-call weights of the one-logarithm sampler (written by dr_ransac_init, read by every round)
         self._side = None
         self._gap = None         # scratch word of the one-launch dispatch gap in front of the sampler (see __call__)
-        self._dev_seed = None
-        self._seed_queue = []
         # Super-rounds (round 6, test mode).  The loop of ransac.py:55-144 runs `ransac_batch_size` hypotheses per iteration of a
         # Python loop; with the reference's default of 64 a call is up to 79 iterations of four launches each.  A DEVICE round here is
         # R consecutive batches at once: the sampler draws row b of the round with the noise of row b % B of batch b // B (per-call
@@ -555,34 +594,6 @@ class BatchedRANSAC(object):
         # entry repeated; None = automatic: rounds of 1024 hypotheses when ransac_batch_size is below 1024,
         # one batch per round otherwise; False = always one batch per round (the host loop of rounds 1-5).
         self.super_hypotheses = None
-
-    def _next_seed(self):
-        if self._dev_seed is not None:       # seeds advanced on the device (device_seeds(): graph-capturable steps)
-            self.calls += 1
-            if self._seed_queue:             # drawn ahead for every batch of this call by ONE launch (device_termination)
-                blk, pos = self._seed_queue
-                self._seed_queue = (blk, pos + 1) if pos + 1 < blk.shape[0] else []
-                return blk[pos:pos + 1]
-            return self._dev_seed.next()
-        s = (self.seed * 0x9E3779B97F4A7C15 + self.calls) & (2 ** 64 - 1)
-        self.calls += 1
-        return s
-
-    def _next_seeds(self, R):
-        """the seed of the next batch of a device round of R batches; the R - 1 batches behind it take the consecutive seeds
-        (consumed here: a batch-by-batch driver with the same base seed draws the same hypotheses)"""
-        if R == 1:
-            return self._next_seed()
-        if self._dev_seed is not None:
-            self.calls += R
-            if self._seed_queue:
-                blk, pos = self._seed_queue
-                self._seed_queue = (blk, pos + R) if pos + R < blk.shape[0] else []
-                return blk[pos:pos + 1]
-            return self._dev_seed.next_block(R)[:1]
-        s = (self.seed * 0x9E3779B97F4A7C15 + self.calls) & (2 ** 64 - 1)
-        self.calls += R
-        return s
 
     def plan(self, n_batches=None, dtype=torch.float32):
         """Batches per device round of a test-mode call (see `super_hypotheses`): a list summing to the number of batches the loop
@@ -614,87 +625,61 @@ class BatchedRANSAC(object):
             left -= r
         return out
 
-    def device_seeds(self, device):
-        """From the next call on the per-call seed is computed on the device (ops.DeviceSeed) -- the same sequence of seeds,
-        hence the same hypotheses, but nothing about a call depends on a host-side counter any more, so a call with
-        max_iterations <= ransac_batch_size (one round, no read-back) can be captured in a HIP graph and replayed
-        (differentiable_ransac_amd.graphs.GraphedStep)."""
-        self._dev_seed = ops.DeviceSeed(self.seed, device, self.calls)
-        return self
-
     def hypotheses(self, matches, logits, gumbels=None):
         """matches [P,N,4], logits [P,N] -> models [P,B,S,3,3], valid [P,B,S], idx [P,B,k] (differentiable w.r.t. logits)."""
         return self._hypotheses(matches, logits, gumbels)[:3]
+
+    def _solve(self, samples, weights=None, gate=None):
+        """samples [P,B,k,c] -> models [P,B,S,3,3], valid [P,B,S].  gate (a later round of a device-terminated call): the gated
+        five-point entry, for minimal f32 samples."""
+        if self.solver in ("nister", "stewenius"):
+            if gate is not None and self.k == 5 and samples.dtype == torch.float32:
+                return ops.solve_essential_gated(samples, self.solver, gate)
+            return ops.solve_essential(samples, weights, self.solver)
+        if self.solver == "f8":
+            F, v = ops.solve_fundamental8(samples, weights)
+            return F.unsqueeze(2), v.unsqueeze(2)
+        return ops.solve_f7(samples)
 
     def _hypotheses(self, matches, logits, gumbels=None, gate=None, R=1):
         """hypotheses() + the (seed, noise) pair of the draw when the weighted refit will need row 0's soft weights again
         (returned, not stashed on self: two rounds are in flight on two streams when `pipeline` is on), else None.
         R > 1 (test mode, see `super_hypotheses`): R consecutive batches in one go -> models [P, R * B, S, 3, 3]; explicit noise is the
         R batches' tensors concatenated along the hypothesis axis."""
-        if R > 1:
-            Bq = R * self.B
-            if gumbels is None and matches.dtype == torch.float32 and logits.dtype == torch.float32 and matches.shape[-1] == 4:
-                idx, samples = ops.gumbel_topk_gather(matches, logits, Bq, self.k, self.tau, self._next_seeds(R), gate=gate, sub=self.B,
-                                                      race_ws=self._race_ws)
-            else:
-                if gumbels is None:
-                    raise ValueError("super-rounds with in-kernel noise serve f32 two-view correspondences (plan() says so)")
-                idx = ops.gumbel_topk(logits, Bq, self.k, self.tau, gumbels, self._next_seeds(R), soft=False)["idx"]
-                samples = ops.gather(matches, idx)
-            if self.solver in ("nister", "stewenius"):
-                if gate is not None and self.k == 5 and samples.dtype == torch.float32:
-                    models, valid = ops.solve_essential_gated(samples, self.solver, gate)
-                else:
-                    models, valid = ops.solve_essential(samples, None, self.solver)
-            elif self.solver == "f8":
-                F, v = ops.solve_fundamental8(samples, None)
-                models, valid = F.unsqueeze(2), v.unsqueeze(2)
-            else:
-                models, valid = ops.solve_f7(samples)
-            return models, valid, idx, None
-        if self.weighted and self.solver == "f8" and not self.train and self.refit:
-            # the weighted LSQ refit (ransac.py:151-153) needs y_soft of hypothesis 0 of the LAST batch a pair ran: the seed is
-            # handed back so that __call__ can re-draw that one row (ops.soft_weights_row0).  weighted=1 implies the Gumbel
-            # sampler (__init__ refuses it with 'uniform' / 'topdown')
-            seed = self._next_seed()
-            samples, w, idx = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, gumbels, seed)
-            F, v = ops.solve_fundamental8(samples, w)
-            return F.unsqueeze(2), v.unsqueeze(2), idx, (seed, gumbels)
-        if (self.sampling == "uniform" and gumbels is None and self.solver == "f8" and self.k == 8
-                and matches.dtype == torch.float32 and matches.shape[-1] == 4):
-            # sampler + gather + 8-point solve in ONE launch (BASELINE configs[0] is launch-bound: six launches -> four)
-            idx, F, v = ops.solve_f8_uniform(matches, self.B, self._next_seed())
-            return F.unsqueeze(2), v.unsqueeze(2), idx, None
+        B, w, row0, solve_gate = R * self.B, None, None, None
+        f32_two_view = matches.dtype == torch.float32 and matches.shape[-1] == 4
         if self.sampling == "uniform" and gumbels is None:
-            idx = ops.uniform_sample(matches.shape[0], self.B, self.k, matches.shape[1], self._next_seed(), matches.device)
-            samples, w = ops.gather(matches, idx), None
+            if self.solver == "f8" and self.k == 8 and f32_two_view:
+                # sampler + gather + 8-point solve in ONE launch (BASELINE configs[0] is launch-bound: six launches -> four)
+                idx, F, v = ops.solve_f8_uniform(matches, B, self._seeds.next())
+                return F.unsqueeze(2), v.unsqueeze(2), idx, None
+            idx = ops.uniform_sample(matches.shape[0], B, self.k, matches.shape[1], self._seeds.next(), matches.device)
+            samples = ops.gather(matches, idx)
         elif self.sampling == "topdown" and gumbels is None:
-            idx = ops.topdown_sample(logits, self.B, self.k, self._next_seed())
-            samples, w = ops.gather(matches, idx), None
-        elif not self.train and not self.weighted:
-            # test mode consumes the index sets only (`points[samples != 0]`, ransac.py:65): no soft-max statistics, and
-            # the samples are the points themselves (not points x a straight-through value of 1 +- 1 ulp)
-            if gumbels is None and matches.dtype == torch.float32 and logits.dtype == torch.float32 and matches.shape[-1] == 4:
-                idx, samples = ops.gumbel_topk_gather(matches, logits, self.B, self.k, self.tau, self._next_seed(), gate=gate,
-                                                      race_ws=self._race_ws)   # one launch
-                w = None
-                if gate is not None and self.solver in ("nister", "stewenius") and self.k == 5:
-                    models, valid = ops.solve_essential_gated(samples, self.solver, gate)
-                    return models, valid, idx, None
-            else:
-                idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, gumbels, self._next_seed(), soft=False)["idx"]
-                samples, w = ops.gather(matches, idx), None
+            idx = ops.topdown_sample(logits, B, self.k, self._seeds.next())
+            samples = ops.gather(matches, idx)
+        elif self.train or self.weighted:
+            seed = self._seeds.next()
+            samples, w, idx = ops.SampleGather.apply(matches, logits, B, self.k, self.tau, gumbels, seed)
+            if self.weighted and self.solver == "f8" and not self.train and self.refit:
+                # the weighted LSQ refit (ransac.py:151-153) needs y_soft of hypothesis 0 of the LAST batch a pair ran: the seed is
+                # handed back so that __call__ can re-draw that one row (ops.soft_weights_row0).  weighted=1 implies the Gumbel
+                # sampler (__init__ refuses it with 'uniform' / 'topdown'); the 7-point solver takes no weights
+                row0 = (seed, gumbels)
+        # test mode consumes the index sets only (`points[samples != 0]`, ransac.py:65): no soft-max statistics, and the samples are
+        # the points themselves (not points x a straight-through value of 1 +- 1 ulp)
+        elif gumbels is None and f32_two_view and logits.dtype == torch.float32:
+            idx, samples = ops.gumbel_topk_gather(matches, logits, B, self.k, self.tau, self._seeds.next(R), gate=gate,
+                                                  sub=self.B if R > 1 else 0, race_ws=self._race_ws)   # one launch
+            solve_gate = gate
         else:
-            samples, w, idx = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, gumbels, self._next_seed())
-        wts = w if self.weighted else None
-        if self.solver in ("nister", "stewenius"):
-            models, valid = ops.solve_essential(samples, wts, self.solver)
-        elif self.solver == "f8":
-            F, v = ops.solve_fundamental8(samples, wts)
-            models, valid = F.unsqueeze(2), v.unsqueeze(2)
-        else:
-            models, valid = ops.solve_f7(samples)
-        return models, valid, idx, None
+            if gumbels is None and R > 1:
+                raise ValueError("super-rounds with in-kernel noise serve f32 two-view correspondences (plan() says so)")
+            idx = ops.gumbel_topk(logits, B, self.k, self.tau, gumbels, self._seeds.next(R), soft=False)["idx"]
+            samples = ops.gather(matches, idx)
+            solve_gate = gate if R > 1 else None      # (one batch per round: ungated as found, docs/LOG.md)
+        models, valid = self._solve(samples, w if self.weighted else None, solve_gate)
+        return models, valid, idx, row0
 
     def __call__(self, matches, logits, K1=None, K2=None, gt_model=None, gumbels=None):
         P, N, _ = matches.shape
@@ -710,7 +695,7 @@ class BatchedRANSAC(object):
                     # the training path proper (train mode implies the Gumbel sampler: __init__ refuses the index-only samplings):
                     # sampler + gather, then solver + best-of-ten as ONE autograd node whose backward
                     # takes the gradient of the chosen model in sparse form (ops.solve_select_essential)
-                    samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._next_seed())
+                    samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
                     chosen, _, keep, _, _ = ops.solve_select_essential(samples, gt_model)
                     out.append((chosen, keep))
                     continue
@@ -729,34 +714,25 @@ class BatchedRANSAC(object):
             return torch.cat([c for c, _ in out], dim=1), torch.cat([k for _, k in out], dim=1)
 
         with torch.no_grad():
-            # threshold normalisation (ransac.py:49-53) + per-pair state in one launch
             use_K = K1 is not None and not self.fmat
-            all_masks = None
             matches = matches.contiguous()
-            # The essential-matrix refit candidate (Nister on ALL points, ransac.py:157-165) depends on the matches only:
-            # it is issued on a side stream and joins before the final scoring -- and it is issued FIRST, before the state set-up
-            # (round 5): a refit block wants a whole SIMD's registers and 38.9 KB of LDS on its CU, and once the sampler's 32 768
-            # light workgroups are in the queue it does not get them until the sampler's grid runs dry (measured at 128 pairs:
-            # launched 6 us after the sampler it ran 15 -> 241 us for 52 us of work, and the solver behind it started 56 us late
-            # on the SIMDs it held).
-            pre = None
-            # device rounds (see `super_hypotheses`): plan[i] batches of B hypotheses in round i
+            # device rounds (see `super_hypotheses`): plan[i] batches of B hypotheses in round i, the first of them batch first[i]
             n_batches = rounds if gumbels is None else min(rounds, len(gumbels))
             plan = self.plan(n_batches, dt) if n_batches > 0 else []
-            first = [sum(plan[:i]) for i in range(len(plan))]         # index of the first batch of device round i
+            first = [sum(plan[:i]) for i in range(len(plan))]
             rounds = len(plan)
-
-            def issue_refit():
+            # The essential-matrix refit candidate (Nister on ALL points, ransac.py:157-165) depends on the matches only: it is issued
+            # on a side stream and joins before the final scoring -- and it is issued FIRST, before the state set-up (round 5; see the
+            # note on dispatch order below).
+            pre = None
+            if self.refit and not self.fmat:
                 if self._side is None:
                     self._side = torch.cuda.Stream(device=dev)
                 self._side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(self._side):
-                    out_ = ops.refit_essential(matches)
+                    pre = ops.refit_essential(matches)
                     if not torch.cuda.is_current_stream_capturing():
                         matches.record_stream(self._side)
-                return out_
-            if self.refit and not self.fmat:
-                pre = issue_refit()
             # (device termination with device seeds: the keys of all batches of the call come out of the set-up launch; one pair in
             #  f32: the state lives in one buffer, which is what the replayed drop-in call hands out)
             draw = self.device_termination and self._dev_seed is not None and n_batches > 1 and gumbels is None
@@ -767,107 +743,75 @@ class BatchedRANSAC(object):
                     and logits.dtype == torch.float32 and matches.shape[-1] == 4
                     and ops.race_form_pays(P, self.B * plan[0], N, self.tau)):
                 race_lg = logits.contiguous()
+            # threshold normalisation (ransac.py:49-53) + per-pair state in one launch
             st, thr = ops.ransac_init(P, N, self.max_iterations, self.threshold, K1 if use_K else None,
                                       K2 if use_K else None, dev, dt, seeds=(self._dev_seed, n_batches) if fold else None,
                                       packed=_FOLD_SETUP and self.device_termination and P == 1, race_logits=race_lg)
             self._race_ws = st.race_ws
-            lo_seen = lo_refits = None
+            # what every round of the call works on (_round, _finish): state, inputs, the masks of the last round (keep_masks) and,
+            # for the weighted refit, per pair the row-0 soft weights of the last batch it ran
+            c = types.SimpleNamespace(st=st, thr=thr, matches=matches, logits=logits, plan=plan, pre=pre, all_masks=None,
+                                      lo_seen=None, lo_refits=None, last_w=None)
             if self.lo:
                 # the local optimisation's per-pair snapshot of (best_score, best_model) -- NaN: the first replacement is always
                 # seen -- and its refit counters (capturable allocations: a replayed call re-fills them)
-                lo_seen = torch.full((P, 10), float("nan"), device=dev, dtype=dt)
-                lo_refits = torch.zeros(P, device=dev, dtype=torch.int32)
+                c.lo_seen = torch.full((P, 10), float("nan"), device=dev, dtype=dt)
+                c.lo_refits = torch.zeros(P, device=dev, dtype=torch.int32)
             if draw and not fold:
                 st.seeds = self._dev_seed.next_block(n_batches)
             if pre is not None and plan and P * self.B * plan[0] >= 65536:
                 # Dispatch order (round 5): a refit block wants a whole SIMD's registers and 38.9 KB of LDS on its CU; once the
-                # sampler's 32 768 light workgroups are in the queue it does not get them until the sampler's grid runs dry.
-                # The refit waits for this stream's earlier work through an event and lost that race by half a microsecond
+                # sampler's 32 768 light workgroups are in the queue it does not get them until the sampler's grid runs dry
+                # (measured at 128 pairs: launched 6 us after the sampler it ran 15 -> 241 us for 52 us of work, and the solver
+                # behind it started 56 us late on the SIMDs it held).  Hence the refit is issued before the set-up -- but it waits for
+                # this stream's earlier work through an event and still lost that race by half a microsecond
                 # (rocprofv3, 128 pairs: sampler dispatched at 5.4 us, refit at 5.9 -- it then ran 232 us for 57 us of work and the
                 # solver behind it started 56 us late on the SIMDs it still held: step 0.947 -> 1.018 ms with the refit).  One
                 # tiny launch in front of the sampler lets the refit's 128 blocks in first: refit 57 us, sampler 178 -> 191 us,
                 # solver 146 us, step 0.996 ms.  (Set-up AND refit on the side stream with this stream waiting for the set-up:
-                # refit first as well, but 57 us between two steps instead of 17: 1.043 ms.)
+                # refit first as well, but 57 us between two steps instead of 17: 1.043 ms.  The refit issued right before the first
+                # scoring launch instead of up front -- scratch/runs/r5_gpu_w.sh, 128 pairs: step with refit 1.015 -> 1.063 ms;
+                # the same on a high-priority stream: 1.069 ms.  Both measured and dropped.)
                 if self._gap is None or self._gap.state.device != matches.device:
                     self._gap = ops.DeviceSeed(0, matches.device)
                 self._gap.next()
+            if self.weighted and self.solver == "f8" and self.refit:
+                c.last_w = torch.zeros((P, N), device=dev, dtype=dt)
+
+            def hyp(r, gate=None):
+                """the hypotheses of device round r; explicit noise: its batches' tensors along the hypothesis axis"""
+                g = None
+                if gumbels is not None:
+                    g = gumbels[first[r]] if plan[r] == 1 else torch.cat(list(gumbels[first[r]:first[r] + plan[r]]), dim=1)
+                return self._hypotheses(matches, logits, g, gate=gate, R=plan[r])
+
+            if self.device_termination:
+                if rounds > 16:
+                    raise ValueError("device_termination issues every round: at most 16 device rounds per call (see super_hypotheses)")
+                if draw:
+                    self._seeds.ahead = (st.seeds, 0)    # consecutive seeds, one per BATCH (drawn by dr_ransac_init)
+                for r in range(rounds):
+                    gate = st if r > 0 else None
+                    self._round(c, r, hyp(r, gate), gate)
+                self._seeds.ahead = None
+                return self._finish(c)
             # Rounds are pipelined: the hypotheses of round r+1 (sampler + solver, latency-bound, independent of round r's
             # outcome) are issued on a second stream before round r is scored, so they run under K4/K6 and under the
             # host's "does any pair continue?" read-back.  If round r ends the loop they are simply dropped.
             main = torch.cuda.current_stream()
-
-            def noise_of(r):
-                if gumbels is None:
-                    return None
-                if plan[r] == 1:
-                    return gumbels[first[r]]
-                return torch.cat(list(gumbels[first[r]:first[r] + plan[r]]), dim=1)
-
-            def have_round(r):
-                return r < rounds
-
-            def sub_of(r):      # dr_ransac_update's sub_models: the round's models are plan[r] batches of B x S
-                return self.B * self.S if plan[r] > 1 else 0
-
-            # (round 5, measured and dropped -- scratch/runs/r5_gpu_w.sh, 128 pairs: the refit issued right before the first
-            #  scoring launch instead of up front: step with refit 1.015 -> 1.063 ms; the same on a high-priority stream: 1.069 ms.)
-            if self.device_termination:
-                if rounds > 16:
-                    raise ValueError("device_termination issues every round: at most 16 device rounds per call (see super_hypotheses)")
-                want_w = bool(self.weighted and self.solver == "f8" and self.refit)
-                last_w = torch.zeros((P, N), device=dev, dtype=dt) if want_w else None
-                if draw:
-                    self._seed_queue = (st.seeds, 0)    # consecutive seeds, one per BATCH (drawn by dr_ransac_init)
-                for r in range(rounds):
-                    gate = st if r > 0 else None
-                    models, valid, _, row0 = self._hypotheses(matches, logits, noise_of(r), gate=gate, R=plan[r])
-                    if want_w:
-                        w0 = ops.soft_weights_row0(logits, self.k, self.tau, row0[1], row0[0])
-                        last_w = torch.where((st.iters.double() < st.max_iters)[:, None], w0, last_w)
-                    flat = models.reshape(P, -1, 3, 3)
-                    scores, masks = ops.msac_score(matches, flat, thr, want_masks=self.keep_masks, valid=valid.reshape(P, -1),
-                                                   gate=gate)
-                    if self.keep_masks:
-                        all_masks = masks
-                    ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.stop_k, self.confidence,
-                                      self.eps, sub_models=sub_of(r))
-                    if lo_seen is not None:
-                        self._local_opt(st, matches, thr, lo_seen, lo_refits)
-                self._seed_queue = []
-                return self._finish(st, matches, thr, pre, last_w, all_masks, lo_refits)
-            ahead = None
-            if have_round(0):
-                h = self._hypotheses(matches, logits, noise_of(0), R=plan[0])
-                ahead = (h[0], h[1], h[3])
+            ahead = hyp(0) if rounds > 0 else None
             r = 0
-            want_w = bool(self.weighted and self.solver == "f8" and self.refit)   # (the 7-point solver takes no weights)
-            last_w = torch.zeros((P, N), device=dev, dtype=dt) if want_w else None
             while ahead is not None:
-                models, valid, row0 = ahead
-                ahead = None
-                if self.pipeline and have_round(r + 1):
+                h, ahead = ahead, None
+                if self.pipeline and r + 1 < rounds:
                     if self._pipe is None:
                         self._pipe = torch.cuda.Stream(device=dev)
                     self._pipe.wait_stream(main)          # inputs (and, for explicit noise, the caller's tensors) are ready
                     with torch.cuda.stream(self._pipe):
-                        h = self._hypotheses(matches, logits, noise_of(r + 1), R=plan[r + 1])
-                        ahead = (h[0], h[1], h[3])
-                if want_w:
-                    # pairs still iterating in this round take this round's row-0 soft weights; terminated pairs keep theirs
-                    # ("the last batch sampled", per pair)
-                    w0 = ops.soft_weights_row0(logits, self.k, self.tau, row0[1], row0[0])
-                    last_w = torch.where((st.iters.double() < st.max_iters)[:, None], w0, last_w)
-                flat = models.reshape(P, -1, 3, 3)
-                scores, masks = ops.msac_score(matches, flat, thr, want_masks=self.keep_masks, valid=valid.reshape(P, -1))
-                if self.keep_masks:
-                    all_masks = masks
-                # K6: arg-max, "better?" test, best mask / inlier count and the adaptive stop of ransac.py:135-142, on the device
-                ops.ransac_update(st, matches, flat, valid.reshape(P, -1), scores, thr, self.B, self.stop_k, self.confidence,
-                                  self.eps, sub_models=sub_of(r))
-                if lo_seen is not None:      # (before the read-back below: it sees the bound the local optimisation set)
-                    self._local_opt(st, matches, thr, lo_seen, lo_refits)
+                        ahead = hyp(r + 1)
+                self._round(c, r, h)      # (local optimisation included: the read-back below sees the bound it set)
                 r += 1
-                if not have_round(r):
+                if r >= rounds:
                     break
                 # host read-back "does any pair continue?" only when another round could follow, and for small batches
                 # only every few rounds (pairs that have terminated are frozen on the device by K6, so a round issued
@@ -876,45 +820,61 @@ class BatchedRANSAC(object):
                 if r % sync_every == 0 and not bool((st.iters.double() < st.max_iters).any()):
                     break
                 if ahead is None:
-                    h = self._hypotheses(matches, logits, noise_of(r), R=plan[r])
-                    ahead = (h[0], h[1], h[3])
+                    ahead = hyp(r)
                 else:
                     main.wait_stream(self._pipe)
                     for t_ in ahead[:2]:
                         t_.record_stream(main)
             if ahead is not None and self._pipe is not None:
                 main.wait_stream(self._pipe)              # dropped speculative work: keep the allocator's stream order simple
-            return self._finish(st, matches, thr, pre, last_w, all_masks, lo_refits)
+            return self._finish(c)
 
-    def _local_opt(self, st, matches, thr, lo_seen, lo_refits):
-        ops.local_optimize(st, matches, thr, self.fmat, self.lo, self.lo_iters, self.stop_k, self.confidence, self.eps,
-                           self.max_iterations, lo_seen, lo_refits)
+    def _round(self, c, r, hyp, gate=None):
+        """What device round r of a test-mode call does once its hypotheses `hyp` (_hypotheses' result) exist: soft-weight carry,
+        scoring, arg-max / "better?" test / best mask / adaptive stop of ransac.py:135-142 on the device (K6), local optimisation.
+        gate: the state, in a later round of a device-terminated call (the launches skip the pairs that have terminated)."""
+        models, valid, _, row0 = hyp
+        P = c.matches.shape[0]
+        if c.last_w is not None:
+            # pairs still iterating in this round take this round's row-0 soft weights; terminated pairs keep theirs
+            # ("the last batch sampled", per pair)
+            w0 = ops.soft_weights_row0(c.logits, self.k, self.tau, row0[1], row0[0])
+            c.last_w = torch.where((c.st.iters.double() < c.st.max_iters)[:, None], w0, c.last_w)
+        flat, valid = models.reshape(P, -1, 3, 3), valid.reshape(P, -1)
+        scores, masks = ops.msac_score(c.matches, flat, c.thr, want_masks=self.keep_masks, valid=valid, gate=gate)
+        if self.keep_masks:
+            c.all_masks = masks
+        # dr_ransac_update's sub_models: the round's models are plan[r] batches of B x S
+        ops.ransac_update(c.st, c.matches, flat, valid, scores, c.thr, self.B, self.stop_k, self.confidence, self.eps,
+                          sub_models=self.B * self.S if c.plan[r] > 1 else 0)
+        if c.lo_seen is not None:
+            ops.local_optimize(c.st, c.matches, c.thr, self.fmat, self.lo, self.lo_iters, self.stop_k, self.confidence, self.eps,
+                               self.max_iterations, c.lo_seen, c.lo_refits)
 
-    def _finish(self, st, matches, thr, pre, last_w, all_masks, lo_refits=None):
+    def _finish(self, c):
         """final refit on the inliers of the best model (ransac.py:148-195) and the result dictionary"""
         self._race_ws = None
-        best_score, best_model, best_mask, best_inl, iters = (st.best_score, st.best_model, st.best_mask,
-                                                              st.best_inliers, st.iters)
+        st = c.st
         if self.refit:
             if self.fmat:
-                F, fvalid = ops.refit_fundamental(matches, best_mask, last_w)   # (weighted) LSQ on the inliers of the best mask
+                F, fvalid = ops.refit_fundamental(c.matches, st.best_mask, c.last_w)   # (weighted) LSQ on the inliers of the best mask
                 cand, cvalid = F.unsqueeze(1), fvalid.unsqueeze(1)
             else:
                 torch.cuda.current_stream().wait_stream(self._side)
-                cand, cvalid = pre
+                cand, cvalid = c.pre
                 if not torch.cuda.is_current_stream_capturing():
                     cand.record_stream(torch.cuda.current_stream())
                     cvalid.record_stream(torch.cuda.current_stream())
             # score the candidates and keep the best one where it beats the RANSAC result: one launch, in place
-            ops.refit_accept(matches, cand, cvalid, thr, best_score, best_model)
-        out = dict(model=best_model, mask=best_mask, score=best_score, iterations=iters, inliers=best_inl,
-                   masks=all_masks, packed=st.packed)
-        if lo_refits is not None:
-            out["lo_refits"] = lo_refits
+            ops.refit_accept(c.matches, cand, cvalid, c.thr, st.best_score, st.best_model)
+        out = dict(model=st.best_model, mask=st.best_mask, score=st.best_score, iterations=st.iters, inliers=st.best_inliers,
+                   masks=c.all_masks, packed=st.packed)
+        if c.lo_refits is not None:
+            out["lo_refits"] = c.lo_refits
         return out
 
 
-class BatchedRANSAC3D(object):
+class BatchedRANSAC3D(_SeededDriver):
     """RANSAC3D (ransac.py:303-450) over a batch of point-cloud pairs in one go: matches [P,N,6] = (p, q), logits [P,N].
 
     One round = K1 Gumbel top-k (k = 3) -> K2 gather -> K3r rigid SVD solver -> K4r squared residuals of every model
@@ -929,24 +889,9 @@ class BatchedRANSAC3D(object):
         self.threshold = threshold
         self.max_iterations = max_iterations
         self.tau = tau
-        self.seed = seed
-        self.calls = 0
-        self._dev_seed = None
+        self._seeds = _Seeds(seed)
         self.flag = flag
         self.keep_masks = keep_masks
-
-    def _next_seed(self):
-        if self._dev_seed is not None:
-            self.calls += 1
-            return self._dev_seed.next()
-        s = (self.seed * 0x9E3779B97F4A7C15 + self.calls) & (2 ** 64 - 1)
-        self.calls += 1
-        return s
-
-    def device_seeds(self, device):
-        """See BatchedRANSAC.device_seeds."""
-        self._dev_seed = ops.DeviceSeed(self.seed, device, self.calls)
-        return self
 
     def __call__(self, matches, logits, gumbels=None):
         P, N, _ = matches.shape
@@ -957,7 +902,7 @@ class BatchedRANSAC3D(object):
             out = []
             for r in range(rounds):
                 g = None if gumbels is None else gumbels[r]
-                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, 3, self.tau, g, self._next_seed())
+                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, 3, self.tau, g, self._seeds.next())
                 model, R, t, scale, valid = ops.solve_rigid_autograd(samples.reshape(P * self.B, 3, 6), None, self.flag)
                 model = model.reshape(P, self.B, 4, 4)
                 res, _ = ops.rigid_residual_autograd(matches, model, self.threshold)
@@ -971,7 +916,7 @@ class BatchedRANSAC3D(object):
             masks = None
             for r in range(rounds):
                 g = None if gumbels is None else gumbels[r]
-                idx = ops.gumbel_topk(logits, self.B, 3, self.tau, g, self._next_seed(), soft=False)["idx"]
+                idx = ops.gumbel_topk(logits, self.B, 3, self.tau, g, self._seeds.next(), soft=False)["idx"]
                 if matches.dtype == torch.float32:
                     # K2 + K3r in one launch (samples read through the index sets), the round's residual sums cleared on the way
                     # the residual sums are ACCUMULATED (atomics: order-nondeterministic in the last bits) into a buffer that
