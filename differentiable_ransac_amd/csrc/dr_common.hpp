@@ -224,7 +224,7 @@ struct Philox {
     lo = (uint32_t)p;
   }
   __host__ __device__ static inline uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(DR_PHILOX_NO_BITOP3)
+#if defined(__HIP_DEVICE_COMPILE__)
     uint32_t r;
     // truth table of a ^ b ^ c; the third operand is the round key -- wave-uniform in every kernel (derived from the seed), so
     // it stays in an SGPR (a "v" constraint costs one v_mov_b32 per use: 6 instructions per round again)
@@ -237,11 +237,9 @@ struct Philox {
   __host__ __device__ static inline void gen(uint64_t seed, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                              uint32_t out[4]) {
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#ifndef DR_PHILOX_ROUNDS
-#define DR_PHILOX_ROUNDS 7
-#endif
+    constexpr int kPhiloxRounds = 7;   // see the header: the smallest Crush-resistant Philox4x32 (10 until round 3)
 #pragma unroll
-    for (int r = 0; r < DR_PHILOX_ROUNDS; ++r) {
+    for (int r = 0; r < kPhiloxRounds; ++r) {
       uint32_t h0, l0, h1, l1;
       mulhilo(M0, c0, h0, l0);
       mulhilo(M1, c2, h1, l1);
@@ -263,11 +261,6 @@ __device__ __forceinline__ float gumbel_from_bits(uint32_t bits) {
   // -ln u in [1.2e-7, 87.4]: both log arguments are normal numbers, so the raw v_log_f32 (no denormal fix-up sequence) is
   // exact to its 1-ulp spec
   const float kLn2 = 0.69314718055994530942f;
-#if defined(DR_K1_NOISE_EXPERIMENT) && DR_K1_NOISE_EXPERIMENT == 1   // timing experiment: no logarithm at all
-  return u;
-#elif defined(DR_K1_NOISE_EXPERIMENT) && DR_K1_NOISE_EXPERIMENT == 2   // timing experiment: one logarithm
-  return -kLn2 * __builtin_amdgcn_logf(u);
-#endif
   // -ln(-ln u) = -ln2 * log2(-ln2 * log2 u) = -ln2 * log2(-log2 u) - ln2 * log2(ln2): the inner scale factor leaves the
   // logarithm as a constant, the sign of log2 u is a free source modifier of the second v_log_f32 -- five instructions per
   // sample (convert, fma, log, log, fma) instead of six

@@ -5,48 +5,28 @@
 
 namespace dr {
 
-// 1: the balanced final stage evaluates the ten constraints on every candidate BEFORE the first Gauss-Newton step and only
-// steps the candidates above the stopping tolerance (0: one unconditional step for everybody, rounds 1-2), and the
-// verification reads the residual norm the last step left in LDS instead of evaluating the constraints again.
-// dr_solve_nister5_f32 at 32 x 1024 samples: 73.8 -> 68.7 us; same valid flags on 327 680 slots, 98.5 % of the models
-// bit-identical, the rest within 1.7e-6 (the skipped step moved them below f32 rounding); error against the true E unchanged
-// (median 9.37e-7, 99.2 % below 1e-4).  Shorter bisection / Newton schedules of the root search, tried in the same pass,
-// lose 0.03-1.1 % of the solutions (profiles/r3_k3_precheck.log): the schedule stays.
-#ifndef DR_K3_PRECHECK
-#define DR_K3_PRECHECK 1
-#endif
-// 1: the Gauss-Newton step forms the Jacobian of the nine trace constraints as (2 dG - tr(dG) I) E + (2 G - tr(G) I) H
-// (G = E E^T, dG = H E^T + E H^T: three 3x3 products per direction instead of six), takes the residual from the same
-// pieces and evaluates |r|^2 at the new point with the symmetric G formed once.  68.7 -> 64 us per 32 x 1024 samples with
-// the pre-check; all 158 800 f32 models of the A/B set bit-identical (the f64 differences round away), same valid flags.
-// 1: the f32 models and validity bytes of a block's 32 samples (11.5 KB + 320 B, contiguous in the output) are assembled in
-// LDS -- identity pattern first, verified solutions over it -- and written out as whole 16-byte pieces of consecutive lanes:
-// 12 + 1 coalesced store instructions per wave instead of ~120 scattered ones (9 dwords per verified solution and per
-// identity filler, 360 bytes apart from lane to lane: every dword its own 64-byte request).  Measured: 55.9 -> 57.7 us per
-// 32 x 1024 samples, step 0.973 vs 0.974 ms -- the scattered stores are not what the final stage waits for (it is ~7 k
-// instructions per wave: the per-lane start vectors, 2.3 Gauss-Newton rounds, three verification rounds).  Off; bit-identical.
-#ifndef DR_K3_STAGE_OUT
-#define DR_K3_STAGE_OUT 0
-#endif
-#ifndef DR_K3_TOL2_F32
-#define DR_K3_TOL2_F32 1e-16   // squared residual norm at which a candidate of the f32 entry points stops iterating (balanced final stage).
-                              // 1e-17 until round 4; 1e-16 measured then: 57.1 -> 54.6 us per 32 x 1024 samples, same valid flags and error
-                              // statistics, 24 of 158 874 models move by up to 7e-6 (ill-conditioned ones: the skipped step mattered) --
-                              // far inside the 1e-4 contract of an f32 model.  Adopted in round 5: a Gauss-Newton step is 1 400 instructions
-                              // that 0.5 % of the candidates ask for, but 40 % of the waves then run (cold code: ~11 us per execution)
-#endif
-#ifndef DR_K3_PRECHECK_F64
-#define DR_K3_PRECHECK_F64 1   // 1: the residual pre-check also with the f64 stopping tolerance (train mode): with converged roots
-                               // most candidates are at rounding level already -- train step 0.2898 -> 0.2865 ms
-#endif
-#ifndef DR_K3_JAC2
-#define DR_K3_JAC2 1
-#endif
-// 1: the root search of the two-lanes-per-sample kernels deals the brackets that hold a sign change out over the wave
-// (real_roots_half_wave) instead of refining every bracket in every lane
-#ifndef DR_K3_WAVE_ROOTS
-#define DR_K3_WAVE_ROOTS 1
-#endif
+// Measured choices of the balanced final stage (balanced_finish) and of the Gauss-Newton step (polish_step):
+// - The ten constraints are evaluated on every candidate BEFORE the first Gauss-Newton step and only the candidates above the
+//   stopping tolerance step (one unconditional step for everybody in rounds 1-2), and the verification reads the residual norm the
+//   last step left in LDS instead of evaluating the constraints again.  dr_solve_nister5_f32 at 32 x 1024 samples: 73.8 -> 68.7 us;
+//   same valid flags on 327 680 slots, 98.5 % of the models bit-identical, the rest within 1.7e-6 (the skipped step moved them below
+//   f32 rounding); error against the true E unchanged (median 9.37e-7, 99.2 % below 1e-4).  Shorter bisection / Newton schedules of
+//   the root search, tried in the same pass, lose 0.03-1.1 % of the solutions (profiles/r3_k3_precheck.log): the schedule stays.
+// - The Gauss-Newton step forms the Jacobian of the nine trace constraints as (2 dG - tr(dG) I) E + (2 G - tr(G) I) H (G = E E^T,
+//   dG = H E^T + E H^T: three 3x3 products per direction instead of six), takes the residual from the same pieces and evaluates
+//   |r|^2 at the new point with the symmetric G formed once.  68.7 -> 64 us per 32 x 1024 samples with the pre-check; all 158 800
+//   f32 models of the A/B set bit-identical (the f64 differences round away), same valid flags.
+// - Not kept: the f32 models and validity bytes of a block's 32 samples (11.5 KB + 320 B, contiguous in the output) assembled in
+//   LDS and written out as whole 16-byte pieces of consecutive lanes, 12 + 1 coalesced store instructions per wave instead of ~120
+//   scattered ones (9 dwords per verified solution and per identity filler, 360 bytes apart from lane to lane: every dword its own
+//   64-byte request).  Measured: 55.9 -> 57.7 us per 32 x 1024 samples, step 0.973 vs 0.974 ms -- the scattered stores are not what
+//   the final stage waits for (it is ~7 k instructions per wave: the per-lane start vectors, 2.3 Gauss-Newton rounds, three
+//   verification rounds).  Bit-identical.
+constexpr double kTol2F32 = 1e-16;   // squared residual norm at which a candidate of the f32 entry points stops iterating (balanced final stage).
+                                     // 1e-17 until round 4; 1e-16 measured then: 57.1 -> 54.6 us per 32 x 1024 samples, same valid flags and error
+                                     // statistics, 24 of 158 874 models move by up to 7e-6 (ill-conditioned ones: the skipped step mattered) --
+                                     // far inside the 1e-4 contract of an f32 model.  Adopted in round 5: a Gauss-Newton step is 1 400 instructions
+                                     // that 0.5 % of the candidates ask for, but 40 % of the waves then run (cold code: ~11 us per execution)
 
 constexpr int kFiveWs = 162;   // doubles of LDS per lane: B block (100) for the minimal path, A^T A + V (162) for n > 5
 
@@ -167,14 +147,7 @@ __device__ __forceinline__ void polish_step(const double (&nb)[4][9], const doub
   double E[9], r[10];
 #pragma unroll
   for (int q = 0; q < 9; ++q) E[q] = u[0] * nb[0][q] + u[1] * nb[1][q] + u[2] * nb[2][q] + u[3] * nb[3][q];
-#if !DR_K3_JAC2
-  essential_residual(E, r);
-  double n0 = 0;
-#pragma unroll
-  for (int q = 0; q < 10; ++q) n0 += r[q] * r[q];
-#endif
   double J[4][10];
-#if DR_K3_JAC2
   // d r[H] = (2 dG - tr(dG) I) E + (2 G - tr(G) I) H  with G = E E^T, dG = H E^T + E H^T : three 3x3 products per direction
   // instead of six
   double A2[9];
@@ -224,46 +197,6 @@ __device__ __forceinline__ void polish_step(const double (&nb)[4][9], const doub
     for (int q = 0; q < 9; ++q) dd += cof[q] * H[q];
     J[k][9] = dd;
   }
-#else
-  double EEt[9], EtE[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int jx = 0; jx < 3; ++jx) {
-      EEt[3 * i + jx] = E[3 * i] * E[3 * jx] + E[3 * i + 1] * E[3 * jx + 1] + E[3 * i + 2] * E[3 * jx + 2];
-      EtE[3 * i + jx] = E[i] * E[jx] + E[3 + i] * E[3 + jx] + E[6 + i] * E[6 + jx];
-    }
-  const double tr = EEt[0] + EEt[4] + EEt[8];
-  const double cof[9] = {E[4] * E[8] - E[5] * E[7], E[5] * E[6] - E[3] * E[8], E[3] * E[7] - E[4] * E[6],
-                         E[2] * E[7] - E[1] * E[8], E[0] * E[8] - E[2] * E[6], E[1] * E[6] - E[0] * E[7],
-                         E[1] * E[5] - E[2] * E[4], E[2] * E[3] - E[0] * E[5], E[0] * E[4] - E[1] * E[3]};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const double(&H)[9] = nb[k];
-    double HEt[9];
-    double trEHt = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int jx = 0; jx < 3; ++jx)
-        HEt[3 * i + jx] = H[3 * i] * E[3 * jx] + H[3 * i + 1] * E[3 * jx + 1] + H[3 * i + 2] * E[3 * jx + 2];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) trEHt += E[q] * H[q];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int jx = 0; jx < 3; ++jx) {
-        const double t1 = H[3 * i] * EtE[jx] + H[3 * i + 1] * EtE[3 + jx] + H[3 * i + 2] * EtE[6 + jx];     // H E^T E
-        const double t2 = HEt[i] * E[jx] + HEt[3 + i] * E[3 + jx] + HEt[6 + i] * E[6 + jx];                  // E H^T E
-        const double t3 = EEt[3 * i] * H[jx] + EEt[3 * i + 1] * H[3 + jx] + EEt[3 * i + 2] * H[6 + jx];     // E E^T H
-        J[k][3 * i + jx] = 2.0 * (t1 + t2 + t3) - 2.0 * trEHt * E[3 * i + jx] - tr * H[3 * i + jx];
-      }
-    double dd = 0;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) dd += cof[q] * H[q];
-    J[k][9] = dd;
-  }
-#endif
   // (J^T J + u u^T) d = J^T r : 4x4 SPD, LDL^T without pivoting
   double a[4][4], g[4];
 #pragma unroll
@@ -308,14 +241,7 @@ __device__ __forceinline__ void polish_step(const double (&nb)[4][9], const doub
   double E2[9], n1 = 0;
 #pragma unroll
   for (int q = 0; q < 9; ++q) E2[q] = un[0] * nb[0][q] + un[1] * nb[1][q] + un[2] * nb[2][q] + un[3] * nb[3][q];
-#if DR_K3_JAC2
   n1 = essential_residual_norm2(E2);
-#else
-  double r2[10];
-  essential_residual(E2, r2);
-#pragma unroll
-  for (int q = 0; q < 10; ++q) n1 += r2[q] * r2[q];
-#endif
   n0_out = n0;
   n1_out = n1;
 }
@@ -397,18 +323,14 @@ struct FinishQueue {
   uint16_t *meta;    // 320: source lane | finite-candidate flag << 6
   int *cnt;          // 64: verified solutions so far of (sample, half) = source lane
   uint16_t *live;    // 2 x 320: candidates that need another Gauss-Newton step (this round | next round)
-  double *rn;        // 320: squared norm of the ten constraints at the candidate's current vector (DR_K3_PRECHECK)
-  float *stage;      // 32 x 90: the block's f32 output, assembled here and written out in whole lines (DR_K3_STAGE_OUT)
-  uint8_t *vstage;   // 32 x 10 validity bytes of the same
-  static constexpr int kQueueDoubles = 4 * 320 + 320 / 4 + 64 / 2 + 2 * 320 / 4 + 320 + (DR_K3_STAGE_OUT ? 32 * 90 / 2 + 320 / 8 : 0);
+  double *rn;        // 320: squared norm of the ten constraints at the candidate's current vector (the residual pre-check)
+  static constexpr int kQueueDoubles = 4 * 320 + 320 / 4 + 64 / 2 + 2 * 320 / 4 + 320;
   static constexpr int kDoubles = 36 * 32 + kQueueDoubles;
   __device__ __forceinline__ explicit FinishQueue(double *lds)
       : nb_src(lds), nb_lds(lds), u(lds + 36 * 32), meta(reinterpret_cast<uint16_t *>(lds + 36 * 32 + 4 * 320)),
         cnt(reinterpret_cast<int *>(lds + 36 * 32 + 4 * 320 + 320 / 4)),
         live(reinterpret_cast<uint16_t *>(lds + 36 * 32 + 4 * 320 + 320 / 4 + 64 / 2)),
-        rn(lds + 36 * 32 + 4 * 320 + 320 / 4 + 64 / 2 + 2 * 320 / 4),
-        stage(reinterpret_cast<float *>(lds + 36 * 32 + 4 * 320 + 320 / 4 + 64 / 2 + 2 * 320 / 4 + 320)),
-        vstage(reinterpret_cast<uint8_t *>(lds + 36 * 32 + 4 * 320 + 320 / 4 + 64 / 2 + 2 * 320 / 4 + 320 + 32 * 90 / 2)) {}
+        rn(lds + 36 * 32 + 4 * 320 + 320 / 4 + 64 / 2 + 2 * 320 / 4) {}
   __device__ __forceinline__ void load_basis(int j, double (&nb)[4][9]) const {
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -466,17 +388,16 @@ __device__ __forceinline__ void balanced_finish(const FinishQueue &fq, int lane,
   fq.cnt[lane] = 0;
   wave_lds_order();
   DR_STAGE(16);   // start vectors + queue
-  const double tol2 = (sizeof(T) == 4 && !models64) ? DR_K3_TOL2_F32 : 1e-28;
+  const double tol2 = (sizeof(T) == 4 && !models64) ? kTol2F32 : 1e-28;
   auto mbcnt = [](unsigned long long bm) {
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
   };
-#if DR_K3_PRECHECK
   // ---- (A') residual of every candidate as the root search left it; only those above the stopping tolerance queue for
-  // Gauss-Newton steps (the others are final: the same rule that ends the iteration after a step).  (DR_K3_PRECHECK_F64 = 0:
-  // with the f64 tolerance of train mode everybody queues unseen.)  Every queued candidate's residual norm is
-  // (re)written by its steps, and (C) reads it back instead of evaluating the ten constraints a last time.
+  // Gauss-Newton steps (the others are final: the same rule that ends the iteration after a step) -- also with the f64 tolerance
+  // of train mode: with converged roots most candidates are at rounding level already (train step 0.2898 -> 0.2865 ms against
+  // everybody queueing unseen).  Every queued candidate's residual norm is (re)written by its steps, and (C) reads it back
+  // instead of evaluating the ten constraints a last time.
   int nlive = 0;
-  const bool precheck = DR_K3_PRECHECK_F64 || tol2 > 1e-20;
 #pragma unroll 1
   for (int base = 0; base < total; base += 64) {
     const int e = base + lane;
@@ -484,25 +405,15 @@ __device__ __forceinline__ void balanced_finish(const FinishQueue &fq, int lane,
     const int ec = has ? e : total - 1;
     const unsigned m = fq.meta[ec];
     bool lv = has && ((m >> 6) & 1u);
-    if (precheck) {
-      double nb[4][9], u[4], E[9];
-      fq.load_basis((m & 63) >> 1, nb);
+    double nb[4][9], u[4], E[9];
+    fq.load_basis((m & 63) >> 1, nb);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) u[k] = fq.u[k * 320 + ec];
+    for (int k = 0; k < 4; ++k) u[k] = fq.u[k * 320 + ec];
 #pragma unroll
-      for (int q = 0; q < 9; ++q) E[q] = u[0] * nb[0][q] + u[1] * nb[1][q] + u[2] * nb[2][q] + u[3] * nb[3][q];
-#if DR_K3_JAC2
-      const double n0 = essential_residual_norm2(E);
-#else
-      double r[10];
-      essential_residual(E, r);
-      double n0 = 0;
-#pragma unroll
-      for (int q = 0; q < 10; ++q) n0 += r[q] * r[q];
-#endif
-      lv = lv && !(n0 <= tol2);
-      if (has) fq.rn[e] = n0;
-    }
+    for (int q = 0; q < 9; ++q) E[q] = u[0] * nb[0][q] + u[1] * nb[1][q] + u[2] * nb[2][q] + u[3] * nb[3][q];
+    const double n0 = essential_residual_norm2(E);
+    lv = lv && !(n0 <= tol2);
+    if (has) fq.rn[e] = n0;
     const unsigned long long bm = __ballot(lv);
     if (lv) fq.live[nlive + mbcnt(bm)] = (uint16_t)e;
     nlive += __popcll(bm);
@@ -549,78 +460,6 @@ __device__ __forceinline__ void balanced_finish(const FinishQueue &fq, int lane,
   if (lane == 0) atomicAdd(&::dr::g_stage_cycles[15], (unsigned long long)_steps);
 #endif
   DR_STAGE(18);   // Gauss-Newton steps of the candidates that asked for them
-#else
-  // ---- (A) first step
-  int nlive = 0;
-#pragma unroll 1
-  for (int base = 0; base < total; base += 64) {
-    const int e = base + lane;
-    const bool has = e < total;
-    const int ec = has ? e : total - 1;
-    const unsigned m = fq.meta[ec];
-    double nb[4][9], u[4];
-    fq.load_basis((m & 63) >> 1, nb);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) u[k] = fq.u[k * 320 + ec];
-    const bool good = has && ((m >> 6) & 1u);
-    double un[4], n0, n1;
-    polish_step(nb, u, un, n0, n1);
-    const bool better = n1 <= n0 && is_finite(n1);
-    const bool lv = good && better && (n1 > tol2) && (n1 < 0.25 * n0);
-    if (has && better) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) fq.u[k * 320 + e] = un[k];
-    }
-    const unsigned long long bm = __ballot(lv);
-    if (lv) fq.live[nlive + mbcnt(bm)] = (uint16_t)e;
-    nlive += __popcll(bm);
-  }
-  wave_lds_order();
-  // ---- (B) steps 2..8 of the candidates that asked for them
-#pragma unroll 1
-  for (int it = 1; it < 8 && nlive > 0; ++it) {
-    const uint16_t *cur = fq.live + 320 * ((it - 1) & 1);
-    uint16_t *nxt = fq.live + 320 * (it & 1);
-    int nnext = 0;
-#pragma unroll 1
-    for (int base = 0; base < nlive; base += 64) {
-      const bool has = base + lane < nlive;
-      const int e = cur[has ? base + lane : base];
-      double nb[4][9], u[4], un[4], n0, n1;
-      fq.load_basis((fq.meta[e] & 63) >> 1, nb);
-#pragma unroll
-      for (int k = 0; k < 4; ++k) u[k] = fq.u[k * 320 + e];
-      polish_step(nb, u, un, n0, n1);
-      const bool better = n1 <= n0 && is_finite(n1);
-      if (has && better) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) fq.u[k * 320 + e] = un[k];
-      }
-      const bool lv = has && better && (n1 > tol2) && (n1 < 0.25 * n0);
-      const unsigned long long bm = __ballot(lv);
-      if (lv) nxt[nnext + mbcnt(bm)] = (uint16_t)e;
-      nnext += __popcll(bm);
-    }
-    nlive = nnext;
-    wave_lds_order();
-  }
-#endif
-  constexpr bool kStage = DR_K3_STAGE_OUT && sizeof(T) == 4;
-  if (kStage) {
-    // every slot starts as the eye(3) filler with validity 0
-#pragma unroll 1
-    for (int i = lane; i < 32 * 90 / 4; i += 64) {
-      const int e0 = (4 * i) % 9;
-      float4 v;
-      v.x = (e0 % 4 == 0) ? 1.f : 0.f;
-      v.y = (((e0 + 1) % 9) % 4 == 0) ? 1.f : 0.f;
-      v.z = (((e0 + 2) % 9) % 4 == 0) ? 1.f : 0.f;
-      v.w = (((e0 + 3) % 9) % 4 == 0) ? 1.f : 0.f;
-      *reinterpret_cast<float4 *>(fq.stage + 4 * i) = v;
-    }
-    for (int i = lane; i < 320 / 4; i += 64) *reinterpret_cast<uint32_t *>(fq.vstage + 4 * i) = 0u;
-    wave_lds_order();
-  }
   // ---- (C) verification of the ten constraints, rank among the verified candidates of the same source lane, store
 #pragma unroll 1
   for (int base = 0; base < total; base += 64) {
@@ -630,21 +469,13 @@ __device__ __forceinline__ void balanced_finish(const FinishQueue &fq, int lane,
     const unsigned m = fq.meta[ec];
     const int src = m & 63;
     const int j = src >> 1;
-    double nb[4][9], u[4], E[9], r[10];
+    double nb[4][9], u[4], E[9];
     fq.load_basis(j, nb);
 #pragma unroll
     for (int k = 0; k < 4; ++k) u[k] = fq.u[k * 320 + ec];
 #pragma unroll
     for (int q = 0; q < 9; ++q) E[q] = u[0] * nb[0][q] + u[1] * nb[1][q] + u[2] * nb[2][q] + u[3] * nb[3][q];
-#if DR_K3_PRECHECK
     const double rn = fq.rn[ec];   // the residual of this very vector, from the pre-check or from the step that produced it
-    (void)r;
-#else
-    essential_residual(E, r);
-    double rn = 0;
-#pragma unroll
-    for (int q = 0; q < 10; ++q) rn += r[q] * r[q];
-#endif
     const bool good = has && ((m >> 6) & 1u) && is_finite(rn) && rn <= 1e-14;
     const int gid = has ? src : 64 + lane;
     const int prev = __shfl_up(gid, 1, 64);
@@ -659,70 +490,22 @@ __device__ __forceinline__ void balanced_finish(const FinishQueue &fq, int lane,
     if (good && rank < 10) {
       const int slot = (src & 1) ? 9 - rank : rank;
       const size_t sm_ = s0 + (size_t)j;
-      if (kStage) {
-        float *dst = fq.stage + (j * 10 + slot) * 9;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int jx = 0; jx < 3; ++jx) dst[3 * i + jx] = (float)E[3 * jx + i];   // stored transposed (nister.py:407)
-        fq.vstage[j * 10 + slot] = 1;
-        if (models64) {
-#pragma unroll
-          for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int jx = 0; jx < 3; ++jx) models64[sm_ * 90 + 9 * slot + 3 * i + jx] = E[3 * jx + i];
-        }
-      } else {
-#ifdef DR_K3_NOSTORE   // timing experiment: the final stage without its global stores (one data-dependent store keeps E alive)
-        if (E[0] == 123.456) valid[sm_ * 10 + slot] = 1;
-#else
-        store_model<T>(E, models + sm_ * 90 + 9 * slot, models64 ? models64 + sm_ * 90 + 9 * slot : nullptr);
-        valid[sm_ * 10 + slot] = 1;
-#endif
-      }
+      store_model<T>(E, models + sm_ * 90 + 9 * slot, models64 ? models64 + sm_ * 90 + 9 * slot : nullptr);
+      valid[sm_ * 10 + slot] = 1;
     }
   }
   DR_STAGE(19);   // verification, rank, store
   // eye(3) between the two halves' solutions
-#ifndef DR_K3_NOSTORE
-  if ((!kStage || models64) && active && (lane & 1) == 0) {
+  if (active && (lane & 1) == 0) {
     const int lo = min(fq.cnt[lane], 10), hi = min(fq.cnt[lane + 1], 10);
     const size_t sm_ = s0 + (size_t)(lane >> 1);
     for (int s = min(lo, 10 - hi); s < 10 - hi; ++s) {
-      if (!kStage) {
-        write_identity<T>(models + sm_ * 90 + 9 * s);
-        valid[sm_ * 10 + s] = 0;
-      }
+      write_identity<T>(models + sm_ * 90 + 9 * s);
+      valid[sm_ * 10 + s] = 0;
       if (models64) write_identity<double>(models64 + sm_ * 90 + 9 * s);
     }
   }
-#endif
   DR_STAGE(20);   // identity fillers
-  if (kStage) {
-    // the block's output rows [s0, s0 + ns) x 90 floats and x 10 bytes are contiguous: whole 16-byte pieces, lane after lane
-    wave_lds_order();
-    const int ns = __popcll(__ballot(active)) >> 1;
-    const int nf = ns * 90, nv = ns * 10;
-    float *out = reinterpret_cast<float *>(models) + s0 * 90;    // 16-byte aligned: s0 is a multiple of 32
-#pragma unroll 1
-    for (int i = lane; i < 32 * 90 / 4; i += 64) {
-      const float4 val = *reinterpret_cast<const float4 *>(fq.stage + 4 * i);
-      if (4 * i + 3 < nf) *reinterpret_cast<float4 *>(out + 4 * i) = val;
-      else {
-        if (4 * i < nf) out[4 * i] = val.x;
-        if (4 * i + 1 < nf) out[4 * i + 1] = val.y;
-        if (4 * i + 2 < nf) out[4 * i + 2] = val.z;
-      }
-    }
-    uint8_t *vout = valid + s0 * 10;                                // 4-byte aligned: s0 * 10 is a multiple of 320
-    for (int i = lane; i < 320 / 4; i += 64) {
-      const uint32_t w = *reinterpret_cast<const uint32_t *>(fq.vstage + 4 * i);
-      if (4 * i + 3 < nv) *reinterpret_cast<uint32_t *>(vout + 4 * i) = w;
-      else
-        for (int b = 0; b < 4; ++b)
-          if (4 * i + b < nv) vout[4 * i + b] = (uint8_t)(w >> (8 * b));
-    }
-  }
 }
 
 // ---- Nister: B(z) from the reduced rows, det B(z), roots, back-substitution -----------------------------
@@ -835,7 +618,7 @@ __device__ __forceinline__ void nister_finish(const double (&nb)[4][9], const do
 constexpr int kPairFinishDoubles = (36 + 39) * 32;
 constexpr int kmax(int a, int b) { return a > b ? a : b; }
 constexpr int kNisterPairDoubles =
-    kmax(100 * 32, kmax(FinishQueue::kDoubles, kPairFinishDoubles + (DR_K3_WAVE_ROOTS ? kmax(RootWs<10>::kDoubles, DR_K3_STURM ? SturmWs<10>::kDoubles : 0) : 0)));
+    kmax(100 * 32, kmax(FinishQueue::kDoubles, kPairFinishDoubles + kmax(RootWs<10>::kDoubles, SturmWs<10>::kDoubles)));
 
 // B(z) (rows k = e - z f, l = g - z h, m = i - z j of the reduced system; columns x: degree 3, y: degree 3, 1: degree 4) as
 // 39 doubles bz[13 r + (0..3 | 4..7 | 8..12)] and its determinant's coefficients cs[0..10] (ascending)
@@ -931,15 +714,7 @@ __device__ __forceinline__ void nister_back_pair(const double (&cs)[11], double 
   double roots[10];
   int nroots;
   DR_STAGE_BEGIN();
-#if DR_K3_WAVE_ROOTS
-#if DR_K3_STURM
   real_roots_half_sturm<10>(cs, half != 0, roots, nroots, lds + kPairFinishDoubles, lane);
-#else
-  real_roots_half_wave<10>(cs, half != 0, roots, nroots, lds + kPairFinishDoubles, lane);
-#endif
-#else
-  real_roots_half<10>(cs, half != 0, roots, nroots);
-#endif
   DR_STAGE(3);
   if (!active) nroots = 0;
   double xs[10], ys[10];
@@ -951,10 +726,6 @@ __device__ __forceinline__ void nister_back_pair(const double (&cs)[11], double 
     nister_xy_of_roots(bz, roots, nroots, xs, ys, cand);
   }
   DR_STAGE(4);
-#ifdef DR_K3_SKIP_FINAL   // timing experiment: everything but the final stage (the results are kept alive by one store)
-  if (active && lane == 0) models[s0 * 90] = (T)(xs[0] + ys[1] + (double)cand);
-  return;
-#endif
   balanced_finish<T>(fq, lane, nroots, xs, ys, roots, cand, s0, active, models, valid, models64);
   DR_STAGE(11);   // the balanced final stage alone
 }

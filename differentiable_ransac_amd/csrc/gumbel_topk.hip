@@ -21,19 +21,12 @@
 
 namespace dr {
 
-#ifndef DR_K1_FAST
-#define DR_K1_FAST 1   // 0: always the general kernel (A/B builds)
-#endif
-#ifndef DR_K1_PASSB_LDS
-#define DR_K1_PASSB_LDS 0   // 1: register kernel: the (few) lanes whose maximum reaches the threshold park their 32 values in LDS and
-#endif                      // the whole wave scans those, instead of a ballot per element of every group (see pass B there).
-                            // Measured in the step: 1.0219 vs 1.0195 ms (slower: the compare + branch per element it
-                            // replaces mostly falls through) -- off.
-#ifndef DR_K1_PASSB_ATOMIC
-#define DR_K1_PASSB_ATOMIC 0   // 1: register kernel collects the candidates in the lanes that own them (LDS counter) instead of by
-                               // wave-wide ballots.  In the step (scratch/r3_gpu_s.sh): 1.035 / 1.036 ms against 1.026 / 1.032 ms
-                               // with the ballots -- the per-element divergent branches cost more than the ballots they replace: off
-#endif
+// Pass B of the register kernel (gumbel_topk_fast_kernel) collects its candidates by wave-wide ballots.  Tried and not kept:
+// the (few) lanes whose maximum reaches the threshold park their 32 values in LDS and the whole wave scans those, instead of a
+// ballot per element of every group -- in the step 1.0219 vs 1.0195 ms (slower: the compare + branch per element it replaces
+// mostly falls through); the candidates collected in the lanes that own them (LDS counter) -- in the step (scratch/r3_gpu_s.sh)
+// 1.035 / 1.036 ms against 1.026 / 1.032 ms with the ballots: the per-element divergent branches cost more than the ballots
+// they replace.
 constexpr int kRowsPerBlock = 4;   // one wave per row
 constexpr int kMaxK = 8;
 constexpr int kMaxCand = 64;
@@ -332,15 +325,6 @@ __global__ __launch_bounds__(256) void gumbel_race_weights_kernel(const float *_
 // groups of g in 32 REGISTERS instead of an LDS row cache, and none of the per-iteration mode tests of load_group exist.
 // Measured at 32 x 1024 x 2000 (scratch/ab_k1.py): general kernel 77.7 us in test mode (Philox 29.5, the two logarithms
 // 7.7, everything else 42-48), this kernel 60.0 us (everything else: 29); train mode 88.1 -> 74.4 us.
-#ifndef DR_K1_SALU_SELECT
-#define DR_K1_SALU_SELECT 1   // the selection on wave compare masks (0 = the LDS list of rounds 2-5: A/B); 2 = the one-logarithm form only
-#endif
-#ifndef DR_K1_WV_SGPR
-#define DR_K1_WV_SGPR 1     // the wave index through v_readfirstlane (row, seed, Philox round keys in SGPRs); 2 = index-only mode only
-#endif
-#ifndef DR_K1_DBG_SELECT
-#define DR_K1_DBG_SELECT 0
-#endif
 constexpr int kFastGroups = 8;   // groups per lane: 64 lanes x 8 groups x 4 elements = 2048
 
 // train mode, K2 fused: the correspondence times the straight-through weight (1 - y) + y (gumbel_sampler.py:40: y_hard -
@@ -376,19 +360,11 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
   static_assert(!(kSoft && kScreen), "the soft-max statistics need every element's score");
   __shared__ float s_val[kRowsPerBlock][kMaxCand];
   __shared__ int s_idx[kRowsPerBlock][kMaxCand];
-#if DR_K1_PASSB_ATOMIC
-  __shared__ int s_cnt[kRowsPerBlock];
-#endif
-#if DR_K1_PASSB_LDS
-  constexpr int kHotMax = 8, kHotStride = 4 * kFastGroups + 4;   // stride 36 words: rows start in different banks, 16 B aligned
-  __shared__ __align__(16) float s_stage[kRowsPerBlock][kHotMax * kHotStride];
-  __shared__ int s_hot[kRowsPerBlock][kHotMax];
-#endif
   if (seed_ptr) seed = *seed_ptr;
   // (the wave index through v_readfirstlane: the row, its seed and the twelve Philox round keys then live in SGPRs)
   const int lane = threadIdx.x & 63;
   int wv = threadIdx.x >> 6;
-  if (DR_K1_WV_SGPR == 1 || (DR_K1_WV_SGPR == 2 && !kSoft)) wv = __builtin_amdgcn_readfirstlane(wv);
+  wv = __builtin_amdgcn_readfirstlane(wv);
   const int p = blockIdx.y, b = blockIdx.x * kRowsPerBlock + wv;
   if (b >= B) return;   // whole wave exits together (no block-level barrier is used below)
   int bq;
@@ -542,14 +518,9 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
   // the soft-max weight of a selected score (kSoft)
   auto y_of = [&](float score) { return race ? __builtin_amdgcn_rcpf(-score) * inv_sm : exp_t<float>(score - wmx) * inv_sm; };
 
-#if DR_K1_DBG_SELECT == 1   // timing experiments (scratch/ab_k1_sel.py): pass A alone
-  if (lane < k) idx[row * k + lane] = __float_as_int(lmax);
-  return;
-#endif
   // ---------------- threshold: any t that at least k LANE MAXIMA reach has the k winners among { g >= t }
   bool settled = false;   // (wave-uniform)
   float thr = -INFINITY;
-#if DR_K1_SALU_SELECT
   if constexpr (!kScreen) if (race) {
     // Round 6, the one-logarithm form: t by COUNTING.  The keys of a pair are a Poisson process in t: E #{ key >= t } = -t c_p with
     // c_p = ln 2 sum_n 1 / w_n (gumbel_race_weights_kernel), so t is searched as t = -lam / c_p from lam = 6: a compare + a count per
@@ -570,7 +541,6 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
     }
     if (have_lo && clo <= 16) { settled = true; thr = tlo; }
   }
-#endif
   if (!settled) {   // the k-th largest lane maximum: k rounds of a wave-wide maximum
     float v = lmax;
     for (int r = 0; r < k; ++r) {
@@ -579,19 +549,14 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
       if (lane == __ffsll((long long)who) - 1) v = -INFINITY;
     }
   }
-#if DR_K1_DBG_SELECT == 2   // pass A + threshold
-  if (lane < k) idx[row * k + lane] = __float_as_int(thr);
-  return;
-#endif
 
-#if DR_K1_SALU_SELECT
-  if constexpr (!kScreen) if (DR_K1_SALU_SELECT == 1 || settled) {
+  if constexpr (!kScreen) {
     // ---------------- round 6: the selection on wave compare masks (scalar unit), no LDS -------------------------------------------
     // The candidates { g >= thr } are read off 32 compare masks by the scalar unit in ascending point index -- group, lane,
     // component -- and dealt to lanes 0 .. n-1 (a v_readlane and two selects under the scalar mask of lane n): n == k needs no
     // ranking at all; n > k ranks by (value, index) over v_readlane.  Same winners, same output order as the list below (the total
     // order is the same); a row with more than 64 candidates takes the list.  (profiles/r6_k1_selection.md: 789 -> 578 vector
-    // instructions per row in the one-logarithm form, identical outputs on 99 cases, scratch/k1_select_check.py.  Keeping the
+    // instructions per row in the one-logarithm form, identical outputs on 99 cases against the LDS list alone.  Keeping the
     // group maxima from pass A and testing them first: 0.8985-0.8998 vs 0.8963-0.8968 ms per step without -- not kept.)
     int n = 0;
     int cv_i = __float_as_int(-INFINITY), ci = 0x7fffffff;
@@ -653,73 +618,9 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
       }
     }
   }
-#endif
 
   // ---------------- pass B: the candidates { g >= thr } into the wave's LDS list
   int ncand = 0;
-#if DR_K1_PASSB_ATOMIC
-  // Only the lanes whose maximum reaches the threshold (k .. ~10 of 64) hold candidates: they walk their own elements and take
-  // list slots with an LDS counter.  The list order is then arbitrary -- the ranking below is by (value, index), a total order,
-  // so the result does not depend on it.  (Round 2's wave-wide compaction kept the general kernel's order with a ballot, a
-  // popcount and an mbcnt per element of every group that holds a candidate: ~160 of the ~250 vector instructions the
-  // selection costs per row.)
-  if (lane == 0) s_cnt[wv] = 0;
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  if (lmax >= thr) {
-#pragma unroll
-    for (int i = 0; i < kFastGroups; ++i) {
-      if (!(fmaxf(fmaxf(g[i][0], g[i][1]), fmaxf(g[i][2], g[i][3])) >= thr)) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (g[i][j] >= thr) {
-          const int pos = atomicAdd(&s_cnt[wv], 1);
-          if (pos < kMaxCand) { cand_val[pos] = g[i][j]; cand_idx[pos] = 4 * (lane + 64 * i) + j; }
-        }
-      }
-    }
-  }
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  ncand = s_cnt[wv];
-#else
-#if DR_K1_PASSB_LDS
-  // Only the lanes whose maximum reaches the threshold hold candidates: exactly k of 64 unless values tie.  They park their 32
-  // values in LDS (eight 16-byte writes under one exec mask) and the WAVE scans the k x 32 values, 64 per step: three steps
-  // for k = 5 instead of a compare + branch per element of every group and a ballot / popcount / mbcnt per candidate.  The
-  // list order differs from the element-order scan; the ranking below is by (value, index), a total order, so the winners and
-  // their output positions do not depend on it.
-  const unsigned long long hotb = __ballot(lmax >= thr);
-  const int nhot = __popcll(hotb);
-  if (nhot <= kHotMax) {
-    float *stage = s_stage[wv];
-    if (lmax >= thr) {
-      const int hr = __popcll(hotb & ((1ull << lane) - 1ull));
-#pragma unroll
-      for (int i = 0; i < kFastGroups; ++i)
-        *reinterpret_cast<float4 *>(stage + hr * kHotStride + 4 * i) = make_float4(g[i][0], g[i][1], g[i][2], g[i][3]);
-      s_hot[wv][hr] = lane;
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    const int total = nhot * 4 * kFastGroups;
-#pragma unroll 1
-    for (int base = 0; base < total; base += 64) {
-      const int sl = base + lane;
-      const bool in = sl < total;
-      const int h = in ? sl / (4 * kFastGroups) : 0, e = sl % (4 * kFastGroups);
-      const float val = in ? stage[h * kHotStride + e] : -INFINITY;
-      const int src = s_hot[wv][h];
-      const bool c = in && val >= thr;
-      const unsigned long long bal = __ballot(c);
-      if (bal) {
-        const int pos = ncand + __popcll(bal & ((1ull << lane) - 1ull));
-        if (c && pos < kMaxCand) { cand_val[pos] = val; cand_idx[pos] = 4 * (src + 64 * (e >> 2)) + (e & 3); }
-        ncand += __popcll(bal);
-      }
-    }
-  } else
-#endif
 #pragma unroll
   for (int i = 0; i < kFastGroups; ++i) {
     if (64 * i >= groups) break;   // wave-uniform
@@ -738,7 +639,6 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
   __builtin_amdgcn_wave_barrier();
-#endif
 
   if (ncand <= kMaxCand) {
     const bool have = lane < ncand;
@@ -890,9 +790,6 @@ __global__ __launch_bounds__(256) void gumbel_screen_kernel(const float *__restr
 //     T from the WHOLE row itself -- the same loads, the same order, hence the same value in every block (block 0 publishes it) --
 //     which costs a block ~12 float4 loads and ~50 exponentials per thread at 50 000 points (the row is 200 KB: L2 / MALL hits
 //     after the first block) and saves the partial-sum launch with its dependency: 4.1 + 4.8 us + a graph edge -> one kernel.
-#ifndef DR_K1_SCREEN_FUSED
-#define DR_K1_SCREEN_FUSED 1
-#endif
 __global__ __launch_bounds__(1024) void gumbel_screen_fused_kernel(const float *__restrict__ logits, int N, float lambda,
                                                                   float *__restrict__ T_out, uint32_t *__restrict__ tb) {
   __shared__ float s_mx[16], s_sm[16];
@@ -1002,12 +899,6 @@ __global__ __launch_bounds__(256) void gumbel_screen_short_kernel(const float *_
 // lists at the end by k rounds of arg-max over the lanes' heads.  Same Philox counters, same g, same order (value
 // descending, index ascending): the index sets are those of the general kernel (tests/test_gpu_round2.py).
 // f32, in-kernel noise, logits given, tau = 1, N % 4 == 0, no dense outputs.
-#ifndef DR_K1_STREAM
-#define DR_K1_STREAM 1   // 0: the general two-pass kernel (A/B builds)
-#endif
-#ifndef DR_K1_STREAM_SPLIT
-#define DR_K1_STREAM_SPLIT 1   // 0: always one wave per row
-#endif
 // kW = waves per row (1 or kRowsPerBlock).  With few rows (BASELINE configs[3]: 2048 hypotheses of ONE pair) a wave per row is
 // two waves per SIMD on this chip: the kernel's 32 registers would allow eight, and its dependent Philox rounds and logarithms
 // want them.  kW = 4: the block's four waves take interleaved 64-group slices of ONE row, each keeps the top k of its slice,
@@ -1200,7 +1091,7 @@ static void stream_launch(bool soft, dim3 grid, dim3 block, hipStream_t st, cons
                           const float *Tp = nullptr, int sub = 0) {
   // few rows: four waves per row (one row per block) -- the wave-per-row grid would leave the SIMDs at <= 4 waves each
   const long rows = (long)grid.y * B;
-  if (DR_K1_STREAM_SPLIT && rows <= 4096 && N >= 4 * 64 * 4 * 4) {
+  if (rows <= 4096 && N >= 4 * 64 * 4 * 4) {
     const dim3 g2(B, grid.y);
     if (soft) hipLaunchKernelGGL((gumbel_topk_stream_kernel<K, true, kRowsPerBlock>), g2, block, 0, st, logits, seed, B, N, k, idx, y_sel, lse, seed_ptr);
     else hipLaunchKernelGGL((gumbel_topk_stream_kernel<K, false, kRowsPerBlock>), g2, block, 0, st, logits, seed, B, N, k, idx, y_sel, lse, seed_ptr, tb, Tp, sub);
@@ -1228,7 +1119,7 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
   dim3 block(kRowsPerBlock * 64);
   const bool soft = y_sel != nullptr;   // the entry points have checked: y_sel and lse both given, or neither (then no dense outputs)
   if constexpr (sizeof(T) == 4) {
-    if (DR_K1_FAST && logits && !gumbel && tau == T(1) && (N & 3) == 0 && N <= 4 * 64 * kFastGroups && !y_soft && !ret && !gumbel_out) {
+    if (logits && !gumbel && tau == T(1) && (N & 3) == 0 && N <= 4 * 64 * kFastGroups && !y_soft && !ret && !gumbel_out) {
       if (soft) {
         if (race_ws && !race_ready)
           hipLaunchKernelGGL(gumbel_race_weights_kernel, dim3(P), dim3(256), 0, st, (const float *)logits, N, P, race_ws);
@@ -1257,9 +1148,9 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
       }
       return check_launch("gumbel_topk_fast_kernel");
     }
-    // measured (scratch/ab_k1_stream.py): 50 000 x 2048 rows, k = 3: 226 -> 113 us; 4096 x 32 768 rows, k = 5: 196 -> 178 us;
+    // measured against the general two-pass kernel: 50 000 x 2048 rows, k = 3: 226 -> 113 us; 4096 x 32 768 rows, k = 5: 196 -> 178 us;
     // k = 8 lists cost what the second pass costs (256 vs 250 us at N = 20 000) -> the general kernel keeps k > 5
-    if (DR_K1_STREAM && logits && !gumbel && tau == T(1) && (N & 3) == 0 && N > 4 * 64 * kFastGroups && k <= 5 && !y_soft && !ret &&
+    if (logits && !gumbel && tau == T(1) && (N & 3) == 0 && N > 4 * 64 * kFastGroups && k <= 5 && !y_soft && !ret &&
         !gumbel_out) {
       const uint32_t *tb = nullptr;
       const float *Tp = nullptr;
@@ -1267,7 +1158,7 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
         // workspace: P x N words + P scores + P x 16 partial sums; lambda = 20 + k: P(fewer than k of a row's points reach T) < 1e-7
         float *Tw = reinterpret_cast<float *>(screen_ws + (size_t)P * N);
         float *part = Tw + P;
-        if (DR_K1_SCREEN_FUSED && (long)((N + 1023) / 1024) * N <= (16L << 20)) {   // (row re-reads bounded: beyond, the two-launch form)
+        if ((long)((N + 1023) / 1024) * N <= (16L << 20)) {   // (row re-reads bounded: beyond, the two-launch form)
           hipLaunchKernelGGL(gumbel_screen_fused_kernel, dim3((N + 1023) / 1024, P), dim3(1024), 0, st, (const float *)logits, N,
                              (float)(20 + k), Tw, screen_ws);
         } else {
@@ -1301,10 +1192,6 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
   return check_launch("gumbel_topk_kernel");
 }
 
-#ifndef DR_K1_BWD_RACE
-#define DR_K1_BWD_RACE 1
-#endif
-
 // ---- backward of K1 (+K2):  grad_logits[p,n] = (1/tau) sum_b y_bn (a_bn - sum_m y_bm a_bm), a non-zero only at idx
 template <typename T>
 __global__ __launch_bounds__(256) void gumbel_bwd_kernel(GumbelArgs<T> a, const int32_t *__restrict__ idx,
@@ -1334,7 +1221,6 @@ __global__ __launch_bounds__(256) void gumbel_bwd_kernel(GumbelArgs<T> a, const 
     l[j] = (n < a.N) ? (a.logits ? a.logits[(size_t)p * a.N + n] : T(1)) : T(0);
   }
   const int b_lo = blockIdx.z * rows_per_block, b_hi = min(a.B, b_lo + rows_per_block);
-#if DR_K1_BWD_RACE
   // f32, in-kernel noise, tau = 1: y = exp(l + G - lse) with exp(G) = 1 / (-ln u) = -1 / (ln2 log2 u), so
   //   y dot = w_j [exp(lref - lse) dot / ln2] (-1 / log2 u),   w_j = exp(l_j - lref) constant over the rows:
   // per element convert, fma, ONE logarithm, a reciprocal and an fma -- the second logarithm, the add, the subtract, the
@@ -1347,7 +1233,6 @@ __global__ __launch_bounds__(256) void gumbel_bwd_kernel(GumbelArgs<T> a, const 
 #pragma unroll
   for (int j = 1; j < 4; ++j) lref = (4 * q + j < a.N) ? fmaxf(lref, (float)l[j]) : lref;
   float racc[4] = {0.f, 0.f, 0.f, 0.f};
-#endif
   for (int b0 = b_lo; b0 < b_hi; b0 += 256) {
     const int nb = min(256, b_hi - b0);
     __syncthreads();
@@ -1400,7 +1285,6 @@ __global__ __launch_bounds__(256) void gumbel_bwd_kernel(GumbelArgs<T> a, const 
       }
     }
     __syncthreads();
-#if DR_K1_BWD_RACE
     if (race) {
       if (q < groups) {
         for (int r = 0; r < nb; ++r) {
@@ -1413,7 +1297,6 @@ __global__ __launch_bounds__(256) void gumbel_bwd_kernel(GumbelArgs<T> a, const 
       }
       continue;
     }
-#endif
     if (q < groups) {
       for (int r = 0; r < nb; ++r) {
         const int b = b0 + r;
@@ -1436,12 +1319,10 @@ __global__ __launch_bounds__(256) void gumbel_bwd_kernel(GumbelArgs<T> a, const 
       }
     }
   }
-#if DR_K1_BWD_RACE
   if (race) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] += (T)(__expf((float)l[j] - lref) * racc[j]);
   }
-#endif
 #pragma unroll
   for (int j = 0; j < 4; ++j)
     if (4 * q + j < a.N) atomicAdd(grad_logits + (size_t)p * a.N + 4 * q + j, acc[j] / a.tau);
@@ -1611,14 +1492,8 @@ static int gumbel_bwd_impl(const T *logits, const T *gumbel, uint64_t seed, cons
   const size_t smem = sizeof(T) * 256 * 2;
   const int gx = ((N + 3) / 4 + 255) / 256;
   // enough row chunks to put >= ~2048 blocks on the chip, at least 32 rows each
-#ifndef DR_K1_BWD_BLOCKS
-#define DR_K1_BWD_BLOCKS 2048
-#endif
-#ifndef DR_K1_BWD_MINROWS
-#define DR_K1_BWD_MINROWS 32
-#endif
-  int chunks = (int)std::min<long>((B + DR_K1_BWD_MINROWS - 1) / DR_K1_BWD_MINROWS,
-                                   std::max<long>(1, DR_K1_BWD_BLOCKS / std::max<long>(1, (long)gx * P)));
+  constexpr long kBwdBlocks = 2048, kBwdMinRows = 32;
+  int chunks = (int)std::min<long>((B + kBwdMinRows - 1) / kBwdMinRows, std::max<long>(1, kBwdBlocks / std::max<long>(1, (long)gx * P)));
   const int rows_per_block = (B + chunks - 1) / chunks;
   chunks = (B + rows_per_block - 1) / rows_per_block;
   if (hipMemsetAsync(grad_logits, 0, sizeof(T) * (size_t)P * N, (hipStream_t)stream) != hipSuccess)

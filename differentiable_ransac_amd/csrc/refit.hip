@@ -93,9 +93,6 @@ __device__ __forceinline__ void refit_essential_pair(const T *__restrict__ mt, c
   double *red = gram + 81;
   const double mu[4] = {0, 0, 0, 0};
   gram_accumulate<false, T>(mt, mk, static_cast<const T *>(nullptr), N, mu, 1.0, 1.0, gram, red);
-#if defined(DR_REFIT_STOP) && DR_REFIT_STOP == 1
-  return;
-#endif
   if (threadIdx.x >= 64) return;
   // the rest is one latency-bound wave per pair, usually running next to the scoring kernel of the same call (8 VALU-bound
   // waves per SIMD): raise its issue priority so that it proceeds at its own pace and the scoring waves fill the gaps
@@ -115,10 +112,6 @@ __device__ __forceinline__ void refit_essential_pair(const T *__restrict__ mt, c
 #pragma unroll
       for (int r = 0; r < 9; ++r) nb[3 - t][r] = ev[t][r];
   }
-#if defined(DR_REFIT_STOP) && DR_REFIT_STOP == 2
-  if (lane == 0) models[0] = (T)nb[0][0];
-  return;
-#endif
   double e[3][3][4];
   basis_to_entries(nb, e);
   LaneWs w{lds, 1};   // every lane solves the same system: one shared slot, same-address writes of equal values

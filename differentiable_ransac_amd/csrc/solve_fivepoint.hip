@@ -11,18 +11,6 @@
 // -> Gauss-Newton polish on the defining constraints -> verification.
 #include "fivepoint_device.hpp"
 
-// 1: the two-phase Nister kernel hands over B(z) only and computes the null-space basis again in the back pass (A/B, round 5)
-#ifndef DR_K3_FB_REBASIS
-#define DR_K3_FB_REBASIS 0
-#endif
-// waves per SIMD the minimal-sample kernels are compiled for (register budget = 512 / DR_K3_WAVES)
-#ifndef DR_K3_WAVES
-#define DR_K3_WAVES 1
-#endif
-// 1: the candidates of a wave are dealt out evenly over its lanes for the polish / verification stage (balanced_finish)
-#ifndef DR_K3_BALANCED
-#define DR_K3_BALANCED 1
-#endif
 
 namespace dr {
 
@@ -58,9 +46,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
 // out over the wave instead of staying with its lane: brackets that hold a sign change (real_roots_half_wave: 1083 of the
 // 3520 bracket refinements a wave used to run) and candidate solutions (balanced_finish: ~150 per wave, 2.3 per lane,
 // where the busiest lane has 6-7).  Same arithmetic per bracket / candidate, so the output is bit-identical to the
-// per-lane version (-DDR_K3_BALANCED=0 -DDR_K3_WAVE_ROOTS=0); 105 -> 72 us at 32 pairs x 1024, 386 -> 265 us at 128 pairs.
+// per-lane version of round 1; 105 -> 72 us at 32 pairs x 1024, 386 -> 265 us at 128 pairs.
 template <typename T>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DR_K3_WAVES, DR_K3_WAVES))) void nister5_pair_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void nister5_pair_kernel(
     const T *__restrict__ samples, const T *__restrict__ weights, int Bt, T *__restrict__ models,
     uint8_t *__restrict__ valid, double *__restrict__ models64, int spb, PairGate gate, int per_pair) {
   // gate (rounds > 1 of a multi-round call): a block all of whose samples belong to terminated pairs returns at once
@@ -84,14 +72,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DR_K3_WAVES,
   double e[3][3][4];
   basis_to_entries(nb, e);
   double X[6][10];
-  const bool ok = constraints_reduce<NisterOrder, 4, DR_K3_BALANCED != 0>(e, w, 1.0, X, lane & 1);
+  const bool ok = constraints_reduce<NisterOrder, 4, true>(e, w, 1.0, X, lane & 1);
   DR_STAGE(2);
-#if DR_K3_BALANCED
   nister_finish_pair<T>(nb, X, ok, lds, lane, (size_t)blockIdx.x * spb, active, models, valid, models64);
-#else
-  nister_finish<T, true>(nb, X, ok, models + (size_t)sc * 90, valid + (size_t)sc * 10, active, lane & 1,
-                         models64 ? models64 + (size_t)sc * 90 : nullptr);
-#endif
   DR_STAGE(5);
 }
 
@@ -102,9 +85,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DR_K3_WAVES,
 // roots come from the same root finder; the eigenvector follows from rows 0-5 of (M - lambda I) v = 0 with
 // the structural rows substituted (stewenius_xyz_of_roots).  Everything after the constraint solve is statically indexed and
 // lives in VGPRs; like the Nister kernel, two lanes share one sample and each takes one half of the root search.
-// (The per-lane final stage of round 1, -DDR_K3_BALANCED=0, is gone from this kernel in round 5: the balanced one is the product.)
 template <typename T>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DR_K3_WAVES, DR_K3_WAVES))) void stewenius5_pair_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void stewenius5_pair_kernel(
     const T *__restrict__ samples, int Bt, T *__restrict__ models, uint8_t *__restrict__ valid, int spb, PairGate gate, int per_pair) {
   if (gate.closed_range((blockIdx.x * spb) / per_pair, (min(blockIdx.x * spb + spb, Bt) - 1) / per_pair)) return;
   // spb = samples per block (32, or 16 / 8 / 4 on small grids): see nister5_pair_kernel
@@ -138,11 +120,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DR_K3_WAVES,
 #pragma unroll
     for (int t = 0; t <= 10; ++t) cs[t] = (t == 0 || t == 10) ? 1.0 : 0.0;
   }
-#if DR_K3_STURM
   real_roots_half_sturm<10>(cs, half != 0, roots, nroots, lds, lane);   // the right block's LDS is free again
-#else
-  real_roots_half_wave<10>(cs, half != 0, roots, nroots, lds, lane);
-#endif
   if (!ok || !active) nroots = 0;
   // eigenvector of every root per lane (cheap), then polish / verification dealt out over the wave (balanced_finish)
   const FinishQueue fq(lds);   // the root-search workspace is dead: basis, candidate queue and vectors take its place
@@ -172,11 +150,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   if (gate.closed_range((blockIdx.x * 64) / per_pair, (min(blockIdx.x * 64 + 64, Bt) - 1) / per_pair)) return;
   extern __shared__ __align__(16) double lds[];
   const int lane = threadIdx.x;
-#if DR_K3_FB_REBASIS
-  AccDouble hand[39];        // this lane's sample: B(z) (the basis is computed again by the sample's lane pair in its pass)
-#else
   AccDouble hand[36 + 39];   // this lane's sample: basis | B(z)
-#endif
   double cs[11];
   DR_STAGE_BEGIN();
   {
@@ -187,12 +161,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     {
       double nb[4][9];
       fivepoint_basis_minimal<T>(samples + (size_t)sc * 20, weights ? weights + (size_t)sc * 5 : nullptr, nb);
-#if !DR_K3_FB_REBASIS
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int q = 0; q < 9; ++q) hand[9 * t + q].put(nb[t][q]);
-#endif
       basis_to_entries(nb, e);
     }
     double X[6][10];
@@ -200,7 +172,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     double bz[39];
     nister_bz_det(X, bz, cs);
 #pragma unroll
-    for (int k = 0; k < 39; ++k) hand[(DR_K3_FB_REBASIS ? 0 : 36) + k].put(bz[k]);
+    for (int k = 0; k < 39; ++k) hand[36 + k].put(bz[k]);
     if (!ok || !act) {   // 1 + z^10: no real root in either half of the search, no bracket in the wave's queues
 #pragma unroll
       for (int i = 0; i <= 10; ++i) cs[i] = (i == 0 || i == 10) ? 1.0 : 0.0;
@@ -212,25 +184,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     const size_t s0 = (size_t)blockIdx.x * 64 + 32 * p;
     if (s0 >= (size_t)Bt) break;
     wave_lds_order();   // the front stage / the previous pass is done with the LDS
-#if DR_K3_FB_REBASIS
-    if ((lane >> 5) == p) {
-      double *img = lds + 36 * 32 + (lane & 31);   // FinishQueue layout: B(z) behind the basis
-#pragma unroll
-      for (int k = 0; k < 39; ++k) img[k * 32] = hand[k].get();
-    }
-    {
-      const size_t sj = s0 + (lane >> 1) < (size_t)Bt ? s0 + (lane >> 1) : (size_t)Bt - 1;
-      double nb[4][9];
-      fivepoint_basis_minimal<T>(samples + sj * 20, weights ? weights + sj * 5 : nullptr, nb);
-      park_basis(FinishQueue(lds), nb, lane);
-    }
-#else
     if ((lane >> 5) == p) {
       double *img = lds + (lane & 31);   // FinishQueue layout: basis element e of sample j at [e * 32 + j], then B(z)
 #pragma unroll
       for (int k = 0; k < 36 + 39; ++k) img[k * 32] = hand[k].get();
     }
-#endif
     double csp[11];
 #pragma unroll
     for (int i = 0; i <= 10; ++i) csp[i] = lane_read(cs[i], 32 * p + (lane >> 1));
@@ -299,11 +257,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     }
     double roots[10];
     int nroots;
-#if DR_K3_STURM
     real_roots_half_sturm<10>(csp, half != 0, roots, nroots, lds, lane);
-#else
-    real_roots_half_wave<10>(csp, half != 0, roots, nroots, lds, lane);
-#endif
     if (!active) nroots = 0;
     const FinishQueue fq(lds);
     {
@@ -327,10 +281,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   }
 }
 
-static inline bool aligned_out(const void *models, const void *valid) {
-  return !DR_K3_STAGE_OUT || ((reinterpret_cast<uintptr_t>(models) & 15u) == 0 && (reinterpret_cast<uintptr_t>(valid) & 3u) == 0);
-}
-
 // SIMDs of the current device (4 per CU), cached per device: one process may drive several GPUs
 static inline int device_simds() {
   static int simds[64] = {0};
@@ -346,24 +296,20 @@ static inline int device_simds() {
 
 // samples per 64-lane block of the two-lanes-per-sample kernels: 32, or fewer (down to 4) while the grid stays within one block
 // per SIMD -- a one-pair call (1024 samples) is 256 blocks of 4 samples instead of 32 blocks of 32 on 1024 SIMDs.  Always even
-// (>= 4): the staged-output alignment of balanced_finish relies on s0 * 90 floats being a multiple of 16 bytes.
+// (>= 4).
 static inline int samples_per_block(int Bt) {
   int spb = 32;
   const int simds = device_simds();
   while (spb > 4 && (long)(Bt + spb / 2 - 1) / (spb / 2) <= simds) spb /= 2;
-  return spb;   // 32, 16, 8 or 4: even, so a block's first output row (s0 * 90 floats, s0 * 10 bytes) keeps the staged-output alignment
+  return spb;   // 32, 16, 8 or 4
 }
 
 // Two-phase kernels or lane pairs?  A pair-kernel block (32 samples) costs kPairCost, a two-phase block (64 samples) kFbCost
 // (relative units from the measured kernels, profiles/r5_k3_variants.md); blocks run one per SIMD, so a launch takes
 // ceil(blocks / SIMDs) rounds.  131 072 samples: 4 x pair against 2 x two-phase; 32 768 samples (one round of pair blocks
 // on 1024 SIMDs) stay with the lane pairs, which also serve the small grids (samples_per_block).
-#ifndef DR_K3_FB_COST_NISTER
-#define DR_K3_FB_COST_NISTER 174   // per cent of a pair-kernel block (measured: 132.9 us in two rounds against 153.4 in four)
-#endif
-#ifndef DR_K3_FB_COST_STEW
-#define DR_K3_FB_COST_STEW 183     // (171.8 us in two rounds against 187.6 in four)
-#endif
+constexpr int kFbCostNister = 174;   // per cent of a pair-kernel block (measured: 132.9 us in two rounds against 153.4 in four)
+constexpr int kFbCostStew = 183;     // (171.8 us in two rounds against 187.6 in four)
 static inline bool fivepoint_two_phase(int Bt, int fb_cost_pct) {
   const long simds = device_simds();
   const long rounds_pair = ((Bt + 31) / 32 + simds - 1) / simds;
@@ -386,9 +332,9 @@ int nister_launch(const T *samples, const T *weights, int Bt, int n, T *models, 
   if (n == 5) {
     // minimal samples: two lanes per sample; LDS per 32-sample block: 100 doubles per sample for the constraint solve,
     // later basis + B(z) / candidate queue + root-search workspace (36.5 KiB => four blocks per CU, one per SIMD)
-    const size_t smem = sizeof(double) * (DR_K3_BALANCED ? kNisterPairDoubles : 100 * 32);
-    if (DR_K3_BALANCED && (path == 2 || (path == 0 && fivepoint_two_phase(Bt, DR_K3_FB_COST_NISTER)))) {
-      static_assert(!DR_K3_BALANCED || 70 * 64 <= kNisterPairDoubles, "front stage: rows 0-6 of 64 right blocks");
+    const size_t smem = sizeof(double) * kNisterPairDoubles;
+    if (path == 2 || (path == 0 && fivepoint_two_phase(Bt, kFbCostNister))) {
+      static_assert(70 * 64 <= kNisterPairDoubles, "front stage: rows 0-6 of 64 right blocks");
       hipLaunchKernelGGL((nister5_fb_kernel<T>), dim3((Bt + 63) / 64), dim3(64), smem, st, samples, weights, Bt, models, valid,
                          models64, gate, per_pair);
       return check_launch("nister5_fb_kernel");
@@ -411,7 +357,7 @@ int stewenius_launch(const T *samples, int Bt, T *models, uint8_t *valid, hipStr
   // the right 10x10 block of 32 samples, later the root-search workspace, then the candidate queue
   constexpr int kDoubles = (FinishQueue::kDoubles > 100 * 32) ? FinishQueue::kDoubles : 100 * 32;
   static_assert(RootWs<10>::kDoubles <= kDoubles && SturmWs<10>::kDoubles <= kDoubles, "root-search workspace");
-  if (path == 2 || (path == 0 && fivepoint_two_phase(Bt, DR_K3_FB_COST_STEW))) {
+  if (path == 2 || (path == 0 && fivepoint_two_phase(Bt, kFbCostStew))) {
     // front stage: rows 0-6 of 64 right blocks (35 KiB); back: root search / candidate queue + the reduced rows of 32 samples
     constexpr int kBack = (SturmWs<10>::kDoubles > FinishQueue::kDoubles ? SturmWs<10>::kDoubles : FinishQueue::kDoubles) + 60 * 32;
     constexpr int kFb = 70 * 64 > kBack ? 70 * 64 : kBack;
@@ -430,13 +376,10 @@ int stewenius_launch(const T *samples, int Bt, T *models, uint8_t *valid, hipStr
 // ---- test hook: the real-root search of the two-lanes-per-sample kernels on given degree-10 polynomials -------------------
 // One lane pair per polynomial (even lane: |z| <= 1, odd lane: |z| > 1 through the reversed polynomial), exactly as the solver
 // kernels call it.  method 0 = derivative chain (real_roots_half_wave), 1 = Sturm isolation (real_roots_half_sturm).
-// DR_DBG_ROOTS_WAVES (round 6 experiment): waves per SIMD the standalone root-search kernel is compiled for -- what a separate
-// root-search LAUNCH between a front and a finish kernel would run at (scratch/roots_occupancy.py)
-#ifndef DR_DBG_ROOTS_WAVES
-#define DR_DBG_ROOTS_WAVES 1
-#endif
+// (Round 6 experiment: this kernel compiled for more waves per SIMD -- what a separate root-search LAUNCH between a front and a
+// finish kernel would run at.)
 template <int kMethod>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DR_DBG_ROOTS_WAVES, DR_DBG_ROOTS_WAVES))) void debug_roots10_kernel(const double *__restrict__ coef, int n, double *__restrict__ roots,
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void debug_roots10_kernel(const double *__restrict__ coef, int n, double *__restrict__ roots,
                                                            int32_t *__restrict__ counts) {
   extern __shared__ __align__(16) double lds[];
   const int lane = threadIdx.x, half = lane & 1;
@@ -472,7 +415,6 @@ extern "C" {
 int dr_solve_nister5_f32(const float *samples, const float *weights, int Bt, int n, float *models, double *models_f64, uint8_t *valid,
                          int path, int per_pair, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
   DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(dr::aligned_out(models, valid), "models must be 16-byte aligned and valid 4-byte aligned (whole-line output stores)");
   DR_REQUIRE(Bt > 0 && n >= 5, "need Bt > 0 and n >= 5 points per sample");
   DR_REQUIRE(path >= 0 && path <= 2, "path: 0 automatic, 1 lane pairs, 2 two-phase");
   DR_REQUIRE(n == 5 || (!models_f64 && path == 0 && !gate_iters), "f64 models, explicit paths and gates serve minimal samples (n = 5)");
@@ -506,7 +448,6 @@ int dr_debug_real_roots10(const double *coef, int n, int method, double *roots, 
 int dr_solve_stewenius5_f32(const float *samples, int Bt, float *models, uint8_t *valid, int path, int per_pair,
                             const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
   DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(dr::aligned_out(models, valid), "models must be 16-byte aligned and valid 4-byte aligned (whole-line output stores)");
   DR_REQUIRE(Bt > 0, "need Bt > 0");
   DR_REQUIRE(path >= 0 && path <= 2, "path: 0 automatic, 1 lane pairs, 2 two-phase");
   DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither");

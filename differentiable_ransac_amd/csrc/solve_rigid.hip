@@ -235,43 +235,23 @@ __global__ __launch_bounds__(kRThreads) void rigid_residual_kernel(const T *__re
 // (NaN -> 0 = outlier), packed with v_perm_b32 like the MSAC masks (1.25 instructions per point instead of 3.5), plain
 // LDS read-modify-write of a wave-private partial, and 16-model tiles (twice as many, half as long blocks: the 3 200 waves
 // of a 32-model grid were 3.1 per SIMD -- SIMDs with four waves set the time, the others idled a quarter of it).
-#ifndef DR_K4R_16
-#define DR_K4R_16 1
-#endif
-#ifndef DR_K4R_PTS
-#define DR_K4R_PTS 8    // points per lane of the packed kernel: 8 (round 5) or 16 (rounds 2-4).  Config 4, same box, in the step
-                        // (scratch/runs/r5_gpu_ab.sh, r5_gpu_ac.sh): launch 46.1 -> 43.4 us under rocprofv3 (0.281 -> 0.298 of HBM),
-                        // step 0.1335 -> 0.1297 ms; 76 registers = six waves per SIMD instead of three; an occupancy hint of
-                        // seven waves: 0.1323, of eight (spills): 0.153
-#endif
-#ifndef DR_K4R_GROUP8
-#define DR_K4R_GROUP8 1  // models per scalar fetch of the 8-point form (1: 0.1296, 2: 0.1300-0.1305, 3: 0.1305, 4: 0.1306, 8: 0.1402 ms):
-                         // at six waves per SIMD the scalar-cache round trip of a model hides behind the other waves
-#endif
-#ifndef DR_K4R_TILE
-#define DR_K4R_TILE 0    // > 0: fixed models per block (A/B builds); 0: chosen per launch so that the grid is whole rounds of blocks
-#endif
-constexpr int kR16Threads = 128, kR16Pts = 16, kR16Chunk = kR16Threads * kR16Pts, kR16MaxTile = 64;
+// Round 5: EIGHT points per lane instead of the sixteen of rounds 2-4 (an 8-byte mask store per lane and model instead of a 16-byte
+// one, the per-model reduction shared by half as many points).  Config 4, same box, in the step (scratch/runs/r5_gpu_ab.sh,
+// r5_gpu_ac.sh): launch 46.1 -> 43.4 us under rocprofv3 (0.281 -> 0.298 of HBM), step 0.1335 -> 0.1297 ms; 76 registers = six waves
+// per SIMD instead of three (138 registers); an occupancy hint of seven waves: 0.1323, of eight (spills): 0.153; a register budget
+// pinned to four waves spills two point registers.  Models per scalar fetch (1: 0.1296, 2: 0.1300-0.1305, 3: 0.1305, 4: 0.1306,
+// 8: 0.1402 ms; the sixteen-point form fetched four together): one -- at six waves per SIMD the scalar-cache round trip of a model
+// hides behind the other waves.
+constexpr int kR16Threads = 128, kR16MaxTile = 64;
 typedef float v2r __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ v2r rsplat(float a) { return (v2r){a, a}; }
-#ifndef DR_K4R_GROUP
-#define DR_K4R_GROUP 4   // models whose coefficients are requested from the scalar cache together
-#endif
-#ifndef DR_K4R_WAVES
-#define DR_K4R_WAVES 0   // > 0: register budget pinned to that many waves per SIMD (A/B builds; 4 spills two point registers)
-#endif
-#if DR_K4R_WAVES > 0
-#define DR_K4R_OCC __attribute__((amdgpu_waves_per_eu(DR_K4R_WAVES, DR_K4R_WAVES)))
-#else
-#define DR_K4R_OCC
-#endif
-// kPts (round 5): 16 points per lane (96 point registers, 138 in all: three waves per SIMD) or 8 (48 / ~90: five waves per SIMD, an
-// 8-byte mask store per lane and model instead of a 16-byte one, the per-model reduction shared by half as many points)
+// (kPts = 8 is the only instantiation; it stays a template parameter because it is part of the kernel's symbol)
 template <int kPts>
-__global__ __launch_bounds__(kR16Threads) DR_K4R_OCC void rigid_residual_kernel_f32_pk(const float *__restrict__ pts, const float *__restrict__ models,
+__global__ __launch_bounds__(kR16Threads) void rigid_residual_kernel_f32_pk(const float *__restrict__ pts, const float *__restrict__ models,
                                                                            float threshold, int M, int N, float *__restrict__ res_sum,
                                                                            uint8_t *__restrict__ masks, int chunks_per_block,
                                                                            int use_atomic, int tile) {
+  static_assert(kPts == 8, "one 8-byte mask store per lane and model");
   constexpr int kChunk = kR16Threads * kPts;
   __shared__ float part[kR16Threads / 64][kR16MaxTile];
   const int p = blockIdx.z, m0 = blockIdx.x * tile;
@@ -291,7 +271,7 @@ __global__ __launch_bounds__(kR16Threads) DR_K4R_OCC void rigid_residual_kernel_
     // compiler has no operand pairs to assemble per model (its own vectoriser spent 178 v_mov per model doing that)
     v2r xp[kPts / 2][6];
     {
-      float x[kPts * 6];   // kPts points x 6 floats = 24 / 12 float4 per lane, contiguous
+      float x[kPts * 6];   // kPts points x 6 floats = 12 float4 per lane, contiguous
       // lanes past the end read the row's first points instead (unconditional loads issue back to back; a predicated load
       // each waited for the one before: 24 memory round trips per chunk) -- their results are never stored or summed
       const float4 *src = reinterpret_cast<const float4 *>(pt + (size_t)(have ? n0 : 0) * 6);
@@ -306,64 +286,49 @@ __global__ __launch_bounds__(kR16Threads) DR_K4R_OCC void rigid_residual_kernel_
         for (int d = 0; d < 6; ++d) xp[j][d] = (v2r){x[12 * j + d], x[12 * j + 6 + d]};
     }
     uint8_t *mrow = masks + ((size_t)p * M + m0) * N;   // wave-uniform row base; the lane part is the 32-bit offset n0
-    // models in groups of kGroup: the 12 coefficients of all of them are requested from the scalar cache together (one
-    // round trip per group instead of one per model: the compiler puts `s_waitcnt lgkmcnt(0)` right behind any s_load whose
-    // destination shares an SGPR pair with a live splat operand, so a hand-written "prefetch the next model" is not one)
-    constexpr int kGroup = kPts == 8 ? DR_K4R_GROUP8 : DR_K4R_GROUP;
+    // one model per scalar-cache round trip (the compiler puts `s_waitcnt lgkmcnt(0)` right behind any s_load whose destination
+    // shares an SGPR pair with a live splat operand, so a hand-written "prefetch the next model" is not one)
 #pragma unroll 1
-    for (int mg = 0; mg < mcount; mg += kGroup) {
-      float mm[kGroup][12];
+    for (int ml = 0; ml < mcount; ++ml) {
+      float m[12];
 #pragma unroll
-      for (int u = 0; u < kGroup; ++u) {
-        const int mu = min(mg + u, mcount - 1);
+      for (int q = 0; q < 12; ++q) m[q] = md[ml * 16 + q];
+      v2r acc2 = (v2r){0.f, 0.f};
+      uint32_t wq[kPts / 4];
 #pragma unroll
-        for (int q = 0; q < 12; ++q) mm[u][q] = md[mu * 16 + q];
-      }
+      for (int g = 0; g < kPts / 4; ++g) {
+        uint32_t sb[4];
 #pragma unroll
-      for (int u = 0; u < kGroup; ++u) {
-        const int ml = mg + u;
-        const bool live = ml < mcount;    // wave-uniform; a tail slot re-evaluates the tile's last model and drops the result
-        const float (&m)[12] = mm[u];
-        v2r acc2 = (v2r){0.f, 0.f};
-        uint32_t wq[kPts / 4];
+        for (int h = 0; h < 2; ++h) {
+          const int j = 2 * g + h;
+          v2r d2 = (v2r){0.f, 0.f};
 #pragma unroll
-        for (int g = 0; g < kPts / 4; ++g) {
-          uint32_t sb[4];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int j = 2 * g + h;
-            v2r d2 = (v2r){0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-              // e = (q_i - t_i) - R_i . p, every step with ONE scalar (SGPR) coefficient operand: no model coefficient has to
-              // be copied into a VGPR pair to serve as an FMA addend (three v_mov_b64 and six registers per model otherwise)
-              v2r e = xp[j][3 + i] - rsplat(m[4 * i + 3]);
-              e = e - xp[j][2] * rsplat(m[4 * i + 2]);
-              e = e - xp[j][1] * rsplat(m[4 * i + 1]);
-              e = e - xp[j][0] * rsplat(m[4 * i]);
-              d2 = e * e + d2;
-            }
-            acc2 = acc2 + d2;
-            // inlier <=> d2 < thr <=> fl(thr - d2) > 0 (a difference of two floats is zero only if they are equal); clamped
-            // to [0, 1], NaN -> 0: "positive" = biased exponent >= 64 = bit 5 of the top byte (values below 2^-63 cannot
-            // occur as a difference of f32 numbers of the sizes thresholds and squared distances have)
-            v2r cl;
-            asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(cl) : "v"(thr2), "v"(d2));
-            sb[2 * h] = __float_as_uint(cl[0]);
-            sb[2 * h + 1] = __float_as_uint(cl[1]);
+          for (int i = 0; i < 3; ++i) {
+            // e = (q_i - t_i) - R_i . p, every step with ONE scalar (SGPR) coefficient operand: no model coefficient has to
+            // be copied into a VGPR pair to serve as an FMA addend (three v_mov_b64 and six registers per model otherwise)
+            v2r e = xp[j][3 + i] - rsplat(m[4 * i + 3]);
+            e = e - xp[j][2] * rsplat(m[4 * i + 2]);
+            e = e - xp[j][1] * rsplat(m[4 * i + 1]);
+            e = e - xp[j][0] * rsplat(m[4 * i]);
+            d2 = e * e + d2;
           }
-          const uint32_t lo2 = __builtin_amdgcn_perm(sb[1], sb[0], 0x0c0c0703u);      // [s0.b3, s1.b3, 0, 0]
-          const uint32_t hi2 = __builtin_amdgcn_perm(sb[3], sb[2], 0x07030c0cu);      // [0, 0, s2.b3, s3.b3]
-          wq[g] = ((lo2 | hi2) >> 5) & 0x01010101u;   // top byte = sign, exponent bits 7..1: exponent bit 6 sits at bit 5
+          acc2 = acc2 + d2;
+          // inlier <=> d2 < thr <=> fl(thr - d2) > 0 (a difference of two floats is zero only if they are equal); clamped
+          // to [0, 1], NaN -> 0: "positive" = biased exponent >= 64 = bit 5 of the top byte (values below 2^-63 cannot
+          // occur as a difference of f32 numbers of the sizes thresholds and squared distances have)
+          v2r cl;
+          asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1] clamp" : "=v"(cl) : "v"(thr2), "v"(d2));
+          sb[2 * h] = __float_as_uint(cl[0]);
+          sb[2 * h + 1] = __float_as_uint(cl[1]);
         }
-        float acc = acc2[0] + acc2[1];
-        if (have && live) {
-          if constexpr (kPts == 16) *reinterpret_cast<uint4 *>(mrow + (size_t)ml * N + (uint32_t)n0) = make_uint4(wq[0], wq[1], wq[2], wq[3]);
-          else *reinterpret_cast<uint2 *>(mrow + (size_t)ml * N + (uint32_t)n0) = make_uint2(wq[0], wq[1]);
-        }
-        acc = wave_sum_lane63(have ? acc : 0.f);
-        if (lane == 63 && live) atomicAdd(&part[wv][ml], acc);   // ds_add_f32, no return: the wave does not wait for its own LDS round trip (the plain += was a ds_read + s_waitcnt + ds_write per model)
+        const uint32_t lo2 = __builtin_amdgcn_perm(sb[1], sb[0], 0x0c0c0703u);      // [s0.b3, s1.b3, 0, 0]
+        const uint32_t hi2 = __builtin_amdgcn_perm(sb[3], sb[2], 0x07030c0cu);      // [0, 0, s2.b3, s3.b3]
+        wq[g] = ((lo2 | hi2) >> 5) & 0x01010101u;   // top byte = sign, exponent bits 7..1: exponent bit 6 sits at bit 5
       }
+      float acc = acc2[0] + acc2[1];
+      if (have) *reinterpret_cast<uint2 *>(mrow + (size_t)ml * N + (uint32_t)n0) = make_uint2(wq[0], wq[1]);
+      acc = wave_sum_lane63(have ? acc : 0.f);
+      if (lane == 63) atomicAdd(&part[wv][ml], acc);   // ds_add_f32, no return: the wave does not wait for its own LDS round trip (the plain += was a ds_read + s_waitcnt + ds_write per model)
     }
   }
   __syncthreads();
@@ -382,32 +347,29 @@ int rigid_residual_launch(const T *pts, const T *models, T threshold, int P, int
                           hipStream_t st, bool sums_zeroed = false) {
   if constexpr (sizeof(T) == 4) {
     // (thresholds below 1e-12 would put `thr - d2` near the bit-6 exponent test's blind spot: general kernel)
-    if (DR_K4R_16 && masks && N % 16 == 0 && (reinterpret_cast<uintptr_t>(pts) & 15) == 0 && threshold > T(1e-12)) {
+    if (masks && N % 16 == 0 && (reinterpret_cast<uintptr_t>(pts) & 15) == 0 && threshold > T(1e-12)) {
       // One block = (pair, model tile, point chunk); every block of a launch takes the same time (tile x chunk evaluations), so
       // the launch takes ceil(blocks / resident blocks) block times: 3 200 blocks on 1 536 resident ones (138 registers: three
       // waves per SIMD, six 2-wave blocks per CU) are THREE rounds for 2.08 rounds of work.  The tile is therefore chosen per
       // launch: the largest grid that is a whole number of rounds -- at C4 (one pair, 25 chunks of 2048 points) 61 tiles of 34
       // models = 1 525 blocks, one round.
-      constexpr int kPts = DR_K4R_PTS;
+      constexpr int kPts = 8;
       constexpr int kChunkL = kR16Threads * kPts;
       static int resident = 0;
       if (!resident) {
         int dev = 0, cus = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        // resident 2-wave blocks per CU: 16 points = 138 registers = three waves per SIMD; 8 points = 76 registers = six
-        resident = (DR_K4R_WAVES > 0 ? 2 * DR_K4R_WAVES : (kPts == 8 ? 12 : 6)) * max(cus, 1);
+        // resident 2-wave blocks per CU: 76 registers = six waves per SIMD
+        resident = 12 * max(cus, 1);
       }
       const int chunks = (N + kChunkL - 1) / kChunkL;
       int ny = chunks;                      // one chunk per block whenever the row is longer than a chunk (atomics across them)
-      int tile = DR_K4R_TILE;
-      if (tile <= 0) {
-        const long per_tile = (long)P * ny;                       // blocks added by one more tile
-        const long min_tiles = (M + kR16MaxTile - 1) / kR16MaxTile;
-        long rounds = max(1L, (per_tile * min_tiles + resident - 1) / resident);
-        long tiles_t = max(min_tiles, rounds * resident / per_tile);      // as many tiles as fit in `rounds` whole rounds
-        tile = (int)((M + tiles_t - 1) / tiles_t);
-        tile = min(kR16MaxTile, max(4, (tile + 1) & ~1));
-      }
+      const long per_tile = (long)P * ny;                       // blocks added by one more tile
+      const long min_tiles = (M + kR16MaxTile - 1) / kR16MaxTile;
+      long rounds = max(1L, (per_tile * min_tiles + resident - 1) / resident);
+      long tiles_t = max(min_tiles, rounds * resident / per_tile);      // as many tiles as fit in `rounds` whole rounds
+      int tile = (int)((M + tiles_t - 1) / tiles_t);
+      tile = min(kR16MaxTile, max(4, (tile + 1) & ~1));
       const int tiles = (M + tile - 1) / tile;
       const int cpb = 1;
       const int use_atomic = ny > 1 || sums_zeroed;   // (pre-zeroed sums are added to, never stored over)

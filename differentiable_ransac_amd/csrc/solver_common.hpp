@@ -38,18 +38,15 @@ __device__ __forceinline__ double rcp_nr(double x) {
   return z * fma(-x, z, 2.0);
 }
 
-// Round 6 (DR_K3_FAST_DIV): divisions and square roots of the five-point stages by v_rcp_f64 / v_rsq_f64 + two Newton steps (5-6
+// Round 6: divisions and square roots of the five-point stages by v_rcp_f64 / v_rsq_f64 + two Newton steps (5-6
 // instructions, results within 1-2 ulp) instead of the IEEE sequences (div_scale x 2, rcp, 4-5 fma, div_fmas, div_fixup: 10-12
 // instructions in one dependent chain; sqrt likewise) -- ~110 of them per sample, a tenth of the kernels' instruction stream.
 // Same behaviour at the edges the callers test for: b = 0 or non-finite gives a non-finite quotient (NaN instead of inf: every caller
 // asks is_finite), fsqrt(0) = 0.
-#ifndef DR_K3_FAST_DIV
-#define DR_K3_FAST_DIV 1
-#endif
-__device__ __forceinline__ double frcp(double b) { return DR_K3_FAST_DIV ? rcp_nr(b) : 1.0 / b; }
-__device__ __forceinline__ double fdiv(double a, double b) { return DR_K3_FAST_DIV ? a * rcp_nr(b) : a / b; }
-__device__ __forceinline__ double fsqrt(double x) { return DR_K3_FAST_DIV ? (x > 0 ? x * rsqrt_nr(x) : x) : sqrt(x); }
-__device__ __forceinline__ double frsqrt(double x) { return DR_K3_FAST_DIV ? rsqrt_nr(x) : 1.0 / sqrt(x); }
+__device__ __forceinline__ double frcp(double b) { return rcp_nr(b); }
+__device__ __forceinline__ double fdiv(double a, double b) { return a * rcp_nr(b); }
+__device__ __forceinline__ double fsqrt(double x) { return x > 0 ? x * rsqrt_nr(x) : x; }
+__device__ __forceinline__ double frsqrt(double x) { return rsqrt_nr(x); }
 
 
 // ------------------------------------------------------------------------------------------------
@@ -114,57 +111,22 @@ __device__ __forceinline__ void null_space_qr(double (&A)[K][9], double (&nb)[9 
 //     of width 2^(1-kBis); the five-point callers polish (x, y, z) on the defining constraints afterwards.
 // Replaces the per-sample companion-matrix eigvals of nister.py:361-370 / the Sturm recursion of math_utils.py.
 // ------------------------------------------------------------------------------------------------
-// DR_ROOT_F32_LOW = 1: the levels below the polynomial itself (which only provide the breakpoints between which the next
-// level looks for sign changes) run in f32 -- half the cycles per FMA and per select on gfx950.  A breakpoint y~ = y* + e
-// (y* a critical point of the next level's polynomial g, g'(y*) = 0) is used only through sign g(y~) = sign(g(y*) +
-// g''(y*) e^2 / 2): second order in e, so f32 breakpoints bracket the same roots unless two of them are closer than ~1e-6
-// (nearly a double root, where the f64 search is at the mercy of rounding as well).  The last level, which produces the
-// roots, is always f64.
-#ifndef DR_ROOT_F32_LOW
-#define DR_ROOT_F32_LOW 0
-#endif
-#ifndef DR_K3_STURM
-#define DR_K3_STURM 1   // 1: the two-lanes-per-sample kernels isolate the roots by a Sturm sequence (real_roots_half_sturm)
-#endif
-#ifndef DR_K3_STURM_DRAIN
-#define DR_K3_STURM_DRAIN 0   // 1: emitting an isolated interval does not cost a step of the isolation loop (round 5: 13 -> 11 steps for
-                              // the slowest lane of a wave, but every step pays the extra loop: 165.1 -> 170.9 us at 131 072 samples; off)
-#endif
-#ifndef DR_K3_STURM_FALLBACK
-#define DR_K3_STURM_FALLBACK 1   // 1: a lane whose Sturm chain loses a degree has its roots found by the whole wave on a grid (round 5)
-#endif
-#ifndef DR_K3_SYMG
-#define DR_K3_SYMG 1          // 1: the six distinct entries of E E^T once in Nister's lane-pair kernel (constraint_rows; round 5)
-#endif
-#ifndef DR_K3_ISO_FLAT
-#define DR_K3_ISO_FLAT 1      // 1: the isolation step as predicates + selects instead of an if / else-if chain (round 5)
-#endif
-#ifndef DR_ROOT_BIS_LOW
-#define DR_ROOT_BIS_LOW 6
-#define DR_ROOT_NEWT_LOW 4
-#endif
+// The fixed schedule of the levels below the polynomial itself (the last level's is the callers' template argument):
+constexpr int kRootBisLow = 6, kRootNewtLow = 4;
 __device__ __forceinline__ double root_rcp(double v) { return __builtin_amdgcn_rcp(v); }
 // The safeguarded Newton step of the fixed schedules: y - step when that stays inside the bracket [a, b], else the midpoint --
 // EXCEPT when the step has already shrunk to rounding level.  After `a = y` (or `b = y`) a converged iterate sits ON the end of
 // its bracket, and a last-bit step (zero, or one ulp outwards: the sign of f is noise there) used to fail the strict test
 // `a < yn < b` and send the iterate to the midpoint -- half a bracket away from the root it had found, which the remaining
 // steps of the schedule then only bisected back (rounds 1-2: 22 % of the roots left the refinement with a backward error above
-// 1e-13, up to 1e-2, and the Gauss-Newton polish repaired them; tests/test_gpu_roots.py).  DR_ROOT_KEEP_CONVERGED=0: old rule.
-#ifndef DR_ROOT_KEEP_CONVERGED
-#define DR_ROOT_KEEP_CONVERGED 1
-#endif
+// 1e-13, up to 1e-2, and the Gauss-Newton polish repaired them; tests/test_gpu_roots.py).
 template <typename F>
 __device__ __forceinline__ F safeguarded_newton(F y, F step, F a, F b) {
   F yn = y - step;
-#if DR_ROOT_KEEP_CONVERGED
   const F tiny = (sizeof(F) == 8 ? (F)4e-16 : (F)5e-7) * ((F)1 + fabs(y));
   if (!(yn >= a && yn <= b)) yn = (fabs(step) <= tiny) ? y : (F)0.5 * (a + b);
-#else
-  if (!(yn > a && yn < b)) yn = (F)0.5 * (a + b);
-#endif
   return yn;
 }
-__device__ __forceinline__ float root_rcp(float v) { return __builtin_amdgcn_rcpf(v); }
 
 template <int D, int kBisLast, int kNewtLast>
 __device__ __forceinline__ void roots_in_unit(const double (&c)[D + 1], double (&x)[D], unsigned &mask, double tail_tol) {
@@ -173,9 +135,9 @@ __device__ __forceinline__ void roots_in_unit(const double (&c)[D + 1], double (
   for (int i = 0; i <= D; ++i) pts[i] = 1.0;
   pts[0] = -1.0;
   mask = 0;
-  // one level: F = arithmetic type of the level, d = degree (a constant after unrolling)
-  auto level = [&](auto tag, const int d) {
-    using F = decltype(tag);
+  // one level: d = degree (a constant after unrolling)
+  auto level = [&](const int d) {
+    using F = double;
     F q[D + 1];  // q = p^(D-d): degree d, ascending
 #pragma unroll
     for (int i = 0; i <= D; ++i) q[i] = 0;
@@ -218,8 +180,8 @@ __device__ __forceinline__ void roots_in_unit(const double (&c)[D + 1], double (
 #ifdef DR_PROFILE_STAGES
     if (D == 10) atomicAdd(&::dr::g_stage_cycles[5 + d], (unsigned long long)__popc(has));   // brackets with a sign change, per level
 #endif
-    const int kBis = (d == D) ? kBisLast : DR_ROOT_BIS_LOW;
-    const int kNewt = (d == D) ? kNewtLast : DR_ROOT_NEWT_LOW;
+    const int kBis = (d == D) ? kBisLast : kRootBisLow;
+    const int kNewt = (d == D) ? kNewtLast : kRootNewtLow;
 #pragma unroll 1
     for (int it = 0; it < kBis; ++it) {
 #pragma unroll
@@ -293,19 +255,13 @@ __device__ __forceinline__ void roots_in_unit(const double (&c)[D + 1], double (
     }
   };
 #pragma unroll
-  for (int d = 1; d <= D; ++d) {
-    if (DR_ROOT_F32_LOW && d < D) level(float{}, d);
-    else level(double{}, d);
-  }
+  for (int d = 1; d <= D; ++d) level(d);
 }
 
 // One half of the search (two lanes per sample: the even lane takes |z| <= 1, the odd lane |z| > 1 through the reversed
 // polynomial).  roots[0..count-1] dense.
-#ifndef DR_ROOT_BIS_LAST
-#define DR_ROOT_BIS_LAST 10
-#define DR_ROOT_NEWT_LAST 6
-#endif
-template <int D, int kBisLast = DR_ROOT_BIS_LAST, int kNewtLast = DR_ROOT_NEWT_LAST>
+constexpr int kRootBisLast = 10, kRootNewtLast = 6;
+template <int D, int kBisLast = kRootBisLast, int kNewtLast = kRootNewtLast>
 __device__ __forceinline__ void real_roots_half(const double (&c)[D + 1], bool outer, double (&roots)[D], int &count) {
   double cmax = 0;
 #pragma unroll
@@ -477,8 +433,8 @@ __device__ __forceinline__ void root_levels_wave(const double (&c)[D + 1], const
 #ifdef DR_PROFILE_STAGES
   if (lane == 0) ws.prof[0] += __builtin_readcyclecounter() - _lvl_t0;   // per-lane part, all levels
 #endif
-  const int kBis = (d == D) ? kBisLast : DR_ROOT_BIS_LOW;
-  const int kNewt = (d == D) ? kNewtLast : DR_ROOT_NEWT_LOW;
+  const int kBis = (d == D) ? kBisLast : kRootBisLow;
+  const int kNewt = (d == D) ? kNewtLast : kRootNewtLow;
   if (offs <= 64) root_tasks<D, d, 1>(ws, cur, nxt, offs, lane, kBis, kNewt);
   else if (offs <= 128) root_tasks<D, d, 2>(ws, cur, nxt, offs, lane, kBis, kNewt);
   else root_tasks<D, d, 3>(ws, cur, nxt, offs, lane, kBis, kNewt);
@@ -491,7 +447,7 @@ __device__ __forceinline__ void root_levels_wave(const double (&c)[D + 1], const
 }
 
 // wave-cooperative real_roots_half: every lane of the (single-wave) block must call it
-template <int D, int kBisLast = DR_ROOT_BIS_LAST, int kNewtLast = DR_ROOT_NEWT_LAST>
+template <int D, int kBisLast = kRootBisLast, int kNewtLast = kRootNewtLast>
 __device__ __forceinline__ void real_roots_half_wave(const double (&c)[D + 1], bool outer, double (&roots)[D], int &count, double *lds_ws,
                                                      int lane) {
   const RootWs<D> ws(lds_ws);
@@ -539,7 +495,7 @@ __device__ __forceinline__ void real_roots_half_wave(const double (&c)[D + 1], b
 }
 
 // ------------------------------------------------------------------------------------------------
-// Root ISOLATION by a Sturm sequence (DR_K3_STURM): the derivative chain above isolates the roots of p by finding, level by
+// Root ISOLATION by a Sturm sequence: the derivative chain above isolates the roots of p by finding, level by
 // level, ALL roots of p', p'', ... in [-1, 1] first -- 45 k of the 56 k cycles a wave spends in the root search, although a
 // sample-half holds 2.3 real roots on average.  Here a lane builds the Sturm chain of its polynomial once (f0 = p, f1 = p',
 // f_{k+1} = -rem(f_{k-1}, f_k) as division-free pseudo-remainders with positive multipliers, each renormalised to max |coef| = 1
@@ -551,17 +507,11 @@ __device__ __forceinline__ void real_roots_half_wave(const double (&c)[D + 1], b
 // same as the idealised derivative chain misses).  The isolated roots are then refined by the SAME wave-wide task rounds on p
 // (bisection + Newton on a bracket with a sign change), so the final accuracy is the one of the level-D tasks.
 // ------------------------------------------------------------------------------------------------
-#ifndef DR_K3_VAR_SCHED
-#define DR_K3_VAR_SCHED 0
-#endif
-// 1 (round 6): the chain evaluation of the isolation step as one hand-scheduled asm block (sturm_eval_asm.hpp): bit-identical roots,
-// 66 instead of ~130 instructions per evaluation; Nister 159.7 -> 156.3 us, Stewenius 192.6 -> 189.2 us at 131 072 samples (same box)
-#ifndef DR_K3_VAR_ASM
-#define DR_K3_VAR_ASM 1
-#endif
-#ifndef DR_K3_TASK_ESTRIN
-#define DR_K3_TASK_ESTRIN 0
-#endif
+// Round 6: the chain evaluation of the isolation step is one hand-scheduled asm block (sturm_eval_asm.hpp): bit-identical roots,
+// 66 instead of ~130 instructions per evaluation; Nister 159.7 -> 156.3 us, Stewenius 192.6 -> 189.2 us at 131 072 samples (same box).
+// Not kept (profiles/r6_k3_variants.md): __builtin_amdgcn_sched_barrier between the Horner levels (no effect on the ISA); Estrin's
+// scheme for the refine tasks (degree 10 in four dependent levels instead of ten): +1...3 % -- the tasks are issue-bound, not
+// latency-bound.
 template <int D>
 struct SturmWs {
   double *lo, *hi;     // D x 64 each: entry e of lane l at [e * 64 + l]; after the refine tasks lo holds the root
@@ -573,35 +523,6 @@ struct SturmWs {
       : lo(ws), hi(ws + D * 64), vv(reinterpret_cast<uint32_t *>(ws + 2 * D * 64)), q(ws + 2 * D * 64 + D * 64 / 2),
         queue(reinterpret_cast<uint16_t *>(ws + 2 * D * 64 + D * 64 / 2 + (D + 1) * 64)) {}
 };
-
-// Estrin's scheme for the refine tasks (round 6, DR_K3_TASK_ESTRIN): a bracket's bisection / Newton steps are one dependent chain per
-// task, and a wave alone on its SIMD waits ~8.5 clocks for every dependent v_fma_f64 -- Horner's rule for degree 10 is ten of them in
-// a row.  Pairing the coefficients (q0 + q1 x) + x^2 (q2 + q3 x) ... costs three squarings and three more FMAs and is four levels deep.
-template <int D>
-__device__ __forceinline__ double estrin_eval(const double (&q)[D + 1], double x) {
-  static_assert(D == 10, "written out for the degree-10 polynomials of the five-point solvers");
-  const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-  const double a0 = __builtin_fma(q[1], x, q[0]), a1 = __builtin_fma(q[3], x, q[2]), a2 = __builtin_fma(q[5], x, q[4]);
-  const double a3 = __builtin_fma(q[7], x, q[6]), a4 = __builtin_fma(q[9], x, q[8]);
-  const double b0 = __builtin_fma(a1, x2, a0), b1 = __builtin_fma(a3, x2, a2), b2 = __builtin_fma(q[10], x2, a4);
-  const double c0 = __builtin_fma(b1, x4, b0);
-  return __builtin_fma(b2, x8, c0);
-}
-// value and derivative: p' = sum (j + 1) q[j + 1] x^j, degree 9, by the same pairing
-template <int D>
-__device__ __forceinline__ void estrin_eval_d(const double (&q)[D + 1], double x, double &fx, double &dfx) {
-  static_assert(D == 10, "written out for the degree-10 polynomials of the five-point solvers");
-  const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-  const double a0 = __builtin_fma(q[1], x, q[0]), a1 = __builtin_fma(q[3], x, q[2]), a2 = __builtin_fma(q[5], x, q[4]);
-  const double a3 = __builtin_fma(q[7], x, q[6]), a4 = __builtin_fma(q[9], x, q[8]);
-  const double b0 = __builtin_fma(a1, x2, a0), b1 = __builtin_fma(a3, x2, a2), b2 = __builtin_fma(q[10], x2, a4);
-  fx = __builtin_fma(b2, x8, __builtin_fma(b1, x4, b0));
-  const double e0 = __builtin_fma(2.0 * q[2], x, q[1]), e1 = __builtin_fma(4.0 * q[4], x, 3.0 * q[3]);
-  const double e2 = __builtin_fma(6.0 * q[6], x, 5.0 * q[5]), e3 = __builtin_fma(8.0 * q[8], x, 7.0 * q[7]);
-  const double e4 = __builtin_fma(10.0 * q[10], x, 9.0 * q[9]);
-  const double g0 = __builtin_fma(e1, x2, e0), g1 = __builtin_fma(e3, x2, e2);
-  dfx = __builtin_fma(e4, x8, __builtin_fma(g1, x4, g0));
-}
 
 // the refine rounds: root_tasks with the bracket ends in separate arrays and the polynomial always of degree D
 template <int D, int R>
@@ -629,13 +550,9 @@ __device__ __forceinline__ void sturm_tasks(const SturmWs<D> &ws, int total, int
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         const double m = 0.5 * (a[r] + b[r]);
-#if DR_K3_TASK_ESTRIN
-        const double fx = estrin_eval<D>(qq[r], m);
-#else
         double fx = qq[r][D];
 #pragma unroll
         for (int k = D - 1; k >= 0; --k) fx = fx * m + qq[r][k];
-#endif
         const bool left = (fx < 0) == neg[r], hit = fx == 0.0;   // a midpoint that IS the root closes the bracket on it
         a[r] = (left || hit) ? m : a[r];
         b[r] = (left && !hit) ? b[r] : m;
@@ -647,17 +564,12 @@ __device__ __forceinline__ void sturm_tasks(const SturmWs<D> &ws, int total, int
     for (int it = 0; it < kNewt; ++it) {
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-#if DR_K3_TASK_ESTRIN
-        double fx, dfx;
-        estrin_eval_d<D>(qq[r], y[r], fx, dfx);
-#else
         double fx = qq[r][D], dfx = 0;
 #pragma unroll
         for (int k = D - 1; k >= 0; --k) {
           dfx = dfx * y[r] + fx;
           fx = fx * y[r] + qq[r][k];
         }
-#endif
         const bool left = (fx < 0) == neg[r];
         a[r] = left ? y[r] : a[r];
         b[r] = left ? b[r] : y[r];
@@ -820,7 +732,7 @@ __device__ __forceinline__ int wave_grid_roots(const double (&q)[D + 1], double 
 }
 
 // wave-cooperative (block = one wave): every lane must call it.  Same outputs as real_roots_half_wave.
-template <int D, int kBisLast = DR_ROOT_BIS_LAST, int kNewtLast = DR_ROOT_NEWT_LAST>
+template <int D, int kBisLast = kRootBisLast, int kNewtLast = kRootNewtLast>
 __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], bool outer, double (&roots)[D], int &count, double *lds_ws,
                                                       int lane) {
   const SturmWs<D> ws(lds_ws);
@@ -892,14 +804,12 @@ __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], 
   auto variations = [&](double x) -> unsigned {
     // all Horner chains advance together (step i touches every polynomial that still has a coefficient left): eleven independent
     // dependency chains instead of one after the other
-#if DR_K3_VAR_ASM
     if constexpr (D == 10) {
       // round 6: the 55 FMAs as one hand-scheduled asm block (csrc/sturm_eval_asm.hpp), the sign bits by v_alignbit_b32
       const unsigned w = sturm_signs10(F, x);
       const unsigned ch = (w ^ (w >> 1)) & ((1u << D) - 1u);
       return (unsigned)__popc(ch) | ((w & 1u) << 4);
     }
-#endif
     double val[D + 1];
 #pragma unroll
     for (int k = 0; k <= D; ++k) val[k] = F[k][D - k];
@@ -907,11 +817,6 @@ __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], 
     for (int i = 1; i <= D; ++i) {
 #pragma unroll
       for (int k = 0; k + i <= D; ++k) val[k] = val[k] * x + F[k][D - k - i];
-#if DR_K3_VAR_SCHED
-      // round 6: the scheduler, short of registers, otherwise runs the chains one after the other (a dependent v_fma_f64 every
-      // ~8.5 clocks at one wave per SIMD instead of an independent one every ~4.3): nothing moves across a Horner level
-      __builtin_amdgcn_sched_barrier(0);
-#endif
     }
     unsigned w = 0;
 #pragma unroll
@@ -938,12 +843,13 @@ __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], 
     v = ws.vv[tc * 64 + lane];
     top += have ? 1 : 0;
   };
-#if DR_K3_ISO_FLAT
   // Round 5: the step without control flow.  Rounds 3-4 walked an if / else-if chain (isolated -> emit + pop | cannot split -> pop |
   // left part isolated -> emit, go right | left part holds roots -> push right, go left | go right); with 64 lanes in different
   // states the wave executed every arm one after the other, ~250 instructions per step where the evaluation of the chain is ~100.
   // Here a lane derives its action as predicates, writes at most ONE record (the emitted interval or the pushed right part),
   // updates its interval with selects and pops under one mask.  Same intervals, same order: the roots are bit-identical.
+  // (Not kept: emitting an isolated interval without spending a step of this loop -- 13 -> 11 steps for the slowest lane of a wave, but
+  // every step pays the extra loop: 165.1 -> 170.9 us at 131 072 samples.)
 #pragma unroll 1
   for (int guard = 0; guard < 64 * D; ++guard) {
     if (!__any(have)) break;
@@ -984,72 +890,6 @@ __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], 
     v = move_l ? (vmid | (v & 0xff00u)) : (to_left ? ((v & 31u) | (vmid << 8)) : v);
     if (iso || drop) pop();
   }
-#else
-#pragma unroll 1
-  for (int guard = 0; guard < 64 * D; ++guard) {
-    if (!__any(have)) break;
-#ifdef DR_PROFILE_STAGES
-    ++_iters;
-#endif
-#if DR_K3_STURM_DRAIN
-    // isolated intervals go to the output list and the next pending one comes off the stack (LDS only) WITHOUT costing the wave a
-    // step: rounds 3-4 spent one step of the loop -- i.e. one evaluation of the chain by every other lane -- per emitted interval
-    // (4-5 of the ~13 steps the slowest lane of a wave needs); same intervals in the same order, so the roots are bit-identical
-    while (have && ((int)(v & 15u) - (int)((v >> 8) & 15u) == 1)) {
-      ws.lo[nout * 64 + lane] = l;
-      ws.hi[nout * 64 + lane] = h;
-      ws.vv[nout * 64 + lane] = v;
-      ++nout;
-      pop();
-    }
-    if (!__any(have)) break;
-    const bool iso = false;
-#else
-    // one action per lane and step: an isolated interval goes to the output list and the next pending one comes off the stack
-    // (LDS only), any other interval is split at its midpoint (one evaluation of the chain)
-    const bool iso = have && ((int)(v & 15u) - (int)((v >> 8) & 15u) == 1);
-#endif
-    if (iso) {
-      ws.lo[nout * 64 + lane] = l;
-      ws.hi[nout * 64 + lane] = h;
-      ws.vv[nout * 64 + lane] = v;
-      ++nout;
-      pop();
-    } else if (have) {
-      // split a hair off the centre: a root AT a split point would be counted with the sign of +0 (nice inputs have nice roots:
-      // 0, 1/2, 1/4 ... are exactly where plain halving of (-1, 1] looks)
-      const double mid = __builtin_fma(h - l, 0.49999952316284180, l);
-      const unsigned vmid = variations(mid);
-      const int nl = (int)(v & 15u) - (int)(vmid & 15u), nr = (int)(vmid & 15u) - (int)((v >> 8) & 15u);
-      // an interval that cannot be split any more (a multiple root to rounding) or whose halves both come out empty
-      // (inconsistent counts of a degenerate chain) is dropped
-      const bool splittable = mid > l && mid < h && (h - l) > 1e-12;
-      if (!splittable || (nl < 1 && nr < 1)) {
-        pop();
-      } else if (nl == 1 && nr >= 1 && top - 2 >= nout) {
-        // the left part is isolated: straight to the output list (it is the leftmost interval of this lane), go on with the right
-        ws.lo[nout * 64 + lane] = l;
-        ws.hi[nout * 64 + lane] = mid;
-        ws.vv[nout * 64 + lane] = (v & 31u) | ((vmid & 31u) << 8);
-        ++nout;
-        l = mid;
-        v = (vmid & 31u) | (v & 0xff00u);
-      } else if (nl >= 1) {
-        if (nr >= 1 && top - 2 >= nout) {   // right part waits on the stack (dropped if there is no room: degenerate counts)
-          --top;
-          ws.lo[top * 64 + lane] = mid;
-          ws.hi[top * 64 + lane] = h;
-          ws.vv[top * 64 + lane] = (vmid & 31u) | (v & 0xff00u);
-        }
-        h = mid;
-        v = (v & 31u) | ((vmid & 31u) << 8);
-      } else {
-        l = mid;
-        v = (vmid & 31u) | (v & 0xff00u);
-      }
-    }
-  }
-#endif
   wave_lds_order();
 #ifdef DR_PROFILE_STAGES
   if (D == 10 && lane == 0) { atomicAdd(&::dr::g_stage_cycles[7], __builtin_readcyclecounter() - _st0); atomicAdd(&::dr::g_stage_cycles[9], (unsigned long long)_iters); atomicMax(&::dr::g_stage_cycles[10], (unsigned long long)_iters); }
@@ -1098,7 +938,6 @@ __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], 
     const double r = ws.lo[i * 64 + lane];
     roots[i] = (i < count) ? r : 0.0;
   }
-#if DR_K3_STURM_FALLBACK
   // (1 + z^D is the polynomial the callers hand to lanes WITHOUT a sample -- partial blocks, few samples per block on small grids,
   // rank-deficient systems: its chain loses eight degrees at once and it has no real root: nothing to look for.  Forgetting this
   // sent every idle lane of a one-pair call through the fallback: 30 -> 189 us.)
@@ -1143,7 +982,6 @@ __device__ __forceinline__ void real_roots_half_sturm(const double (&c)[D + 1], 
       wave_lds_order();
     }
   }
-#endif
 }
 
 // roots[0..count-1] = all real roots found (|z| <= 1 ascending first, then the |z| > 1 ones); count <= D
@@ -1485,9 +1323,6 @@ __device__ __forceinline__ void smallest_eigvec9_invit(const double (&A)[9][9], 
 }
 
 // symmetric 3x3 Jacobi in registers; eigenvalues in d[], eigenvectors = columns of V
-#ifndef DR_JACOBI3_FAST
-#define DR_JACOBI3_FAST 1
-#endif
 __device__ __forceinline__ void jacobi_eig3(double (&A)[3][3], double (&V)[3][3], double (&d)[3]) {
 #pragma unroll
   for (int i = 0; i < 3; ++i)
@@ -1505,7 +1340,6 @@ __device__ __forceinline__ void jacobi_eig3(double (&A)[3][3], double (&V)[3][3]
         const double apq = A[p][q];
         double c = 1.0, s = 0.0;
         if (fabs(apq) > 1e-300 && !done) {
-#if DR_JACOBI3_FAST
           // round 6: t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) with theta = h / (2 apq) is sgn(h) 2 apq / (|h| + sqrt(h^2 + 4 apq^2)):
           // one reciprocal square root for the root, one reciprocal, one reciprocal square root for c (rsq / rcp + two Newton steps
           // each) instead of three IEEE divisions and two square roots -- the rotation is a dependent chain one lane waits for
@@ -1517,12 +1351,6 @@ __device__ __forceinline__ void jacobi_eig3(double (&A)[3][3], double (&V)[3][3]
             c = rsqrt_nr(__builtin_fma(t, t, 1.0));
             s = t * c;
           }
-#else
-          const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-          const double t = dsign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          c = 1.0 / sqrt(t * t + 1.0);
-          s = t * c;
-#endif
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -1780,7 +1608,7 @@ __device__ __forceinline__ bool constraints_reduce(const double (&e)[3][3][4], c
                                    double (&X)[10 - kFirstRow][10], int half = 0) {
   double A[10][10];
   // A-part to registers, B-part to LDS
-  constraint_rows<Ord, DR_K3_SYMG != 0 && kFirstRow == 4>(e, s, A, [&](int r, int t, double v) { Bw[r * 10 + t] = v; });   // kFirstRow == 4: Nister
+  constraint_rows<Ord, kFirstRow == 4>(e, s, A, [&](int r, int t, double v) { Bw[r * 10 + t] = v; });   // kFirstRow == 4: Nister
   // ---- Householder QR of A: reflector j lives in A[j..9][j] (v, with v_j = A[j][j]), R above the diagonal + rdiag
   // (kept inline here, not through householder_qr10 / qr10_solve_column: the shipped pair kernels' register allocation is
   // sensitive to the form -- 16 579 -> 16 766 instructions for Stewenius' through the helpers)

@@ -1,10 +1,9 @@
-"""K1 timing experiments (wrong noise in all but `base`): how much of the sampler is Philox, how much the two logarithms?
+"""K1 alone: the sampler launch in test and train mode.  (The Philox / logarithm share experiments of round 2 were builds under
+compile-time knobs that left the sources: scratch/README.md, "Removed build knobs".)
   build: python scratch/ab_k1.py --build      run (GPU box): python scratch/ab_k1.py"""
 import ctypes, os, subprocess, sys
 sys.path.insert(0, '.')
-variants = {'base': [], 'general': ['-DDR_K1_FAST=0'], 'nolog': ['-DDR_K1_NOISE_EXPERIMENT=1'], 'onelog': ['-DDR_K1_NOISE_EXPERIMENT=2'],
-            'philox7': ['-DDR_PHILOX_ROUNDS=7'], 'philox0': ['-DDR_PHILOX_ROUNDS=0'],
-            'philox0_nolog': ['-DDR_PHILOX_ROUNDS=0', '-DDR_K1_NOISE_EXPERIMENT=1']}
+variants = {'base': []}
 if '--build' in sys.argv:
     for name, flags in variants.items():
         if [a for a in sys.argv[1:] if not a.startswith('--')] and name not in sys.argv: continue

@@ -5,14 +5,12 @@ import torch
 src = sorted(glob.glob('differentiable_ransac_amd/csrc/*.hip'))
 out = 'gpurun_out/libdransac_prof.so'
 os.makedirs('gpurun_out', exist_ok=True)
-extra = [a for a in sys.argv[1:] if a.startswith('-D')]
-tag = ''.join(a.replace('-D', '_').replace('=', '') for a in extra)
 if '--build' in sys.argv:
     subprocess.check_call(['/opt/rocm/bin/hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-shared', '-ffp-contract=fast',
-                           '-DDR_PROFILE_STAGES', *extra, '-o', f'scratch/libdransac_prof{tag}.so', *src])
+                           '-DDR_PROFILE_STAGES', '-o', 'scratch/libdransac_prof.so', *src])
     sys.exit(0)
 import differentiable_ransac_amd._lib as L
-L.LIB_PATH = os.path.abspath(f'scratch/libdransac_prof{tag}.so')
+L.LIB_PATH = os.path.abspath('scratch/libdransac_prof.so')
 from differentiable_ransac_amd import ops, synth
 dev = 'cuda'
 P, N, B = int(os.environ.get('K3_PAIRS', 32)), 2000, 1024
