@@ -4,8 +4,8 @@
 //   fundamental:  Hartley-normalised LSQ 8-point on the INLIERS of the best mask (ransac.py:150-155,
 //                 fundamental_matrix_estimator.py:172-174,177-260).
 // One 256-thread block per pair: the four waves accumulate the 9x9 Gram matrix of the (weighted / masked) epipolar rows
-// cooperatively (three passes for F: centroid, mean distances, Gram), then wave 0 -- all 64 lanes redundantly, lane 0
-// stores -- runs the same device code as the per-sample solvers (Jacobi eigen-decomposition, five-point pipeline).
+// cooperatively (three passes for F: centroid, mean distances, Gram), then wave 0 takes the eigenvectors it needs from a
+// wave-cooperative Jacobi eigen-decomposition (F: the smallest one, E: the four smallest) and, for E, runs the five-point pipeline.
 // The ragged inlier sets never leave the device.
 #include <algorithm>
 #include <cstdlib>
@@ -172,14 +172,19 @@ __device__ __forceinline__ void refit_fundamental_pair(const T *__restrict__ mt,
   gram_accumulate<true, T>(mt, mk, wt, N, mu, r1, r2, gram, red);
   if (threadIdx.x >= 64) return;
   const int lane = threadIdx.x;
+  // The null vector (only the last right singular vector is needed, fundamental_matrix_estimator.py:249-254) is the Gram matrix's
+  // smallest eigenvector from the wave-cooperative Jacobi the essential refit runs: exact to rounding for ANY gap between the two
+  // smallest eigenvalues.  (Until the refit tests against f64 this was a fixed 24 steps of inverse iteration, whose error is
+  // (lambda_9 / lambda_8)^24: fine on clean inliers, ratio < 0.05, and off by 1e-4 ... 1e-1 on a selection that holds outliers,
+  // ratio 0.6 ... 0.95 -- the mask local optimisation refits an early best model on.)
   double f[9];
   {
-    double A[9][9];
+    double *Vl = gram + 96 + 4 * 45, *cs = Vl + 81;
+    jacobi_eig9_wave(gram, Vl, cs, lane);
+    double ev[1][9];
+    smallest_eigvecs9_lds<1>(gram, Vl, ev);
 #pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) A[i][j] = gram[i * 9 + j];
-    smallest_eigvec9_invit(A, f);   // only the last right singular vector is needed (fundamental_matrix_estimator.py:249-254)
+    for (int r = 0; r < 9; ++r) f[r] = ev[0][r];
   }
   double G[3][3];
 #pragma unroll

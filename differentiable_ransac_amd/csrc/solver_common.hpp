@@ -1268,60 +1268,6 @@ __device__ __forceinline__ void smallest_eigvecs9_lds(const double *A, const dou
   }
 }
 
-// Eigenvector of the SMALLEST eigenvalue of a symmetric positive semi-definite 9x9 matrix by inverse iteration on a
-// Cholesky factor (A + 1e-14 tr(A) I, so that an exactly singular A -- noise-free data -- still factors): ~200 flops
-// for the factor + 162 per iteration, against ~29 k for the cyclic Jacobi above, which it replaces where only this one
-// vector is needed (LSQ fundamental matrix).  Error after m iterations ~ (lambda_9 / lambda_8)^m; 24 iterations.
-__device__ __forceinline__ void smallest_eigvec9_invit(const double (&A)[9][9], double (&x)[9]) {
-  double L[9][9];
-  double tr = 0;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) tr += A[i][i];
-  const double shift = 1e-14 * tr;
-  double inv[9];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    double d = A[j][j] + shift;
-#pragma unroll
-    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
-    d = fmax(d, 1e-300);
-    const double r = 1.0 / sqrt(d);
-    inv[j] = r;
-#pragma unroll
-    for (int i = j + 1; i < 9; ++i) {
-      double v = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v * r;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 9; ++i) x[i] = 1.0 / 3.0 + 0.01 * i;   // fixed start, not orthogonal to anything in particular
-#pragma unroll 1
-  for (int it = 0; it < 24; ++it) {
-    double y[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {        // L y = x
-      double v = x[i];
-#pragma unroll
-      for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-      y[i] = v * inv[i];
-    }
-    double nn = 0;
-#pragma unroll
-    for (int i = 8; i >= 0; --i) {       // L^T z = y
-      double v = y[i];
-#pragma unroll
-      for (int k = i + 1; k < 9; ++k) v -= L[k][i] * x[k];
-      x[i] = v * inv[i];
-      nn += x[i] * x[i];
-    }
-    const double sc = 1.0 / sqrt(nn);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) x[i] *= sc;
-  }
-}
-
 // symmetric 3x3 Jacobi in registers; eigenvalues in d[], eigenvectors = columns of V
 __device__ __forceinline__ void jacobi_eig3(double (&A)[3][3], double (&V)[3][3], double (&d)[3]) {
 #pragma unroll

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import cpu_ref as O
+from tests import refit_ref
 from tests.conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -298,7 +299,9 @@ def test_batched_refit_kernels(dev):
     for p in range(P):
         Fo = O.fundamental_8pt(dF["matches"][p][mask[p]].double().unsqueeze(0))[0]
         s = torch.sign((F[p].cpu().double() * Fo).sum())
-        assert ((F[p].cpu().double() * s - Fo).abs().max() / Fo.abs().max()) < 1e-3
+        # the rule of tests/test_gpu_refit.py for this input (a wide eigen-gap, f32 in and out: the output's rounding dominates)
+        cond = refit_ref.f_refit(dF["matches"][p].double(), mask[p])[2]
+        assert ((F[p].cpu().double() * s - Fo).abs().max() / Fo.abs().max()) <= refit_ref.f_tolerance(cond, torch.float32)
         assert (O.canonical(F[p].cpu().double()) - O.canonical(dF["gt_F"][p].double())).abs().max() < 0.05
     few = torch.zeros(P, N, dtype=torch.bool)
     few[:, :5] = True
