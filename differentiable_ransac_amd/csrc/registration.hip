@@ -1,0 +1,561 @@
+// Robust 3-D registration (test mode of ransac.BatchedRegistration): rigid models from minimal samples by a correct Kabsch fit,
+// MSAC score and inlier count of every model against every point, the per-pair state step with the adaptive stop, and the Kabsch
+// refit over the rows a mask selects.
+//   matches [P,N,6] = (p, q); a model is the row-major 4x4 [[R, t], [0, 0, 0, 1]]; q_hat = R p + t, d2 = |q - q_hat|^2.
+//   The threshold is a DISTANCE and enters as thr2 = threshold^2 per pair: inlier <=> d2 < thr2 (dr_rigid_residual compares d2
+//   with its threshold argument itself).  MSAC score = sum_n max(0, 1 - d2_n / thr2).
+// Unlike dr_solve_rigid (the reference's estimate_model, kept for parity with its training branch: cov^T cov with flag, the
+// row-sum translation of rigid...:66) this is the least-squares rigid fit: R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T,
+// t = c1 - R c0.
+#include "ransac_device.hpp"
+#include "solver_common.hpp"
+
+namespace dr {
+
+// ---- the 3x3 step shared by the minimal solver and the refit -------------------------------------------------------------
+// one Hestenes (one-sided Jacobi) rotation: makes columns ga, gb of G = H V orthogonal, V's columns follow
+__device__ __forceinline__ void hestenes_rotate(double (&ga)[3], double (&gb)[3], double (&va)[3], double (&vb)[3]) {
+  const double a = ga[0] * ga[0] + ga[1] * ga[1] + ga[2] * ga[2];
+  const double b = gb[0] * gb[0] + gb[1] * gb[1] + gb[2] * gb[2];
+  const double c = ga[0] * gb[0] + ga[1] * gb[1] + ga[2] * gb[2];
+  const double h = b - a;
+  const double x = h * h + 4.0 * c * c;
+  if (!(fabs(c) > 1e-300) || !(x > 1e-280) || !is_finite(x)) return;
+  const double t = (h >= 0 ? 2.0 * c : -2.0 * c) / (fabs(h) + sqrt(x));
+  const double cs = 1.0 / sqrt(t * t + 1.0), sn = t * cs;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double g0 = ga[i], g1 = gb[i], v0 = va[i], v1 = vb[i];
+    ga[i] = cs * g0 - sn * g1;
+    gb[i] = sn * g0 + cs * g1;
+    va[i] = cs * v0 - sn * v1;
+    vb[i] = sn * v0 + cs * v1;
+  }
+}
+
+__device__ __forceinline__ void swap_if(bool sw, double (&a)[3], double (&b)[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double x = a[i], y = b[i];
+    a[i] = sw ? y : x;
+    b[i] = sw ? x : y;
+  }
+}
+
+// H = sum w (p - c0)(q - c1)^T, c = (c0, c1) -> R, t; false (R, t = identity) when anything is non-finite or H has fewer than two
+// usable singular directions.  The construction of rigid_kernel: jacobi_eig3 of H^T H, the two dominant right vectors v0, v1, left
+// vectors by H v, Gram-Schmidt, third vectors by cross products -- R = [v0 v1 v0xv1][u0 u1 u0xu1]^T is a proper rotation, equal to
+// V diag(1, 1, det(V U^T)) U^T.  Two things are added to it here, because this result is compared with an SVD:
+//  - H^T H squares the conditioning, and its eigenvectors come out to eps sigma_1^2 / sigma_2^2; two Hestenes sweeps on G = H V
+//    (one-sided rotations, which work on H itself) bring them to the eps sigma_1 / sigma_2 of the rotation's own conditioning;
+//  - the degeneracy rule "second eigenvalue of H^T H <= 1e-24 x the first" is evaluated on the Rayleigh quotients |H v1|^2 and
+//    |H v0|^2 after that: the diagonal the two-sided Jacobi leaves carries eps lambda_1 of rotation residue, which would make an
+//    exactly collinear sample look like sigma_2 = 1e-8 sigma_1.
+__device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&c)[6], double (&R)[3][3], double (&t)[3]) {
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ok = ok && is_finite(H[i][j]);
+#pragma unroll
+  for (int d = 0; d < 6; ++d) ok = ok && is_finite(c[d]);
+  double ata[3][3], V[3][3], ev[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ata[i][j] = ok ? H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j] : (i == j ? 1.0 : 0.0);
+  jacobi_eig3(ata, V, ev);
+  double v[3][3];   // v[c] = column c of V, sorted by descending eigenvalue below
+#pragma unroll
+  for (int cidx = 0; cidx < 3; ++cidx)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[cidx][k] = V[k][cidx];
+  {
+    bool sw = ev[0] < ev[1];
+    swap_if(sw, v[0], v[1]);
+    { const double a = ev[0], b = ev[1]; ev[0] = sw ? b : a; ev[1] = sw ? a : b; }
+    sw = ev[1] < ev[2];
+    swap_if(sw, v[1], v[2]);
+    { const double a = ev[1], b = ev[2]; ev[1] = sw ? b : a; ev[2] = sw ? a : b; }
+    sw = ev[0] < ev[1];
+    swap_if(sw, v[0], v[1]);
+  }
+  double g[3][3];   // g[c] = H v[c]
+#pragma unroll
+  for (int cidx = 0; cidx < 3; ++cidx)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) g[cidx][k] = H[k][0] * v[cidx][0] + H[k][1] * v[cidx][1] + H[k][2] * v[cidx][2];
+#pragma unroll
+  for (int sweep = 0; sweep < 2; ++sweep) {
+    hestenes_rotate(g[0], g[1], v[0], v[1]);
+    hestenes_rotate(g[0], g[2], v[0], v[2]);
+    hestenes_rotate(g[1], g[2], v[1], v[2]);
+  }
+  double n2[3];
+#pragma unroll
+  for (int cidx = 0; cidx < 3; ++cidx) n2[cidx] = g[cidx][0] * g[cidx][0] + g[cidx][1] * g[cidx][1] + g[cidx][2] * g[cidx][2];
+  {
+    bool sw = n2[0] < n2[1];
+    swap_if(sw, v[0], v[1]); swap_if(sw, g[0], g[1]);
+    { const double a = n2[0], b = n2[1]; n2[0] = sw ? b : a; n2[1] = sw ? a : b; }
+    sw = n2[1] < n2[2];
+    swap_if(sw, v[1], v[2]); swap_if(sw, g[1], g[2]);
+    { const double a = n2[1], b = n2[2]; n2[1] = sw ? b : a; n2[2] = sw ? a : b; }
+    sw = n2[0] < n2[1];
+    swap_if(sw, v[0], v[1]); swap_if(sw, g[0], g[1]);
+    { const double a = n2[0], b = n2[1]; n2[0] = sw ? b : a; n2[1] = sw ? a : b; }
+  }
+  double u0[3], u1[3], v0[3], v1[3];
+  const double s1sq = n2[0];
+  const double r0 = 1.0 / sqrt(s1sq);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { u0[k] = g[0][k] * r0; v0[k] = v[0][k]; }
+  const double du = u0[0] * g[1][0] + u0[1] * g[1][1] + u0[2] * g[1][2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) u1[k] = g[1][k] - du * u0[k];
+  const double s2sq = u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2];
+  ok = ok && s2sq > 1e-24 * s1sq;      // (false for NaN and for s1sq = 0)
+  const double r1 = 1.0 / sqrt(s2sq);
+  const double dv = v0[0] * v[1][0] + v0[1] * v[1][1] + v0[2] * v[1][2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { u1[k] *= r1; v1[k] = v[1][k] - dv * v0[k]; }
+  const double rv = 1.0 / sqrt(v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2]);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) v1[k] *= rv;
+  const double v2[3] = {v0[1] * v1[2] - v0[2] * v1[1], v0[2] * v1[0] - v0[0] * v1[2], v0[0] * v1[1] - v0[1] * v1[0]};
+  const double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      R[i][j] = v0[i] * u0[j] + v1[i] * u1[j] + v2[i] * u2[j];
+      ok = ok && is_finite(R[i][j]);
+    }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    t[i] = c[3 + i] - (R[i][0] * c[0] + R[i][1] * c[1] + R[i][2] * c[2]);
+    ok = ok && is_finite(t[i]);
+  }
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      t[i] = 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
+    }
+  }
+  return ok;
+}
+
+template <typename T>
+__device__ __forceinline__ void store_model(T *__restrict__ m, const double (&R)[3][3], const double (&t)[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) m[4 * i + j] = (T)R[i][j];
+    m[4 * i + 3] = (T)t[i];
+  }
+  m[12] = m[13] = m[14] = T(0);
+  m[15] = T(1);
+}
+
+// d2 of one point under one model, the ONE form the score and the update kernel share (their inlier decisions agree bit for bit)
+template <typename T>
+__device__ __forceinline__ T rigid_d2(const T (&m)[12], const T (&x)[6]) {
+  T d2 = T(0);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const T pred = fma(m[4 * i], x[0], fma(m[4 * i + 1], x[1], fma(m[4 * i + 2], x[2], m[4 * i + 3])));
+    const T e = x[3 + i] - pred;
+    d2 = fma(e, e, d2);
+  }
+  return d2;
+}
+
+// ---- (1) minimal samples -> rigid models: one lane = one sample of 3 <= k <= 8 rows read through the index sets -------------
+template <typename T>
+__global__ __launch_bounds__(64) void kabsch_gather_kernel(const T *__restrict__ matches, const int32_t *__restrict__ idx, int Bt,
+                                                           int B, int N, int k, T *__restrict__ models,
+                                                           uint8_t *__restrict__ valid) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= Bt) return;
+  const T *base = matches + (size_t)(s / B) * N * 6;
+  const int32_t *gi = idx + (size_t)s * k;
+  bool in_range = true;
+  for (int r = 0; r < k; ++r) in_range = in_range && gi[r] >= 0 && gi[r] < N;
+  auto rowp = [&](int r) -> const T * { return base + (size_t)(in_range ? gi[r] : 0) * 6; };   // (a bad index reads row 0, valid = 0)
+  double c[6] = {0, 0, 0, 0, 0, 0};
+  for (int r = 0; r < k; ++r) {
+    const T *x = rowp(r);
+#pragma unroll
+    for (int d = 0; d < 6; ++d) c[d] += (double)x[d];
+  }
+  const double rn = 1.0 / (double)k;
+#pragma unroll
+  for (int d = 0; d < 6; ++d) c[d] *= rn;
+  double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  for (int r = 0; r < k; ++r) {
+    const T *x = rowp(r);
+    double dp[3], dq[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      dp[d] = (double)x[d] - c[d];
+      dq[d] = (double)x[3 + d] - c[3 + d];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) H[i][j] += dp[i] * dq[j];
+  }
+  double R[3][3], t[3];
+  bool ok = kabsch3(H, c, R, t);
+  if (ok && !in_range) {
+    ok = false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      t[i] = 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
+    }
+  }
+  store_model(models + (size_t)s * 16, R, t);
+  valid[s] = ok;
+}
+
+// ---- (2) MSAC score and inlier count of every model against every point ----------------------------------------------------
+// The mapping of rigid_residual_kernel: a lane owns 8 consecutive points in registers, the model is wave-uniform.  One block =
+// (pair, tile of kSModels models) and walks ALL the pair's points chunk by chunk, so the sum of a (pair, model) is reduced in one
+// fixed order -- lane, wave butterfly, chunk after chunk into the wave's LDS slot, the four slots in order -- and a repeated launch
+// gives the same bits (scores are compared strictly downstream).  No [P,M,N] tensor, no floating-point atomics.
+constexpr int kSThreads = 256, kSPts = 8, kSChunk = kSThreads * kSPts, kSModels = 16;
+
+template <typename T>
+__global__ __launch_bounds__(kSThreads) void rigid_msac_score_kernel(const T *__restrict__ pts, const T *__restrict__ models,
+                                                                     const uint8_t *__restrict__ valid, const T *__restrict__ thr2,
+                                                                     int M, int N, T *__restrict__ scores,
+                                                                     int32_t *__restrict__ inliers, PairGate gate) {
+  __shared__ T part[kSThreads / 64][kSModels];
+  __shared__ int pcnt[kSThreads / 64][kSModels];
+  const int p = blockIdx.y, m0 = blockIdx.x * kSModels;
+  if (gate.closed(p)) return;   // a terminated pair of a multi-round call (block-uniform): its scores keep their contents
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int mcount = min(kSModels, M - m0);
+  const T *pt = pts + (size_t)p * N * 6;
+  const T *md = models + ((size_t)p * M + m0) * 16;
+  const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
+  const T t2 = thr2[p];
+  const T inv = T(1) / t2;
+  if (tid < (kSThreads / 64) * kSModels) {
+    (&part[0][0])[tid] = T(0);
+    (&pcnt[0][0])[tid] = 0;
+  }
+  __syncthreads();
+  for (int c0 = 0; c0 < N; c0 += kSChunk) {
+    const int n0 = c0 + tid * kSPts;
+    T x[kSPts][6];
+#pragma unroll
+    for (int j = 0; j < kSPts; ++j)
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[j][d] = (n0 + j < N) ? pt[(size_t)(n0 + j) * 6 + d] : T(0);
+    const int nvalid = min(kSPts, max(0, N - n0));
+    for (int ml = 0; ml < mcount; ++ml) {
+      if (vd && !vd[ml]) continue;   // (wave-uniform)
+      T m[12];
+#pragma unroll
+      for (int q = 0; q < 12; ++q) m[q] = md[ml * 16 + q];
+      T acc = T(0);
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < kSPts; ++j) {
+        const T d2 = rigid_d2<T>(m, x[j]);
+        const T sv = T(1) - d2 * inv;
+        const bool live = j < nvalid;
+        acc += (live && sv > T(0)) ? sv : T(0);      // a NaN distance contributes nothing
+        cnt += (live && d2 < t2) ? 1 : 0;
+      }
+      acc = wave_sum(acc);
+      cnt = wave_sum(cnt);
+      if (lane == 0) {
+        part[wv][ml] += acc;
+        pcnt[wv][ml] += cnt;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < mcount) {
+    const bool ok = !vd || vd[tid];
+    T v = T(0);
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kSThreads / 64; ++w) {
+      v += part[w][tid];
+      n += pcnt[w][tid];
+    }
+    scores[(size_t)p * M + m0 + tid] = ok ? v : T(-1);
+    if (inliers) inliers[(size_t)p * M + m0 + tid] = ok ? n : 0;
+  }
+}
+
+// ---- (3) the state step of dr_ransac_update for 4x4 models and 6-column points -------------------------------------------------
+// One block per pair: the block is the only writer of the pair's state (no ping-pong needed).  Terminated pairs return at once.
+constexpr int kRUThreads = 256;
+
+template <typename T>
+__global__ __launch_bounds__(kRUThreads) void registration_update_kernel(
+    const T *__restrict__ pts, const T *__restrict__ models, const uint8_t *__restrict__ valid, const T *__restrict__ scores,
+    const T *__restrict__ thr2, int M, int N, int B, double confidence, double eps, int max_iterations,
+    T *__restrict__ best_score, T *__restrict__ best_model, uint8_t *__restrict__ best_mask, int32_t *__restrict__ best_inliers,
+    int32_t *__restrict__ iters, double *__restrict__ max_iters) {
+  __shared__ T s_val[kRUThreads / 64];
+  __shared__ int s_idx[kRUThreads / 64];
+  __shared__ int s_cnt[kRUThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int it = iters[p];
+  if ((double)it >= max_iters[p]) return;   // this pair has terminated (uniform across the block)
+  const T bs = best_score[p];
+  const T *sc = scores + (size_t)p * M;
+  const uint8_t *vd = valid ? valid + (size_t)p * M : nullptr;
+  T bv = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int m = tid; m < M; m += kRUThreads) {
+    const T v = sc[m];
+    const bool ok = (!vd || vd[m]) && v == v;
+    if (ok && (v > bv || (v == bv && m < bi))) { bv = v; bi = m; }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  if (lane == 0) { s_val[wv] = bv; s_idx[wv] = bi; }
+  __syncthreads();   // (every thread has read iters / max_iters / best_score by now: thread 0 may write them below)
+  bv = s_val[0]; bi = s_idx[0];
+#pragma unroll
+  for (int w = 1; w < kRUThreads / 64; ++w)
+    if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+  const bool have = bi != 0x7fffffff;              // (a -inf score of a valid model has an index too)
+  const bool better = have && (bv > bs || it == 0);
+  if (better) {
+    T m[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) m[q] = models[((size_t)p * M + bi) * 16 + q];
+    const T t2 = thr2[p];
+    int cnt = 0;
+    for (int n = tid; n < N; n += kRUThreads) {
+      const T *xp = pts + ((size_t)p * N + n) * 6;
+      T x[6];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = xp[d];
+      const bool in = rigid_d2<T>(m, x) < t2;
+      best_mask[(size_t)p * N + n] = in;
+      cnt += in;
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (tid < 16) best_model[(size_t)p * 16 + tid] = models[((size_t)p * M + bi) * 16 + tid];
+    if (tid == 0) {
+      int inl = 0;
+#pragma unroll
+      for (int w = 0; w < kRUThreads / 64; ++w) inl += s_cnt[w];
+      best_inliers[p] = inl;
+      best_score[p] = bv;
+      max_iters[p] = adaptive_max_iters(inl, N, 3, confidence, eps, max_iterations);
+    }
+  }
+  if (tid == 0) iters[p] = it + B;
+}
+
+// ---- (4) Kabsch refit over the rows a mask selects: one block per pair, f64, two passes, fixed-order reduction ---------------
+constexpr int kRFThreads = 256;
+
+template <int K>
+__device__ __forceinline__ void block_sum_f64(double (&v)[K], double (*s)[K]) {   // s: shared [kRFThreads / 64][K]
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const double w = wave_sum(v[i]);
+    if (lane == 0) s[wv][i] = w;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    double a = s[0][i];
+#pragma unroll
+    for (int w = 1; w < kRFThreads / 64; ++w) a += s[w][i];
+    v[i] = a;
+  }
+  __syncthreads();   // (the buffer may be reused)
+}
+
+template <typename T>
+__global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__restrict__ pts, const uint8_t *__restrict__ mask,
+                                                                 const T *__restrict__ weights, int N, T *__restrict__ model,
+                                                                 uint8_t *__restrict__ valid) {
+  __shared__ double s_red[kRFThreads / 64][9];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const T *pt = pts + (size_t)p * N * 6;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+  // pass 1: weighted sums of p and q, the weight sum and the row count (entries 0..5, 6, 7; entry 8 unused)
+  double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int n = tid; n < N; n += kRFThreads) {
+    if (mk && !mk[n]) continue;
+    const double w = wt ? (double)wt[n] : 1.0;
+#pragma unroll
+    for (int d = 0; d < 6; ++d) a[d] += w * (double)pt[(size_t)n * 6 + d];
+    a[6] += w;
+    a[7] += 1.0;
+  }
+  block_sum_f64<9>(a, s_red);
+  const double rows = a[7], rw = 1.0 / a[6];
+  double c[6];
+#pragma unroll
+  for (int d = 0; d < 6; ++d) c[d] = a[d] * rw;
+  // pass 2: H = sum w (p - c0)(q - c1)^T
+  double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int n = tid; n < N; n += kRFThreads) {
+    if (mk && !mk[n]) continue;
+    const double w = wt ? (double)wt[n] : 1.0;
+    double dp[3], dq[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      dp[d] = w * ((double)pt[(size_t)n * 6 + d] - c[d]);
+      dq[d] = (double)pt[(size_t)n * 6 + 3 + d] - c[3 + d];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) h[3 * i + j] += dp[i] * dq[j];
+  }
+  block_sum_f64<9>(h, s_red);
+  if (tid != 0) return;
+  double H[3][3], R[3][3], t[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
+  bool ok = kabsch3(H, c, R, t);
+  if (ok && !(rows >= 3.0 && a[6] > 0.0)) {
+    ok = false;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      t[i] = 0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
+    }
+  }
+  store_model(model + (size_t)p * 16, R, t);
+  valid[p] = ok;
+}
+
+template <typename T>
+int kabsch_gather_entry(const T *matches, const int32_t *idx, int P, int B, int N, int k, T *models, uint8_t *valid, void *stream) {
+  const int Bt = P * B;
+  hipLaunchKernelGGL((kabsch_gather_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, matches, idx, Bt, B, N, k,
+                     models, valid);
+  return check_launch("kabsch_gather_kernel");
+}
+
+template <typename T>
+int rigid_msac_score_entry(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
+                           int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
+  PairGate gate;
+  gate.iters = gate_iters;
+  gate.max_iters = gate_max_iters;
+  hipLaunchKernelGGL((rigid_msac_score_kernel<T>), dim3((M + kSModels - 1) / kSModels, P), dim3(kSThreads), 0, (hipStream_t)stream,
+                     matches, models, valid, thr2, M, N, scores, inliers, gate);
+  return check_launch("rigid_msac_score_kernel");
+}
+
+template <typename T>
+int registration_update_entry(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P, int M,
+                              int N, int B, double confidence, double eps, int max_iterations, T *best_score, T *best_model,
+                              uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters, void *stream) {
+  hipLaunchKernelGGL((registration_update_kernel<T>), dim3(P), dim3(kRUThreads), 0, (hipStream_t)stream, matches, models, valid,
+                     scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask, best_inliers, iters,
+                     max_iters);
+  return check_launch("registration_update_kernel");
+}
+
+template <typename T>
+int refit_rigid_entry(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *model, uint8_t *valid, void *stream) {
+  hipLaunchKernelGGL((refit_rigid_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, mask, weights, N, model,
+                     valid);
+  return check_launch("refit_rigid_kernel");
+}
+
+}  // namespace dr
+
+extern "C" {
+
+#define DR_KABSCH_GATHER_CHECKS                                                                                           \
+  DR_REQUIRE(matches && idx && models && valid, "null pointer");                                                          \
+  DR_REQUIRE(P > 0 && B > 0 && N > 0 && k >= 3 && k <= 8 && (long)P * B < (1l << 31), "need P, B, N > 0 and 3 <= k <= 8 rows per sample")
+
+int dr_kabsch_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, int k, float *models, uint8_t *valid,
+                         void *stream) {
+  DR_KABSCH_GATHER_CHECKS;
+  return dr::kabsch_gather_entry<float>(matches, idx, P, B, N, k, models, valid, stream);
+}
+int dr_kabsch_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, int k, double *models, uint8_t *valid,
+                         void *stream) {
+  DR_KABSCH_GATHER_CHECKS;
+  return dr::kabsch_gather_entry<double>(matches, idx, P, B, N, k, models, valid, stream);
+}
+
+#define DR_RIGID_MSAC_CHECKS                                                                              \
+  DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                        \
+  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                         \
+  DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither")
+
+int dr_rigid_msac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
+                            float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                            void *stream) {
+  DR_RIGID_MSAC_CHECKS;
+  return dr::rigid_msac_score_entry<float>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
+}
+int dr_rigid_msac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
+                            int N, double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                            void *stream) {
+  DR_RIGID_MSAC_CHECKS;
+  return dr::rigid_msac_score_entry<double>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
+}
+
+#define DR_REGISTRATION_UPDATE_CHECKS                                                                                      \
+  DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters, \
+             "null pointer");                                                                                              \
+  DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes")
+
+int dr_registration_update_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores,
+                               const float *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
+                               float *best_score, float *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
+                               double *max_iters, void *stream) {
+  DR_REGISTRATION_UPDATE_CHECKS;
+  return dr::registration_update_entry<float>(matches, models, valid, scores, thr2, P, M, N, B, confidence, eps, max_iterations,
+                                              best_score, best_model, best_mask, best_inliers, iters, max_iters, stream);
+}
+int dr_registration_update_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores,
+                               const double *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
+                               double *best_score, double *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
+                               double *max_iters, void *stream) {
+  DR_REGISTRATION_UPDATE_CHECKS;
+  return dr::registration_update_entry<double>(matches, models, valid, scores, thr2, P, M, N, B, confidence, eps, max_iterations,
+                                               best_score, best_model, best_mask, best_inliers, iters, max_iters, stream);
+}
+
+int dr_refit_rigid_f32(const float *matches, const uint8_t *mask, const float *weights, int P, int N, float *model, uint8_t *valid,
+                       void *stream) {
+  DR_REQUIRE(matches && model && valid, "null pointer");
+  DR_REQUIRE(P > 0 && N > 0, "bad sizes");
+  return dr::refit_rigid_entry<float>(matches, mask, weights, P, N, model, valid, stream);
+}
+int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model, uint8_t *valid,
+                       void *stream) {
+  DR_REQUIRE(matches && model && valid, "null pointer");
+  DR_REQUIRE(P > 0 && N > 0, "bad sizes");
+  return dr::refit_rigid_entry<double>(matches, mask, weights, P, N, model, valid, stream);
+}
+
+}  // extern "C"

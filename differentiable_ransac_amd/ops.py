@@ -666,6 +666,89 @@ def ransac3d_update(pts: torch.Tensor, models: torch.Tensor, valid: Optional[tor
     return out_res, out_model, idx
 
 
+# ------------------------------------------------------------------------------------------ robust 3-D registration
+# matches [P,N,6] = (p, q), models [.,4,4] = [[R, t], [0, 0, 0, 1]], q_hat = R p + t.  `threshold` is a DISTANCE here: a point is an
+# inlier iff |q - q_hat|^2 < threshold^2 (rigid_residual compares the squared distance with its threshold itself).
+def thr2_tensor(threshold, P: int, like: torch.Tensor) -> torch.Tensor:
+    """threshold^2 per pair, [P] in the correspondences' dtype: what the kernels take (a driver computes it once per call and hands
+    it to the wrappers below as `thr2=`)"""
+    t = _thr_tensor(threshold, P, like)
+    return t * t
+
+
+def kabsch_gather(matches: torch.Tensor, idx: torch.Tensor):
+    """dr_kabsch_gather: matches [P,N,6], idx [P,B,k] int32 (3 <= k <= 8) -> (models [P,B,4,4], valid [P,B] bool): the least-squares
+    rigid fit (Kabsch) of every sample; a degenerate sample (coincident / collinear rows) is the identity with valid = 0."""
+    if matches.dim() != 3 or matches.shape[-1] != 6 or idx.dim() != 3 or idx.dtype != torch.int32:
+        raise L.DransacError("kabsch_gather: correspondences [P,N,6] and int32 index sets [P,B,k]")
+    P, N, _ = matches.shape
+    _, B, k = idx.shape
+    models = torch.empty((P, B, 4, 4), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_kabsch_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B),
+           c_int(N), c_int(k), ptr(models), ptr(valid), stream())
+    return models, valid
+
+
+def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
+                     want_inliers: bool = True, gate=None, thr2: Optional[torch.Tensor] = None):
+    """dr_rigid_msac_score: matches [P,N,6], models [P,M,4,4], threshold = inlier DISTANCE (float or [P]) ->
+    (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None).  Invalid slots score
+    -1.  Bit-repeatable (fixed reduction order).  gate = RegistrationState: the blocks of terminated pairs return at once."""
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
+    scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
+    inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
+    L.call(f"dr_rigid_msac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
+    return scores, inliers
+
+
+class RegistrationState:
+    """Per-pair state of a BatchedRegistration call, on the device: best_score [P], best_model [P,4,4] (identity), best_mask [P,N],
+    best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch (capturable)."""
+
+    def __init__(self, P: int, N: int, max_iterations: int, device, dtype):
+        self.best_score = torch.zeros(P, device=device, dtype=dtype)
+        self.best_model = torch.eye(4, device=device, dtype=dtype).repeat(P, 1, 1)
+        self.best_mask = torch.zeros(P, N, device=device, dtype=torch.bool)
+        self.best_inliers = torch.zeros(P, device=device, dtype=torch.int32)
+        self.iters = torch.zeros(P, device=device, dtype=torch.int32)
+        self.max_iters = torch.full((P,), float(max_iterations), device=device, dtype=torch.float64)
+        self.max_iterations = int(max_iterations)
+
+
+def registration_update(state: RegistrationState, matches, models, valid, scores, threshold, B: int,
+                        confidence: float = 0.999, eps: float = 1e-5, thr2: Optional[torch.Tensor] = None) -> None:
+    """dr_registration_update, in place on `state`: per pair with iters < max_iters the first arg-max of scores [P,M] over valid,
+    non-NaN models replaces the state if score > best_score or iters == 0 (mask and inlier count recomputed with the DISTANCE
+    `threshold`, max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 3))); iters += B."""
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
+    L.call(f"dr_registration_update_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(scores.contiguous()), ptr(thr2), c_int(P), c_int(M), c_int(N), c_int(int(B)), L.c_double(confidence), L.c_double(eps),
+           c_int(state.max_iterations), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
+           ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
+
+
+def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
+    """dr_refit_rigid: the Kabsch fit over the rows mask [P,N] selects (None = all), weights [P,N] (optional) multiplying a row's
+    term in the means and in H -> (model [P,4,4], valid [P] bool); valid = 0 below three rows or for a degenerate selection."""
+    P, N, _ = matches.shape
+    if weights is not None and weights.shape != (P, N):
+        raise L.DransacError("refit weights are [P,N], one per point")
+    if mask is not None and mask.shape != (P, N):
+        raise L.DransacError("the refit mask is [P,N], one flag per point")
+    model = torch.empty((P, 4, 4), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_refit_rigid_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
+           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(model), ptr(valid),
+           stream())
+    return model, valid
+
+
 def select_closest(models: torch.Tensor, valid: Optional[torch.Tensor], gt: torch.Tensor, want_keep: bool = False):
     """K5: models [P,B,S,3,3], valid [P,B,S] | None, gt [P,3,3] -> chosen [P,B,3,3], which [P,B] int32 (+ keep [P,B] bool =
     `which >= 0` from the same launch when want_keep)."""

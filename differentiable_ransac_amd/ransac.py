@@ -936,3 +936,86 @@ class BatchedRANSAC3D(_SeededDriver):
                 best, best_model, _ = ops.ransac3d_update(matches, model, valid.reshape(P, self.B), res, self.threshold, best,
                                                           best_model, best_mask)
             return dict(model=best_model, residual=best, mask=best_mask, masks=masks)
+
+
+class BatchedRegistration(_SeededDriver):
+    """Robust rigid registration of point-cloud pairs, test mode only: matches [P,N,6] = (p, q), logits [P,N] ->
+    dict(model [P,4,4] = [[R, t], [0, 0, 0, 1]] with q ~ R p + t, mask [P,N], score [P], inliers [P], iterations [P]).
+
+    One round = K1 Gumbel top-k (index sets of `num_samples` points) -> dr_kabsch_gather (the least-squares rigid fit of every
+    sample: a correct Kabsch solver, not the reference's estimate_model that RANSAC3D / BatchedRANSAC3D reproduce) ->
+    dr_rigid_msac_score (MSAC score and inlier count of every model against every point) -> dr_registration_update (arg-max,
+    "better?" test, mask, adaptive stop with sample size 3, all per-pair state on the device).  The host reads back "does any
+    pair continue?" after each round.  With `refit`, the Kabsch fit on the best mask replaces the model where it scores strictly
+    higher; the mask stays the RANSAC winner's, as in the two-view path.
+
+    `threshold` is a DISTANCE: a point is an inlier iff |q - (R p + t)|^2 < threshold^2 (BatchedRANSAC3D and
+    ops.rigid_residual compare the squared distance with their threshold itself).
+
+    device_termination = True issues every round, gated on the device, with no read-back, so that a call can be captured by
+    graphs.GraphedStep; it is refused above 16 rounds.  Pipelining, super-rounds and local optimisation: not here."""
+
+    def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
+                 num_samples=3, refit=True, eps=1e-5):
+        if not 3 <= int(num_samples) <= 8:
+            raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
+        if int(max_iterations) < 1:
+            raise ValueError(f"max_iterations must be at least 1, got {max_iterations!r}")
+        if int(ransac_batch_size) < 1:
+            raise ValueError(f"ransac_batch_size must be at least 1, got {ransac_batch_size!r}")
+        self.B = int(ransac_batch_size)
+        self.k = int(num_samples)
+        self.threshold = threshold
+        self.confidence = confidence
+        self.max_iterations = int(max_iterations)
+        self.tau = tau
+        self._seeds = _Seeds(seed)
+        self.refit = refit
+        self.eps = eps
+        self._device_termination = False
+
+    @property
+    def rounds(self):
+        """rounds a call can run at most"""
+        return max(1, math.ceil(self.max_iterations / self.B))
+
+    @property
+    def device_termination(self):
+        return self._device_termination
+
+    @device_termination.setter
+    def device_termination(self, on):
+        if on and self.rounds > 16:
+            raise ValueError(f"device_termination issues every round: at most 16 rounds per call, this driver has {self.rounds} "
+                             "(raise ransac_batch_size or lower max_iterations)")
+        self._device_termination = bool(on)
+
+    def __call__(self, matches, logits, gumbels=None):
+        """`gumbels` (optional, list of [P,B,N] tensors, one per round) replaces the in-kernel noise: parity runs."""
+        P, N, c = matches.shape
+        if c != 6:
+            raise ValueError("matches must be [P,N,6] = (p, q)")
+        rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
+        if self._device_termination and rounds > 16:      # (max_iterations / ransac_batch_size assigned after the switch)
+            raise ValueError("device_termination issues every round: at most 16 rounds per call")
+        with torch.no_grad():
+            matches = matches.contiguous()
+            st = ops.RegistrationState(P, N, self.max_iterations, matches.device, matches.dtype)
+            thr2 = ops.thr2_tensor(self.threshold, P, matches)
+            for r in range(rounds):
+                gate = st if (self._device_termination and r > 0) else None
+                g = None if gumbels is None else gumbels[r]
+                idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
+                models, valid = ops.kabsch_gather(matches, idx)
+                scores, _ = ops.rigid_msac_score(matches, models, None, valid, want_inliers=False, gate=gate, thr2=thr2)
+                ops.registration_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
+                if not self._device_termination and r + 1 < rounds and not bool((st.iters.double() < st.max_iters).any()):
+                    break
+            model, score = st.best_model, st.best_score
+            if self.refit:
+                cand, cvalid = ops.refit_rigid(matches, st.best_mask)
+                cscore, _ = ops.rigid_msac_score(matches, cand.unsqueeze(1), None, cvalid.unsqueeze(1), want_inliers=False, thr2=thr2)
+                take = cscore[:, 0] > score          # (an invalid candidate scores -1 and never wins)
+                model = torch.where(take[:, None, None], cand, model)
+                score = torch.where(take, cscore[:, 0], score)
+            return dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)

@@ -338,7 +338,51 @@ int dr_ransac3d_update_f64(const double *pts, const double *models, const uint8_
                            double *best_model_out, uint8_t *best_mask, int32_t *best_idx, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * K5  train-mode best-of-S selection      RANSAC.__call__, ransac.py:87-96
+ * Robust 3-D registration (test mode; ransac.BatchedRegistration).  Not a restatement of upstream code: the reference's
+ * `valid=True` branch of RANSAC3D raises NameError, and dr_solve_rigid reproduces its estimate_model on purpose (Q9, the row-sum
+ * translation of rigid...:66).  matches [P,N,6] = (p, q); models [.,16] = row-major 4x4 [[R, t], [0, 0, 0, 1]]; q_hat = R p + t,
+ * d2 = |q - q_hat|^2.  The threshold is a DISTANCE and enters as thr2 [P] = threshold^2: a point is an inlier iff d2 < thr2
+ * (dr_rigid_residual compares d2 with its threshold argument itself).  MSAC score = sum_n max(0, 1 - d2_n / thr2).
+ *
+ *   dr_kabsch_gather        idx [P,B,k] int32, 3 <= k <= 8 -> models [P,B,16], valid [P,B]: the least-squares rigid fit of every
+ *     sample, f64 inside: c0, c1 = means, H = sum (p - c0)(q - c1)^T = U S V^T, R = V diag(1, 1, det(V U^T)) U^T, t = c1 - R c0.
+ *     valid = 0, model = identity: anything non-finite, an index outside [0, N), or the second eigenvalue of H^T H <= 1e-24 x the
+ *     first (sigma_2 <= 1e-12 sigma_1: coincident or collinear rows).
+ *   dr_rigid_msac_score     models [P,M,16], valid [P,M] or NULL -> scores [P,M], inliers [P,M] int32 (or NULL); invalid slots
+ *     score -1 (0 inliers).  No [P,M,N] tensor; every sum is reduced in one fixed order, so a repeated launch gives the same bits.
+ *     gate_iters / gate_max_iters (optional): the blocks of pairs with iters >= max_iters return at once.
+ *   dr_registration_update  dr_ransac_update's state step: for every pair with iters < max_iters, the first arg-max of scores over
+ *     valid, non-NaN models replaces the state if score > best_score or iters == 0 -- best_score, best_model [P,16], best_mask [P,N]
+ *     and best_inliers recomputed for the winner, max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 3)) in f64 --
+ *     and iters += B.  No valid model: only iters moves.  Terminated pairs are untouched.  One block per pair writes its state.
+ *   dr_refit_rigid          the fit of dr_kabsch_gather over the rows mask [P,N] selects (NULL = all), weights [P,N] (optional)
+ *     multiplying a row's term in the means and in H -> model [P,16], valid [P]; valid = 0 below three rows or for a degenerate H.
+ * ------------------------------------------------------------------------------------------ */
+int dr_kabsch_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, int k, float *models, uint8_t *valid,
+                         void *stream);
+int dr_kabsch_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, int k, double *models, uint8_t *valid,
+                         void *stream);
+int dr_rigid_msac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
+                            float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                            void *stream);
+int dr_rigid_msac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
+                            int N, double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                            void *stream);
+int dr_registration_update_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores,
+                               const float *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
+                               float *best_score, float *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
+                               double *max_iters, void *stream);
+int dr_registration_update_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores,
+                               const double *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
+                               double *best_score, double *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
+                               double *max_iters, void *stream);
+int dr_refit_rigid_f32(const float *matches, const uint8_t *mask, const float *weights, int P, int N, float *model, uint8_t *valid,
+                       void *stream);
+int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model, uint8_t *valid,
+                       void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K5  train-mode best-of-S selection     RANSAC.__call__, ransac.py:87-96
  *   chosen[p,b] = models[p,b,argmin_s ||models[p,b,s] - gt[p]||_F]; invalid slots (valid == 0) are
  *   skipped; which [P*B] int32 (-1 when no slot is valid; chosen = eye(3) then).
  * ------------------------------------------------------------------------------------------ */
