@@ -627,27 +627,9 @@ __global__ __launch_bounds__(kThreads) void select_best_kernel(const T *__restri
   __shared__ int s_idx[kThreads / kWave];
   __shared__ int s_cnt[kThreads / kWave];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const T *sc = scores + (size_t)p * M;
-  const uint8_t *vd = valid ? valid + (size_t)p * M : nullptr;
-  T bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int m = tid; m < M; m += kThreads) {
-    T v = sc[m];
-    bool ok = (v == v) && (!vd || vd[m]);
-    if (ok && (v > bv || (v == bv && m < bi))) { bv = v; bi = m; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    T ov = __shfl_xor(bv, o, 64);
-    int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { s_val[wv] = bv; s_idx[wv] = bi; }
-  __syncthreads();
-  bv = s_val[0]; bi = s_idx[0];
-#pragma unroll
-  for (int w = 1; w < kThreads / kWave; ++w)
-    if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+  T bv;
+  int bi;
+  block_arg_best<T, kThreads, true>(scores + (size_t)p * M, valid ? valid + (size_t)p * M : nullptr, M, s_val, s_idx, bv, bi);
   const bool none = bi == 0x7fffffff;
   T m[9];
 #pragma unroll
@@ -731,11 +713,6 @@ constexpr int kUpdThreads = 1024;
 // and the kernel WALKS them in order with that loop's own rule: stop when iters >= max_iters, arg-max of the sub-batch, better-test,
 // best mask / inlier count, new max_iters, iters += B.  State after the launch = state after that many iterations of the loop.
 constexpr int kUpdMaxSub = 512;   // sub-batches per launch
-
-template <typename T>
-__device__ __forceinline__ void argmax_merge(T &bv, int &bi, T ov, int oi) {
-  if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-}
 
 template <typename T>
 __global__ __launch_bounds__(kUpdThreads) void ransac_update_kernel(

@@ -1,5 +1,6 @@
 // Per-point and per-pair pieces of the test-mode loop that several launches share: the Sampson / MSAC rule of the scoring,
-// update, refit-acceptance and local-optimisation kernels, and the adaptive stop of ransac.py:202-215.
+// update, refit-acceptance and local-optimisation kernels, the adaptive stop of ransac.py:202-215, and the first arg-best over a
+// pair's scores of the selection and update kernels (2-D and 3-D).
 #pragma once
 #include "dr_common.hpp"
 
@@ -40,6 +41,33 @@ __device__ __forceinline__ double adaptive_max_iters(int inliers, int N, int k, 
   double nmi = (double)max_iterations;
   if (!(prob >= 1.0 - eps)) nmi = fmax(0.0, log10(1.0 - confidence) / log10(1.0 - rk + eps));
   return fmin((double)max_iterations, nmi);
+}
+
+// (bv, bi) <- the better of (bv, bi) and (ov, oi): the larger value (kMax = false: the smaller), the lower index on a tie
+template <typename T, bool kMax = true>
+__device__ __forceinline__ void argmax_merge(T &bv, int &bi, T ov, int oi) {
+  if ((kMax ? ov > bv : ov < bv) || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+}
+
+// First arg-best of row[0 .. M) over the entries that are valid (valid == NULL: all of them) and not NaN, by a block of kThreads
+// threads: strided scan, wave butterfly, ONE __syncthreads(), then every thread merges the wave results itself, so all threads
+// return the same (bv, bi).  bi = 0x7fffffff: no entry qualifies.  s_val, s_idx: shared, kThreads / 64 entries each.
+template <typename T, int kThreads, bool kMax>
+__device__ __forceinline__ void block_arg_best(const T *__restrict__ row, const uint8_t *__restrict__ valid, int M, T *s_val,
+                                               int *s_idx, T &bv, int &bi) {
+  bv = kMax ? -INFINITY : INFINITY;
+  bi = 0x7fffffff;
+  for (int m = threadIdx.x; m < M; m += kThreads) {
+    const T v = row[m];
+    if ((!valid || valid[m]) && v == v) argmax_merge<T, kMax>(bv, bi, v, m);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) argmax_merge<T, kMax>(bv, bi, __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
+  if ((threadIdx.x & 63) == 0) { s_val[threadIdx.x >> 6] = bv; s_idx[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  bv = s_val[0]; bi = s_idx[0];
+#pragma unroll
+  for (int w = 1; w < kThreads / 64; ++w) argmax_merge<T, kMax>(bv, bi, s_val[w], s_idx[w]);
 }
 
 }  // namespace dr

@@ -7,7 +7,7 @@
 // Unlike dr_solve_rigid (the reference's estimate_model, kept for parity with its training branch: cov^T cov with flag, the
 // row-sum translation of rigid...:66) this is the least-squares rigid fit: R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T,
 // t = c1 - R c0.
-#include "ransac_device.hpp"
+#include "rigid_device.hpp"
 #include "solver_common.hpp"
 
 namespace dr {
@@ -33,26 +33,19 @@ __device__ __forceinline__ void hestenes_rotate(double (&ga)[3], double (&gb)[3]
   }
 }
 
-__device__ __forceinline__ void swap_if(bool sw, double (&a)[3], double (&b)[3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double x = a[i], y = b[i];
-    a[i] = sw ? y : x;
-    b[i] = sw ? x : y;
-  }
-}
-
-// H = sum w (p - c0)(q - c1)^T, c = (c0, c1) -> R, t; false (R, t = identity) when anything is non-finite or H has fewer than two
-// usable singular directions.  The construction of rigid_kernel: jacobi_eig3 of H^T H, the two dominant right vectors v0, v1, left
-// vectors by H v, Gram-Schmidt, third vectors by cross products -- R = [v0 v1 v0xv1][u0 u1 u0xu1]^T is a proper rotation, equal to
-// V diag(1, 1, det(V U^T)) U^T.  Two things are added to it here, because this result is compared with an SVD:
+// H = sum w (p - c0)(q - c1)^T, c = (c0, c1) -> R, t; false (R, t = identity) when the caller's sample or selection is not `usable`,
+// anything is non-finite or H has fewer than two usable singular directions.  The construction of rigid_kernel (its shared steps
+// are rigid_device.hpp's): jacobi_eig3 of H^T H, the two dominant right vectors v0, v1, left vectors by H v, Gram-Schmidt, third
+// vectors by cross products -- R = [v0 v1 v0xv1][u0 u1 u0xu1]^T is a proper rotation, equal to V diag(1, 1, det(V U^T)) U^T.
+// Two things are added to it here, because this result is compared with an SVD:
 //  - H^T H squares the conditioning, and its eigenvectors come out to eps sigma_1^2 / sigma_2^2; two Hestenes sweeps on G = H V
 //    (one-sided rotations, which work on H itself) bring them to the eps sigma_1 / sigma_2 of the rotation's own conditioning;
 //  - the degeneracy rule "second eigenvalue of H^T H <= 1e-24 x the first" is evaluated on the Rayleigh quotients |H v1|^2 and
 //    |H v0|^2 after that: the diagonal the two-sided Jacobi leaves carries eps lambda_1 of rotation residue, which would make an
 //    exactly collinear sample look like sigma_2 = 1e-8 sigma_1.
-__device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&c)[6], double (&R)[3][3], double (&t)[3]) {
-  bool ok = true;
+__device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&c)[6], bool usable, double (&R)[3][3],
+                                        double (&t)[3]) {
+  bool ok = usable;
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -60,26 +53,18 @@ __device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&
 #pragma unroll
   for (int d = 0; d < 6; ++d) ok = ok && is_finite(c[d]);
   double ata[3][3], V[3][3], ev[3];
+  gram3(H, ata);
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) ata[i][j] = ok ? H[0][i] * H[0][j] + H[1][i] * H[1][j] + H[2][i] * H[2][j] : (i == j ? 1.0 : 0.0);
+    for (int j = 0; j < 3; ++j) ata[i][j] = ok ? ata[i][j] : (i == j ? 1.0 : 0.0);
   jacobi_eig3(ata, V, ev);
   double v[3][3];   // v[c] = column c of V, sorted by descending eigenvalue below
 #pragma unroll
   for (int cidx = 0; cidx < 3; ++cidx)
 #pragma unroll
     for (int k = 0; k < 3; ++k) v[cidx][k] = V[k][cidx];
-  {
-    bool sw = ev[0] < ev[1];
-    swap_if(sw, v[0], v[1]);
-    { const double a = ev[0], b = ev[1]; ev[0] = sw ? b : a; ev[1] = sw ? a : b; }
-    sw = ev[1] < ev[2];
-    swap_if(sw, v[1], v[2]);
-    { const double a = ev[1], b = ev[2]; ev[1] = sw ? b : a; ev[2] = sw ? a : b; }
-    sw = ev[0] < ev[1];
-    swap_if(sw, v[0], v[1]);
-  }
+  sort3_desc(ev, v);
   double g[3][3];   // g[c] = H v[c]
 #pragma unroll
   for (int cidx = 0; cidx < 3; ++cidx)
@@ -94,17 +79,7 @@ __device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&
   double n2[3];
 #pragma unroll
   for (int cidx = 0; cidx < 3; ++cidx) n2[cidx] = g[cidx][0] * g[cidx][0] + g[cidx][1] * g[cidx][1] + g[cidx][2] * g[cidx][2];
-  {
-    bool sw = n2[0] < n2[1];
-    swap_if(sw, v[0], v[1]); swap_if(sw, g[0], g[1]);
-    { const double a = n2[0], b = n2[1]; n2[0] = sw ? b : a; n2[1] = sw ? a : b; }
-    sw = n2[1] < n2[2];
-    swap_if(sw, v[1], v[2]); swap_if(sw, g[1], g[2]);
-    { const double a = n2[1], b = n2[2]; n2[1] = sw ? b : a; n2[2] = sw ? a : b; }
-    sw = n2[0] < n2[1];
-    swap_if(sw, v[0], v[1]); swap_if(sw, g[0], g[1]);
-    { const double a = n2[0], b = n2[1]; n2[0] = sw ? b : a; n2[1] = sw ? a : b; }
-  }
+  sort3_desc(n2, v, g);
   double u0[3], u1[3], v0[3], v1[3];
   const double s1sq = n2[0];
   const double r0 = 1.0 / sqrt(s1sq);
@@ -122,54 +97,14 @@ __device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&
   const double rv = 1.0 / sqrt(v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2]);
 #pragma unroll
   for (int k = 0; k < 3; ++k) v1[k] *= rv;
-  const double v2[3] = {v0[1] * v1[2] - v0[2] * v1[1], v0[2] * v1[0] - v0[0] * v1[2], v0[0] * v1[1] - v0[1] * v1[0]};
-  const double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      R[i][j] = v0[i] * u0[j] + v1[i] * u1[j] + v2[i] * u2[j];
-      ok = ok && is_finite(R[i][j]);
-    }
+  ok = ok && rotation_from_frames(v0, v1, u0, u1, R);
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     t[i] = c[3 + i] - (R[i][0] * c[0] + R[i][1] * c[1] + R[i][2] * c[2]);
     ok = ok && is_finite(t[i]);
   }
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      t[i] = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
-    }
-  }
+  if (!ok) set_identity(R, t);
   return ok;
-}
-
-template <typename T>
-__device__ __forceinline__ void store_model(T *__restrict__ m, const double (&R)[3][3], const double (&t)[3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) m[4 * i + j] = (T)R[i][j];
-    m[4 * i + 3] = (T)t[i];
-  }
-  m[12] = m[13] = m[14] = T(0);
-  m[15] = T(1);
-}
-
-// d2 of one point under one model, the ONE form the score and the update kernel share (their inlier decisions agree bit for bit)
-template <typename T>
-__device__ __forceinline__ T rigid_d2(const T (&m)[12], const T (&x)[6]) {
-  T d2 = T(0);
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const T pred = fma(m[4 * i], x[0], fma(m[4 * i + 1], x[1], fma(m[4 * i + 2], x[2], m[4 * i + 3])));
-    const T e = x[3 + i] - pred;
-    d2 = fma(e, e, d2);
-  }
-  return d2;
 }
 
 // ---- (1) minimal samples -> rigid models: one lane = one sample of 3 <= k <= 8 rows read through the index sets -------------
@@ -208,18 +143,8 @@ __global__ __launch_bounds__(64) void kabsch_gather_kernel(const T *__restrict__
       for (int j = 0; j < 3; ++j) H[i][j] += dp[i] * dq[j];
   }
   double R[3][3], t[3];
-  bool ok = kabsch3(H, c, R, t);
-  if (ok && !in_range) {
-    ok = false;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      t[i] = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
-    }
-  }
-  store_model(models + (size_t)s * 16, R, t);
-  valid[s] = ok;
+  valid[s] = kabsch3(H, c, in_range, R, t);
+  store_rigid_model(models + (size_t)s * 16, R, t);
 }
 
 // ---- (2) MSAC score and inlier count of every model against every point ----------------------------------------------------
@@ -253,11 +178,7 @@ __global__ __launch_bounds__(kSThreads) void rigid_msac_score_kernel(const T *__
   for (int c0 = 0; c0 < N; c0 += kSChunk) {
     const int n0 = c0 + tid * kSPts;
     T x[kSPts][6];
-#pragma unroll
-    for (int j = 0; j < kSPts; ++j)
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[j][d] = (n0 + j < N) ? pt[(size_t)(n0 + j) * 6 + d] : T(0);
-    const int nvalid = min(kSPts, max(0, N - n0));
+    const int nvalid = load_points8(pt, n0, N, x);
     for (int ml = 0; ml < mcount; ++ml) {
       if (vd && !vd[ml]) continue;   // (wave-uniform)
       T m[12];
@@ -313,27 +234,10 @@ __global__ __launch_bounds__(kRUThreads) void registration_update_kernel(
   const int it = iters[p];
   if ((double)it >= max_iters[p]) return;   // this pair has terminated (uniform across the block)
   const T bs = best_score[p];
-  const T *sc = scores + (size_t)p * M;
-  const uint8_t *vd = valid ? valid + (size_t)p * M : nullptr;
-  T bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int m = tid; m < M; m += kRUThreads) {
-    const T v = sc[m];
-    const bool ok = (!vd || vd[m]) && v == v;
-    if (ok && (v > bv || (v == bv && m < bi))) { bv = v; bi = m; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const T ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { s_val[wv] = bv; s_idx[wv] = bi; }
-  __syncthreads();   // (every thread has read iters / max_iters / best_score by now: thread 0 may write them below)
-  bv = s_val[0]; bi = s_idx[0];
-#pragma unroll
-  for (int w = 1; w < kRUThreads / 64; ++w)
-    if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+  T bv;
+  int bi;
+  // (its barrier comes after every thread has read iters / max_iters / best_score above: thread 0 may write them below)
+  block_arg_best<T, kRUThreads, true>(scores + (size_t)p * M, valid ? valid + (size_t)p * M : nullptr, M, s_val, s_idx, bv, bi);
   const bool have = bi != 0x7fffffff;              // (a -inf score of a valid model has an index too)
   const bool better = have && (bv > bs || it == 0);
   if (better) {
@@ -436,18 +340,8 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__rest
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
-  bool ok = kabsch3(H, c, R, t);
-  if (ok && !(rows >= 3.0 && a[6] > 0.0)) {
-    ok = false;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      t[i] = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
-    }
-  }
-  store_model(model + (size_t)p * 16, R, t);
-  valid[p] = ok;
+  valid[p] = kabsch3(H, c, rows >= 3.0 && a[6] > 0.0, R, t);
+  store_rigid_model(model + (size_t)p * 16, R, t);
 }
 
 template <typename T>

@@ -1,6 +1,11 @@
 // K3r -- rigid-transformation solver (RigidTransformationSVDBasedSolver.estimate_model, rigid…:11-74),
 // K4r -- squared residual of rigid models (squared_residual, rigid…:76-89, called at ransac.py:380),
 // K5  -- train-mode best-of-S selection (ransac.py:87-96).
+// What K3r / K4r / the 3-D K6 have in common with the registration kernels (registration.hip) is in rigid_device.hpp: the distance
+// of a point under a model, the model store, A^T A, the rotation from two orthonormal frames, the 8-point load; the arg-min of K6
+// is ransac_device.hpp's block_arg_best.  Not shared: the reference's centroid / covariance loop (mean-distance scaling, w^2) and
+// its frsqrt Gram-Schmidt, which differ from Kabsch's by more than a parameter, and the packed K4r, whose form is its speed.
+#include "rigid_device.hpp"
 #include "solver_common.hpp"
 
 namespace dr {
@@ -62,19 +67,14 @@ __global__ __launch_bounds__(64) void rigid_kernel(const T *__restrict__ samples
       ok = ok && is_finite(cov[i][j]);
     }
   // tgt = cov^T cov (flag, the reference default, Q9) or cov^T ; SVD tgt = U S V^T ; R = V U^T with det fix
-  double tg[3][3];
+  double tg[3][3], ata[3][3], V[3][3], ev[3];
+  if (flag) gram3(cov, tg);
+  else
 #pragma unroll
-  for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < 3; ++i)
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      if (flag) tg[i][j] = cov[0][i] * cov[0][j] + cov[1][i] * cov[1][j] + cov[2][i] * cov[2][j];
-      else tg[i][j] = cov[j][i];
-    }
-  double ata[3][3], V[3][3], ev[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) ata[i][j] = tg[0][i] * tg[0][j] + tg[1][i] * tg[1][j] + tg[2][i] * tg[2][j];
+      for (int j = 0; j < 3; ++j) tg[i][j] = cov[j][i];
+  gram3(tg, ata);
   jacobi_eig3(ata, V, ev);
   // two dominant right-singular vectors v0, v1 (columns of V with the largest eigenvalues)
   int i0 = 0, i1 = 1;
@@ -109,37 +109,14 @@ __global__ __launch_bounds__(64) void rigid_kernel(const T *__restrict__ samples
   for (int k = 0; k < 3; ++k) u1[k] *= n1;
   // third vectors by cross product: V' = [v0 v1 v0xv1], U' = [u0 u1 u0xu1]  => R = V' U'^T is a proper rotation,
   // identical to the reference's V U^T after its det(R) < 0 column flip (:59-62)
-  const double v2[3] = {v0[1] * v1[2] - v0[2] * v1[1], v0[2] * v1[0] - v0[0] * v1[2], v0[0] * v1[1] - v0[1] * v1[0]};
-  const double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
   double R[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      R[i][j] = v0[i] * u0[j] + v1[i] * u1[j] + v2[i] * u2[j];
-      ok = ok && is_finite(R[i][j]);
-    }
+  ok = ok && rotation_from_frames(v0, v1, u0, u1, R);
   // t_j = c1_j - c0_j * sum_i R_ij   (:66 -- an element-wise product summed over rows, not -R c0)
   double t[3];
 #pragma unroll
   for (int j = 0; j < 3; ++j) t[j] = c[3 + j] - c[j] * (R[0][j] + R[1][j] + R[2][j]);
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      t[i] = 0;
-#pragma unroll
-      for (int j = 0; j < 3; ++j) R[i][j] = (i == j);
-    }
-  }
-  T *m = models + (size_t)s * 16;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) m[4 * i + j] = (T)R[i][j];
-    m[4 * i + 3] = (T)t[i];
-  }
-  m[12] = m[13] = m[14] = T(0);
-  m[15] = T(1);
+  if (!ok) set_identity(R, t);
+  store_rigid_model(models + (size_t)s * 16, R, t);
   if (Rout)
 #pragma unroll
     for (int i = 0; i < 3; ++i)
@@ -175,11 +152,7 @@ __global__ __launch_bounds__(kRThreads) void rigid_residual_kernel(const T *__re
     if (c * kRChunk >= N) break;
     const int n0 = c * kRChunk + tid * kRPts;
     T x[kRPts][6];
-#pragma unroll
-    for (int j = 0; j < kRPts; ++j)
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[j][d] = (n0 + j < N) ? pt[(size_t)(n0 + j) * 6 + d] : T(0);
-    const int nvalid = min(kRPts, max(0, N - n0));
+    const int nvalid = load_points8(pt, n0, N, x);
     for (int ml = 0; ml < mcount; ++ml) {
       T m[12];
 #pragma unroll
@@ -188,13 +161,7 @@ __global__ __launch_bounds__(kRThreads) void rigid_residual_kernel(const T *__re
       uint32_t lo = 0, hi = 0;
 #pragma unroll
       for (int j = 0; j < kRPts; ++j) {
-        T d2 = T(0);
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const T pred = fma(m[4 * i], x[j][0], fma(m[4 * i + 1], x[j][1], fma(m[4 * i + 2], x[j][2], m[4 * i + 3])));
-          const T e = x[j][3 + i] - pred;
-          d2 = fma(e, e, d2);
-        }
+        const T d2 = rigid_d2<T>(m, x[j]);
         const bool live = j < nvalid;
         acc += live ? d2 : T(0);
         const bool in = live && d2 < threshold;
@@ -414,9 +381,7 @@ __global__ __launch_bounds__(kU3Threads) void ransac3d_update_kernel(
     int32_t *__restrict__ best_idx) {
   __shared__ T s_val[kU3Threads / 64];
   __shared__ int s_idx[kU3Threads / 64];
-  const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const T *rs = res + (size_t)p * M;
-  const uint8_t *vd = valid ? valid + (size_t)p * M : nullptr;
+  const int p = blockIdx.y, tid = threadIdx.x;
   // the thread's first two points are requested BEFORE the arg-min (they do not depend on the winner): the kernel is one
   // dependent chain -- sums -> winner -> its model -> points -> mask bytes -- and this takes the longest link out of it
   // (round 5, config 4: 9.1 -> see profiles/r5_kernel_stats_c4.md)
@@ -440,25 +405,9 @@ __global__ __launch_bounds__(kU3Threads) void ransac3d_update_kernel(
       for (int q = 0; q < 6; ++q) xa[u][q] = T(0);
     }
   }
-  T bv = INFINITY;
-  int bi = 0x7fffffff;
-  for (int m = tid; m < M; m += kU3Threads) {
-    const T v = rs[m];
-    const bool ok = (!vd || vd[m]) && v == v;
-    if (ok && (v < bv || (v == bv && m < bi))) { bv = v; bi = m; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const T ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov < bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { s_val[wv] = bv; s_idx[wv] = bi; }
-  __syncthreads();
-  bv = s_val[0]; bi = s_idx[0];
-#pragma unroll
-  for (int w = 1; w < kU3Threads / 64; ++w)
-    if (s_val[w] < bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+  T bv;
+  int bi;
+  block_arg_best<T, kU3Threads, false>(res + (size_t)p * M, valid ? valid + (size_t)p * M : nullptr, M, s_val, s_idx, bv, bi);
   // best_res_in == NULL: the first round of a call -- no previous state (residual +inf, model = identity, mask = empty), so the
   // driver allocates and fills nothing before its first round (three torch fill / copy launches per call otherwise)
   const bool first = best_res_in == nullptr;
@@ -482,22 +431,18 @@ __global__ __launch_bounds__(kU3Threads) void ransac3d_update_kernel(
   T m[12];
 #pragma unroll
   for (int q = 0; q < 12; ++q) m[q] = models[((size_t)p * M + bi) * 16 + q];
-  auto inlier = [&](const T *x) {
-    T d2 = T(0);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {     // the operation order of rigid_residual_kernel: the mask equals the winner's row of K4r
-      const T pred = fma(m[4 * i], x[0], fma(m[4 * i + 1], x[1], fma(m[4 * i + 2], x[2], m[4 * i + 3])));
-      const T e = x[3 + i] - pred;
-      d2 = fma(e, e, d2);
-    }
-    return d2 < threshold;
-  };
+  // rigid_d2 is rigid_residual_kernel's distance too: the mask equals the winner's row of K4r
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     const int n = n_begin + tid + u * kU3Threads;
-    if (n < n_end) best_mask[(size_t)p * N + n] = inlier(xa[u]);
+    if (n < n_end) best_mask[(size_t)p * N + n] = rigid_d2<T>(m, xa[u]) < threshold;
   }
-  for (int n = n_begin + tid + 2 * kU3Threads; n < n_end; n += kU3Threads) best_mask[(size_t)p * N + n] = inlier(pts + ((size_t)p * N + n) * 6);
+  for (int n = n_begin + tid + 2 * kU3Threads; n < n_end; n += kU3Threads) {
+    T x[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) x[q] = pts[((size_t)p * N + n) * 6 + q];
+    best_mask[(size_t)p * N + n] = rigid_d2<T>(m, x) < threshold;
+  }
 }
 
 template <typename T>

@@ -52,6 +52,39 @@ def scene(seed, N, inlier_share, noise=0.005, outlier_side=4.0):
     return dict(matches=np.concatenate([p, q], 1), R=R, t=t, inlier=inlier)
 
 
+def _nearest_rotation(A):
+    """the rotation nearest to an almost orthogonal A"""
+    U, _, Vt = np.linalg.svd(A)
+    return U @ Vt
+
+
+def boundary_scene(seed, N, M, thr=THRESHOLD):
+    """every row q = R p + t + e with |e| uniform in [0, 2 thr], so that many points sit near the inlier decision of a model close
+    to the pose; M such models: the pose times a rotation by N(0, (thr / 4)^2) rad per axis, plus N(0, (thr / 4)^2) per
+    translation entry.  -> (matches [N,6], models [M,4,4])"""
+    rng = np.random.default_rng(seed)
+    R, t = random_rotation(rng), rng.standard_normal(3)
+    p = rng.uniform(0.0, 1.0, (N, 3))
+    e = rng.standard_normal((N, 3))
+    e *= rng.uniform(0.0, 2.0 * thr, (N, 1)) / np.linalg.norm(e, axis=1, keepdims=True)
+    models = np.tile(np.eye(4), (M, 1, 1))
+    for j in range(M):
+        W = _cross_matrix(0.25 * thr * rng.standard_normal(3)).astype(np.float64)
+        models[j, :3, :3] = _nearest_rotation(np.eye(3) + W + 0.5 * W @ W) @ R
+        models[j, :3, 3] = t + 0.25 * thr * rng.standard_normal(3)
+    return np.concatenate([p, p @ R.T + t + e], 1), models
+
+
+def best_gap(values, largest):
+    """relative gap between the best and the second-best of `values` (inf for a single value): a reduction-order rounding, far
+    below it, cannot change the winner"""
+    v = np.sort(np.asarray(values, np.float64))
+    if len(v) < 2:
+        return math.inf
+    a, b = (v[-1], v[-2]) if largest else (v[0], v[1])
+    return abs(a - b) / abs(a)
+
+
 LD = np.longdouble
 
 

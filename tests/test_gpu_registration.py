@@ -242,6 +242,33 @@ def test_update_against_oracle(dev, dt, N, M):
         assert float(after["max_iters"][6]) < 2 * B < float(after["max_iters"][7])
 
 
+@pytest.mark.parametrize("dt", DTYPES)
+@pytest.mark.parametrize("N", [257, 2049])
+def test_update_winner_agrees_with_its_score_row(dev, dt, N):
+    """the score and the update kernel take d2 from one function (rigid_device.hpp: rigid_d2), so the winner's inlier count, mask
+    and score are the ones its column of dr_rigid_msac_score reported -- exactly, with many points at the threshold"""
+    from differentiable_ransac_amd import ops
+    P, M = 2, 17
+    sc = [R.boundary_scene(70 + p, N, M) for p in range(P)]
+    m, models = _rounded(np.stack([s[0] for s in sc]), dt), _rounded(np.stack([s[1] for s in sc]), dt)
+    for p in range(P):      # the condition on the input: a strict arg-max, in f64
+        gap = R.best_gap([R.msac(m[p], models[p, j], _thr(dt))[0] for j in range(M)], largest=True)
+        print(f"pair {p}: relative gap of the two best scores {gap:.3g}")
+        assert gap >= 1e-3
+    tm, tmod = torch.from_numpy(m).to(dev, dt), torch.from_numpy(models).to(dev, dt)
+    scores, inliers = ops.rigid_msac_score(tm, tmod, THR, want_inliers=True)
+    st = ops.RegistrationState(P, N, 2000, dev, dt)
+    ops.registration_update(st, tm, tmod, None, scores, THR, M)
+    b = scores.cpu().argmax(1)
+    for p in range(P):
+        near = int((np.abs(R.ratio2(models[p, int(b[p])], m[p], _thr(dt)) - 1.0) < 0.05).sum())
+        print(f"pair {p}: winner {int(b[p])}, inliers {int(st.best_inliers[p])} (score row {int(inliers[p, b[p]])}), "
+              f"points within 5 % of the threshold {near}")
+        assert int(st.best_inliers[p]) == int(inliers[p, b[p]]), p
+        assert int(st.best_mask[p].sum()) == int(st.best_inliers[p]), p
+        assert float(st.best_score[p]) == float(scores[p, b[p]]), p
+
+
 # ------------------------------------------------------------------------------------------------ dr_refit_rigid
 def _ragged_masks(N, rng):
     """0, 2, 3, 50 % and all rows selected"""
