@@ -281,13 +281,14 @@ __global__ __launch_bounds__(kThreads) void msac_score_kernel_f32_fast(const flo
           rc[0] = __builtin_amdgcn_rcpf(jj[0]);
           rc[1] = __builtin_amdgcn_rcpf(jj[1]);
           const v2f sv = (rr * rc) * splat(inv_thr2) - splat(1.0f);   // s = d2/thr2 - 1
-          sb[2 * j] = __float_as_uint(sv[0]);
-          sb[2 * j + 1] = __float_as_uint(sv[1]);
-          // min(sv, 0) by one integer instruction each: for IEEE bit patterns min_i32(bits(sv), 0) is sv when the sign bit is
-          // set and +0 otherwise (fmaxf costs two -- the compiler canonicalises its operand first); acc holds the negated sum
+          // min(sv, 0) by an ORDERED compare: sv where sv < 0 and +0 otherwise, so a NaN (a 0/0 point: jj = r = 0, whose 0 * inf
+          // the hardware returns with the sign bit SET) selects +0: no inlier, nothing added.  Both the mask bytes below (sign bit
+          // of sb) and the score read the selected word; acc holds the negated sum
+          sb[2 * j] = sv[0] < 0.f ? __float_as_uint(sv[0]) : 0u;
+          sb[2 * j + 1] = sv[1] < 0.f ? __float_as_uint(sv[1]) : 0u;
           v2f mn;
-          mn[0] = __int_as_float(min((int)sb[2 * j], 0));
-          mn[1] = __int_as_float(min((int)sb[2 * j + 1], 0));
+          mn[0] = __uint_as_float(sb[2 * j]);
+          mn[1] = __uint_as_float(sb[2 * j + 1]);
           acc = mn * w[j] + acc;
         }
         float a = -(acc[0] + acc[1]);
