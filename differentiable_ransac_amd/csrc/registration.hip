@@ -1,6 +1,6 @@
-// Robust 3-D registration (test mode of ransac.BatchedRegistration): rigid models from minimal samples by a correct Kabsch fit,
-// MSAC score and inlier count of every model against every point, the per-pair state step with the adaptive stop, and the Kabsch
-// refit over the rows a mask selects.
+// Robust 3-D registration (ransac.BatchedRegistration): rigid models from minimal samples by a correct Kabsch fit, MSAC score and
+// inlier count of every model against every point, the per-pair state step with the adaptive stop, and the Kabsch refit over the
+// rows a mask selects; for train mode the fit of explicit (weighted) samples and the backward of both fits (kabsch3_bwd).
 //   matches [P,N,6] = (p, q); a model is the row-major 4x4 [[R, t], [0, 0, 0, 1]]; q_hat = R p + t, d2 = |q - q_hat|^2.
 //   The threshold is a DISTANCE and enters as thr2 = threshold^2 per pair: inlier <=> d2 < thr2 (dr_rigid_residual compares d2
 //   with its threshold argument itself).  MSAC score = sum_n max(0, 1 - d2_n / thr2).
@@ -107,7 +107,97 @@ __device__ __forceinline__ bool kabsch3(const double (&H)[3][3], const double (&
   return ok;
 }
 
-// ---- (1) minimal samples -> rigid models: one lane = one sample of 3 <= k <= 8 rows read through the index sets -------------
+// ---- the derivative of the fit: (gR, gt) -> (gH, g_c0, g_c1) -----------------------------------------------------------------
+// The optimum is characterised by A = R H being symmetric (A = V D S V^T).  A perturbation dH turns R by exp([w]x) with
+// K w = -vee(R dH - dH^T R^T), K = tr(A) I - A (symmetric, eigenvalues s1 + s2, s1 + d s3, s2 + d s3), so no SVD is differentiated:
+//   G = gR - gt c0^T (t = c1 - R c0), g_c1 = gt, g_c0 = -R^T gt;  Y = G R^T, a = vee(Y - Y^T), z = K^-1 a (adjugate);  gH = -R^T [z]x.
+// false (everything zero) when the forward was not `ok`, or det K or any result is not finite: a sample without a usable model, or
+// one at the reflection tie / collinear limit where the rotation is not differentiable, passes no gradient on.
+__device__ __forceinline__ bool kabsch3_bwd(const double (&H)[3][3], const double (&c)[6], const double (&R)[3][3], bool ok,
+                                            const double (&gR)[3][3], const double (&gt)[3], double (&gH)[3][3], double (&gc0)[3],
+                                            double (&gc1)[3]) {
+  double A[3][3], Y[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      A[i][j] = R[i][0] * H[0][j] + R[i][1] * H[1][j] + R[i][2] * H[2][j];
+      Y[i][j] = (gR[i][0] - gt[i] * c[0]) * R[j][0] + (gR[i][1] - gt[i] * c[1]) * R[j][1] + (gR[i][2] - gt[i] * c[2]) * R[j][2];
+    }
+  const double tr = A[0][0] + A[1][1] + A[2][2];
+  const double k00 = tr - A[0][0], k11 = tr - A[1][1], k22 = tr - A[2][2];
+  const double k01 = -0.5 * (A[0][1] + A[1][0]), k02 = -0.5 * (A[0][2] + A[2][0]), k12 = -0.5 * (A[1][2] + A[2][1]);
+  const double a[3] = {Y[2][1] - Y[1][2], Y[0][2] - Y[2][0], Y[1][0] - Y[0][1]};
+  const double c00 = k11 * k22 - k12 * k12, c01 = k02 * k12 - k01 * k22, c02 = k01 * k12 - k02 * k11;
+  const double c11 = k00 * k22 - k02 * k02, c12 = k01 * k02 - k00 * k12, c22 = k00 * k11 - k01 * k01;
+  const double det = k00 * c00 + k01 * c01 + k02 * c02;
+  const double rd = 1.0 / det;
+  const double z[3] = {(c00 * a[0] + c01 * a[1] + c02 * a[2]) * rd, (c01 * a[0] + c11 * a[1] + c12 * a[2]) * rd,
+                       (c02 * a[0] + c12 * a[1] + c22 * a[2]) * rd};
+  const double Z[3][3] = {{0.0, -z[2], z[1]}, {z[2], 0.0, -z[0]}, {-z[1], z[0], 0.0}};
+  ok = ok && is_finite(det);
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    gc1[i] = gt[i];
+    gc0[i] = -(R[0][i] * gt[0] + R[1][i] * gt[1] + R[2][i] * gt[2]);
+    ok = ok && is_finite(gc0[i]) && is_finite(gc1[i]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      gH[i][j] = -(R[0][i] * Z[0][j] + R[1][i] * Z[1][j] + R[2][i] * Z[2][j]);
+      ok = ok && is_finite(gH[i][j]);
+    }
+  }
+  if (!ok) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      gc0[i] = gc1[i] = 0.0;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) gH[i][j] = 0.0;
+    }
+  }
+  return ok;
+}
+
+// ---- (1) minimal samples -> rigid models: one lane = one sample of 3 <= k <= 8 rows -----------------------------------------
+// the weighted means c = (c0, c1), H = sum w (p - c0)(q - c1)^T and W = sum w of one sample, f64: rowp(r) -> the six values of row r,
+// wt(r) -> its weight.  Unit weights give the bits of the plain sums (x 1.0 is exact, and W = k)
+template <typename RowFn, typename WFn>
+__device__ __forceinline__ double sample_moments(int k, RowFn rowp, WFn wt, double (&c)[6], double (&H)[3][3]) {
+  double W = 0.0;
+#pragma unroll
+  for (int d = 0; d < 6; ++d) c[d] = 0.0;
+  for (int r = 0; r < k; ++r) {
+    const auto *x = rowp(r);
+    const double w = wt(r);
+#pragma unroll
+    for (int d = 0; d < 6; ++d) c[d] += w * (double)x[d];
+    W += w;
+  }
+  const double rn = 1.0 / W;
+#pragma unroll
+  for (int d = 0; d < 6; ++d) c[d] *= rn;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
+  for (int r = 0; r < k; ++r) {
+    const auto *x = rowp(r);
+    const double w = wt(r);
+    double dp[3], dq[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      dp[d] = w * ((double)x[d] - c[d]);
+      dq[d] = (double)x[3 + d] - c[3 + d];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) H[i][j] += dp[i] * dq[j];
+  }
+  return W;
+}
+
+// rows read through the index sets
 template <typename T>
 __global__ __launch_bounds__(64) void kabsch_gather_kernel(const T *__restrict__ matches, const int32_t *__restrict__ idx, int Bt,
                                                            int B, int N, int k, T *__restrict__ models,
@@ -119,32 +209,70 @@ __global__ __launch_bounds__(64) void kabsch_gather_kernel(const T *__restrict__
   bool in_range = true;
   for (int r = 0; r < k; ++r) in_range = in_range && gi[r] >= 0 && gi[r] < N;
   auto rowp = [&](int r) -> const T * { return base + (size_t)(in_range ? gi[r] : 0) * 6; };   // (a bad index reads row 0, valid = 0)
-  double c[6] = {0, 0, 0, 0, 0, 0};
-  for (int r = 0; r < k; ++r) {
-    const T *x = rowp(r);
+  double c[6], H[3][3], R[3][3], t[3];
+  sample_moments(k, rowp, [](int) { return 1.0; }, c, H);
+  valid[s] = kabsch3(H, c, in_range, R, t);
+  store_rigid_model(models + (size_t)s * 16, R, t);
+}
+
+// explicit sample tensors [Bt,k,6] with optional weights [Bt,k]: what train mode fits (the straight-through samples of SampleGather).
+// Without weights, on samples = matches[idx], the models and validity of kabsch_gather_kernel bit for bit.
+template <typename T>
+__global__ __launch_bounds__(64) void kabsch_kernel(const T *__restrict__ samples, const T *__restrict__ weights, int Bt, int k,
+                                                    T *__restrict__ models, uint8_t *__restrict__ valid) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= Bt) return;
+  const T *base = samples + (size_t)s * k * 6;
+  const T *wb = weights ? weights + (size_t)s * k : nullptr;
+  double c[6], H[3][3], R[3][3], t[3];
+  const double W = sample_moments(k, [&](int r) { return base + r * 6; }, [&](int r) { return wb ? (double)wb[r] : 1.0; }, c, H);
+  valid[s] = kabsch3(H, c, W > 0.0, R, t);
+  store_rigid_model(models + (size_t)s * 16, R, t);
+}
+
+// its backward: the forward recomputed in f64 from the inputs (no stored model), rows re-read for the third pass; every output element
+// is written, exact zeros for a sample without a valid fit or a finite derivative.  Only rows 0..2 of grad_models are read.
+template <typename T>
+__global__ __launch_bounds__(64) void kabsch_bwd_kernel(const T *__restrict__ samples, const T *__restrict__ weights,
+                                                        const T *__restrict__ grad_models, int Bt, int k, T *__restrict__ grad_samples,
+                                                        T *__restrict__ grad_weights) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= Bt) return;
+  const T *base = samples + (size_t)s * k * 6;
+  const T *wb = weights ? weights + (size_t)s * k : nullptr;
+  double c[6], H[3][3], R[3][3], t[3];
+  const double W = sample_moments(k, [&](int r) { return base + r * 6; }, [&](int r) { return wb ? (double)wb[r] : 1.0; }, c, H);
+  const bool fwd = kabsch3(H, c, W > 0.0, R, t);
+  const T *gm = grad_models + (size_t)s * 16;
+  double gR[3][3], gt[3], gH[3][3], gc0[3], gc1[3];
 #pragma unroll
-    for (int d = 0; d < 6; ++d) c[d] += (double)x[d];
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gR[i][j] = (double)gm[4 * i + j];
+    gt[i] = (double)gm[4 * i + 3];
   }
-  const double rn = 1.0 / (double)k;
-#pragma unroll
-  for (int d = 0; d < 6; ++d) c[d] *= rn;
-  double H[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
+  const bool ok = kabsch3_bwd(H, c, R, fwd, gR, gt, gH, gc0, gc1);
+  const double rW = 1.0 / W;
+  T *gs = grad_samples + (size_t)s * k * 6;
   for (int r = 0; r < k; ++r) {
-    const T *x = rowp(r);
-    double dp[3], dq[3];
+    const T *x = base + r * 6;
+    const double w = wb ? (double)wb[r] : 1.0;
+    double dp[3], dq[3], gw = 0.0;
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
       dp[d] = (double)x[d] - c[d];
       dq[d] = (double)x[3 + d] - c[3 + d];
     }
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) H[i][j] += dp[i] * dq[j];
+    for (int d = 0; d < 3; ++d) {
+      const double hq = gH[d][0] * dq[0] + gH[d][1] * dq[1] + gH[d][2] * dq[2];      // (gH dq)_d
+      const double hp = gH[0][d] * dp[0] + gH[1][d] * dp[1] + gH[2][d] * dp[2];      // (gH^T dp)_d
+      gs[r * 6 + d] = ok ? (T)(w * (hq + rW * gc0[d])) : T(0);
+      gs[r * 6 + 3 + d] = ok ? (T)(w * (hp + rW * gc1[d])) : T(0);
+      gw += dp[d] * hq + rW * (dp[d] * gc0[d] + dq[d] * gc1[d]);
+    }
+    if (grad_weights) grad_weights[(size_t)s * k + r] = ok ? (T)gw : T(0);
   }
-  double R[3][3], t[3];
-  valid[s] = kabsch3(H, c, in_range, R, t);
-  store_rigid_model(models + (size_t)s * 16, R, t);
 }
 
 // ---- (2) MSAC score and inlier count of every model against every point ----------------------------------------------------
@@ -293,15 +421,12 @@ __device__ __forceinline__ void block_sum_f64(double (&v)[K], double (*s)[K]) { 
   __syncthreads();   // (the buffer may be reused)
 }
 
+// the two passes of the fit, by the whole block: -> c = (c0, c1), h = H row-major, rows = the selected rows, the weight sum (every
+// thread holds all of them afterwards)
 template <typename T>
-__global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__restrict__ pts, const uint8_t *__restrict__ mask,
-                                                                 const T *__restrict__ weights, int N, T *__restrict__ model,
-                                                                 uint8_t *__restrict__ valid) {
-  __shared__ double s_red[kRFThreads / 64][9];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const T *pt = pts + (size_t)p * N * 6;
-  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
-  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+__device__ __forceinline__ double refit_moments(const T *__restrict__ pt, const uint8_t *__restrict__ mk, const T *__restrict__ wt,
+                                                int N, double (*s_red)[9], double (&c)[6], double (&h)[9], double &rows) {
+  const int tid = threadIdx.x;
   // pass 1: weighted sums of p and q, the weight sum and the row count (entries 0..5, 6, 7; entry 8 unused)
   double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int n = tid; n < N; n += kRFThreads) {
@@ -313,12 +438,13 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__rest
     a[7] += 1.0;
   }
   block_sum_f64<9>(a, s_red);
-  const double rows = a[7], rw = 1.0 / a[6];
-  double c[6];
+  rows = a[7];
+  const double rw = 1.0 / a[6];
 #pragma unroll
   for (int d = 0; d < 6; ++d) c[d] = a[d] * rw;
   // pass 2: H = sum w (p - c0)(q - c1)^T
-  double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) h[i] = 0.0;
   for (int n = tid; n < N; n += kRFThreads) {
     if (mk && !mk[n]) continue;
     const double w = wt ? (double)wt[n] : 1.0;
@@ -334,14 +460,111 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__rest
       for (int j = 0; j < 3; ++j) h[3 * i + j] += dp[i] * dq[j];
   }
   block_sum_f64<9>(h, s_red);
-  if (tid != 0) return;
+  return a[6];
+}
+
+template <typename T>
+__global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__restrict__ pts, const uint8_t *__restrict__ mask,
+                                                                 const T *__restrict__ weights, int N, T *__restrict__ model,
+                                                                 uint8_t *__restrict__ valid) {
+  __shared__ double s_red[kRFThreads / 64][9];
+  const int p = blockIdx.x;
+  double c[6], h[9], rows;
+  const double W = refit_moments(pts + (size_t)p * N * 6, mask ? mask + (size_t)p * N : nullptr,
+                                 weights ? weights + (size_t)p * N : nullptr, N, s_red, c, h, rows);
+  if (threadIdx.x != 0) return;
   double H[3][3], R[3][3], t[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
-  valid[p] = kabsch3(H, c, rows >= 3.0 && a[6] > 0.0, R, t);
+  valid[p] = kabsch3(H, c, rows >= 3.0 && W > 0.0, R, t);
   store_rigid_model(model + (size_t)p * 16, R, t);
+}
+
+// its backward: the same two passes (same order, same bits), thread 0 runs the fit and kabsch3_bwd and hands gH, g_c0, g_c1, 1 / W
+// to the block through LDS, a third pass writes the gradient of EVERY row -- element by element, so a wave's stores are contiguous --
+// with exact zeros for the rows the mask drops and for a pair without a valid fit.  No atomics: a repeated launch gives the same bits.
+template <typename T>
+__global__ __launch_bounds__(kRFThreads) void refit_rigid_bwd_kernel(const T *__restrict__ pts, const uint8_t *__restrict__ mask,
+                                                                     const T *__restrict__ weights, const T *__restrict__ grad_model,
+                                                                     int N, T *__restrict__ grad_matches,
+                                                                     T *__restrict__ grad_weights) {
+  __shared__ double s_red[kRFThreads / 64][9];
+  __shared__ double s_g[16];   // gH (9), g_c0 (3), g_c1 (3), 1 / W
+  __shared__ int s_ok;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const T *pt = pts + (size_t)p * N * 6;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+  double c[6], h[9], rows;
+  const double W = refit_moments(pt, mk, wt, N, s_red, c, h, rows);
+  if (tid == 0) {
+    const T *gm = grad_model + (size_t)p * 16;
+    double H[3][3], R[3][3], t[3], gR[3][3], gt[3], gH[3][3], gc0[3], gc1[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        H[i][j] = h[3 * i + j];
+        gR[i][j] = (double)gm[4 * i + j];
+      }
+      gt[i] = (double)gm[4 * i + 3];
+    }
+    const bool fwd = kabsch3(H, c, rows >= 3.0 && W > 0.0, R, t);
+    s_ok = kabsch3_bwd(H, c, R, fwd, gR, gt, gH, gc0, gc1);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) s_g[3 * i + j] = gH[i][j];
+      s_g[9 + i] = gc0[i];
+      s_g[12 + i] = gc1[i];
+    }
+    s_g[15] = 1.0 / W;
+  }
+  __syncthreads();
+  const bool ok = s_ok != 0;
+  const double rW = s_g[15];
+  if (grad_matches) {
+    T *gx = grad_matches + (size_t)p * N * 6;
+    for (int e = tid; e < 6 * N; e += kRFThreads) {
+      const int n = e / 6, d = e - 6 * n;
+      double v = 0.0;
+      if (ok && (!mk || mk[n])) {
+        const double w = wt ? (double)wt[n] : 1.0;
+        if (d < 3) {   // w (gH dq + g_c0 / W)_d
+          const double dq[3] = {(double)pt[(size_t)n * 6 + 3] - c[3], (double)pt[(size_t)n * 6 + 4] - c[4],
+                                (double)pt[(size_t)n * 6 + 5] - c[5]};
+          v = w * (s_g[3 * d] * dq[0] + s_g[3 * d + 1] * dq[1] + s_g[3 * d + 2] * dq[2] + rW * s_g[9 + d]);
+        } else {       // w (gH^T dp + g_c1 / W)_j
+          const int j = d - 3;
+          const double dp[3] = {(double)pt[(size_t)n * 6] - c[0], (double)pt[(size_t)n * 6 + 1] - c[1],
+                                (double)pt[(size_t)n * 6 + 2] - c[2]};
+          v = w * (s_g[j] * dp[0] + s_g[3 + j] * dp[1] + s_g[6 + j] * dp[2] + rW * s_g[12 + j]);
+        }
+      }
+      gx[e] = (T)v;
+    }
+  }
+  if (grad_weights) {
+    T *gw = grad_weights + (size_t)p * N;
+    for (int n = tid; n < N; n += kRFThreads) {
+      double v = 0.0;
+      if (ok && (!mk || mk[n])) {
+        double dp[3], dq[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          dp[d] = (double)pt[(size_t)n * 6 + d] - c[d];
+          dq[d] = (double)pt[(size_t)n * 6 + 3 + d] - c[3 + d];
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d)
+          v += dp[d] * (s_g[3 * d] * dq[0] + s_g[3 * d + 1] * dq[1] + s_g[3 * d + 2] * dq[2]) +
+               rW * (dp[d] * s_g[9 + d] + dq[d] * s_g[12 + d]);
+      }
+      gw[n] = (T)v;
+    }
+  }
 }
 
 template <typename T>
@@ -350,6 +573,21 @@ int kabsch_gather_entry(const T *matches, const int32_t *idx, int P, int B, int 
   hipLaunchKernelGGL((kabsch_gather_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, matches, idx, Bt, B, N, k,
                      models, valid);
   return check_launch("kabsch_gather_kernel");
+}
+
+template <typename T>
+int kabsch_entry(const T *samples, const T *weights, int Bt, int k, T *models, uint8_t *valid, void *stream) {
+  hipLaunchKernelGGL((kabsch_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, weights, Bt, k, models,
+                     valid);
+  return check_launch("kabsch_kernel");
+}
+
+template <typename T>
+int kabsch_bwd_entry(const T *samples, const T *weights, const T *grad_models, int Bt, int k, T *grad_samples, T *grad_weights,
+                     void *stream) {
+  hipLaunchKernelGGL((kabsch_bwd_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, weights, grad_models,
+                     Bt, k, grad_samples, grad_weights);
+  return check_launch("kabsch_bwd_kernel");
 }
 
 template <typename T>
@@ -380,6 +618,14 @@ int refit_rigid_entry(const T *matches, const uint8_t *mask, const T *weights, i
   return check_launch("refit_rigid_kernel");
 }
 
+template <typename T>
+int refit_rigid_bwd_entry(const T *matches, const uint8_t *mask, const T *weights, const T *grad_model, int P, int N, T *grad_matches,
+                          T *grad_weights, void *stream) {
+  hipLaunchKernelGGL((refit_rigid_bwd_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, mask, weights,
+                     grad_model, N, grad_matches, grad_weights);
+  return check_launch("refit_rigid_bwd_kernel");
+}
+
 }  // namespace dr
 
 extern "C" {
@@ -397,6 +643,29 @@ int dr_kabsch_gather_f64(const double *matches, const int32_t *idx, int P, int B
                          void *stream) {
   DR_KABSCH_GATHER_CHECKS;
   return dr::kabsch_gather_entry<double>(matches, idx, P, B, N, k, models, valid, stream);
+}
+
+#define DR_KABSCH_CHECKS(out0, out1)                                                                       \
+  DR_REQUIRE(samples && out0 && out1, "null pointer");                                                      \
+  DR_REQUIRE(Bt > 0 && k >= 3 && k <= 8, "need Bt > 0 and 3 <= k <= 8 rows per sample")
+
+int dr_kabsch_f32(const float *samples, const float *weights, int Bt, int k, float *models, uint8_t *valid, void *stream) {
+  DR_KABSCH_CHECKS(models, valid);
+  return dr::kabsch_entry<float>(samples, weights, Bt, k, models, valid, stream);
+}
+int dr_kabsch_f64(const double *samples, const double *weights, int Bt, int k, double *models, uint8_t *valid, void *stream) {
+  DR_KABSCH_CHECKS(models, valid);
+  return dr::kabsch_entry<double>(samples, weights, Bt, k, models, valid, stream);
+}
+int dr_kabsch_bwd_f32(const float *samples, const float *weights, const float *grad_models, int Bt, int k, float *grad_samples,
+                      float *grad_weights, void *stream) {
+  DR_KABSCH_CHECKS(grad_models, grad_samples);
+  return dr::kabsch_bwd_entry<float>(samples, weights, grad_models, Bt, k, grad_samples, grad_weights, stream);
+}
+int dr_kabsch_bwd_f64(const double *samples, const double *weights, const double *grad_models, int Bt, int k, double *grad_samples,
+                      double *grad_weights, void *stream) {
+  DR_KABSCH_CHECKS(grad_models, grad_samples);
+  return dr::kabsch_bwd_entry<double>(samples, weights, grad_models, Bt, k, grad_samples, grad_weights, stream);
 }
 
 #define DR_RIGID_MSAC_CHECKS                                                                              \
@@ -450,6 +719,22 @@ int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double 
   DR_REQUIRE(matches && model && valid, "null pointer");
   DR_REQUIRE(P > 0 && N > 0, "bad sizes");
   return dr::refit_rigid_entry<double>(matches, mask, weights, P, N, model, valid, stream);
+}
+
+
+#define DR_REFIT_RIGID_BWD_CHECKS                                                                    \
+  DR_REQUIRE(matches && grad_model && (grad_matches || grad_weights), "null pointer");               \
+  DR_REQUIRE(P > 0 && N > 0 && (long)N * 6 < (1l << 31), "bad sizes")
+
+int dr_refit_rigid_bwd_f32(const float *matches, const uint8_t *mask, const float *weights, const float *grad_model, int P, int N,
+                           float *grad_matches, float *grad_weights, void *stream) {
+  DR_REFIT_RIGID_BWD_CHECKS;
+  return dr::refit_rigid_bwd_entry<float>(matches, mask, weights, grad_model, P, N, grad_matches, grad_weights, stream);
+}
+int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const double *weights, const double *grad_model, int P, int N,
+                           double *grad_matches, double *grad_weights, void *stream) {
+  DR_REFIT_RIGID_BWD_CHECKS;
+  return dr::refit_rigid_bwd_entry<double>(matches, mask, weights, grad_model, P, N, grad_matches, grad_weights, stream);
 }
 
 }  // extern "C"

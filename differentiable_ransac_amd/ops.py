@@ -749,6 +749,19 @@ def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weig
     return model, valid
 
 
+def _kabsch_fwd(samples: torch.Tensor, weights: Optional[torch.Tensor]):
+    """dr_kabsch on flattened samples [Bt,k,6] (contiguous), weights [Bt,k] | None -> (models [Bt,4,4], valid [Bt] bool)"""
+    Bt, k, _ = samples.shape
+    models = torch.empty((Bt, 4, 4), device=samples.device, dtype=samples.dtype)
+    valid = torch.empty((Bt,), device=samples.device, dtype=torch.bool)
+    L.call(f"dr_kabsch_{L.suffix(samples.dtype)}", ptr(samples), ptr(weights), c_int(Bt), c_int(k), ptr(models), ptr(valid), stream())
+    return models, valid
+
+
+def _grad_top_rows(g: torch.Tensor, dtype) -> torch.Tensor:
+    return g.to(dtype).reshape(-1, 4, 4).contiguous()
+
+
 def select_closest(models: torch.Tensor, valid: Optional[torch.Tensor], gt: torch.Tensor, want_keep: bool = False):
     """K5: models [P,B,S,3,3], valid [P,B,S] | None, gt [P,3,3] -> chosen [P,B,3,3], which [P,B] int32 (+ keep [P,B] bool =
     `which >= 0` from the same launch when want_keep)."""
@@ -983,6 +996,87 @@ class _SolveRigid(torch.autograd.Function):
 
 def solve_rigid_autograd(samples, weights=None, flag=True):
     return _SolveRigid.apply(samples, weights, flag)
+
+
+class _Kabsch(torch.autograd.Function):
+    """dr_kabsch / dr_kabsch_bwd: the backward recomputes the fit from the samples, so no model is saved"""
+
+    @staticmethod
+    def forward(ctx, samples, weights):
+        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+        s, Bt, k = _flat_samples(samples, 6)
+        w = None if weights is None else weights.reshape(Bt, k).to(s.dtype).contiguous()
+        models, valid = _kabsch_fwd(s, w)
+        ctx.save_for_backward(s, *(() if w is None else (w,)))
+        ctx.shapes = (samples.shape, None if weights is None else (weights.shape, weights.dtype))
+        lead = samples.shape[:-2]
+        valid = valid.reshape(lead)
+        ctx.mark_non_differentiable(valid)
+        return models.reshape(*lead, 4, 4), valid
+
+    @staticmethod
+    def backward(ctx, g_models, _gv):
+        if g_models is None:
+            return None, None
+        s, *w = ctx.saved_tensors
+        w = w[0] if w else None
+        Bt, k, _ = s.shape
+        gs = torch.empty_like(s)
+        gw = torch.empty((Bt, k), device=s.device, dtype=s.dtype) if (w is not None and ctx.needs_input_grad[1]) else None
+        L.call(f"dr_kabsch_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(w), ptr(_grad_top_rows(g_models, s.dtype)), c_int(Bt), c_int(k),
+               ptr(gs), ptr(gw), stream())
+        sshape, wshape = ctx.shapes
+        return gs.reshape(sshape), None if gw is None else gw.reshape(wshape[0]).to(wshape[1])
+
+
+def kabsch(samples, weights=None):
+    """samples [..., k, 6] = (p, q) rows, 3 <= k <= 8, weights [..., k] | None -> (models [..., 4, 4], valid [...] bool): the weighted
+    least-squares rigid fit (Kabsch) of every sample, with autograd to `samples` and `weights` in f32 and f64 (dr_kabsch,
+    dr_kabsch_bwd).  Without weights, on samples = matches[idx], the models of kabsch_gather bit for bit.  A sample without a valid fit
+    (valid = 0: the identity), or with a non-finite derivative, passes exact zeros back."""
+    if samples.dim() < 3 or samples.shape[-1] != 6 or not 3 <= samples.shape[-2] <= 8:
+        raise L.DransacError("kabsch: samples [..., k, 6] with 3 <= k <= 8 rows per sample")
+    if weights is not None and weights.shape != samples.shape[:-1]:
+        raise L.DransacError("kabsch: weights are [..., k], one per sample row")
+    return _Kabsch.apply(samples, weights)
+
+
+class _WeightedKabsch(torch.autograd.Function):
+    """dr_refit_rigid / dr_refit_rigid_bwd"""
+
+    @staticmethod
+    def forward(ctx, matches, weights, mask):
+        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+        m = matches.contiguous()
+        w = None if weights is None else weights.to(m.dtype).contiguous()
+        model, valid = refit_rigid(m, mask, w)
+        ctx.save_for_backward(m, *(() if w is None else (w,)))
+        ctx.mask = None if mask is None else _u8(mask)
+        ctx.wdtype = None if weights is None else weights.dtype
+        ctx.mark_non_differentiable(valid)
+        return model, valid
+
+    @staticmethod
+    def backward(ctx, g_model, _gv):
+        if g_model is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None
+        m, *w = ctx.saved_tensors
+        w = w[0] if w else None
+        P, N, _ = m.shape
+        gm = torch.empty_like(m) if ctx.needs_input_grad[0] else None
+        gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if (w is not None and ctx.needs_input_grad[1]) else None
+        L.call(f"dr_refit_rigid_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w), ptr(_grad_top_rows(g_model, m.dtype)),
+               c_int(P), c_int(N), ptr(gm), ptr(gw), stream())
+        return gm, None if gw is None else gw.to(ctx.wdtype), None
+
+
+def weighted_kabsch(matches, weights=None, mask=None):
+    """matches [P,N,6], weights [P,N] | None, mask [P,N] | None -> (model [P,4,4], valid [P] bool): refit_rigid (the weighted Procrustes
+    fit over the rows the mask selects) with autograd to `weights` and / or `matches`, whichever require it (dr_refit_rigid_bwd).
+    Rows the mask drops, and every row of a pair without a valid fit, get exact zeros; bit-repeatable."""
+    if matches.dim() != 3 or matches.shape[-1] != 6:
+        raise L.DransacError("weighted_kabsch: correspondences [P,N,6]")
+    return _WeightedKabsch.apply(matches, weights, mask)
 
 
 class _MsacScore(torch.autograd.Function):

@@ -939,7 +939,7 @@ class BatchedRANSAC3D(_SeededDriver):
 
 
 class BatchedRegistration(_SeededDriver):
-    """Robust rigid registration of point-cloud pairs, test mode only: matches [P,N,6] = (p, q), logits [P,N] ->
+    """Robust rigid registration of point-cloud pairs: matches [P,N,6] = (p, q), logits [P,N] -> in test mode (the default)
     dict(model [P,4,4] = [[R, t], [0, 0, 0, 1]] with q ~ R p + t, mask [P,N], score [P], inliers [P], iterations [P]).
 
     One round = K1 Gumbel top-k (index sets of `num_samples` points) -> dr_kabsch_gather (the least-squares rigid fit of every
@@ -953,10 +953,16 @@ class BatchedRegistration(_SeededDriver):
     ops.rigid_residual compare the squared distance with their threshold itself).
 
     device_termination = True issues every round, gated on the device, with no read-back, so that a call can be captured by
-    graphs.GraphedStep; it is refused above 16 rounds.  Pipelining, super-rounds and local optimisation: not here."""
+    graphs.GraphedStep; it is refused above 16 rounds.  Pipelining, super-rounds and local optimisation: not here.
+
+    train = True: every round runs (no adaptive stop, as in the reference's train branches), each one ops.SampleGather (the
+    straight-through samples of the Gumbel top-k) followed by ops.kabsch, and the call returns dict(models [P, rounds * B, 4, 4],
+    keep [P, rounds * B] = the fit's validity) with autograd to the logits, and to `matches` where they require it.  The pose loss is
+    the user's, in torch, on the returned models.  `refit`, `confidence` and `device_termination` play no part, and nothing is read
+    back to the host."""
 
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
-                 num_samples=3, refit=True, eps=1e-5):
+                 num_samples=3, refit=True, eps=1e-5, train=False):
         if not 3 <= int(num_samples) <= 8:
             raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
         if int(max_iterations) < 1:
@@ -972,6 +978,7 @@ class BatchedRegistration(_SeededDriver):
         self._seeds = _Seeds(seed)
         self.refit = refit
         self.eps = eps
+        self.train = bool(train)
         self._device_termination = False
 
     @property
@@ -996,6 +1003,13 @@ class BatchedRegistration(_SeededDriver):
         if c != 6:
             raise ValueError("matches must be [P,N,6] = (p, q)")
         rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
+        if self.train:
+            out = []
+            for r in range(rounds):
+                g = None if gumbels is None else gumbels[r]
+                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
+                out.append(ops.kabsch(samples))
+            return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
         if self._device_termination and rounds > 16:      # (max_iterations / ransac_batch_size assigned after the switch)
             raise ValueError("device_termination issues every round: at most 16 rounds per call")
         with torch.no_grad():

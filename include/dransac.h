@@ -357,6 +357,21 @@ int dr_ransac3d_update_f64(const double *pts, const double *models, const uint8_
  *     and iters += B.  No valid model: only iters moves.  Terminated pairs are untouched.  One block per pair writes its state.
  *   dr_refit_rigid          the fit of dr_kabsch_gather over the rows mask [P,N] selects (NULL = all), weights [P,N] (optional)
  *     multiplying a row's term in the means and in H -> model [P,16], valid [P]; valid = 0 below three rows or for a degenerate H.
+ *
+ * Train mode (ops.kabsch, ops.weighted_kabsch, BatchedRegistration(train=True)).  With weights w >= 0 (1 when NULL), W = sum w:
+ * c0 = sum w p / W, c1 = sum w q / W, H = sum w (p - c0)(q - c1)^T.  The backward entries recompute this forward in f64 from their
+ * inputs (no stored model) and differentiate the optimality condition "R H is symmetric" (no SVD): with G = gR - gt c0^T,
+ * A = sym(R H), K = tr(A) I - A, Y = G R^T, a = (Y21 - Y12, Y02 - Y20, Y10 - Y01), z = K^-1 a: gH = -R^T [z]x, g_c0 = -R^T gt,
+ * g_c1 = gt, and per row g_p = w gH dq + (w / W) g_c0, g_q = w gH^T dp + (w / W) g_c1, g_w = dp^T gH dq + (dp.g_c0 + dq.g_c1) / W.
+ * gR, gt are rows 0..2 of a row-major 4x4 gradient; its last row is not read.  A fit that is not valid, or whose det K or result
+ * is not finite, passes exact zeros on.  Every output element is written; no atomics, so a repeated launch gives the same bits.
+ *
+ *   dr_kabsch               samples [Bt,k,6], 3 <= k <= 8, weights [Bt,k] or NULL -> models [Bt,16], valid [Bt]: the fit of
+ *     dr_kabsch_gather on explicit sample tensors; without weights, on samples = matches[idx], its models and valid bit for bit.
+ *     valid = 0 also for W <= 0.
+ *   dr_kabsch_bwd           grad_models [Bt,16] -> grad_samples [Bt,k,6], grad_weights [Bt,k] (or NULL: not wanted).
+ *   dr_refit_rigid_bwd      grad_model [P,16] -> grad_matches [P,N,6] and / or grad_weights [P,N] (NULL: not wanted; at least one);
+ *     rows the mask drops get exact zeros, and so does every row of a pair with fewer than three rows or an invalid fit.
  * ------------------------------------------------------------------------------------------ */
 int dr_kabsch_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, int k, float *models, uint8_t *valid,
                          void *stream);
@@ -380,6 +395,16 @@ int dr_refit_rigid_f32(const float *matches, const uint8_t *mask, const float *w
                        void *stream);
 int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model, uint8_t *valid,
                        void *stream);
+int dr_kabsch_f32(const float *samples, const float *weights, int Bt, int k, float *models, uint8_t *valid, void *stream);
+int dr_kabsch_f64(const double *samples, const double *weights, int Bt, int k, double *models, uint8_t *valid, void *stream);
+int dr_kabsch_bwd_f32(const float *samples, const float *weights, const float *grad_models, int Bt, int k, float *grad_samples,
+                      float *grad_weights, void *stream);
+int dr_kabsch_bwd_f64(const double *samples, const double *weights, const double *grad_models, int Bt, int k, double *grad_samples,
+                      double *grad_weights, void *stream);
+int dr_refit_rigid_bwd_f32(const float *matches, const uint8_t *mask, const float *weights, const float *grad_model, int P, int N,
+                           float *grad_matches, float *grad_weights, void *stream);
+int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const double *weights, const double *grad_model, int P, int N,
+                           double *grad_matches, double *grad_weights, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * K5  train-mode best-of-S selection     RANSAC.__call__, ransac.py:87-96
