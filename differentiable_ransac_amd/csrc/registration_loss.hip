@@ -1,0 +1,256 @@
+// The training loss of the robust 3-D registration path (loss.RegistrationLoss): the truncated squared distance of EVERY returned
+// model on the ground-truth inlier points, value and gradient in one pass over the (model x point) grid -- what dr_match_loss_fused
+// is for the two-view path.  Nothing upstream computes this (include/dransac.h states the maths):
+//     d2[m,n] = |R_m p_n + t_m - q_n|^2,   e[m,n] = d2 < thr2 ? d2 / thr2 : 1,   sums[m] = sum_{n in mask} e[m,n]
+// Mapping: one LANE per model (12 model registers, 1 + 1 + 12 accumulators), one wave per block.  The wave compacts the pair's
+// masked points tile by tile into LDS, in ascending order, and every lane walks the tile reading each point as an LDS broadcast: no
+// cross-lane reduction, no atomics, and the order of every sum is the order of the points -- a repeated launch repeats bit for bit.
+// The grid is arithmetic-bound (~38 vector instructions per model x masked point); a tile's staging is ~1 % of its arithmetic.
+#include "rigid_device.hpp"
+
+namespace dr {
+
+constexpr int kRLTile = 256;      // points staged per tile: 6 KB of LDS in f32, 12 KB in f64
+constexpr int kRLMeanT = 1024;
+
+template <typename T, bool kGrad>
+__global__ __launch_bounds__(64) void registration_loss_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                               const T *__restrict__ models, const uint8_t *__restrict__ keep,
+                                                               const T *__restrict__ thr2, int M, int N, T *__restrict__ sums,
+                                                               T *__restrict__ grad) {
+  __shared__ T s_pt[kRLTile][6];
+  const int p = blockIdx.y, lane = threadIdx.x, m = blockIdx.x * 64 + lane;
+  const T *pt = matches + (size_t)p * N * 6;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T t2 = thr2[p];
+  const bool thr_ok = t2 > T(0);                      // (false for NaN too: every point then takes the truncated branch)
+  // a slot that keep drops is SKIPPED (its model, possibly NaN, is never read); a kept model with a non-finite entry is "bad": every
+  // masked point counts 1 and nothing flows back
+  const bool kept = m < M && (!keep || keep[(size_t)p * M + m] != 0);
+  T md[12];
+  bool finite = true;
+#pragma unroll
+  for (int q = 0; q < 12; ++q) {
+    md[q] = kept ? models[((size_t)p * M + m) * 16 + q] : T(0);
+    finite = finite && is_finite(md[q]);
+  }
+  if (!finite) {
+#pragma unroll
+    for (int q = 0; q < 12; ++q) md[q] = T(0);
+  }
+
+  T acc = T(0), gR[3][3], gt[3];
+  int truncated = 0, n_mask = 0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    gt[i] = T(0);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) gR[i][j] = T(0);
+  }
+
+  for (int n0 = 0; n0 < N; n0 += kRLTile) {
+    // the tile's masked points, compacted in ascending order (ballot + prefix count: the wave is the block)
+    int count = 0;
+#pragma unroll
+    for (int j = 0; j < kRLTile / 64; ++j) {
+      const int n = n0 + j * 64 + lane;
+      const bool on = n < N && (!mk || mk[n] != 0);
+      const unsigned long long b = __ballot(on);
+      const int pos = count + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+      if (on) {
+#pragma unroll
+        for (int d = 0; d < 6; ++d) s_pt[pos][d] = pt[(size_t)n * 6 + d];
+      }
+      count += __popcll(b);
+    }
+    __syncthreads();
+    n_mask += count;
+#pragma unroll 4
+    for (int i = 0; i < count; ++i) {
+      T x[6], e[3];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = s_pt[i][d];
+      // e = q - t - R p, started from q - t so that the partial results shrink towards e: the roundings are of |q - t|, |R_0 p_0 + e|
+      // and |e|, not of |t| and |R p + t| as in rigid_d2's q - (R p + t).  The gradient is a sum of e p^T, and for a model with a
+      // handful of live points the cancellation in e is its whole error: 3-10 x smaller this way on the test scenes (docs/LOG.md)
+      T d2 = T(0);
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        e[r] = fma(-md[4 * r], x[0], fma(-md[4 * r + 1], x[1], fma(-md[4 * r + 2], x[2], x[3 + r] - md[4 * r + 3])));
+        d2 = fma(e[r], e[r], d2);
+      }
+      const bool live = d2 < t2;                      // strict; false for a NaN distance
+      acc += live ? d2 : T(0);
+      truncated += live ? 0 : 1;
+      if (kGrad) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+          const T el = live ? e[r] : T(0);
+          gt[r] += el;
+#pragma unroll
+          for (int c = 0; c < 3; ++c) gR[r][c] = fma(el, x[c], gR[r][c]);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  if (m >= M) return;
+  const size_t slot = (size_t)p * M + m;
+  const bool good = kept && finite && thr_ok;
+  const T inv = thr_ok ? T(1) / t2 : T(0);
+  sums[slot] = !kept ? T(0) : (good ? fma(acc, inv, (T)truncated) : (T)n_mask);
+  if (kGrad) {
+    // e = q - (R p + t) = -r: d sums / d R = (2 / thr2) sum r p^T, d sums / d t = (2 / thr2) sum r, over the live points
+    const T sc = good ? T(-2) * inv : T(0);
+    T *g = grad + slot * 16;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) g[4 * r + c] = good ? sc * gR[r][c] : T(0);
+      g[4 * r + 3] = good ? sc * gt[r] : T(0);
+    }
+    g[12] = g[13] = g[14] = g[15] = T(0);
+  }
+}
+
+// per_pair[p] = sum_m sums[p,m] / max(#kept_p #mask_p, 1), coef[p] = 1 / that denominator, mean = sum_p per_pair[p] / P: ONE block whose
+// sixteen waves take the pairs in turn; lane partials, wave butterfly, waves in order -- a fixed order.  It reads P (5 M + N) bytes
+// on one CU: microseconds at a train step's shape, hence the entries' bound P M < 2^22 (16 MB of sums)
+template <typename T>
+__global__ __launch_bounds__(kRLMeanT) void registration_loss_mean_kernel(const T *__restrict__ sums, const uint8_t *__restrict__ mask,
+                                                                         const uint8_t *__restrict__ keep, int P, int M, int N,
+                                                                         T *__restrict__ per_pair, T *__restrict__ coef,
+                                                                         T *__restrict__ mean) {
+  __shared__ T s_tot[kRLMeanT / 64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  T wave_total = T(0);
+  for (int p = wv; p < P; p += kRLMeanT / 64) {
+    T acc = T(0);
+    int n_in = 0, n_kept = 0;
+    for (int m = lane; m < M; m += 64) {
+      acc += sums[(size_t)p * M + m];
+      if (keep) n_kept += keep[(size_t)p * M + m] != 0;
+    }
+    if (mask)
+      for (int n = lane; n < N; n += 64) n_in += mask[(size_t)p * N + n] != 0;
+    acc = wave_sum(acc);
+    n_in = mask ? wave_sum(n_in) : N;
+    n_kept = keep ? wave_sum(n_kept) : M;
+    const T den = fmax((T)n_in * (T)n_kept, T(1));
+    if (lane == 0) {
+      per_pair[p] = acc / den;
+      coef[p] = T(1) / den;
+    }
+    wave_total += acc / den;
+  }
+  if (lane == 0) s_tot[wv] = wave_total;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    T t = T(0);
+    for (int w = 0; w < kRLMeanT / 64; ++w) t += s_tot[w];
+    mean[0] = t / (T)P;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void registration_loss_scale_kernel(const T *__restrict__ grad_unscaled, const T *__restrict__ coef,
+                                                                     const T *__restrict__ grad_mean, T inv_pairs, size_t per_pair,
+                                                                     size_t total, T *__restrict__ grad_models) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < total) grad_models[i] = grad_unscaled[i] * (coef[i / per_pair] * grad_mean[0] * inv_pairs);
+}
+
+// mask[p,n] = |R p + t - q|^2 < thr2[p] under the ground-truth pose of the pair (rigid_d2: the score kernels' inlier test), count[p]
+template <typename T>
+__global__ __launch_bounds__(256) void registration_gt_mask_kernel(const T *__restrict__ matches, const T *__restrict__ pose,
+                                                                  const T *__restrict__ thr2, int N, uint8_t *__restrict__ mask,
+                                                                  int32_t *__restrict__ count) {
+  __shared__ int s_cnt[4];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  T md[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) md[q] = pose[(size_t)p * 16 + q];
+  const T t2 = thr2[p];
+  int c = 0;
+  for (int n = tid; n < N; n += 256) {
+    T x[6];
+#pragma unroll
+    for (int d = 0; d < 6; ++d) x[d] = matches[((size_t)p * N + n) * 6 + d];
+    const bool on = rigid_d2<T>(md, x) < t2;
+    mask[(size_t)p * N + n] = on ? 1 : 0;
+    c += on ? 1 : 0;
+  }
+  c = wave_sum(c);
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) count[p] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+
+template <typename T, bool kGrad>
+int registration_loss_entry(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2, int P, int M,
+                            int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) {
+  hipLaunchKernelGGL((registration_loss_kernel<T, kGrad>), dim3((M + 63) / 64, P), dim3(64), 0, (hipStream_t)stream, matches, mask,
+                     models, keep, thr2, M, N, sums, grad_unscaled);
+  if (int rc = check_launch("registration_loss_kernel")) return rc;
+  hipLaunchKernelGGL((registration_loss_mean_kernel<T>), dim3(1), dim3(kRLMeanT), 0, (hipStream_t)stream, sums, mask, keep, P, M, N,
+                     per_pair, coef, mean);
+  return check_launch("registration_loss_mean_kernel");
+}
+
+template <typename T>
+int registration_loss_scale_entry(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,
+                                  void *stream) {
+  const size_t total = (size_t)P * M * 16;
+  hipLaunchKernelGGL((registration_loss_scale_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     grad_unscaled, coef, grad_mean, T(1) / (T)P, (size_t)M * 16, total, grad_models);
+  return check_launch("registration_loss_scale_kernel");
+}
+
+template <typename T>
+int registration_gt_mask_entry(const T *matches, const T *gt_pose, const T *thr2, int P, int N, uint8_t *mask, int32_t *count,
+                               void *stream) {
+  hipLaunchKernelGGL((registration_gt_mask_kernel<T>), dim3(P), dim3(256), 0, (hipStream_t)stream, matches, gt_pose, thr2, N, mask,
+                     count);
+  return check_launch("registration_gt_mask_kernel");
+}
+
+}  // namespace dr
+
+extern "C" {
+
+#define DR_REGISTRATION_LOSS_SIZES \
+  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535 && (long)P * M < (1l << 22), "need P, M, N > 0, P <= 65535 and P M < 2^22")
+
+#define DR_REGISTRATION_LOSS_ENTRIES(T, sfx)                                                                                             \
+  int dr_registration_loss_fused_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,    \
+                                       int P, int M, int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) { \
+    DR_REQUIRE(matches && models && thr2 && sums && grad_unscaled && per_pair && coef && mean, "null pointer");                       \
+    DR_REGISTRATION_LOSS_SIZES;                                                                                                        \
+    return dr::registration_loss_entry<T, true>(matches, mask, models, keep, thr2, P, M, N, sums, grad_unscaled, per_pair, coef,       \
+                                                mean, stream);                                                                         \
+  }                                                                                                                                    \
+  int dr_registration_loss_fwd_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,      \
+                                     int P, int M, int N, T *sums, T *per_pair, T *coef, T *mean, void *stream) {                      \
+    DR_REQUIRE(matches && models && thr2 && sums && per_pair && coef && mean, "null pointer");                                        \
+    DR_REGISTRATION_LOSS_SIZES;                                                                                                        \
+    return dr::registration_loss_entry<T, false>(matches, mask, models, keep, thr2, P, M, N, sums, (T *)nullptr, per_pair, coef,       \
+                                                 mean, stream);                                                                        \
+  }                                                                                                                                    \
+  int dr_registration_loss_scale_##sfx(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,       \
+                                       void *stream) {                                                                                 \
+    DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");                                                    \
+    DR_REQUIRE(P > 0 && M > 0 && (long)P * M < (1l << 22), "need P, M > 0 and P M < 2^22");                                            \
+    return dr::registration_loss_scale_entry<T>(grad_unscaled, coef, grad_mean, P, M, grad_models, stream);                            \
+  }                                                                                                                                    \
+  int dr_registration_gt_mask_##sfx(const T *matches, const T *gt_pose, const T *thr2, int P, int N, uint8_t *mask, int32_t *count,   \
+                                    void *stream) {                                                                                    \
+    DR_REQUIRE(matches && gt_pose && thr2 && mask && count, "null pointer");                                                          \
+    DR_REQUIRE(P > 0 && N > 0, "need P, N > 0");                                                                                       \
+    return dr::registration_gt_mask_entry<T>(matches, gt_pose, thr2, P, N, mask, count, stream);                                       \
+  }
+
+DR_REGISTRATION_LOSS_ENTRIES(float, f32)
+DR_REGISTRATION_LOSS_ENTRIES(double, f64)
+
+}  // extern "C"

@@ -1,4 +1,5 @@
-"""The two training losses that follow the hot path: MatchLoss and PoseLoss.
+"""The training losses that follow the hot path: MatchLoss and PoseLoss for the two-view drivers,
+RegistrationLoss (at the end) for the 3-D registration driver.
 
 MatchLoss -- the clamped symmetric-epipolar training loss of the reference (loss.py:107-153), on the fused kernel
 `dr_episym_fwd/bwd`.
@@ -111,3 +112,42 @@ class ClassificationLoss(object):
         return torch.nn.functional.binary_cross_entropy(probs, gt_mask.to(probs.dtype))
 
     __call__ = forward
+
+
+class RegistrationLoss(object):
+    """The training loss of ransac.BatchedRegistration(train=True): the truncated squared distance of every returned model on the
+    ground-truth inlier points, what MatchLoss is for E and F.  Per pair, with d2 = |R p + t - q|^2: the mean over (kept models x
+    masked points) of (d2 / threshold^2 if d2 < threshold^2 else 1); then the mean over the pairs.  The loss lies in [0, 1]; a hopeless
+    hypothesis contributes the constant 1 and no gradient.  Not the reference's 3-D loss (model_cl.py:586-589: the mean squared residual
+    over ALL points, which ops.rigid_residual_autograd reproduces).  Value and gradient come from one pass of
+    `dr_registration_loss_fused`; nothing synchronises, so a whole train step can be captured by graphs.GraphedStep."""
+
+    def __init__(self, threshold):
+        self.threshold = threshold          # inlier DISTANCE, float or [P] (BatchedRegistration's convention)
+
+    def forward(self, models, matches, gt_pose=None, gt_mask=None, keep=None):
+        """models [P,M,4,4] (or [P,4,4]: a test-mode result), matches [P,N,6], gt_mask [P,N] bool or gt_pose [P,4,4] (the mask is then
+        the points within the threshold of that pose: ops.registration_gt_mask; neither = all points), keep [P,M] bool (models to
+        average over, e.g. the fit's validity; None = all) -> scalar loss, differentiable w.r.t. the models ONLY: `matches` that
+        require grad are refused (pass matches.detach(); the driver's own gradient to `matches` is unaffected)."""
+        if models.dim() == 3:
+            models = models[:, None]
+            keep = keep if keep is None or keep.dim() == 2 else keep[:, None]
+        if gt_mask is None and gt_pose is not None:
+            with torch.no_grad():
+                gt_mask = ops.registration_gt_mask(matches, gt_pose.to(matches.dtype), self.threshold)[0]
+        return ops.registration_loss_mean(matches, gt_mask, models, self.threshold, keep)
+
+    __call__ = forward
+
+
+def registration_errors(model, gt_pose):
+    """model [...,4,4], gt_pose broadcastable to it -> (rre_deg, rte): the rotation error acos(clamp((tr(R_gt^T R) - 1) / 2, -1, 1))
+    in degrees and the translation error |t - t_gt|.  Plain torch under no_grad, for evaluation (the acos is singular at the optimum:
+    the training signal is RegistrationLoss)."""
+    with torch.no_grad():
+        R, Rg = model[..., :3, :3], gt_pose[..., :3, :3]
+        c = ((Rg * R).sum((-1, -2)) - 1.0) / 2.0          # tr(Rg^T R) = sum of the entrywise products
+        rre = torch.rad2deg(torch.acos(c.clamp(-1.0, 1.0)))
+        rte = (model[..., :3, 3] - gt_pose[..., :3, 3]).norm(dim=-1)
+        return rre, rte

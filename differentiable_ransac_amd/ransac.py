@@ -957,8 +957,8 @@ class BatchedRegistration(_SeededDriver):
 
     train = True: every round runs (no adaptive stop, as in the reference's train branches), each one ops.SampleGather (the
     straight-through samples of the Gumbel top-k) followed by ops.kabsch, and the call returns dict(models [P, rounds * B, 4, 4],
-    keep [P, rounds * B] = the fit's validity) with autograd to the logits, and to `matches` where they require it.  The pose loss is
-    the user's, in torch, on the returned models.  `refit`, `confidence` and `device_termination` play no part, and nothing is read
+    keep [P, rounds * B] = the fit's validity) with autograd to the logits, and to `matches` where they require it.  The pose loss on
+    the returned models is loss.RegistrationLoss (pass `keep`).  `refit`, `confidence` and `device_termination` play no part, and nothing is read
     back to the host."""
 
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,

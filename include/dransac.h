@@ -407,6 +407,50 @@ int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const dou
                            double *grad_matches, double *grad_weights, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The training loss of the registration path (loss.RegistrationLoss).  Not a restatement of upstream code: RANSACLayer3D's own loss
+ * (model_cl.py:586-589) is the mean squared residual over ALL points, which dr_rigid_residual already reproduces.  matches, models,
+ * thr2 as above; mask [P,N] (the ground-truth inliers; NULL = all points), keep [P,M] (NULL = all models).  With r = R p + t - q:
+ *     d2[p,m,n]   = |r|^2,   e[p,m,n] = d2 < thr2[p] ? d2 / thr2[p] : 1        (strict <, the inlier test of dr_rigid_msac_score)
+ *     sums[p,m]   = sum_{n in mask} e[p,m,n]                                    (#mask_p - sums = the MSAC score on the masked points)
+ *     per_pair[p] = sum_{m kept} sums[p,m] / max(#kept_p #mask_p, 1),   coef[p] = 1 / max(#kept_p #mask_p, 1),   mean = sum_p per_pair / P
+ *     d sums / d R = (2 / thr2) sum r p^T,   d sums / d t = (2 / thr2) sum r     over the masked points with d2 < thr2
+ * The truncated branch and d2 == thr2 pass no gradient; the last row of a 4x4 gradient is written as zeros.  A slot keep drops is
+ * skipped (sums 0, gradient 0, its model is not read: it may be NaN); a kept model with a non-finite entry has sums = #mask_p and a
+ * zero gradient; a pair with an empty mask or no kept model has per_pair 0 and zero gradients.  Every output element is written; no
+ * floating-point atomics and one fixed order for every sum (ascending points per model, lanes then waves in the reduction), so a
+ * repeated launch gives the same bits.  Sums are accumulated in the type of the inputs: sums[p,m] is evaluated as
+ * (sum of the d2 below thr2) x (1 / thr2) + (number of masked points at or above it), one rounding of the quotient per model and not
+ * one per point, and d2 as |q - t - R p|^2 started from q - t, so neither is dr_rigid_msac_score's value to the last bit.  A thr2[p]
+ * that is not > 0 (NaN included) leaves no point below it: sums = #mask_p for every kept model of the pair and zero gradients.
+ * P <= 65535 and P M < 2^22 (the per-pair / mean reduction is one block).
+ *
+ *   dr_registration_loss_fused   sums [P,M], grad_unscaled [P,M,16] = d sums[p,m] / d model, per_pair [P], coef [P], mean [1]: value and
+ *     gradient from one pass over the (model x point) grid (two launches: the grid, then the per-pair / mean reduction).
+ *   dr_registration_loss_scale   grad_models = grad_unscaled x coef[p] x grad_mean[0] / P: the whole backward of the mean.
+ *   dr_registration_loss_fwd     the value only (sums, per_pair, coef, mean).
+ *   dr_registration_gt_mask      gt_pose [P,16] -> mask [P,N] = (d2 < thr2[p]) under the pair's pose, count [P] int32.
+ * ------------------------------------------------------------------------------------------ */
+int dr_registration_loss_fused_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep,
+                                   const float *thr2, int P, int M, int N, float *sums, float *grad_unscaled, float *per_pair,
+                                   float *coef, float *mean, void *stream);
+int dr_registration_loss_fused_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                   const double *thr2, int P, int M, int N, double *sums, double *grad_unscaled, double *per_pair,
+                                   double *coef, double *mean, void *stream);
+int dr_registration_loss_scale_f32(const float *grad_unscaled, const float *coef, const float *grad_mean, int P, int M,
+                                   float *grad_models, void *stream);
+int dr_registration_loss_scale_f64(const double *grad_unscaled, const double *coef, const double *grad_mean, int P, int M,
+                                   double *grad_models, void *stream);
+int dr_registration_loss_fwd_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep, const float *thr2,
+                                 int P, int M, int N, float *sums, float *per_pair, float *coef, float *mean, void *stream);
+int dr_registration_loss_fwd_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                 const double *thr2, int P, int M, int N, double *sums, double *per_pair, double *coef, double *mean,
+                                 void *stream);
+int dr_registration_gt_mask_f32(const float *matches, const float *gt_pose, const float *thr2, int P, int N, uint8_t *mask,
+                                int32_t *count, void *stream);
+int dr_registration_gt_mask_f64(const double *matches, const double *gt_pose, const double *thr2, int P, int N, uint8_t *mask,
+                                int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K5  train-mode best-of-S selection     RANSAC.__call__, ransac.py:87-96
  *   chosen[p,b] = models[p,b,argmin_s ||models[p,b,s] - gt[p]||_F]; invalid slots (valid == 0) are
  *   skipped; which [P*B] int32 (-1 when no slot is valid; chosen = eye(3) then).
