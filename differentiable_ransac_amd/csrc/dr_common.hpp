@@ -205,6 +205,10 @@ __device__ __forceinline__ double fast_rcp(double x) { return 1.0 / x; }
 
 // NOTE: never test finiteness with (x - x) == 0: under -ffp-contract=fast the backend may fuse the producer
 // of x into the subtraction (fma(a, b, c - x)) and the "difference" is then a rounding residue, not zero.
+// equal as bit patterns (NaN equals the same NaN, 0 differs from -0): the snapshot gates of the local-optimisation kernels
+__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
+__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
 template <typename T>
 __device__ __forceinline__ bool is_finite(T x) {
   return __builtin_isfinite(x);

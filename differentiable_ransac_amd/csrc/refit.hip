@@ -275,9 +275,6 @@ int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const 
 // predicate -- mask and inlier count.  The loop stops early when a refit loses or leaves the mask as it was (the next refit
 // would see the same rows: same model, same outcome).  Then max_iters from the new inlier count (ransac.py:135-142) and the
 // snapshot.  The refit's candidates live in LDS behind the refit workspace.
-__device__ __forceinline__ bool same_bits(float a, float b) { return __float_as_uint(a) == __float_as_uint(b); }
-__device__ __forceinline__ bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
-
 // kMode: 0 = F, 1 = E with the light final stage, 2 = E with the wave-cooperative one (chosen per launch like refit_launch)
 template <typename T, int kMode>
 __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 1 ? 2 : 1, kMode == 1 ? 2 : 1))) void local_opt_kernel(

@@ -567,6 +567,148 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_bwd_kernel(const T *__
   }
 }
 
+// ---- (5) local optimisation of the pair state (BatchedRegistration(lo = 1 / 2)): one block per pair, right behind (3) ----------
+// A pair whose (best_score, best_model) still equals its snapshot lo_seen[p] bit for bit -- only (3) replaces them, and the snapshot
+// starts as NaN -- returns at once, whether or not it has terminated.  Otherwise, up to `iters` times: the fit of (4) over the best
+// mask (refit_moments + kabsch3, f64), the candidate rounded to T as (4) stores it, its MSAC score and inlier count over all N points
+// with the per-point terms of (2) and (3); the candidate is taken only if it scores STRICTLY higher ((3) and the driver's final refit
+// use > too), and then a further pass rewrites the mask and compares it with the old one.  The loop ends on an invalid or non-finite
+// fit, on a candidate that loses, and on an accepted mask that equals the previous one (the next fit would see the same rows).  Then
+// max_iters from the inlier count, the snapshot, and lo_refits[p] += fits run.  Below three inliers only the snapshot is stored.
+// Mapping (a latency kernel: a pair's fits are serial, each one four block-stride passes over 24 N bytes that stay in L2):
+//  - the points are NOT staged in LDS: one path for every N (a staged copy needs a size limit and a second path behind it), and a
+//    pass has 6 ceil(N / 256) independent loads per thread in flight, so it costs about one L2 round trip;
+//  - the candidate's mask is not held anywhere before acceptance: the accepting pass evaluates rigid_d2 < thr2 again, the same
+//    expression on the same values as the counting pass, so the count is the written mask's count, for every N;
+//  - every thread runs kabsch3 on the block's sums (same inputs, same instructions, same bits): no broadcast and no barrier
+//    between the fit and the score pass.  Thread n owns points n, n + 256, ... in every pass, mask bytes included.
+// Sums: lane, wave butterfly, the four waves in order -- no floating-point atomics, a repeated launch gives the same bits.
+template <typename T>
+__global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
+    const T *__restrict__ pts, const T *__restrict__ thr2, int N, int iters, double confidence, double eps, int max_iterations,
+    T *__restrict__ best_score, T *__restrict__ best_model, uint8_t *__restrict__ best_mask, int32_t *__restrict__ best_inliers,
+    double *__restrict__ max_iters, T *__restrict__ lo_seen, int32_t *__restrict__ lo_refits) {
+  __shared__ double s_red[kRFThreads / 64][9];
+  __shared__ T s_part[kRFThreads / 64];
+  __shared__ int s_cnt[kRFThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const T *pt = pts + (size_t)p * N * 6;
+  uint8_t *mk = best_mask + (size_t)p * N;
+  T *seen = lo_seen + (size_t)p * 17;
+  T bs = best_score[p];
+  T bm[16];
+  bool same = same_bits(bs, seen[0]);
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    bm[q] = best_model[(size_t)p * 16 + q];
+    same = same && same_bits(bm[q], seen[1 + q]);
+  }
+  int inl = best_inliers[p];
+  __syncthreads();      // (every thread has read the state and the snapshot: thread 0 writes them below)
+  if (same) return;     // block-uniform: no replacement since the last visit
+  const T t2 = thr2[p];
+  const T inv = T(1) / t2;
+  const bool run = inl >= 3;
+  bool taken = false;
+  int fits = 0;
+  for (int it = 0; run && it < iters; ++it) {
+    double c[6], h[9], rows;
+    const double W = refit_moments(pt, mk, static_cast<const T *>(nullptr), N, s_red, c, h, rows);
+    double H[3][3], R[3][3], t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
+    bool ok = kabsch3(H, c, rows >= 3.0 && W > 0.0, R, t);
+    ++fits;
+    T m[12];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) m[4 * i + j] = (T)R[i][j];
+      m[4 * i + 3] = (T)t[i];
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) ok = ok && is_finite(m[q]);
+    if (!ok) break;     // (block-uniform, like every exit below: all threads hold the same sums)
+    T acc = T(0);
+    int cnt = 0;
+    for (int n = tid; n < N; n += kRFThreads) {
+      T x[6];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
+      const T d2 = rigid_d2<T>(m, x);
+      const T sv = T(1) - d2 * inv;
+      acc += sv > T(0) ? sv : T(0);      // a NaN distance contributes nothing
+      cnt += d2 < t2 ? 1 : 0;
+    }
+    acc = wave_sum(acc);
+    cnt = wave_sum(cnt);
+    if (lane == 0) {
+      s_part[wv] = acc;
+      s_cnt[wv] = cnt;
+    }
+    __syncthreads();
+    T sc = s_part[0];
+    cnt = s_cnt[0];
+#pragma unroll
+    for (int w = 1; w < kRFThreads / 64; ++w) {
+      sc += s_part[w];
+      cnt += s_cnt[w];
+    }
+    __syncthreads();    // (s_part / s_cnt are reused below and by the next fit)
+    if (!(sc > bs)) break;
+    int chg = 0;
+    for (int n = tid; n < N; n += kRFThreads) {
+      T x[6];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
+      const uint8_t in = rigid_d2<T>(m, x) < t2;
+      chg |= in != mk[n];
+      mk[n] = in;
+    }
+    chg = wave_sum(chg);
+    if (lane == 0) s_cnt[wv] = chg;
+    __syncthreads();
+    const bool changed = (s_cnt[0] | s_cnt[1] | s_cnt[2] | s_cnt[3]) != 0;   // (next written behind refit_moments' barriers)
+    bs = sc;
+    inl = cnt;
+    taken = true;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) bm[q] = m[q];
+    bm[12] = bm[13] = bm[14] = T(0);
+    bm[15] = T(1);
+    if (!changed) break;
+  }
+  if (tid == 0) {
+    if (taken) {
+      best_score[p] = bs;
+      best_inliers[p] = inl;
+#pragma unroll
+      for (int q = 0; q < 16; ++q) best_model[(size_t)p * 16 + q] = bm[q];
+    }
+    if (run) max_iters[p] = adaptive_max_iters(inl, N, 3, confidence, eps, max_iterations);
+    seen[0] = bs;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) seen[1 + q] = bm[q];
+    if (lo_refits) lo_refits[p] += fits;
+  }
+}
+
+template <typename T>
+int registration_local_opt_entry(const T *matches, const T *thr2, int P, int N, int lo, int lo_iters, double confidence, double eps,
+                                 int max_iterations, T *best_score, T *best_model, uint8_t *best_mask, int32_t *best_inliers,
+                                 double *max_iters, T *lo_seen, int32_t *lo_refits, void *stream) {
+  DR_REQUIRE(matches && thr2 && best_score && best_model && best_mask && best_inliers && max_iters && lo_seen, "null pointer");
+  DR_REQUIRE(P > 0 && N > 0 && max_iterations > 0, "bad sizes");
+  DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");
+  DR_REQUIRE(lo_iters >= 1, "lo_iters must be at least 1");
+  hipLaunchKernelGGL((registration_local_opt_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, thr2, N,
+                     lo == 1 ? 1 : lo_iters, confidence, eps, max_iterations, best_score, best_model, best_mask, best_inliers,
+                     max_iters, lo_seen, lo_refits);
+  return check_launch("registration_local_opt_kernel");
+}
+
 template <typename T>
 int kabsch_gather_entry(const T *matches, const int32_t *idx, int P, int B, int N, int k, T *models, uint8_t *valid, void *stream) {
   const int Bt = P * B;
@@ -721,6 +863,19 @@ int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double 
   return dr::refit_rigid_entry<double>(matches, mask, weights, P, N, model, valid, stream);
 }
 
+
+int dr_registration_local_opt_f32(const float *matches, const float *thr2, int P, int N, int lo, int lo_iters, double confidence,
+                                  double eps, int max_iterations, float *best_score, float *best_model, uint8_t *best_mask,
+                                  int32_t *best_inliers, double *max_iters, float *lo_seen, int32_t *lo_refits, void *stream) {
+  return dr::registration_local_opt_entry<float>(matches, thr2, P, N, lo, lo_iters, confidence, eps, max_iterations, best_score,
+                                                 best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, stream);
+}
+int dr_registration_local_opt_f64(const double *matches, const double *thr2, int P, int N, int lo, int lo_iters, double confidence,
+                                  double eps, int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
+                                  int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits, void *stream) {
+  return dr::registration_local_opt_entry<double>(matches, thr2, P, N, lo, lo_iters, confidence, eps, max_iterations, best_score,
+                                                  best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, stream);
+}
 
 #define DR_REFIT_RIGID_BWD_CHECKS                                                                    \
   DR_REQUIRE(matches && grad_model && (grad_matches || grad_weights), "null pointer");               \

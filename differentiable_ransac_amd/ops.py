@@ -733,6 +733,29 @@ def registration_update(state: RegistrationState, matches, models, valid, scores
            ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
 
 
+def registration_local_optimize(state: RegistrationState, matches, thr2, lo: int, lo_iters: int, confidence: float = 0.999,
+                                eps: float = 1e-5, max_iterations: Optional[int] = None, lo_seen: Optional[torch.Tensor] = None,
+                                lo_refits: Optional[torch.Tensor] = None) -> None:
+    """dr_registration_local_opt: local optimisation (lo = 1: one Kabsch refit on the inliers, lo = 2: up to lo_iters, each kept only
+    where it scores strictly higher), in place on `state`, for the pairs whose best model dr_registration_update replaced since the
+    last visit.  thr2 [P] = threshold^2 (thr2_tensor).  lo_seen [P,17] (matches' dtype) is the per-call snapshot, filled with NaN
+    before the first round; lo_refits [P] int32 (optional) accumulates the fits run per pair.  One launch, no synchronisation."""
+    tensors = (matches, thr2, lo_seen, lo_refits, state.best_score, state.best_model, state.best_mask, state.best_inliers,
+               state.max_iters)
+    if any(t is not None and not t.is_cuda for t in tensors):
+        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    P, N, _ = matches.shape
+    if lo_seen is None or lo_seen.shape != (P, 17) or lo_seen.dtype != matches.dtype or not lo_seen.is_contiguous():
+        raise L.DransacError("registration_local_optimize: lo_seen must be a contiguous [P,17] tensor of the matches' dtype")
+    if lo_refits is not None and (lo_refits.shape != (P,) or lo_refits.dtype != torch.int32):
+        raise L.DransacError("registration_local_optimize: lo_refits must be [P] int32")
+    mi = state.max_iterations if max_iterations is None else max_iterations
+    L.call(f"dr_registration_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), c_int(P), c_int(N),
+           c_int(int(lo)), c_int(int(lo_iters)), L.c_double(confidence), L.c_double(eps), c_int(int(mi)), ptr(state.best_score),
+           ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.max_iters),
+           ptr(lo_seen), ptr(lo_refits), stream())
+
+
 def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
     """dr_refit_rigid: the Kabsch fit over the rows mask [P,N] selects (None = all), weights [P,N] (optional) multiplying a row's
     term in the means and in H -> (model [P,4,4], valid [P] bool); valid = 0 below three rows or for a degenerate selection."""

@@ -953,7 +953,13 @@ class BatchedRegistration(_SeededDriver):
     ops.rigid_residual compare the squared distance with their threshold itself).
 
     device_termination = True issues every round, gated on the device, with no read-back, so that a call can be captured by
-    graphs.GraphedStep; it is refused above 16 rounds.  Pipelining, super-rounds and local optimisation: not here.
+    graphs.GraphedStep; it is refused above 16 rounds.  Pipelining and super-rounds: not here.
+
+    lo = 1 / 2 (test mode only): local optimisation on the device, one dr_registration_local_opt launch behind every
+    dr_registration_update, in the same stream and with no read-back: a pair whose best model the round replaced gets one Kabsch refit
+    on its inliers (lo = 1) or up to `lo_iters` of them (lo = 2), each kept only where it scores strictly higher; mask, inlier count
+    and stop bound follow, so the read-back after the round sees the tightened bound, and the final `refit` starts from LO's mask.
+    The result gains lo_refits [P], the fits run per pair.  lo = 0 is the path without it: no launch, no allocation, no key.
 
     train = True: every round runs (no adaptive stop, as in the reference's train branches), each one ops.SampleGather (the
     straight-through samples of the Gumbel top-k) followed by ops.kabsch, and the call returns dict(models [P, rounds * B, 4, 4],
@@ -962,7 +968,10 @@ class BatchedRegistration(_SeededDriver):
     back to the host."""
 
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
-                 num_samples=3, refit=True, eps=1e-5, train=False):
+                 num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64):
+        _check_lo(lo, lo_iters)
+        if lo and train:
+            raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
         if not 3 <= int(num_samples) <= 8:
             raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
         if int(max_iterations) < 1:
@@ -979,6 +988,8 @@ class BatchedRegistration(_SeededDriver):
         self.refit = refit
         self.eps = eps
         self.train = bool(train)
+        self.lo = int(lo)
+        self.lo_iters = int(lo_iters)
         self._device_termination = False
 
     @property
@@ -1016,6 +1027,10 @@ class BatchedRegistration(_SeededDriver):
             matches = matches.contiguous()
             st = ops.RegistrationState(P, N, self.max_iterations, matches.device, matches.dtype)
             thr2 = ops.thr2_tensor(self.threshold, P, matches)
+            lo_seen = lo_refits = None
+            if self.lo:
+                lo_seen = torch.full((P, 17), float("nan"), device=matches.device, dtype=matches.dtype)
+                lo_refits = torch.zeros(P, device=matches.device, dtype=torch.int32)
             for r in range(rounds):
                 gate = st if (self._device_termination and r > 0) else None
                 g = None if gumbels is None else gumbels[r]
@@ -1023,6 +1038,9 @@ class BatchedRegistration(_SeededDriver):
                 models, valid = ops.kabsch_gather(matches, idx)
                 scores, _ = ops.rigid_msac_score(matches, models, None, valid, want_inliers=False, gate=gate, thr2=thr2)
                 ops.registration_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
+                if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
+                    ops.registration_local_optimize(st, matches, thr2, self.lo, self.lo_iters, self.confidence, self.eps,
+                                                    self.max_iterations, lo_seen, lo_refits)
                 if not self._device_termination and r + 1 < rounds and not bool((st.iters.double() < st.max_iters).any()):
                     break
             model, score = st.best_model, st.best_score
@@ -1032,4 +1050,7 @@ class BatchedRegistration(_SeededDriver):
                 take = cscore[:, 0] > score          # (an invalid candidate scores -1 and never wins)
                 model = torch.where(take[:, None, None], cand, model)
                 score = torch.where(take, cscore[:, 0], score)
-            return dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)
+            out = dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)
+            if self.lo:
+                out["lo_refits"] = lo_refits
+            return out

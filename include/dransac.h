@@ -357,6 +357,16 @@ int dr_ransac3d_update_f64(const double *pts, const double *models, const uint8_
  *     and iters += B.  No valid model: only iters moves.  Terminated pairs are untouched.  One block per pair writes its state.
  *   dr_refit_rigid          the fit of dr_kabsch_gather over the rows mask [P,N] selects (NULL = all), weights [P,N] (optional)
  *     multiplying a row's term in the means and in H -> model [P,16], valid [P]; valid = 0 below three rows or for a degenerate H.
+ *   dr_registration_local_opt  local optimisation of the pair state (BatchedRegistration(lo = 1 | 2)), one launch behind every
+ *     dr_registration_update, no read-back.  lo_seen [P,17] is the caller's snapshot (best_score, best_model [16]) of the last visit,
+ *     initialised to NaN: a pair whose state still equals it bit for bit returns with nothing written, terminated or not.  Below
+ *     three best_inliers only the snapshot is stored.  Otherwise, once (lo = 1) or up to lo_iters times (lo = 2): dr_refit_rigid's
+ *     fit over best_mask; its MSAC score and inlier count over all N points (d2 < thr2, strict; one fixed reduction order, no
+ *     floating-point atomics); taken only if score > best_score -- strict, as in dr_registration_update -- and then best_score,
+ *     best_model, best_mask (the candidate's own row) and best_inliers (that mask's count) are rewritten.  The loop ends on an invalid
+ *     or non-finite fit, on a candidate that loses, and on an accepted mask equal to the previous one.  Then max_iters =
+ *     min(max_iterations, adaptive_iteration_number(best_inliers, N, 3)) in f64, the snapshot is stored, and lo_refits[p] (NULL = not
+ *     counted) grows by the number of fits run.  DR_EINVAL: a null required pointer, P or N < 1, lo not 1 or 2, lo_iters < 1.
  *
  * Train mode (ops.kabsch, ops.weighted_kabsch, BatchedRegistration(train=True)).  With weights w >= 0 (1 when NULL), W = sum w:
  * c0 = sum w p / W, c1 = sum w q / W, H = sum w (p - c0)(q - c1)^T.  The backward entries recompute this forward in f64 from their
@@ -395,6 +405,12 @@ int dr_refit_rigid_f32(const float *matches, const uint8_t *mask, const float *w
                        void *stream);
 int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model, uint8_t *valid,
                        void *stream);
+int dr_registration_local_opt_f32(const float *matches, const float *thr2, int P, int N, int lo, int lo_iters, double confidence,
+                                  double eps, int max_iterations, float *best_score, float *best_model, uint8_t *best_mask,
+                                  int32_t *best_inliers, double *max_iters, float *lo_seen, int32_t *lo_refits, void *stream);
+int dr_registration_local_opt_f64(const double *matches, const double *thr2, int P, int N, int lo, int lo_iters, double confidence,
+                                  double eps, int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
+                                  int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits, void *stream);
 int dr_kabsch_f32(const float *samples, const float *weights, int Bt, int k, float *models, uint8_t *valid, void *stream);
 int dr_kabsch_f64(const double *samples, const double *weights, int Bt, int k, double *models, uint8_t *valid, void *stream);
 int dr_kabsch_bwd_f32(const float *samples, const float *weights, const float *grad_models, int Bt, int k, float *grad_samples,
