@@ -334,14 +334,7 @@ __device__ __forceinline__ float4 straight_through(float4 m, float y) {
   return make_float4(m.x * st, m.y * st, m.z * st, m.w * st);
 }
 
-// kScreen (round 5, index-only mode): the screening words of the long-row kernel for SHORT rows.  A point can only be among the k
-// winners if its score reaches T = logsumexp(logits) - ln(lambda), i.e. if its Philox word reaches a per-point threshold that
-// depends on the pair's logits only (gumbel_screen_short_kernel: screen_tb [P,N] words, screen_T [P]).  The wave compares the 64
-// words of an element slot against their thresholds -- no logarithm -- and only the lanes that pass (~lambda = 11 + k elements of
-// the row) evaluate their score, exactly as the unscreened kernel would have (same word, same logit, same rounding): the winners
-// are ranked among them by (value, index).  A row with fewer than k evaluated scores >= T (4e-4 of the rows at lambda = 16), or
-// more candidates than the list holds, takes the unscreened path below.
-template <bool kSoft, bool kScreen = false>
+template <bool kSoft>
 __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(const float *__restrict__ logits, uint64_t seed,
                                                                              int B, int N, int k, int32_t *__restrict__ idx,
                                                                              float *__restrict__ y_sel,
@@ -349,15 +342,12 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
                                                                              const uint64_t *__restrict__ seed_ptr,
                                                                              const float4 *__restrict__ gather_src = nullptr,
                                                                              float4 *__restrict__ gather_dst = nullptr,
-                                                                             PairGate gate = PairGate(),
-                                                                             const uint32_t *__restrict__ screen_tb = nullptr,
-                                                                             const float *__restrict__ screen_T = nullptr,
-                                                                             int sub = 0, const float *__restrict__ race_ws = nullptr,
+                                                                             PairGate gate = PairGate(), int sub = 0,
+                                                                             const float *__restrict__ race_ws = nullptr,
                                                                              int P_race = 0) {
-  // race_ws (index-only mode, unscreened): the exponential-race form (gumbel_race_weights_kernel), one logarithm per element
+  // race_ws: the exponential-race form (gumbel_race_weights_kernel), one logarithm per element
   // gather_src / gather_dst (index-only mode): K2 fused -- the winners' correspondences [P,N] x float4 -> samples [P,B,k] x float4
   if (gate.closed(blockIdx.y)) return;   // this pair has terminated (block-uniform): its rows keep what the last round drew
-  static_assert(!(kSoft && kScreen), "the soft-max statistics need every element's score");
   __shared__ float s_val[kRowsPerBlock][kMaxCand];
   __shared__ int s_idx[kRowsPerBlock][kMaxCand];
   if (seed_ptr) seed = *seed_ptr;
@@ -375,84 +365,10 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
   float *cand_val = s_val[wv];
   int *cand_idx = s_idx[wv];
 
-  if constexpr (kScreen) {
-    const float Tf = screen_T[p];
-    if (Tf != INFINITY) {   // (non-finite logits, or a threshold beyond the margin's reach: the pair is not screened)
-      // One element SLOT (group i, component j) at a time: the wave compares the slot's 64 words with their thresholds (one
-      // v_cmp; the result is a wave mask in SGPRs) and, only if some lane passed (~40 % of the slots at lambda = 16), those lanes
-      // transform THEIR word -- a register with a static index -- add the logit they hold and append the score to the wave's
-      // list.  No word is parked anywhere, no load depends on a hit (first version, `s_words`: 32 KiB of LDS per block and a
-      // global logit load per evaluation round -- slower than the unscreened kernel although it issued 40 % less).
-      const uint4 *tb4 = reinterpret_cast<const uint4 *>(screen_tb + (size_t)p * N);
-      int ncand = 0, reach = 0;
-      uint4 t_nx = lane < groups ? tb4[lane] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-      float4 l_nx = lane < groups ? lg[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < kFastGroups; ++i) {
-        if (64 * i >= groups) break;   // wave-uniform
-        const int q = lane + 64 * i;
-        const bool inb = q < groups;
-        const uint4 t4 = t_nx;
-        const float4 l4v = l_nx;
-        if (i + 1 < kFastGroups) {     // the next group's thresholds and logits are requested before this group's Philox rounds
-          const int qn = q + 64;
-          t_nx = qn < groups ? tb4[qn] : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-          l_nx = qn < groups ? lg[qn] : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        uint32_t r[4];
-        Philox::gen(seed, (uint32_t)q, (uint32_t)bq, (uint32_t)p, 0u, r);
-        const uint32_t tt[4] = {t4.x, t4.y, t4.z, t4.w};
-        const float ll[4] = {l4v.x, l4v.y, l4v.z, l4v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const bool has = inb && r[j] >= tt[j];
-          const unsigned long long bal = __builtin_amdgcn_ballot_w64(has);   // (the compare's own mask: __ballot adds a select + compare)
-          if (bal) {
-            float gv = -INFINITY;
-            if (has) {
-              gv = ll[j] + gumbel_from_bits(r[j]);
-              const int pos = ncand + __popcll(bal & ((1ull << lane) - 1ull));
-              if (pos < kMaxCand) { cand_val[pos] = gv; cand_idx[pos] = 4 * q + j; }
-            }
-            ncand += __popcll(bal);
-            reach += __popcll(__builtin_amdgcn_ballot_w64(has && gv >= Tf));
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      if (reach >= k && ncand <= kMaxCand) {
-        // the k winners are all >= T, hence all in the list: rank by (value descending, index ascending)
-        const bool have = lane < ncand;
-        const float cv = have ? cand_val[lane] : -INFINITY;
-        const int ci = have ? cand_idx[lane] : 0x7fffffff;
-        int rank = 0;
-        for (int j = 0; j < ncand; ++j) {
-          const float ov = cand_val[j];
-          const int oi = cand_idx[j];
-          rank += (ov > cv) || (ov == cv && oi < ci);
-        }
-        const bool win = have && rank < k;
-        const unsigned long long wb = __ballot(win);
-        int pos = 0;
-        for (int j = 0; j < ncand; ++j) {
-          if ((wb >> j) & 1ull) pos += cand_idx[j] < ci;
-        }
-        if (win) {
-          idx[row * k + pos] = ci;
-          if (gather_dst) gather_dst[row * k + pos] = gather_src[(size_t)p * N + ci];
-        }
-        return;
-      }
-      __builtin_amdgcn_wave_barrier();   // too few scores reach T (or too many candidates): the unscreened path
-    }
-  }
-
   // ---------------- pass A: g into registers, online soft-max, lane maximum
   float g[kFastGroups][4];
   float mx = -INFINITY, sm = 0.f, lmax = -INFINITY;
-  bool race = false;
-  if constexpr (!kScreen) race = race_ws != nullptr && reinterpret_cast<const int *>(race_ws + (size_t)P_race * N)[p] != 0;
+  const bool race = race_ws != nullptr && reinterpret_cast<const int *>(race_ws + (size_t)P_race * N)[p] != 0;
   if (race) {   // wave-uniform (per pair)
     // kSoft (train mode): exp(g_n - lmax) = exp(logit_n - lmax) / (-ln u_n) = 1 / (ln 2 (-key_n)) -- the soft-max statistics of the
     // row from the SAME keys: e_n = 1 / (-key_n), y_n = e_n / sum e, lse = lmax + ln(sum e) - ln ln 2.  A reciprocal and an add per
@@ -517,11 +433,22 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
   }
   // the soft-max weight of a selected score (kSoft)
   auto y_of = [&](float score) { return race ? __builtin_amdgcn_rcpf(-score) * inv_sm : exp_t<float>(score - wmx) * inv_sm; };
+  // THE winner write of all three selection back-ends: the row's pos-th winner (ascending point index) is point `index` with
+  // the score `score` -- idx, and the gathered correspondence (kSoft: y_sel, and the correspondence times its straight-through weight)
+  auto write_winner = [&](int pos, int index, float score) {
+    idx[row * k + pos] = index;
+    if (kSoft) {
+      const float y = y_of(score);
+      y_sel[row * k + pos] = y;
+      if (gather_dst) gather_dst[row * k + pos] = straight_through(gather_src[(size_t)p * N + index], y);
+    }
+    if (!kSoft && gather_dst) gather_dst[row * k + pos] = gather_src[(size_t)p * N + index];
+  };
 
   // ---------------- threshold: any t that at least k LANE MAXIMA reach has the k winners among { g >= t }
   bool settled = false;   // (wave-uniform)
   float thr = -INFINITY;
-  if constexpr (!kScreen) if (race) {
+  if (race) {
     // Round 6, the one-logarithm form: t by COUNTING.  The keys of a pair are a Poisson process in t: E #{ key >= t } = -t c_p with
     // c_p = ln 2 sum_n 1 / w_n (gumbel_race_weights_kernel), so t is searched as t = -lam / c_p from lam = 6: a compare + a count per
     // probe (one vector instruction; the k rounds of a wave-wide maximum below are 64), a secant step on the count until the count
@@ -541,16 +468,18 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
     }
     if (have_lo && clo <= 16) { settled = true; thr = tlo; }
   }
-  if (!settled) {   // the k-th largest lane maximum: k rounds of a wave-wide maximum
+  // the exact threshold: the k-th largest lane maximum, by k rounds of a wave-wide maximum
+  auto exact_threshold = [&] {
     float v = lmax;
     for (int r = 0; r < k; ++r) {
       thr = row_max(v);
       const unsigned long long who = __ballot(v == thr);
       if (lane == __ffsll((long long)who) - 1) v = -INFINITY;
     }
-  }
+  };
+  if (!settled) exact_threshold();
 
-  if constexpr (!kScreen) {
+  {   // (a scope of its own: n, cv_i and ci end with it.  Without the braces the compiler schedules the kernel differently, 88 vs 86 VGPRs)
     // ---------------- round 6: the selection on wave compare masks (scalar unit), no LDS -------------------------------------------
     // The candidates { g >= thr } are read off 32 compare masks by the scalar unit in ascending point index -- group, lane,
     // component -- and dealt to lanes 0 .. n-1 (a v_readlane and two selects under the scalar mask of lane n): n == k needs no
@@ -597,26 +526,11 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
         win = win && rank < k;
         pos = __popcll(__builtin_amdgcn_ballot_w64(win) & ((1ull << lane) - 1ull));   // (the lanes are in index order)
       }
-      if (win) {
-        idx[row * k + pos] = ci;
-        if (kSoft) {
-          const float y = y_of(cv);
-          y_sel[row * k + pos] = y;
-          if (gather_dst) gather_dst[row * k + pos] = straight_through(gather_src[(size_t)p * N + ci], y);
-        }
-        if (!kSoft && gather_dst) gather_dst[row * k + pos] = gather_src[(size_t)p * N + ci];
-      }
+      if (win) write_winner(pos, ci, cv);
       if (kSoft && lane == 0) lse_out[row] = lse;
       return;
     }
-    if (settled) {   // (more than 64 candidates at a searched threshold: the list wants the exact one)
-      float v = lmax;
-      for (int r = 0; r < k; ++r) {
-        thr = row_max(v);
-        const unsigned long long who = __ballot(v == thr);
-        if (lane == __ffsll((long long)who) - 1) v = -INFINITY;
-      }
-    }
+    if (settled) exact_threshold();   // (more than 64 candidates at a searched threshold: the list wants the exact one)
   }
 
   // ---------------- pass B: the candidates { g >= thr } into the wave's LDS list
@@ -656,15 +570,7 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
     for (int j = 0; j < ncand; ++j) {
       if ((wb >> j) & 1ull) pos += cand_idx[j] < ci;
     }
-    if (win) {
-      idx[row * k + pos] = ci;
-      if (kSoft) {
-        const float y = y_of(cv);
-        y_sel[row * k + pos] = y;
-        if (gather_dst) gather_dst[row * k + pos] = straight_through(gather_src[(size_t)p * N + ci], y);
-      }
-      if (!kSoft && gather_dst) gather_dst[row * k + pos] = gather_src[(size_t)p * N + ci];
-    }
+    if (win) write_winner(pos, ci, cv);
   } else {
     // slow path (massive ties): k rounds of (value desc, index asc) arg-max with exclusion of earlier winners
     int won[kMaxK];
@@ -697,13 +603,7 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
       for (int r = 0; r < k; ++r) if (r == lane) { me = won[r]; mg = wong[r]; }
       int pos = 0;
       for (int r = 0; r < k; ++r) pos += won[r] < me;
-      idx[row * k + pos] = me;
-      if (kSoft) {
-        const float y = y_of(mg);
-        y_sel[row * k + pos] = y;
-        if (gather_dst) gather_dst[row * k + pos] = straight_through(gather_src[(size_t)p * N + me], y);
-      }
-      if (!kSoft && gather_dst) gather_dst[row * k + pos] = gather_src[(size_t)p * N + me];
+      write_winner(pos, me, mg);
     }
   }
   if (kSoft && lane == 0) lse_out[row] = lse;
@@ -715,22 +615,22 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_fast_kernel(co
 // Poisson(lambda) such points into a row.  tb_n is rounded DOWN (score >= T - margin, four roundings of the 24-bit conversion),
 // so no point that reaches T is ever missed; T itself only sets the expected count -- it may be approximate (f32 log-sum-exp),
 // but words and sampler must use the SAME value: it is computed once per pair and read back by both.
-constexpr float kScreenMargin = 1e-3f;   // the device logarithms are good to ~1e-6
-// (a) per pair and eighth of the row: running (max, sum of exp) of its slice -- kScreenParts blocks of 256 threads, ONE pass, four
+constexpr float kWordMargin = 1e-3f;   // the device logarithms are good to ~1e-6
+// (a) per pair and eighth of the row: running (max, sum of exp) of its slice -- kRowParts blocks of 256 threads, ONE pass, four
 //     logits per load, every load of a thread in flight at once (first version: every block of the word kernel re-derived T from
 //     the whole row, 40 us at 50 000 points; second: one 1024-thread block per pair, 6.9 us)
-constexpr int kScreenParts = 8;
+constexpr int kRowParts = 8;
 __global__ __launch_bounds__(256) void gumbel_screen_part_kernel(const float *__restrict__ logits, int N, float *__restrict__ part) {
   __shared__ float s_mx[4], s_sm[4];
   const int p = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float4 *l4 = reinterpret_cast<const float4 *>(logits + (size_t)p * N);   // N % 4 == 0 (the long-row kernel's condition)
   const int groups = N >> 2;
   float mx = -INFINITY, sm = 0.f;
-  for (int q0 = blockIdx.x * 256 + tid; q0 < groups; q0 += 8 * kScreenParts * 256) {
+  for (int q0 = blockIdx.x * 256 + tid; q0 < groups; q0 += 8 * kRowParts * 256) {
     float4 v[8];
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
-      const int q = q0 + u * kScreenParts * 256;
+      const int q = q0 + u * kRowParts * 256;
       v[u] = q < groups ? l4[q] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
     }
 #pragma unroll
@@ -749,8 +649,8 @@ __global__ __launch_bounds__(256) void gumbel_screen_part_kernel(const float *__
     float bm = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
     float bs = 0.f;
     for (int w = 0; w < 4; ++w) bs += (s_mx[w] == -INFINITY) ? 0.f : s_sm[w] * __expf(s_mx[w] - bm);
-    part[((size_t)p * kScreenParts + blockIdx.x) * 2] = bm;
-    part[((size_t)p * kScreenParts + blockIdx.x) * 2 + 1] = bs;
+    part[((size_t)p * kRowParts + blockIdx.x) * 2] = bm;
+    part[((size_t)p * kRowParts + blockIdx.x) * 2 + 1] = bs;
   }
 }
 // (b) the words, one point per thread.  Every block combines the pair's eight partial sums itself -- the same values in the same
@@ -761,11 +661,11 @@ __global__ __launch_bounds__(256) void gumbel_screen_kernel(const float *__restr
   const int p = blockIdx.y, n = blockIdx.x * 256 + threadIdx.x;
   float bm = -INFINITY;
 #pragma unroll
-  for (int i = 0; i < kScreenParts; ++i) bm = fmaxf(bm, part[((size_t)p * kScreenParts + i) * 2]);
+  for (int i = 0; i < kRowParts; ++i) bm = fmaxf(bm, part[((size_t)p * kRowParts + i) * 2]);
   float bs = 0.f;
 #pragma unroll
-  for (int i = 0; i < kScreenParts; ++i) {
-    const float m = part[((size_t)p * kScreenParts + i) * 2], v = part[((size_t)p * kScreenParts + i) * 2 + 1];
+  for (int i = 0; i < kRowParts; ++i) {
+    const float m = part[((size_t)p * kRowParts + i) * 2], v = part[((size_t)p * kRowParts + i) * 2 + 1];
     bs += (m == -INFINITY) ? 0.f : v * __expf(m - bm);
   }
   float Tf = bm + __logf(bs) - __logf(lambda);
@@ -777,7 +677,7 @@ __global__ __launch_bounds__(256) void gumbel_screen_kernel(const float *__restr
   if (n >= N) return;
   constexpr double kTiny = 1.17549435e-38, kScale = 2.3283064365386963e-10 * (1.0 - 1.1920928955078125e-07 - 1.17549435e-38);
   // G >= a  <=>  u >= exp(-exp(-a)),  u = fl(fl24(w) * 2^-32 c + tiny)  (gumbel_from_bits),  a = T - margin - logit_n
-  const double a = ((double)Tf - (double)kScreenMargin) - (double)logits[(size_t)p * N + n];
+  const double a = ((double)Tf - (double)kWordMargin) - (double)logits[(size_t)p * N + n];
   const double e = exp(-a);
   const double us = (e < 745.0) ? exp(-e) : 0.0;
   double w = floor((us - kTiny) / kScale) - 1024.0;
@@ -829,66 +729,13 @@ __global__ __launch_bounds__(1024) void gumbel_screen_fused_kernel(const float *
   if (blockIdx.x == 0 && tid == 0) T_out[p] = Tf;
   if (n >= N) return;
   constexpr double kTiny = 1.17549435e-38, kScale = 2.3283064365386963e-10 * (1.0 - 1.1920928955078125e-07 - 1.17549435e-38);
-  const double a = ((double)Tf - (double)kScreenMargin) - (double)mine;
+  const double a = ((double)Tf - (double)kWordMargin) - (double)mine;
   const double e = exp(-a);
   const double us = (e < 745.0) ? exp(-e) : 0.0;
   double w = floor((us - kTiny) / kScale) - 1024.0;
   if (!(w == w)) w = 0.0;
   w = fmin(fmax(w, 0.0), 4294967295.0);
   tb[(size_t)p * N + n] = (Tf == INFINITY) ? 0xffffffffu : (uint32_t)w;
-}
-
-// (c) short rows (N <= 2048, N % 4 == 0: the register-resident sampler): T and the words of a pair by ONE block of 256 threads --
-//     one launch per call instead of two
-__global__ __launch_bounds__(256) void gumbel_screen_short_kernel(const float *__restrict__ logits, int N, float lambda,
-                                                                 float *__restrict__ T_out, uint32_t *__restrict__ tb) {
-  __shared__ float s_mx[4], s_sm[4];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const float4 *l4 = reinterpret_cast<const float4 *>(logits + (size_t)p * N);
-  const int groups = N >> 2;
-  float4 v[2];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int q = tid + 256 * u;
-    v[u] = q < groups ? l4[q] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    mx = fmaxf(mx, fmaxf(fmaxf(v[u].x, v[u].y), fmaxf(v[u].z, v[u].w)));
-  }
-  const float wmx = row_max(mx);
-  if (lane == 0) s_mx[wv] = wmx;
-  __syncthreads();
-  const float bm = fmaxf(fmaxf(s_mx[0], s_mx[1]), fmaxf(s_mx[2], s_mx[3]));
-  float sm = 0.f;
-  if (bm > -INFINITY) {
-#pragma unroll
-    for (int u = 0; u < 2; ++u) sm += (__expf(v[u].x - bm) + __expf(v[u].y - bm)) + (__expf(v[u].z - bm) + __expf(v[u].w - bm));
-  }
-  sm = row_sum(sm);
-  if (lane == 0) s_sm[wv] = sm;
-  __syncthreads();
-  const float bs = (s_sm[0] + s_sm[1]) + (s_sm[2] + s_sm[3]);
-  float Tf = bm + __logf(bs) - __logf(lambda);
-  if (!(Tf == Tf) || Tf == INFINITY || Tf == -INFINITY || fabsf(Tf) > 4096.f) Tf = INFINITY;   // as gumbel_screen_kernel
-  if (tid == 0) T_out[p] = Tf;
-  constexpr double kTiny = 1.17549435e-38, kScale = 2.3283064365386963e-10 * (1.0 - 1.1920928955078125e-07 - 1.17549435e-38);
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int q = tid + 256 * u;
-    if (q >= groups) continue;
-    const float lv[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-    uint32_t wv4[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const double a = ((double)Tf - (double)kScreenMargin) - (double)lv[j];
-      const double e = exp(-a);
-      const double us = (e < 745.0) ? exp(-e) : 0.0;
-      double w = floor((us - kTiny) / kScale) - 1024.0;
-      if (!(w == w)) w = 0.0;
-      w = fmin(fmax(w, 0.0), 4294967295.0);
-      wv4[j] = (Tf == INFINITY) ? 0xffffffffu : (uint32_t)w;
-    }
-    reinterpret_cast<uint4 *>(tb + (size_t)p * N)[q] = make_uint4(wv4[0], wv4[1], wv4[2], wv4[3]);
-  }
 }
 
 // ---- rows longer than the register kernel holds (N > 2048): ONE pass ----------------------------------------------------
@@ -1107,7 +954,7 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
                       const uint64_t *seed_ptr = nullptr, const float4 *gather_src = nullptr, float4 *gather_dst = nullptr,
                       bool *gathered = nullptr, uint32_t *screen_ws = nullptr, PairGate gate = PairGate(), int sub = 0,
                       float *race_ws = nullptr, bool race_ready = false) {
-  // race_ws (index-only mode, register kernel, no screen): (N + 32) * P floats -- the one-logarithm form; race_ready: the weights are
+  // race_ws (register kernel): (N + 32) * P floats -- the one-logarithm form; race_ready: the weights are
   // already in it (dr_ransac_init wrote them for the whole call): no prologue launch
   // sub (index-only mode, in-kernel noise): rows per sub-batch of a super-round (GumbelArgs::sub); 0 = one batch
   if (gathered) *gathered = false;
@@ -1120,32 +967,17 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
   const bool soft = y_sel != nullptr;   // the entry points have checked: y_sel and lse both given, or neither (then no dense outputs)
   if constexpr (sizeof(T) == 4) {
     if (logits && !gumbel && tau == T(1) && (N & 3) == 0 && N <= 4 * 64 * kFastGroups && !y_soft && !ret && !gumbel_out) {
-      if (soft) {
-        if (race_ws && !race_ready)
-          hipLaunchKernelGGL(gumbel_race_weights_kernel, dim3(P), dim3(256), 0, st, (const float *)logits, N, P, race_ws);
+      if (race_ws && !race_ready)
+        hipLaunchKernelGGL(gumbel_race_weights_kernel, dim3(P), dim3(256), 0, st, (const float *)logits, N, P, race_ws);
+      if (soft)   // (train mode: no gate, no sub-batches)
         hipLaunchKernelGGL((gumbel_topk_fast_kernel<true>), grid, block, 0, st, (const float *)logits, seed, B, N, k, idx,
-                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, PairGate(), (const uint32_t *)nullptr,
-                           (const float *)nullptr, 0, (const float *)race_ws, P);
-        if (gathered) *gathered = gather_dst != nullptr;
-      }
-      else if (screen_ws && k <= 5 && B >= 64) {
-        // screened (round 5): workspace = P x N words + P scores
-        float *Tw = reinterpret_cast<float *>(screen_ws + (size_t)P * N);
-        hipLaunchKernelGGL(gumbel_screen_short_kernel, dim3(P), dim3(256), 0, st, (const float *)logits, N, (float)(11 + k), Tw, screen_ws);
-        hipLaunchKernelGGL((gumbel_topk_fast_kernel<false, true>), grid, block, 0, st, (const float *)logits, seed, B, N, k, idx,
-                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, gate, (const uint32_t *)screen_ws,
-                           (const float *)Tw, sub);
-        if (gathered) *gathered = gather_dst != nullptr;
-      }
+                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, PairGate(), 0,
+                           (const float *)race_ws, P);
       else
-      {
-        if (race_ws && !race_ready)
-          hipLaunchKernelGGL(gumbel_race_weights_kernel, dim3(P), dim3(256), 0, st, (const float *)logits, N, P, race_ws);
         hipLaunchKernelGGL((gumbel_topk_fast_kernel<false>), grid, block, 0, st, (const float *)logits, seed, B, N, k, idx,
-                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, gate, (const uint32_t *)nullptr,
-                           (const float *)nullptr, sub, (const float *)race_ws, P);
-        if (gathered) *gathered = gather_dst != nullptr;
-      }
+                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, gate, sub,
+                           (const float *)race_ws, P);
+      if (gathered) *gathered = gather_dst != nullptr;
       return check_launch("gumbel_topk_fast_kernel");
     }
     // measured against the general two-pass kernel: 50 000 x 2048 rows, k = 3: 226 -> 113 us; 4096 x 32 768 rows, k = 5: 196 -> 178 us;
@@ -1162,7 +994,7 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
           hipLaunchKernelGGL(gumbel_screen_fused_kernel, dim3((N + 1023) / 1024, P), dim3(1024), 0, st, (const float *)logits, N,
                              (float)(20 + k), Tw, screen_ws);
         } else {
-          hipLaunchKernelGGL(gumbel_screen_part_kernel, dim3(kScreenParts, P), dim3(256), 0, st, (const float *)logits, N, part);
+          hipLaunchKernelGGL(gumbel_screen_part_kernel, dim3(kRowParts, P), dim3(256), 0, st, (const float *)logits, N, part);
           hipLaunchKernelGGL(gumbel_screen_kernel, dim3((N + 255) / 256, P), dim3(256), 0, st, (const float *)logits, N, (float)(20 + k),
                              part, Tw, screen_ws);
         }
@@ -1602,7 +1434,7 @@ int dr_seed_next_n(uint64_t *state, uint64_t *seeds_out, int n, void *stream) {
 // ransac.py:65).  One launch when the register kernel serves the shape, sampler + gather launches otherwise.
 static int gumbel_topk_gather_impl(const float *logits, const float *matches, uint64_t seed, const uint64_t *seed_dev, float tau, int P,
                                    int B, int N, int k, int32_t *idx, float *samples, dr::PairGate gate, void *stream,
-                                   uint32_t *screen_ws = nullptr, int sub = 0, float *race_ws = nullptr, bool race_ready = false) {
+                                   int sub = 0, float *race_ws = nullptr, bool race_ready = false) {
   const float *y_sel = nullptr, *lse = nullptr, *y_soft = nullptr, *ret = nullptr;
   DR_REQUIRE(logits && matches && samples, "null pointer");
   DR_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(samples) & 15) == 0, "16-byte alignment");
@@ -1610,7 +1442,7 @@ static int gumbel_topk_gather_impl(const float *logits, const float *matches, ui
   bool gathered = false;
   if (int rc = dr::gumbel_fwd_launch<float>(logits, nullptr, seed, tau, P, B, N, k, idx, nullptr, nullptr, nullptr, nullptr, nullptr,
                                             (hipStream_t)stream, seed_dev, reinterpret_cast<const float4 *>(matches),
-                                            reinterpret_cast<float4 *>(samples), &gathered, screen_ws, gate, sub, race_ws, race_ready))
+                                            reinterpret_cast<float4 *>(samples), &gathered, nullptr, gate, sub, race_ws, race_ready))
     return rc;
   if (gathered) return 0;
   hipLaunchKernelGGL((dr::gather_fwd_kernel<float>), dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, matches, idx,
@@ -1658,26 +1490,20 @@ int dr_gumbel_topk_gather_bwd_f32(const float *logits, const float *matches, uin
 // call): pairs whose iteration counter has reached its bound are skipped (gate_iters [P] int32, gate_max_iters [P] f64: the state
 // dr_ransac_update keeps; the rows of a skipped pair keep their contents).
 // Only the register-resident kernel (N <= 2048, N % 4 == 0, tau = 1) looks at the gate; other shapes simply run.
-// screen_ws (optional, (N + 32) * P words, 16-byte aligned; round 5): short rows (N <= 2048, N % 4 == 0, tau = 1, k <= 5, B >= 64)
-// then take the SCREENED register kernel -- per point the smallest Philox word that can lift it to the score logsumexp - ln(11 + k),
-// only the ~16 points of a row that pass are evaluated; the index sets are those of the unscreened kernel, bit for bit.
 // sub (round 6): > 0 = the B rows are consecutive sub-batches of `sub` rows -- row b draws what row b % sub of a call with the seed
 // (seed | *seed_dev) + b / sub draws: one launch samples what ceil(B / sub) calls of a batch-by-batch loop sample (dr_ransac_update's
 // `sub_models` walks them in order); 0 = one batch.  Soft (train-mode) outputs have no sub-batch form.
 int dr_gumbel_topk_gather_f32(const float *logits, const float *matches, uint64_t seed, const uint64_t *seed_dev, float tau,
-                              int P, int B, int N, int k, int32_t *idx, float *samples, uint32_t *screen_ws,
+                              int P, int B, int N, int k, int32_t *idx, float *samples,
                               const int32_t *gate_iters, const double *gate_max_iters, int sub, float *race_ws, int race_ready,
                               void *stream) {
   DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither");
   DR_REQUIRE(sub >= 0, "sub-batch size");
-  DR_REQUIRE(!(race_ws && screen_ws), "one workspace: the screened or the one-logarithm form");
   DR_REQUIRE((reinterpret_cast<uintptr_t>(race_ws) & 15) == 0, "workspace alignment");
-  DR_REQUIRE((reinterpret_cast<uintptr_t>(screen_ws) & 15) == 0, "workspace alignment");
   dr::PairGate gate;
   gate.iters = gate_iters;
   gate.max_iters = gate_max_iters;
-  return gumbel_topk_gather_impl(logits, matches, seed, seed_dev, tau, P, B, N, k, idx, samples, gate, stream, screen_ws, sub, race_ws,
-                                 race_ready != 0);
+  return gumbel_topk_gather_impl(logits, matches, seed, seed_dev, tau, P, B, N, k, idx, samples, gate, stream, sub, race_ws, race_ready != 0);
 }
 
 // K1, index sets only, in-kernel noise, with an optional screening workspace ((N + 32) * P words, 16-byte aligned): long rows

@@ -8,7 +8,6 @@
 // wave-cooperative Jacobi eigen-decomposition (F: the smallest one, E: the four smallest) and, for E, runs the five-point pipeline.
 // The ragged inlier sets never leave the device.
 #include <algorithm>
-#include <cstdlib>
 #include "fivepoint_device.hpp"
 #include "ransac_device.hpp"
 
@@ -223,17 +222,6 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                             weights ? weights + (size_t)p * N : nullptr, N, lds, models + (size_t)p * 9, valid + p);
 }
 
-// A/B knob (DRANSAC_REFIT_PAIR_MIN): launches of at least this many pairs take the wave-cooperative final stage
-static inline int refit_pair_finish_min_pairs() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("DRANSAC_REFIT_PAIR_MIN");
-    v = e ? atoi(e) : kRefitPairFinishMinPairs;
-    if (v < 1) v = 1;
-  }
-  return v;
-}
-
 template <typename T>
 int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *models,
                  uint8_t *valid, hipStream_t st) {
@@ -246,7 +234,7 @@ int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const 
       attr_f = true;
     }
     hipLaunchKernelGGL((refit_fundamental_kernel<T>), dim3(P), dim3(kRefT), smem, st, matches, mask, weights, N, models, valid);
-  } else if (P >= refit_pair_finish_min_pairs()) {
+  } else if (P >= kRefitPairFinishMinPairs) {
     const size_t smem_p = std::max(smem, sizeof(double) * (size_t)kNisterPairDoubles);   // the solver's workspace, overlaid
     if (!attr_p) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&refit_essential_kernel<T, true>),
@@ -406,7 +394,7 @@ int local_opt_launch(const T *matches, const T *thr, int P, int N, int fundament
   if (fundamental)
     local_opt_go<T, 0>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
                        best_inliers, max_iters, lo_seen, lo_refits);
-  else if (P >= refit_pair_finish_min_pairs())
+  else if (P >= kRefitPairFinishMinPairs)
     local_opt_go<T, 2>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
                        best_inliers, max_iters, lo_seen, lo_refits);
   else

@@ -4,7 +4,6 @@ torch stream and returns freshly allocated torch tensors; nothing synchronises.
 """
 from __future__ import annotations
 
-import os as _os
 from typing import Optional, Tuple
 
 import torch
@@ -12,22 +11,14 @@ import torch
 from . import _lib as L
 from ._lib import c_int, c_uint64, ptr, stream
 
-# Round 5: the screened register kernel for rows of <= 2048 points (dr_gumbel_topk_gather_f32 with a screen_ws workspace) is built,
-# bit-identical (tests/test_gpu_round5.py) and SLOWER than the unscreened one at the shapes measured -- 199.5 vs 164.1 us at 128
-# pairs x 1024 rows x 2000 points, 57.4 vs 45.2 at 32 pairs, 25.6 vs 18.2 at one pair (scratch/ab_k1_screen.py), in both of its forms
-# (words parked in LDS + one evaluation per lane and round: 200.8; slot-wise wave masks, no parking, no dependent load: 199.5):
-# ~16 of 2000 points pass, but Philox (40 % of the row's instructions) cannot be screened and the unscreened transform is 7 vector
-# instructions per element -- a branch per element slot costs what it saves.  Off unless asked for (screen=True, DRANSAC_SCREEN_SHORT=1).
-SCREEN_SHORT_ROWS = _os.environ.get("DRANSAC_SCREEN_SHORT", "0") == "1"
-
-
 # Round 6: the exponential-race form of the index-only sampler (one logarithm per element; dr_gumbel_topk_gather_f32's race_ws).
-# Same top-k up to the rounding of near-ties; off = the two-logarithm form of rounds 1-5 (A/B runs, tests: DRANSAC_K1_RACE=0).
-K1_RACE = _os.environ.get("DRANSAC_K1_RACE", "1") != "0"
-K1_RACE_SOFT = _os.environ.get("DRANSAC_K1_RACE_SOFT", "1") != "0"   # ... in train mode (SampleGather's fused launch)
-_RACE_MIN = tuple(int(v) for v in _os.environ.get("DRANSAC_K1_RACE_MIN", "32768,32").split(","))   # (rows, pairs) from which it is automatic
-FUSED_SAMPLE_GATHER = _os.environ.get("DRANSAC_FUSED_SAMPLE_GATHER", "1") != "0"   # A/B and tests: off = the two-launch forward / backward of rounds 1-4
-FUSED_MATCH_LOSS = True   # tests / A-B runs: False = the two-pass form of rounds 3-4
+# Same top-k up to the rounding of near-ties; False = the two-logarithm form of rounds 1-5.
+# These are plain constants, not configuration: the tests set the attributes to use the older forms as oracles of the newer ones.
+K1_RACE = True
+K1_RACE_SOFT = True          # ... in train mode (SampleGather's fused launch)
+_RACE_MIN = (32768, 32)      # (rows, pairs) from which the form is chosen automatically (race_form_pays)
+FUSED_SAMPLE_GATHER = True   # False = the two-launch forward / backward of rounds 1-4
+FUSED_MATCH_LOSS = True      # False = the two-pass form of rounds 3-4
 
 
 def _u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -308,7 +299,7 @@ def race_form_pays(P: int, B: int, N: int, tau: float) -> bool:
 
 
 def gumbel_topk_gather(matches: torch.Tensor, logits: torch.Tensor, B: int, k: int, tau: float = 1.0, seed=0, gate=None,
-                       screen: Optional[bool] = None, sub: int = 0, race: Optional[bool] = None, race_ws: Optional[torch.Tensor] = None):
+                       sub: int = 0, race: Optional[bool] = None, race_ws: Optional[torch.Tensor] = None):
     """K1 (index sets only, in-kernel noise) + K2 in one call: matches [P,N,4] f32, logits [P,N] f32 ->
     (idx [P,B,k] int32 ascending, samples [P,B,k,4] = matches[p, idx]).  What test mode asks of sampler + gather
     (ransac.py:58-65); `seed`: int or a DeviceSeed.next() tensor.
@@ -322,16 +313,12 @@ def gumbel_topk_gather(matches: torch.Tensor, logits: torch.Tensor, B: int, k: i
     P, N = logits.shape
     idx = torch.empty((P, B, k), device=logits.device, dtype=torch.int32)
     samples = torch.empty((P, B, k, 4), device=logits.device, dtype=torch.float32)
-    # round 5: rows of <= 2048 points through the SCREENED register kernel (a workspace of thresholds per point: same index sets)
-    want_screen = SCREEN_SHORT_ROWS if screen is None else screen
-    ws = (torch.empty((P, N + 32), device=logits.device, dtype=torch.int32)
-          if want_screen and N <= 2048 and N % 4 == 0 and tau == 1.0 and k <= 5 and B >= 64 else None)
     # race_ws: a workspace dr_ransac_init has already filled for these logits (ransac_init(race_logits=...)): no prologue launch
-    ready = race_ws is not None and ws is None and N <= 2048 and N % 4 == 0 and tau == 1.0
-    want_race = not ready and (race_form_pays(P, B, N, tau) if race is None else race) and ws is None and N <= 2048 and N % 4 == 0 and tau == 1.0
+    ready = race_ws is not None and N <= 2048 and N % 4 == 0 and tau == 1.0
+    want_race = not ready and (race_form_pays(P, B, N, tau) if race is None else race) and N <= 2048 and N % 4 == 0 and tau == 1.0
     rws = race_ws if ready else (torch.empty((P, N + 32), device=logits.device, dtype=torch.float32) if want_race else None)
     L.call("dr_gumbel_topk_gather_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B), c_int(N),
-           c_int(k), ptr(idx), ptr(samples), ptr(ws), *_gate_args(gate), c_int(0 if sub >= B else int(sub)), ptr(rws),
+           c_int(k), ptr(idx), ptr(samples), *_gate_args(gate), c_int(0 if sub >= B else int(sub)), ptr(rws),
            c_int(1 if ready else 0), stream())
     return idx, samples
 

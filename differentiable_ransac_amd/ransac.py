@@ -10,15 +10,12 @@ from __future__ import annotations
 
 import collections
 import math
-import os as _os
 import types
 from typing import Dict
 
 import torch
 
 from . import ops
-
-_FOLD_SETUP = _os.environ.get("DRANSAC_FOLD_SETUP", "1") != "0"   # A/B: 0 = seed launch and result gather as separate nodes (round 5)
 
 
 def adaptive_iteration_number(inlier_number, point_number, sample_size, confidence=0.999, eps=1e-5,
@@ -736,17 +733,16 @@ class BatchedRANSAC(_SeededDriver):
             # (device termination with device seeds: the keys of all batches of the call come out of the set-up launch; one pair in
             #  f32: the state lives in one buffer, which is what the replayed drop-in call hands out)
             draw = self.device_termination and self._dev_seed is not None and n_batches > 1 and gumbels is None
-            fold = _FOLD_SETUP and draw
             # the weights of the one-logarithm sampler, once per call, out of the same launch (when that form pays: ops.race_form_pays)
             race_lg = None
-            if (_FOLD_SETUP and plan and gumbels is None and self.sampling == "gumbel" and not self.weighted and dt == torch.float32
+            if (plan and gumbels is None and self.sampling == "gumbel" and not self.weighted and dt == torch.float32
                     and logits.dtype == torch.float32 and matches.shape[-1] == 4
                     and ops.race_form_pays(P, self.B * plan[0], N, self.tau)):
                 race_lg = logits.contiguous()
             # threshold normalisation (ransac.py:49-53) + per-pair state in one launch
             st, thr = ops.ransac_init(P, N, self.max_iterations, self.threshold, K1 if use_K else None,
-                                      K2 if use_K else None, dev, dt, seeds=(self._dev_seed, n_batches) if fold else None,
-                                      packed=_FOLD_SETUP and self.device_termination and P == 1, race_logits=race_lg)
+                                      K2 if use_K else None, dev, dt, seeds=(self._dev_seed, n_batches) if draw else None,
+                                      packed=self.device_termination and P == 1, race_logits=race_lg)
             self._race_ws = st.race_ws
             # what every round of the call works on (_round, _finish): state, inputs, the masks of the last round (keep_masks) and,
             # for the weighted refit, per pair the row-0 soft weights of the last batch it ran
@@ -757,8 +753,6 @@ class BatchedRANSAC(_SeededDriver):
                 # seen -- and its refit counters (capturable allocations: a replayed call re-fills them)
                 c.lo_seen = torch.full((P, 10), float("nan"), device=dev, dtype=dt)
                 c.lo_refits = torch.zeros(P, device=dev, dtype=torch.int32)
-            if draw and not fold:
-                st.seeds = self._dev_seed.next_block(n_batches)
             if pre is not None and plan and P * self.B * plan[0] >= 65536:
                 # Dispatch order (round 5): a refit block wants a whole SIMD's registers and 38.9 KB of LDS on its CU; once the
                 # sampler's 32 768 light workgroups are in the queue it does not get them until the sampler's grid runs dry

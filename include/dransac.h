@@ -58,8 +58,7 @@ const char *dr_last_error(void);
  *   y_sel == NULL and lse == NULL (both, and then no dense outputs) -> index sets only: what test mode consumes
  *   (`points[samples != 0]`, ransac.py:65); the same idx, without the soft-max statistics of the rows.
  * ------------------------------------------------------------------------------------------ */
-/* seed_dev (every sampler entry; round 6: ONE entry per sampler, the `_dseed` twins of rounds 2-5 are inline wrappers in
- * dransac_compat.h): NULL = the Philox key is `seed`; != NULL = the key is read from DEVICE memory (`*seed_dev`) when the kernel
+/* seed_dev (every sampler entry; round 6: ONE entry per sampler, the `_dseed` twins of rounds 2-5 are gone): NULL = the Philox key is `seed`; != NULL = the key is read from DEVICE memory (`*seed_dev`) when the kernel
  * starts and `seed` is ignored -- for steps captured in a HIP graph, where a by-value seed would be frozen at capture time.  Same
  * kernels, same random numbers for equal keys; a device key serves the in-kernel noise of given logits only (no explicit noise,
  * no dense outputs).  dr_seed_next_n advances such a key on the device. */
@@ -100,22 +99,20 @@ int dr_uniform_sample(uint64_t seed, const uint64_t *seed_dev, int P, int B, int
 /* The per-call key of the batched drivers, advanced on the device (every replay of a captured step then draws fresh hypotheses):
  * state[0] = base, state[1] = number of calls so far -> seeds_out[i] = base * 0x9E3779B97F4A7C15 + calls + i (mod 2^64) for
  * i < n (<= 65 536), calls += n: CONSECUTIVE integers, one per call (ransac.py of this package: `_next_seed`).  n = 1 is the
- * `dr_seed_next` of rounds 2-5 (dransac_compat.h). */
+ * `dr_seed_next` of rounds 2-5. */
 int dr_seed_next_n(uint64_t *state, uint64_t *seeds_out, int n, void *stream);
 
 /* K1 in index-only mode + K2 in one call (test mode: `points[samples != 0]`, ransac.py:58-65, with in-kernel noise):
  * idx [P,B,k] ascending and samples [P,B,k,4] = matches[p, idx] (c = 4; 16-byte aligned buffers).  One launch when the
  * register-resident sampler kernel serves the shape (N % 4 == 0, N <= 2048, tau == 1), sampler + gather launches otherwise.
- * Every argument from screen_ws on is optional (NULL / 0): */
+ * Every argument from gate_iters on is optional (NULL / 0): */
 /* gate_iters / gate_max_iters (a round > 1 of a multi-round test-mode call): pairs with gate_iters[p] >= gate_max_iters[p] are
  * skipped, their rows keep their contents (see dr_ransac_update and the solver entries below) */
-/* screen_ws (optional; (N + 32) * P words, 16-byte aligned): rows of <= 2048 points then take the screened register kernel -- only
- * the points whose Philox word can lift them to logsumexp(logits) - ln(11 + k) are evaluated (same index sets, bit for bit). */
 /* sub (round 6, super-rounds): > 0 = the B rows are ceil(B / sub) consecutive SUB-BATCHES of `sub` rows, the batches the loop of
  * ransac.py:55-144 draws one call after the other: row b gets the noise of row b % sub of a call keyed (seed | *seed_dev) + b / sub
  * (the drivers' per-call seeds are consecutive integers), so ONE launch samples what ceil(B / sub) calls of that loop sample and
  * dr_ransac_update(sub_models = sub * S) walks them in order.  0 = one batch. */
-/* race_ws (round 6; optional, (N + 32) * P floats, 16-byte aligned, not together with screen_ws): rows of <= 2048 points (N % 4 == 0,
+/* race_ws (round 6; optional, (N + 32) * P floats, 16-byte aligned): rows of <= 2048 points (N % 4 == 0,
  * tau == 1) then rank key_n = exp(lmax - logit_n) * log2 u_n instead of logit_n - ln(-ln u_n) -- the exponential-race form of the
  * same top-k (gumbel_sampler.py:30-36), ONE logarithm per element; the per-pair weights are written into the workspace by a
  * prologue launch.  Same index sets up to the rounding of near-ties (measured: tests/test_gpu_round6.py); pairs whose logits are
@@ -124,7 +121,7 @@ int dr_seed_next_n(uint64_t *state, uint64_t *seeds_out, int n, void *stream);
  * a flag word and the key density -1 / (ln 2 sum_n 1 / w_n) per pair: this form selects its k winners on wave compare masks, from
  * a threshold searched on that density (same winners, same order as the candidate list of the other forms). */
 int dr_gumbel_topk_gather_f32(const float *logits, const float *matches, uint64_t seed, const uint64_t *seed_dev, float tau,
-                              int P, int B, int N, int k, int32_t *idx, float *samples, uint32_t *screen_ws,
+                              int P, int B, int N, int k, int32_t *idx, float *samples,
                               const int32_t *gate_iters, const double *gate_max_iters, int sub, float *race_ws, int race_ready,
                               void *stream);
 
@@ -196,7 +193,7 @@ int dr_gather_bwd_f64(const double *matches, const int32_t *idx, const double *y
  *                        flag != 0 reproduces the reference default (svd of cov^T cov, R ~ I, Q9).
  * ------------------------------------------------------------------------------------------ */
 /* The f32 five-point entries carry every option of the path (round 6: the `_hp`, `_path_`, `_gated_` twins of rounds 3-5 are
- * inline wrappers in dransac_compat.h); everything after `valid` is optional (NULL / 0):
+ * gone); everything after `valid` is optional (NULL / 0):
  *   models_f64 (Nister, n = 5): train mode -- the models written BOTH as f32 (what the scoring reads) and as f64 polished to the
  *     f64 tolerance (what dr_solve_nister5_bwd_f32 wants), from one launch: the models of dr_solve_nister5_f64 on the widened
  *     samples without the two conversion passes;
