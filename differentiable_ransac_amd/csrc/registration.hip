@@ -345,6 +345,109 @@ __global__ __launch_bounds__(kSThreads) void rigid_msac_score_kernel(const T *__
   }
 }
 
+// ---- (2b) MAGSAC++ score: the mapping of (2), another per-point term ---------------------------------------------------------------
+// The cutoff distance is read as k sigma_max, k^2 = the 0.99 quantile of chi^2 with 3 degrees of freedom (the residual is a 3-vector),
+// the noise scale uniform in [0, sigma_max].  With s = d2 / thr2, u_k = k^2 / 2, c = exp(-u_k):
+//   weight  w(s) = (exp(-u_k s) - c) / (1 - c)                              for s < 1, else 0
+//   loss    l(s) = (1 - exp(-u_k s) - c u_k s) / (1 - c (1 + u_k))          for s < 1, else 1     (int_0^d x w(x) dx over its value at the cutoff)
+//   score        = sum_n (1 - l(s_n)),  1 - l(s) = A e + B s + C,  e = exp(-u_k s),  A = 1 / D,  B = c u_k / D,  C = -c (1 + u_k) / D,
+//                  D = 1 - c (1 + u_k);   inlier <=> d2 < thr2, the test of (2); a NaN distance contributes nothing.
+// The constants are f64 literals (u_k = 11.344866730144373 / 2 and what follows from it, rounded once to T); the division by thr2 is
+// folded into the factors of d2 once per block.
+constexpr double kMagUk = 5.6724333650721865;          // k^2 / 2
+constexpr double kMagA = 1.0234888000258247;           // 1 / D
+constexpr double kMagB = 0.019968525076541437;         // c u_k / D
+constexpr double kMagC0 = -0.02348880002582457;        // -c (1 + u_k) / D
+constexpr double kMagW1 = 1.0034513564514345;          // 1 / (1 - c)
+constexpr double kMagW0 = -0.0034513564514345773;      // -c / (1 - c)
+constexpr double kLog2e = 1.44269504088896340736;
+
+// exp(-u_k s) as f(d2 x): x = -u_k log2(e) / thr2 for f32, -u_k / thr2 for f64.
+//  f32: __builtin_amdgcn_exp2f = v_exp_f32, 1 ulp (the V_EXP_F32 entry of the CDNA ISA guide); for an inlier the argument lies in
+//       [-8.19, 0], so the result is a normal number and the instruction's flush of denormals plays no part.
+//  f64: exp of the device library (OCML), 1 ulp (the double-precision table of the HIP math API reference).
+__device__ __forceinline__ float magsac_exp(float x) { return __builtin_amdgcn_exp2f(x); }
+__device__ __forceinline__ double magsac_exp(double x) { return exp(x); }
+
+template <typename T>
+struct MagsacTerm {
+  T t2, xs, b;      // thr2, the factor of d2 in the exponential's argument, B / thr2
+  __device__ __forceinline__ explicit MagsacTerm(T thr2) : t2(thr2) {
+    const T inv = T(1) / thr2;
+    xs = (T)(sizeof(T) == 4 ? -kMagUk * kLog2e : -kMagUk) * inv;
+    b = (T)kMagB * inv;
+  }
+  __device__ __forceinline__ bool inlier(T d2) const { return d2 < t2; }                  // (false for NaN)
+  __device__ __forceinline__ T gain(T d2) const {                                         // 1 - l(s) where inlier(d2)
+    return fma(magsac_exp(d2 * xs), (T)kMagA, fma(d2, b, (T)kMagC0));
+  }
+  __device__ __forceinline__ T weight(T d2) const {                                       // w(s) where inlier(d2); >= 0
+    const T w = fma(magsac_exp(d2 * xs), (T)kMagW1, (T)kMagW0);
+    return w > T(0) ? w : T(0);
+  }
+};
+
+template <typename T>
+__global__ __launch_bounds__(kSThreads) void rigid_magsac_score_kernel(const T *__restrict__ pts, const T *__restrict__ models,
+                                                                       const uint8_t *__restrict__ valid, const T *__restrict__ thr2,
+                                                                       int M, int N, T *__restrict__ scores,
+                                                                       int32_t *__restrict__ inliers, PairGate gate) {
+  __shared__ T part[kSThreads / 64][kSModels];
+  __shared__ int pcnt[kSThreads / 64][kSModels];
+  const int p = blockIdx.y, m0 = blockIdx.x * kSModels;
+  if (gate.closed(p)) return;   // a terminated pair of a multi-round call (block-uniform): its scores keep their contents
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int mcount = min(kSModels, M - m0);
+  const T *pt = pts + (size_t)p * N * 6;
+  const T *md = models + ((size_t)p * M + m0) * 16;
+  const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
+  const MagsacTerm<T> term(thr2[p]);
+  if (tid < (kSThreads / 64) * kSModels) {
+    (&part[0][0])[tid] = T(0);
+    (&pcnt[0][0])[tid] = 0;
+  }
+  __syncthreads();
+  for (int c0 = 0; c0 < N; c0 += kSChunk) {
+    const int n0 = c0 + tid * kSPts;
+    T x[kSPts][6];
+    const int nvalid = load_points8(pt, n0, N, x);
+    for (int ml = 0; ml < mcount; ++ml) {
+      if (vd && !vd[ml]) continue;   // (wave-uniform)
+      T m[12];
+#pragma unroll
+      for (int q = 0; q < 12; ++q) m[q] = md[ml * 16 + q];
+      T acc = T(0);
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < kSPts; ++j) {
+        const T d2 = rigid_d2<T>(m, x[j]);
+        const bool in = j < nvalid && term.inlier(d2);
+        acc += in ? term.gain(d2) : T(0);
+        cnt += in ? 1 : 0;
+      }
+      acc = wave_sum(acc);
+      cnt = wave_sum(cnt);
+      if (lane == 0) {
+        part[wv][ml] += acc;
+        pcnt[wv][ml] += cnt;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < mcount) {
+    const bool ok = !vd || vd[tid];
+    T v = T(0);
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kSThreads / 64; ++w) {
+      v += part[w][tid];
+      n += pcnt[w][tid];
+    }
+    scores[(size_t)p * M + m0 + tid] = ok ? v : T(-1);
+    if (inliers) inliers[(size_t)p * M + m0 + tid] = ok ? n : 0;
+  }
+}
+
 // ---- (3) the state step of dr_ransac_update for 4x4 models and 6-column points -------------------------------------------------
 // One block per pair: the block is the only writer of the pair's state (no ping-pong needed).  Terminated pairs return at once.
 constexpr int kRUThreads = 256;
@@ -695,6 +798,147 @@ __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
   }
 }
 
+// ---- (6) IRLS polish of the pair state under the MAGSAC++ loss (BatchedRegistration(scoring = "magsac")): one block per pair ----------
+// The sigma-consensus++ step, up to `iters` times from the pair's (best_model, best_score): the weights w(s_n) of (2b) under the current
+// model; the weighted fit over ALL points (the arithmetic of refit_moments with these weights, kabsch3; f64), the candidate rounded to T;
+// its MAGSAC++ score over all points with the per-point term of (2b); taken only if it scores STRICTLY higher.  The loop ends before a
+// fit when fewer than three points have d2 < thr2 (the points with a non-zero weight), on an invalid or non-finite fit, and on a
+// candidate that does not win.  irls_fits[p] += fits run.  best_mask, best_inliers, iters and max_iters are neither read nor written:
+// the mask stays the RANSAC winner's, as with the single final refit of the MSAC path.
+// Mapping: registration_local_opt_kernel's (a latency kernel: the steps of a pair are serial, each one three block-stride passes over
+// 24 N bytes that stay in L2 -- weighted means, weighted H, score).  The weights are not stored: passes 1 and 2 evaluate the same
+// expression on the same values.  Every thread runs kabsch3 on the block's sums; sums go lane, wave butterfly, the four waves in
+// order -- no atomics, no read-back, a repeated launch gives the same bits.
+template <typename T>
+__global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *__restrict__ pts, const T *__restrict__ thr2, int N,
+                                                                       int iters, T *__restrict__ best_score,
+                                                                       T *__restrict__ best_model, int32_t *__restrict__ irls_fits) {
+  __shared__ double s_red[kRFThreads / 64][9];
+  __shared__ T s_part[kRFThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const T *pt = pts + (size_t)p * N * 6;
+  T bs = best_score[p];
+  T m[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) m[q] = best_model[(size_t)p * 16 + q];
+  __syncthreads();      // (every thread has read the state: thread 0 writes it below)
+  const MagsacTerm<T> term(thr2[p]);
+  bool taken = false;
+  int fits = 0;
+  for (int it = 0; it < iters; ++it) {
+    // pass 1: weighted sums of p and q, the weight sum and the number of weighted points (entries 0..5, 6, 7; entry 8 unused)
+    double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int n = tid; n < N; n += kRFThreads) {
+      T x[6];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
+      const T d2 = rigid_d2<T>(m, x);
+      if (!term.inlier(d2)) continue;
+      const double w = (double)term.weight(d2);
+#pragma unroll
+      for (int d = 0; d < 6; ++d) a[d] += w * (double)x[d];
+      a[6] += w;
+      a[7] += 1.0;
+    }
+    block_sum_f64<9>(a, s_red);
+    if (!(a[7] >= 3.0)) break;      // (block-uniform, like every exit below: all threads hold the same sums)
+    const double W = a[6], rw = 1.0 / a[6];
+    double c[6], h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int d = 0; d < 6; ++d) c[d] = a[d] * rw;
+    // pass 2: H = sum w (p - c0)(q - c1)^T
+    for (int n = tid; n < N; n += kRFThreads) {
+      T x[6];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
+      const T d2 = rigid_d2<T>(m, x);
+      if (!term.inlier(d2)) continue;
+      const double w = (double)term.weight(d2);
+      double dp[3], dq[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        dp[d] = w * ((double)x[d] - c[d]);
+        dq[d] = (double)x[3 + d] - c[3 + d];
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) h[3 * i + j] += dp[i] * dq[j];
+    }
+    block_sum_f64<9>(h, s_red);
+    double H[3][3], R[3][3], t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
+    bool ok = kabsch3(H, c, W > 0.0, R, t);
+    ++fits;
+    T cm[12];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) cm[4 * i + j] = (T)R[i][j];
+      cm[4 * i + 3] = (T)t[i];
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) ok = ok && is_finite(cm[q]);
+    if (!ok) break;
+    // pass 3: the candidate's score
+    T acc = T(0);
+    for (int n = tid; n < N; n += kRFThreads) {
+      T x[6];
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
+      const T d2 = rigid_d2<T>(cm, x);
+      acc += term.inlier(d2) ? term.gain(d2) : T(0);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) s_part[wv] = acc;
+    __syncthreads();
+    T sc = s_part[0];
+#pragma unroll
+    for (int w = 1; w < kRFThreads / 64; ++w) sc += s_part[w];
+    __syncthreads();    // (s_part is reused by the next step)
+    if (!(sc > bs)) break;
+    bs = sc;
+    taken = true;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) m[q] = cm[q];
+  }
+  if (tid == 0) {
+    if (taken) {
+      best_score[p] = bs;
+#pragma unroll
+      for (int q = 0; q < 12; ++q) best_model[(size_t)p * 16 + q] = m[q];
+      best_model[(size_t)p * 16 + 12] = best_model[(size_t)p * 16 + 13] = best_model[(size_t)p * 16 + 14] = T(0);
+      best_model[(size_t)p * 16 + 15] = T(1);
+    }
+    irls_fits[p] += fits;
+  }
+}
+
+template <typename T>
+int rigid_magsac_score_entry(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
+                             int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
+  PairGate gate;
+  gate.iters = gate_iters;
+  gate.max_iters = gate_max_iters;
+  hipLaunchKernelGGL((rigid_magsac_score_kernel<T>), dim3((M + kSModels - 1) / kSModels, P), dim3(kSThreads), 0, (hipStream_t)stream,
+                     matches, models, valid, thr2, M, N, scores, inliers, gate);
+  return check_launch("rigid_magsac_score_kernel");
+}
+
+template <typename T>
+int registration_irls_entry(const T *matches, const T *thr2, int P, int N, int irls_iters, T *best_score, T *best_model,
+                            int32_t *irls_fits, void *stream) {
+  DR_REQUIRE(matches && thr2 && best_score && best_model && irls_fits, "null pointer");
+  DR_REQUIRE(P > 0 && N > 0, "bad sizes");
+  DR_REQUIRE(irls_iters >= 1, "irls_iters must be at least 1");
+  hipLaunchKernelGGL((registration_irls_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, thr2, N, irls_iters,
+                     best_score, best_model, irls_fits);
+  return check_launch("registration_irls_kernel");
+}
+
 template <typename T>
 int registration_local_opt_entry(const T *matches, const T *thr2, int P, int N, int lo, int lo_iters, double confidence, double eps,
                                  int max_iterations, T *best_score, T *best_model, uint8_t *best_mask, int32_t *best_inliers,
@@ -826,6 +1070,28 @@ int dr_rigid_msac_score_f64(const double *matches, const double *models, const u
                             void *stream) {
   DR_RIGID_MSAC_CHECKS;
   return dr::rigid_msac_score_entry<double>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
+}
+
+int dr_rigid_magsac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
+                              float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                              void *stream) {
+  DR_RIGID_MSAC_CHECKS;
+  return dr::rigid_magsac_score_entry<float>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
+}
+int dr_rigid_magsac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
+                              int N, double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                              void *stream) {
+  DR_RIGID_MSAC_CHECKS;
+  return dr::rigid_magsac_score_entry<double>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
+}
+
+int dr_registration_irls_f32(const float *matches, const float *thr2, int P, int N, int irls_iters, float *best_score,
+                             float *best_model, int32_t *irls_fits, void *stream) {
+  return dr::registration_irls_entry<float>(matches, thr2, P, N, irls_iters, best_score, best_model, irls_fits, stream);
+}
+int dr_registration_irls_f64(const double *matches, const double *thr2, int P, int N, int irls_iters, double *best_score,
+                             double *best_model, int32_t *irls_fits, void *stream) {
+  return dr::registration_irls_entry<double>(matches, thr2, P, N, irls_iters, best_score, best_model, irls_fits, stream);
 }
 
 #define DR_REGISTRATION_UPDATE_CHECKS                                                                                      \

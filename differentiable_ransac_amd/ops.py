@@ -692,6 +692,22 @@ def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, val
     return scores, inliers
 
 
+def rigid_magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
+                       want_inliers: bool = True, gate=None, thr2: Optional[torch.Tensor] = None):
+    """dr_rigid_magsac_score: rigid_msac_score's arguments and results with the MAGSAC++ score.  `threshold` is the cutoff DISTANCE,
+    read as k sigma_max (k^2 = 11.344866730144373, the 0.99 quantile of chi^2 with 3 degrees of freedom).  With s = d2 / threshold^2,
+    u_k = k^2 / 2, c = exp(-u_k): scores [P,M] = sum_n (1 - l(s_n)), l(s) = (1 - exp(-u_k s) - c u_k s) / (1 - c (1 + u_k)) for s < 1,
+    else 1; inliers = #{d2_n < threshold^2}.  Invalid slots score -1.  Bit-repeatable; gate as in rigid_msac_score."""
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
+    scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
+    inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
+    L.call(f"dr_rigid_magsac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
+    return scores, inliers
+
+
 class RegistrationState:
     """Per-pair state of a BatchedRegistration call, on the device: best_score [P], best_model [P,4,4] (identity), best_mask [P,N],
     best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch (capturable)."""
@@ -741,6 +757,21 @@ def registration_local_optimize(state: RegistrationState, matches, thr2, lo: int
            c_int(int(lo)), c_int(int(lo_iters)), L.c_double(confidence), L.c_double(eps), c_int(int(mi)), ptr(state.best_score),
            ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.max_iters),
            ptr(lo_seen), ptr(lo_refits), stream())
+
+
+def registration_irls(state: RegistrationState, matches, thr2, irls_iters: int, irls_fits: torch.Tensor) -> None:
+    """dr_registration_irls: the IRLS polish under the MAGSAC++ loss, in place on state.best_model / state.best_score: up to irls_iters
+    times the weights w(s) = (exp(-u_k s) - c) / (1 - c) under the current model, the weighted Kabsch fit over all points and the
+    candidate's MAGSAC++ score, taken only where it is strictly higher.  thr2 [P] = threshold^2 (thr2_tensor); irls_fits [P] int32
+    grows by the fits run.  Mask, inlier count and counters of the state are left alone.  One launch, no synchronisation."""
+    tensors = (matches, thr2, irls_fits, state.best_score, state.best_model)
+    if any(t is None or not t.is_cuda for t in tensors):
+        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    P, N, _ = matches.shape
+    if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
+        raise L.DransacError("registration_irls: irls_fits must be [P] int32")
+    L.call(f"dr_registration_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), c_int(P), c_int(N),
+           c_int(int(irls_iters)), ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
 
 
 def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):

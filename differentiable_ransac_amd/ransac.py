@@ -955,6 +955,12 @@ class BatchedRegistration(_SeededDriver):
     and stop bound follow, so the read-back after the round sees the tightened bound, and the final `refit` starts from LO's mask.
     The result gains lo_refits [P], the fits run per pair.  lo = 0 is the path without it: no launch, no allocation, no key.
 
+    scoring = "magsac" (test mode, lo = 0 only): every round is scored by dr_rigid_magsac_score, the MAGSAC++ loss with `threshold`
+    as the cutoff distance k sigma_max (ops.rigid_magsac_score states the formulas); mask, inlier count and the adaptive stop keep
+    using d2 < threshold^2.  With `refit` and irls_iters > 0 the final stage is dr_registration_irls: up to `irls_iters` re-weighted
+    Kabsch fits over all points, each kept only where it scores strictly higher; the mask stays the RANSAC winner's.  The result gains
+    irls_fits [P].  scoring = "msac" is the path without it: no other launch, allocation or key.
+
     train = True: every round runs (no adaptive stop, as in the reference's train branches), each one ops.SampleGather (the
     straight-through samples of the Gumbel top-k) followed by ops.kabsch, and the call returns dict(models [P, rounds * B, 4, 4],
     keep [P, rounds * B] = the fit's validity) with autograd to the logits, and to `matches` where they require it.  The pose loss on
@@ -962,10 +968,18 @@ class BatchedRegistration(_SeededDriver):
     back to the host."""
 
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
-                 num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64):
+                 num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64, scoring="msac", irls_iters=10):
         _check_lo(lo, lo_iters)
         if lo and train:
             raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
+        if scoring not in ("msac", "magsac"):
+            raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
+        if scoring == "magsac" and lo:
+            raise ValueError("scoring='magsac' with lo != 0 is refused: dr_registration_local_opt scores its candidates with MSAC")
+        if scoring == "magsac" and train:
+            raise ValueError("scoring='magsac' with train=True is refused: train mode scores nothing")
+        if int(irls_iters) < 0:
+            raise ValueError(f"irls_iters must be at least 0, got {irls_iters!r}")
         if not 3 <= int(num_samples) <= 8:
             raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
         if int(max_iterations) < 1:
@@ -984,6 +998,8 @@ class BatchedRegistration(_SeededDriver):
         self.train = bool(train)
         self.lo = int(lo)
         self.lo_iters = int(lo_iters)
+        self.scoring = scoring
+        self.irls_iters = int(irls_iters)
         self._device_termination = False
 
     @property
@@ -1025,12 +1041,14 @@ class BatchedRegistration(_SeededDriver):
             if self.lo:
                 lo_seen = torch.full((P, 17), float("nan"), device=matches.device, dtype=matches.dtype)
                 lo_refits = torch.zeros(P, device=matches.device, dtype=torch.int32)
+            magsac = self.scoring == "magsac"
+            score_fn = ops.rigid_magsac_score if magsac else ops.rigid_msac_score
             for r in range(rounds):
                 gate = st if (self._device_termination and r > 0) else None
                 g = None if gumbels is None else gumbels[r]
                 idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
                 models, valid = ops.kabsch_gather(matches, idx)
-                scores, _ = ops.rigid_msac_score(matches, models, None, valid, want_inliers=False, gate=gate, thr2=thr2)
+                scores, _ = score_fn(matches, models, None, valid, want_inliers=False, gate=gate, thr2=thr2)
                 ops.registration_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
                 if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
                     ops.registration_local_optimize(st, matches, thr2, self.lo, self.lo_iters, self.confidence, self.eps,
@@ -1038,6 +1056,12 @@ class BatchedRegistration(_SeededDriver):
                 if not self._device_termination and r + 1 < rounds and not bool((st.iters.double() < st.max_iters).any()):
                     break
             model, score = st.best_model, st.best_score
+            if magsac:      # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
+                irls_fits = torch.zeros(P, device=matches.device, dtype=torch.int32)
+                if self.refit and self.irls_iters > 0:
+                    ops.registration_irls(st, matches, thr2, self.irls_iters, irls_fits)
+                return dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters,
+                            irls_fits=irls_fits)
             if self.refit:
                 cand, cvalid = ops.refit_rigid(matches, st.best_mask)
                 cscore, _ = ops.rigid_msac_score(matches, cand.unsqueeze(1), None, cvalid.unsqueeze(1), want_inliers=False, thr2=thr2)

@@ -364,6 +364,20 @@ int dr_ransac3d_update_f64(const double *pts, const double *models, const uint8_
  *     or non-finite fit, on a candidate that loses, and on an accepted mask equal to the previous one.  Then max_iters =
  *     min(max_iterations, adaptive_iteration_number(best_inliers, N, 3)) in f64, the snapshot is stored, and lo_refits[p] (NULL = not
  *     counted) grows by the number of fits run.  DR_EINVAL: a null required pointer, P or N < 1, lo not 1 or 2, lo_iters < 1.
+ *   dr_rigid_magsac_score   the MAGSAC++ score in dr_rigid_msac_score's place: same arguments, same mapping, same rules (invalid slots
+ *     -1 / 0 inliers, gate, fixed reduction order), another per-point term.  The cutoff distance is read as k sigma_max with
+ *     k^2 = 11.344866730144373, the 0.99 quantile of chi^2 with 3 degrees of freedom, the noise scale uniform in [0, sigma_max].  With
+ *     s = d2 / thr2, u_k = k^2 / 2, c = exp(-u_k):  weight w(s) = (exp(-u_k s) - c) / (1 - c) for s < 1, else 0;  loss
+ *     l(s) = (1 - exp(-u_k s) - c u_k s) / (1 - c (1 + u_k)) for s < 1, else 1 (int_0^d x w(x) dx over its value at the cutoff);
+ *     scores = sum_n (1 - l(s_n)) in [0, N], inliers = #{d2_n < thr2} as above.  A non-finite d2 contributes nothing.  The
+ *     exponential is v_exp_f32 (1 ulp) in f32 and the device library's exp (1 ulp) in f64.
+ *   dr_registration_irls    the IRLS polish of the pair state under that loss (BatchedRegistration(scoring = "magsac")), one launch,
+ *     no read-back: from (best_model, best_score), up to irls_iters times, the weights w(s_n) under the current model, dr_refit_rigid's
+ *     weighted fit over all points, the candidate's MAGSAC++ score over all points; taken only if score > best_score (strict).  The
+ *     loop ends before a fit when fewer than three points have d2 < thr2 (a non-zero weight), on an invalid or non-finite fit and on a
+ *     candidate that does not win.  best_score and best_model [P,16] are rewritten where a candidate won; irls_fits [P] grows by the
+ *     fits run.  The mask, the inlier count, iters and max_iters are not arguments: they stay the RANSAC winner's.  DR_EINVAL: a null
+ *     pointer, P or N < 1, irls_iters < 1.
  *
  * Train mode (ops.kabsch, ops.weighted_kabsch, BatchedRegistration(train=True)).  With weights w >= 0 (1 when NULL), W = sum w:
  * c0 = sum w p / W, c1 = sum w q / W, H = sum w (p - c0)(q - c1)^T.  The backward entries recompute this forward in f64 from their
@@ -408,6 +422,16 @@ int dr_registration_local_opt_f32(const float *matches, const float *thr2, int P
 int dr_registration_local_opt_f64(const double *matches, const double *thr2, int P, int N, int lo, int lo_iters, double confidence,
                                   double eps, int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
                                   int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits, void *stream);
+int dr_rigid_magsac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
+                              float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                              void *stream);
+int dr_rigid_magsac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
+                              int N, double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
+                              void *stream);
+int dr_registration_irls_f32(const float *matches, const float *thr2, int P, int N, int irls_iters, float *best_score,
+                             float *best_model, int32_t *irls_fits, void *stream);
+int dr_registration_irls_f64(const double *matches, const double *thr2, int P, int N, int irls_iters, double *best_score,
+                             double *best_model, int32_t *irls_fits, void *stream);
 int dr_kabsch_f32(const float *samples, const float *weights, int Bt, int k, float *models, uint8_t *valid, void *stream);
 int dr_kabsch_f64(const double *samples, const double *weights, int Bt, int k, double *models, uint8_t *valid, void *stream);
 int dr_kabsch_bwd_f32(const float *samples, const float *weights, const float *grad_models, int Bt, int k, float *grad_samples,
