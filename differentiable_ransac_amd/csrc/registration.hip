@@ -158,21 +158,39 @@ __device__ __forceinline__ bool kabsch3_bwd(const double (&H)[3][3], const doubl
   return ok;
 }
 
+// ---- the two accumulations of every fit here, f64: one row x = (p, q) of weight w into the weighted sums a[0..5] and the weight sum,
+// and, once the means c = (c0, c1) are known, into H = sum w (p - c0)(q - c1)^T.  The per-lane fit of a sample (1) and the per-block
+// fit of a selection (4) share this text, so they round alike; unit weights give the bits of the plain sums (x 1.0 is exact)
+template <typename T>
+__device__ __forceinline__ void moment_sums(const T *x, double w, double *a, double &W) {
+#pragma unroll
+  for (int d = 0; d < 6; ++d) a[d] += w * (double)x[d];
+  W += w;
+}
+
+template <typename T>
+__device__ __forceinline__ void moment_outer(const T *x, double w, const double (&c)[6], double (&H)[3][3]) {
+  double dp[3], dq[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    dp[d] = w * ((double)x[d] - c[d]);
+    dq[d] = (double)x[3 + d] - c[3 + d];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) H[i][j] += dp[i] * dq[j];
+}
+
 // ---- (1) minimal samples -> rigid models: one lane = one sample of 3 <= k <= 8 rows -----------------------------------------
-// the weighted means c = (c0, c1), H = sum w (p - c0)(q - c1)^T and W = sum w of one sample, f64: rowp(r) -> the six values of row r,
-// wt(r) -> its weight.  Unit weights give the bits of the plain sums (x 1.0 is exact, and W = k)
+// the weighted means c = (c0, c1), H and W = sum w of one sample: rowp(r) -> the six values of row r, wt(r) -> its weight (W = k
+// without weights)
 template <typename RowFn, typename WFn>
 __device__ __forceinline__ double sample_moments(int k, RowFn rowp, WFn wt, double (&c)[6], double (&H)[3][3]) {
   double W = 0.0;
 #pragma unroll
   for (int d = 0; d < 6; ++d) c[d] = 0.0;
-  for (int r = 0; r < k; ++r) {
-    const auto *x = rowp(r);
-    const double w = wt(r);
-#pragma unroll
-    for (int d = 0; d < 6; ++d) c[d] += w * (double)x[d];
-    W += w;
-  }
+  for (int r = 0; r < k; ++r) moment_sums(rowp(r), wt(r), c, W);
   const double rn = 1.0 / W;
 #pragma unroll
   for (int d = 0; d < 6; ++d) c[d] *= rn;
@@ -180,20 +198,7 @@ __device__ __forceinline__ double sample_moments(int k, RowFn rowp, WFn wt, doub
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
-  for (int r = 0; r < k; ++r) {
-    const auto *x = rowp(r);
-    const double w = wt(r);
-    double dp[3], dq[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      dp[d] = w * ((double)x[d] - c[d]);
-      dq[d] = (double)x[3 + d] - c[3 + d];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) H[i][j] += dp[i] * dq[j];
-  }
+  for (int r = 0; r < k; ++r) moment_outer(rowp(r), wt(r), c, H);
   return W;
 }
 
@@ -275,77 +280,29 @@ __global__ __launch_bounds__(64) void kabsch_bwd_kernel(const T *__restrict__ sa
   }
 }
 
-// ---- (2) MSAC score and inlier count of every model against every point ----------------------------------------------------
+// ---- (2) score and inlier count of every model against every point, under a per-point term ----------------------------------------
 // The mapping of rigid_residual_kernel: a lane owns 8 consecutive points in registers, the model is wave-uniform.  One block =
 // (pair, tile of kSModels models) and walks ALL the pair's points chunk by chunk, so the sum of a (pair, model) is reduced in one
 // fixed order -- lane, wave butterfly, chunk after chunk into the wave's LDS slot, the four slots in order -- and a repeated launch
 // gives the same bits (scores are compared strictly downstream).  No [P,M,N] tensor, no floating-point atomics.
+// A term is built from thr2 once per block and has inlier(d2) and contrib(d2), the point's part of the score: 0 where it adds nothing,
+// so 0 for a NaN distance too, and 0 for a slot past the end of the row (`live` false; the gate joins the term's own predicate).
+// Only the tile kernel has such slots; block_score walks existing rows and relies on the default live = true.
 constexpr int kSThreads = 256, kSPts = 8, kSChunk = kSThreads * kSPts, kSModels = 16;
 
+// MSAC: max(0, 1 - d2 / thr2).  The contribution and the count keep their own predicates (sv > 0 and d2 < thr2 can differ by a rounding)
 template <typename T>
-__global__ __launch_bounds__(kSThreads) void rigid_msac_score_kernel(const T *__restrict__ pts, const T *__restrict__ models,
-                                                                     const uint8_t *__restrict__ valid, const T *__restrict__ thr2,
-                                                                     int M, int N, T *__restrict__ scores,
-                                                                     int32_t *__restrict__ inliers, PairGate gate) {
-  __shared__ T part[kSThreads / 64][kSModels];
-  __shared__ int pcnt[kSThreads / 64][kSModels];
-  const int p = blockIdx.y, m0 = blockIdx.x * kSModels;
-  if (gate.closed(p)) return;   // a terminated pair of a multi-round call (block-uniform): its scores keep their contents
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int mcount = min(kSModels, M - m0);
-  const T *pt = pts + (size_t)p * N * 6;
-  const T *md = models + ((size_t)p * M + m0) * 16;
-  const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
-  const T t2 = thr2[p];
-  const T inv = T(1) / t2;
-  if (tid < (kSThreads / 64) * kSModels) {
-    (&part[0][0])[tid] = T(0);
-    (&pcnt[0][0])[tid] = 0;
+struct MsacTerm {
+  T t2, inv;
+  __device__ __forceinline__ explicit MsacTerm(T thr2) : t2(thr2), inv(T(1) / thr2) {}
+  __device__ __forceinline__ bool inlier(T d2) const { return d2 < t2; }                  // (false for NaN)
+  __device__ __forceinline__ T contrib(T d2, bool live = true) const {
+    const T sv = T(1) - d2 * inv;
+    return (live && sv > T(0)) ? sv : T(0);
   }
-  __syncthreads();
-  for (int c0 = 0; c0 < N; c0 += kSChunk) {
-    const int n0 = c0 + tid * kSPts;
-    T x[kSPts][6];
-    const int nvalid = load_points8(pt, n0, N, x);
-    for (int ml = 0; ml < mcount; ++ml) {
-      if (vd && !vd[ml]) continue;   // (wave-uniform)
-      T m[12];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) m[q] = md[ml * 16 + q];
-      T acc = T(0);
-      int cnt = 0;
-#pragma unroll
-      for (int j = 0; j < kSPts; ++j) {
-        const T d2 = rigid_d2<T>(m, x[j]);
-        const T sv = T(1) - d2 * inv;
-        const bool live = j < nvalid;
-        acc += (live && sv > T(0)) ? sv : T(0);      // a NaN distance contributes nothing
-        cnt += (live && d2 < t2) ? 1 : 0;
-      }
-      acc = wave_sum(acc);
-      cnt = wave_sum(cnt);
-      if (lane == 0) {
-        part[wv][ml] += acc;
-        pcnt[wv][ml] += cnt;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < mcount) {
-    const bool ok = !vd || vd[tid];
-    T v = T(0);
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < kSThreads / 64; ++w) {
-      v += part[w][tid];
-      n += pcnt[w][tid];
-    }
-    scores[(size_t)p * M + m0 + tid] = ok ? v : T(-1);
-    if (inliers) inliers[(size_t)p * M + m0 + tid] = ok ? n : 0;
-  }
-}
+};
 
-// ---- (2b) MAGSAC++ score: the mapping of (2), another per-point term ---------------------------------------------------------------
+// ---- (2b) the MAGSAC++ term --------------------------------------------------------------------------------------------------------
 // The cutoff distance is read as k sigma_max, k^2 = the 0.99 quantile of chi^2 with 3 degrees of freedom (the residual is a 3-vector),
 // the noise scale uniform in [0, sigma_max].  With s = d2 / thr2, u_k = k^2 / 2, c = exp(-u_k):
 //   weight  w(s) = (exp(-u_k s) - c) / (1 - c)                              for s < 1, else 0
@@ -381,17 +338,19 @@ struct MagsacTerm {
   __device__ __forceinline__ T gain(T d2) const {                                         // 1 - l(s) where inlier(d2)
     return fma(magsac_exp(d2 * xs), (T)kMagA, fma(d2, b, (T)kMagC0));
   }
+  __device__ __forceinline__ T contrib(T d2, bool live = true) const { return (live && inlier(d2)) ? gain(d2) : T(0); }
   __device__ __forceinline__ T weight(T d2) const {                                       // w(s) where inlier(d2); >= 0
     const T w = fma(magsac_exp(d2 * xs), (T)kMagW1, (T)kMagW0);
     return w > T(0) ? w : T(0);
   }
 };
 
-template <typename T>
-__global__ __launch_bounds__(kSThreads) void rigid_magsac_score_kernel(const T *__restrict__ pts, const T *__restrict__ models,
-                                                                       const uint8_t *__restrict__ valid, const T *__restrict__ thr2,
-                                                                       int M, int N, T *__restrict__ scores,
-                                                                       int32_t *__restrict__ inliers, PairGate gate) {
+// the kernel of (2) for either term
+template <typename T, typename Term>
+__global__ __launch_bounds__(kSThreads) void rigid_score_kernel(const T *__restrict__ pts, const T *__restrict__ models,
+                                                                const uint8_t *__restrict__ valid, const T *__restrict__ thr2, int M,
+                                                                int N, T *__restrict__ scores, int32_t *__restrict__ inliers,
+                                                                PairGate gate) {
   __shared__ T part[kSThreads / 64][kSModels];
   __shared__ int pcnt[kSThreads / 64][kSModels];
   const int p = blockIdx.y, m0 = blockIdx.x * kSModels;
@@ -401,7 +360,7 @@ __global__ __launch_bounds__(kSThreads) void rigid_magsac_score_kernel(const T *
   const T *pt = pts + (size_t)p * N * 6;
   const T *md = models + ((size_t)p * M + m0) * 16;
   const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
-  const MagsacTerm<T> term(thr2[p]);
+  const Term term(thr2[p]);
   if (tid < (kSThreads / 64) * kSModels) {
     (&part[0][0])[tid] = T(0);
     (&pcnt[0][0])[tid] = 0;
@@ -421,9 +380,9 @@ __global__ __launch_bounds__(kSThreads) void rigid_magsac_score_kernel(const T *
 #pragma unroll
       for (int j = 0; j < kSPts; ++j) {
         const T d2 = rigid_d2<T>(m, x[j]);
-        const bool in = j < nvalid && term.inlier(d2);
-        acc += in ? term.gain(d2) : T(0);
-        cnt += in ? 1 : 0;
+        const bool live = j < nvalid;
+        acc += term.contrib(d2, live);
+        cnt += (live && term.inlier(d2)) ? 1 : 0;
       }
       acc = wave_sum(acc);
       cnt = wave_sum(cnt);
@@ -506,7 +465,7 @@ __global__ __launch_bounds__(kRUThreads) void registration_update_kernel(
 constexpr int kRFThreads = 256;
 
 template <int K>
-__device__ __forceinline__ void block_sum_f64(double (&v)[K], double (*s)[K]) {   // s: shared [kRFThreads / 64][K]
+__device__ __forceinline__ void block_sum_f64(double *v, double (*s)[K]) {   // v: K sums, s: shared [kRFThreads / 64][K]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < K; ++i) {
@@ -524,20 +483,28 @@ __device__ __forceinline__ void block_sum_f64(double (&v)[K], double (*s)[K]) { 
   __syncthreads();   // (the buffer may be reused)
 }
 
-// the two passes of the fit, by the whole block: -> c = (c0, c1), h = H row-major, rows = the selected rows, the weight sum (every
-// thread holds all of them afterwards)
 template <typename T>
-__device__ __forceinline__ double refit_moments(const T *__restrict__ pt, const uint8_t *__restrict__ mk, const T *__restrict__ wt,
-                                                int N, double (*s_red)[9], double (&c)[6], double (&h)[9], double &rows) {
+__device__ __forceinline__ void load_row(const T *pt, int n, T (&x)[6]) {
+#pragma unroll
+  for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
+}
+
+// the two passes of the fit, by the whole block: -> c = (c0, c1), H, rows = the rows that took part, the weight sum (every thread
+// holds all of them afterwards).  `row` says which rows take part, in two steps, so that a row is dropped as early as its kind allows:
+// row.present(n) before anything of the row is loaded, then row.load(n, x, w), which delivers the six values and the weight and may
+// still drop the row.  Both passes ask, so it must answer alike.  Thread n owns rows n, n + 256, ...
+template <typename T, typename RowFn>
+__device__ __forceinline__ double block_moments(int N, RowFn row, double (*s_red)[9], double (&c)[6], double (&H)[3][3],
+                                                double &rows) {
   const int tid = threadIdx.x;
   // pass 1: weighted sums of p and q, the weight sum and the row count (entries 0..5, 6, 7; entry 8 unused)
   double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int n = tid; n < N; n += kRFThreads) {
-    if (mk && !mk[n]) continue;
-    const double w = wt ? (double)wt[n] : 1.0;
-#pragma unroll
-    for (int d = 0; d < 6; ++d) a[d] += w * (double)pt[(size_t)n * 6 + d];
-    a[6] += w;
+    if (!row.present(n)) continue;
+    T x[6];
+    double w;
+    if (!row.load(n, x, w)) continue;
+    moment_sums(x, w, a, a[6]);
     a[7] += 1.0;
   }
   block_sum_f64<9>(a, s_red);
@@ -547,24 +514,33 @@ __device__ __forceinline__ double refit_moments(const T *__restrict__ pt, const 
   for (int d = 0; d < 6; ++d) c[d] = a[d] * rw;
   // pass 2: H = sum w (p - c0)(q - c1)^T
 #pragma unroll
-  for (int i = 0; i < 9; ++i) h[i] = 0.0;
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) H[i][j] = 0.0;
   for (int n = tid; n < N; n += kRFThreads) {
-    if (mk && !mk[n]) continue;
-    const double w = wt ? (double)wt[n] : 1.0;
-    double dp[3], dq[3];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-      dp[d] = w * ((double)pt[(size_t)n * 6 + d] - c[d]);
-      dq[d] = (double)pt[(size_t)n * 6 + 3 + d] - c[3 + d];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) h[3 * i + j] += dp[i] * dq[j];
+    if (!row.present(n)) continue;
+    T x[6];
+    double w;
+    if (!row.load(n, x, w)) continue;
+    moment_outer(x, w, c, H);
   }
-  block_sum_f64<9>(h, s_red);
+  block_sum_f64<9>(&H[0][0], s_red);
   return a[6];
 }
+
+// the rows of (4) and (5): the mask byte first -- a row it drops is not loaded --, then the row, then the optional weight tensor
+template <typename T>
+struct MaskedRows {
+  const T *pt;
+  const uint8_t *mk;      // nullptr = every row
+  const T *wt;            // nullptr = unit weights
+  __device__ __forceinline__ bool present(int n) const { return !mk || mk[n]; }
+  __device__ __forceinline__ bool load(int n, T (&x)[6], double &w) const {
+    load_row(pt, n, x);
+    w = wt ? (double)wt[n] : 1.0;
+    return true;
+  }
+};
 
 template <typename T>
 __global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__restrict__ pts, const uint8_t *__restrict__ mask,
@@ -572,15 +548,11 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_kernel(const T *__rest
                                                                  uint8_t *__restrict__ valid) {
   __shared__ double s_red[kRFThreads / 64][9];
   const int p = blockIdx.x;
-  double c[6], h[9], rows;
-  const double W = refit_moments(pts + (size_t)p * N * 6, mask ? mask + (size_t)p * N : nullptr,
-                                 weights ? weights + (size_t)p * N : nullptr, N, s_red, c, h, rows);
+  const MaskedRows<T> sel{pts + (size_t)p * N * 6, mask ? mask + (size_t)p * N : nullptr, weights ? weights + (size_t)p * N : nullptr};
+  double c[6], H[3][3], rows;
+  const double W = block_moments<T>(N, sel, s_red, c, H, rows);
   if (threadIdx.x != 0) return;
-  double H[3][3], R[3][3], t[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
+  double R[3][3], t[3];
   valid[p] = kabsch3(H, c, rows >= 3.0 && W > 0.0, R, t);
   store_rigid_model(model + (size_t)p * 16, R, t);
 }
@@ -600,18 +572,15 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_bwd_kernel(const T *__
   const T *pt = pts + (size_t)p * N * 6;
   const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
   const T *wt = weights ? weights + (size_t)p * N : nullptr;
-  double c[6], h[9], rows;
-  const double W = refit_moments(pt, mk, wt, N, s_red, c, h, rows);
+  double c[6], H[3][3], rows;
+  const double W = block_moments<T>(N, MaskedRows<T>{pt, mk, wt}, s_red, c, H, rows);
   if (tid == 0) {
     const T *gm = grad_model + (size_t)p * 16;
-    double H[3][3], R[3][3], t[3], gR[3][3], gt[3], gH[3][3], gc0[3], gc1[3];
+    double R[3][3], t[3], gR[3][3], gt[3], gH[3][3], gc0[3], gc1[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        H[i][j] = h[3 * i + j];
-        gR[i][j] = (double)gm[4 * i + j];
-      }
+      for (int j = 0; j < 3; ++j) gR[i][j] = (double)gm[4 * i + j];
       gt[i] = (double)gm[4 * i + 3];
     }
     const bool fwd = kabsch3(H, c, rows >= 3.0 && W > 0.0, R, t);
@@ -670,18 +639,54 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_bwd_kernel(const T *__
   }
 }
 
+// ---- the score of ONE model over all N points of a pair, by the whole block, with the per-point term of (2): -> the score in every
+// thread, and through `count` (with its slots s_cnt) the number of inliers; a caller that passes neither pays nothing for the count.
+// Sums: lane, wave butterfly, the four waves in order.  Two barriers; s_part / s_cnt are free again on return.
+template <typename T, typename Term>
+__device__ __forceinline__ T block_score(const T *pt, int N, const T (&m)[12], const Term &term, T *s_part, int *s_cnt = nullptr,
+                                         int *count = nullptr) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  T acc = T(0);
+  int cnt = 0;
+  for (int n = tid; n < N; n += kRFThreads) {
+    T x[6];
+    load_row(pt, n, x);
+    const T d2 = rigid_d2<T>(m, x);
+    acc += term.contrib(d2);
+    cnt += term.inlier(d2) ? 1 : 0;
+  }
+  acc = wave_sum(acc);
+  if (count) cnt = wave_sum(cnt);
+  if (lane == 0) {
+    s_part[wv] = acc;
+    if (count) s_cnt[wv] = cnt;
+  }
+  __syncthreads();
+  T sc = s_part[0];
+#pragma unroll
+  for (int w = 1; w < kRFThreads / 64; ++w) sc += s_part[w];
+  if (count) {
+    cnt = s_cnt[0];
+#pragma unroll
+    for (int w = 1; w < kRFThreads / 64; ++w) cnt += s_cnt[w];
+    *count = cnt;
+  }
+  __syncthreads();
+  return sc;
+}
+
 // ---- (5) local optimisation of the pair state (BatchedRegistration(lo = 1 / 2)): one block per pair, right behind (3) ----------
 // A pair whose (best_score, best_model) still equals its snapshot lo_seen[p] bit for bit -- only (3) replaces them, and the snapshot
 // starts as NaN -- returns at once, whether or not it has terminated.  Otherwise, up to `iters` times: the fit of (4) over the best
-// mask (refit_moments + kabsch3, f64), the candidate rounded to T as (4) stores it, its MSAC score and inlier count over all N points
-// with the per-point terms of (2) and (3); the candidate is taken only if it scores STRICTLY higher ((3) and the driver's final refit
+// mask (block_moments + kabsch3, f64), the candidate rounded to T as (4) stores it, its MSAC score and inlier count over all N points
+// (block_score with the term of (2), the test of (3)); the candidate is taken only if it scores STRICTLY higher ((3) and the driver's final refit
 // use > too), and then a further pass rewrites the mask and compares it with the old one.  The loop ends on an invalid or non-finite
 // fit, on a candidate that loses, and on an accepted mask that equals the previous one (the next fit would see the same rows).  Then
 // max_iters from the inlier count, the snapshot, and lo_refits[p] += fits run.  Below three inliers only the snapshot is stored.
 // Mapping (a latency kernel: a pair's fits are serial, each one four block-stride passes over 24 N bytes that stay in L2):
 //  - the points are NOT staged in LDS: one path for every N (a staged copy needs a size limit and a second path behind it), and a
 //    pass has 6 ceil(N / 256) independent loads per thread in flight, so it costs about one L2 round trip;
-//  - the candidate's mask is not held anywhere before acceptance: the accepting pass evaluates rigid_d2 < thr2 again, the same
+//  - the candidate's mask is not held anywhere before acceptance: the accepting pass evaluates term.inlier(rigid_d2) again, the same
 //    expression on the same values as the counting pass, so the count is the written mask's count, for every N;
 //  - every thread runs kabsch3 on the block's sums (same inputs, same instructions, same bits): no broadcast and no barrier
 //    between the fit and the score pass.  Thread n owns points n, n + 256, ... in every pass, mask bytes included.
@@ -709,19 +714,14 @@ __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
   int inl = best_inliers[p];
   __syncthreads();      // (every thread has read the state and the snapshot: thread 0 writes them below)
   if (same) return;     // block-uniform: no replacement since the last visit
-  const T t2 = thr2[p];
-  const T inv = T(1) / t2;
+  const MsacTerm<T> term(thr2[p]);
+  const MaskedRows<T> sel{pt, mk, nullptr};
   const bool run = inl >= 3;
   bool taken = false;
   int fits = 0;
   for (int it = 0; run && it < iters; ++it) {
-    double c[6], h[9], rows;
-    const double W = refit_moments(pt, mk, static_cast<const T *>(nullptr), N, s_red, c, h, rows);
-    double H[3][3], R[3][3], t[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
+    double c[6], H[3][3], rows, R[3][3], t[3];
+    const double W = block_moments<T>(N, sel, s_red, c, H, rows);
     bool ok = kabsch3(H, c, rows >= 3.0 && W > 0.0, R, t);
     ++fits;
     T m[12];
@@ -734,46 +734,21 @@ __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
 #pragma unroll
     for (int q = 0; q < 12; ++q) ok = ok && is_finite(m[q]);
     if (!ok) break;     // (block-uniform, like every exit below: all threads hold the same sums)
-    T acc = T(0);
-    int cnt = 0;
-    for (int n = tid; n < N; n += kRFThreads) {
-      T x[6];
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
-      const T d2 = rigid_d2<T>(m, x);
-      const T sv = T(1) - d2 * inv;
-      acc += sv > T(0) ? sv : T(0);      // a NaN distance contributes nothing
-      cnt += d2 < t2 ? 1 : 0;
-    }
-    acc = wave_sum(acc);
-    cnt = wave_sum(cnt);
-    if (lane == 0) {
-      s_part[wv] = acc;
-      s_cnt[wv] = cnt;
-    }
-    __syncthreads();
-    T sc = s_part[0];
-    cnt = s_cnt[0];
-#pragma unroll
-    for (int w = 1; w < kRFThreads / 64; ++w) {
-      sc += s_part[w];
-      cnt += s_cnt[w];
-    }
-    __syncthreads();    // (s_part / s_cnt are reused below and by the next fit)
+    int cnt;
+    const T sc = block_score(pt, N, m, term, s_part, s_cnt, &cnt);
     if (!(sc > bs)) break;
     int chg = 0;
     for (int n = tid; n < N; n += kRFThreads) {
       T x[6];
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
-      const uint8_t in = rigid_d2<T>(m, x) < t2;
+      load_row(pt, n, x);
+      const uint8_t in = term.inlier(rigid_d2<T>(m, x));
       chg |= in != mk[n];
       mk[n] = in;
     }
     chg = wave_sum(chg);
     if (lane == 0) s_cnt[wv] = chg;
     __syncthreads();
-    const bool changed = (s_cnt[0] | s_cnt[1] | s_cnt[2] | s_cnt[3]) != 0;   // (next written behind refit_moments' barriers)
+    const bool changed = (s_cnt[0] | s_cnt[1] | s_cnt[2] | s_cnt[3]) != 0;   // (next written behind block_moments' barriers)
     bs = sc;
     inl = cnt;
     taken = true;
@@ -800,22 +775,40 @@ __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
 
 // ---- (6) IRLS polish of the pair state under the MAGSAC++ loss (BatchedRegistration(scoring = "magsac")): one block per pair ----------
 // The sigma-consensus++ step, up to `iters` times from the pair's (best_model, best_score): the weights w(s_n) of (2b) under the current
-// model; the weighted fit over ALL points (the arithmetic of refit_moments with these weights, kabsch3; f64), the candidate rounded to T;
-// its MAGSAC++ score over all points with the per-point term of (2b); taken only if it scores STRICTLY higher.  The loop ends before a
-// fit when fewer than three points have d2 < thr2 (the points with a non-zero weight), on an invalid or non-finite fit, and on a
-// candidate that does not win.  irls_fits[p] += fits run.  best_mask, best_inliers, iters and max_iters are neither read nor written:
+// model; the weighted fit over ALL points (block_moments with these weights, kabsch3; f64), the candidate rounded to T;
+// its MAGSAC++ score over all points (block_score with the term of (2b)); taken only if it scores STRICTLY higher.  The loop ends before
+// a fit when fewer than three points have d2 < thr2 (the points with a non-zero weight), on an invalid or non-finite fit, and on a
+// candidate that does not win.  (That first exit is taken on the row count block_moments returns, so its second pass has run by then:
+// one more pass over the points, over means that are inf / NaN when the weight sum is 0 -- nothing of it is used or stored.)
+// irls_fits[p] += fits run.  best_mask, best_inliers, iters and max_iters are neither read nor written:
 // the mask stays the RANSAC winner's, as with the single final refit of the MSAC path.
 // Mapping: registration_local_opt_kernel's (a latency kernel: the steps of a pair are serial, each one three block-stride passes over
 // 24 N bytes that stay in L2 -- weighted means, weighted H, score).  The weights are not stored: passes 1 and 2 evaluate the same
 // expression on the same values.  Every thread runs kabsch3 on the block's sums; sums go lane, wave butterfly, the four waves in
 // order -- no atomics, no read-back, a repeated launch gives the same bits.
+// the rows of a step: those inside the cutoff under the current model (read through the reference at every pass), with the weight of (2b)
+template <typename T>
+struct CutoffRows {
+  const T *pt;
+  const T (&m)[12];
+  const MagsacTerm<T> &term;
+  __device__ __forceinline__ bool present(int) const { return true; }
+  __device__ __forceinline__ bool load(int n, T (&x)[6], double &w) const {
+    load_row(pt, n, x);
+    const T d2 = rigid_d2<T>(m, x);
+    if (!term.inlier(d2)) return false;
+    w = (double)term.weight(d2);
+    return true;
+  }
+};
+
 template <typename T>
 __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *__restrict__ pts, const T *__restrict__ thr2, int N,
                                                                        int iters, T *__restrict__ best_score,
                                                                        T *__restrict__ best_model, int32_t *__restrict__ irls_fits) {
   __shared__ double s_red[kRFThreads / 64][9];
   __shared__ T s_part[kRFThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int p = blockIdx.x;
   const T *pt = pts + (size_t)p * N * 6;
   T bs = best_score[p];
   T m[12];
@@ -823,54 +816,13 @@ __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *
   for (int q = 0; q < 12; ++q) m[q] = best_model[(size_t)p * 16 + q];
   __syncthreads();      // (every thread has read the state: thread 0 writes it below)
   const MagsacTerm<T> term(thr2[p]);
+  const CutoffRows<T> weighted{pt, m, term};
   bool taken = false;
   int fits = 0;
   for (int it = 0; it < iters; ++it) {
-    // pass 1: weighted sums of p and q, the weight sum and the number of weighted points (entries 0..5, 6, 7; entry 8 unused)
-    double a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int n = tid; n < N; n += kRFThreads) {
-      T x[6];
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
-      const T d2 = rigid_d2<T>(m, x);
-      if (!term.inlier(d2)) continue;
-      const double w = (double)term.weight(d2);
-#pragma unroll
-      for (int d = 0; d < 6; ++d) a[d] += w * (double)x[d];
-      a[6] += w;
-      a[7] += 1.0;
-    }
-    block_sum_f64<9>(a, s_red);
-    if (!(a[7] >= 3.0)) break;      // (block-uniform, like every exit below: all threads hold the same sums)
-    const double W = a[6], rw = 1.0 / a[6];
-    double c[6], h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int d = 0; d < 6; ++d) c[d] = a[d] * rw;
-    // pass 2: H = sum w (p - c0)(q - c1)^T
-    for (int n = tid; n < N; n += kRFThreads) {
-      T x[6];
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
-      const T d2 = rigid_d2<T>(m, x);
-      if (!term.inlier(d2)) continue;
-      const double w = (double)term.weight(d2);
-      double dp[3], dq[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) {
-        dp[d] = w * ((double)x[d] - c[d]);
-        dq[d] = (double)x[3 + d] - c[3 + d];
-      }
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) h[3 * i + j] += dp[i] * dq[j];
-    }
-    block_sum_f64<9>(h, s_red);
-    double H[3][3], R[3][3], t[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) H[i][j] = h[3 * i + j];
+    double c[6], H[3][3], rows, R[3][3], t[3];
+    const double W = block_moments<T>(N, weighted, s_red, c, H, rows);
+    if (!(rows >= 3.0)) break;      // (block-uniform, like every exit below: all threads hold the same sums)
     bool ok = kabsch3(H, c, W > 0.0, R, t);
     ++fits;
     T cm[12];
@@ -883,29 +835,14 @@ __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *
 #pragma unroll
     for (int q = 0; q < 12; ++q) ok = ok && is_finite(cm[q]);
     if (!ok) break;
-    // pass 3: the candidate's score
-    T acc = T(0);
-    for (int n = tid; n < N; n += kRFThreads) {
-      T x[6];
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[d] = pt[(size_t)n * 6 + d];
-      const T d2 = rigid_d2<T>(cm, x);
-      acc += term.inlier(d2) ? term.gain(d2) : T(0);
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) s_part[wv] = acc;
-    __syncthreads();
-    T sc = s_part[0];
-#pragma unroll
-    for (int w = 1; w < kRFThreads / 64; ++w) sc += s_part[w];
-    __syncthreads();    // (s_part is reused by the next step)
+    const T sc = block_score(pt, N, cm, term, s_part);
     if (!(sc > bs)) break;
     bs = sc;
     taken = true;
 #pragma unroll
     for (int q = 0; q < 12; ++q) m[q] = cm[q];
   }
-  if (tid == 0) {
+  if (threadIdx.x == 0) {
     if (taken) {
       best_score[p] = bs;
 #pragma unroll
@@ -917,245 +854,130 @@ __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *
   }
 }
 
-template <typename T>
-int rigid_magsac_score_entry(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
-                             int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
+// one launch on the caller's stream -> status
+template <typename... Params, typename... Args>
+int launch(const char *name, void (*kernel)(Params...), dim3 grid, int threads, void *stream, Args... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, (hipStream_t)stream, args...);
+  return check_launch(name);
+}
+
+template <typename T, typename Term>
+int launch_rigid_score(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
+                       int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
   PairGate gate;
   gate.iters = gate_iters;
   gate.max_iters = gate_max_iters;
-  hipLaunchKernelGGL((rigid_magsac_score_kernel<T>), dim3((M + kSModels - 1) / kSModels, P), dim3(kSThreads), 0, (hipStream_t)stream,
-                     matches, models, valid, thr2, M, N, scores, inliers, gate);
-  return check_launch("rigid_magsac_score_kernel");
-}
-
-template <typename T>
-int registration_irls_entry(const T *matches, const T *thr2, int P, int N, int irls_iters, T *best_score, T *best_model,
-                            int32_t *irls_fits, void *stream) {
-  DR_REQUIRE(matches && thr2 && best_score && best_model && irls_fits, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0, "bad sizes");
-  DR_REQUIRE(irls_iters >= 1, "irls_iters must be at least 1");
-  hipLaunchKernelGGL((registration_irls_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, thr2, N, irls_iters,
-                     best_score, best_model, irls_fits);
-  return check_launch("registration_irls_kernel");
-}
-
-template <typename T>
-int registration_local_opt_entry(const T *matches, const T *thr2, int P, int N, int lo, int lo_iters, double confidence, double eps,
-                                 int max_iterations, T *best_score, T *best_model, uint8_t *best_mask, int32_t *best_inliers,
-                                 double *max_iters, T *lo_seen, int32_t *lo_refits, void *stream) {
-  DR_REQUIRE(matches && thr2 && best_score && best_model && best_mask && best_inliers && max_iters && lo_seen, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0 && max_iterations > 0, "bad sizes");
-  DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");
-  DR_REQUIRE(lo_iters >= 1, "lo_iters must be at least 1");
-  hipLaunchKernelGGL((registration_local_opt_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, thr2, N,
-                     lo == 1 ? 1 : lo_iters, confidence, eps, max_iterations, best_score, best_model, best_mask, best_inliers,
-                     max_iters, lo_seen, lo_refits);
-  return check_launch("registration_local_opt_kernel");
-}
-
-template <typename T>
-int kabsch_gather_entry(const T *matches, const int32_t *idx, int P, int B, int N, int k, T *models, uint8_t *valid, void *stream) {
-  const int Bt = P * B;
-  hipLaunchKernelGGL((kabsch_gather_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, matches, idx, Bt, B, N, k,
-                     models, valid);
-  return check_launch("kabsch_gather_kernel");
-}
-
-template <typename T>
-int kabsch_entry(const T *samples, const T *weights, int Bt, int k, T *models, uint8_t *valid, void *stream) {
-  hipLaunchKernelGGL((kabsch_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, weights, Bt, k, models,
-                     valid);
-  return check_launch("kabsch_kernel");
-}
-
-template <typename T>
-int kabsch_bwd_entry(const T *samples, const T *weights, const T *grad_models, int Bt, int k, T *grad_samples, T *grad_weights,
-                     void *stream) {
-  hipLaunchKernelGGL((kabsch_bwd_kernel<T>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, weights, grad_models,
-                     Bt, k, grad_samples, grad_weights);
-  return check_launch("kabsch_bwd_kernel");
-}
-
-template <typename T>
-int rigid_msac_score_entry(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
-                           int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
-  PairGate gate;
-  gate.iters = gate_iters;
-  gate.max_iters = gate_max_iters;
-  hipLaunchKernelGGL((rigid_msac_score_kernel<T>), dim3((M + kSModels - 1) / kSModels, P), dim3(kSThreads), 0, (hipStream_t)stream,
-                     matches, models, valid, thr2, M, N, scores, inliers, gate);
-  return check_launch("rigid_msac_score_kernel");
-}
-
-template <typename T>
-int registration_update_entry(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P, int M,
-                              int N, int B, double confidence, double eps, int max_iterations, T *best_score, T *best_model,
-                              uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters, void *stream) {
-  hipLaunchKernelGGL((registration_update_kernel<T>), dim3(P), dim3(kRUThreads), 0, (hipStream_t)stream, matches, models, valid,
-                     scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask, best_inliers, iters,
-                     max_iters);
-  return check_launch("registration_update_kernel");
-}
-
-template <typename T>
-int refit_rigid_entry(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *model, uint8_t *valid, void *stream) {
-  hipLaunchKernelGGL((refit_rigid_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, mask, weights, N, model,
-                     valid);
-  return check_launch("refit_rigid_kernel");
-}
-
-template <typename T>
-int refit_rigid_bwd_entry(const T *matches, const uint8_t *mask, const T *weights, const T *grad_model, int P, int N, T *grad_matches,
-                          T *grad_weights, void *stream) {
-  hipLaunchKernelGGL((refit_rigid_bwd_kernel<T>), dim3(P), dim3(kRFThreads), 0, (hipStream_t)stream, matches, mask, weights,
-                     grad_model, N, grad_matches, grad_weights);
-  return check_launch("refit_rigid_bwd_kernel");
+  return launch("rigid_score_kernel", rigid_score_kernel<T, Term>, dim3((M + kSModels - 1) / kSModels, P), kSThreads, stream, matches,
+                models, valid, thr2, M, N, scores, inliers, gate);
 }
 
 }  // namespace dr
 
+// ---- the C entries: every op is written once, DR_F32_F64 makes its _f32 and _f64 symbols; an op's argument checks stand at the top of
+// its body (DR_REQUIRE names the symbol in the message), the launch below them
+#define DR_F32_F64(OP) OP(f32, float) OP(f64, double)
+
 extern "C" {
 
-#define DR_KABSCH_GATHER_CHECKS                                                                                           \
-  DR_REQUIRE(matches && idx && models && valid, "null pointer");                                                          \
-  DR_REQUIRE(P > 0 && B > 0 && N > 0 && k >= 3 && k <= 8 && (long)P * B < (1l << 31), "need P, B, N > 0 and 3 <= k <= 8 rows per sample")
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_kabsch_gather_##sfx(const T *matches, const int32_t *idx, int P, int B, int N, int k, T *models, uint8_t *valid,           \
+                             void *stream) {                                                                                        \
+    DR_REQUIRE(matches && idx && models && valid, "null pointer");                                                                  \
+    DR_REQUIRE(P > 0 && B > 0 && N > 0 && k >= 3 && k <= 8 && (long)P * B < (1l << 31),                                             \
+               "need P, B, N > 0 and 3 <= k <= 8 rows per sample");                                                                 \
+    return dr::launch("kabsch_gather_kernel", dr::kabsch_gather_kernel<T>, dim3((P * B + 63) / 64), 64, stream, matches, idx, P * B, \
+                      B, N, k, models, valid);                                                                                      \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
-int dr_kabsch_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, int k, float *models, uint8_t *valid,
-                         void *stream) {
-  DR_KABSCH_GATHER_CHECKS;
-  return dr::kabsch_gather_entry<float>(matches, idx, P, B, N, k, models, valid, stream);
-}
-int dr_kabsch_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, int k, double *models, uint8_t *valid,
-                         void *stream) {
-  DR_KABSCH_GATHER_CHECKS;
-  return dr::kabsch_gather_entry<double>(matches, idx, P, B, N, k, models, valid, stream);
-}
-
-#define DR_KABSCH_CHECKS(out0, out1)                                                                       \
-  DR_REQUIRE(samples && out0 && out1, "null pointer");                                                      \
+#define DR_KABSCH_CHECKS(out0, out1)                   \
+  DR_REQUIRE(samples && out0 && out1, "null pointer"); \
   DR_REQUIRE(Bt > 0 && k >= 3 && k <= 8, "need Bt > 0 and 3 <= k <= 8 rows per sample")
 
-int dr_kabsch_f32(const float *samples, const float *weights, int Bt, int k, float *models, uint8_t *valid, void *stream) {
-  DR_KABSCH_CHECKS(models, valid);
-  return dr::kabsch_entry<float>(samples, weights, Bt, k, models, valid, stream);
-}
-int dr_kabsch_f64(const double *samples, const double *weights, int Bt, int k, double *models, uint8_t *valid, void *stream) {
-  DR_KABSCH_CHECKS(models, valid);
-  return dr::kabsch_entry<double>(samples, weights, Bt, k, models, valid, stream);
-}
-int dr_kabsch_bwd_f32(const float *samples, const float *weights, const float *grad_models, int Bt, int k, float *grad_samples,
-                      float *grad_weights, void *stream) {
-  DR_KABSCH_CHECKS(grad_models, grad_samples);
-  return dr::kabsch_bwd_entry<float>(samples, weights, grad_models, Bt, k, grad_samples, grad_weights, stream);
-}
-int dr_kabsch_bwd_f64(const double *samples, const double *weights, const double *grad_models, int Bt, int k, double *grad_samples,
-                      double *grad_weights, void *stream) {
-  DR_KABSCH_CHECKS(grad_models, grad_samples);
-  return dr::kabsch_bwd_entry<double>(samples, weights, grad_models, Bt, k, grad_samples, grad_weights, stream);
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_kabsch_##sfx(const T *samples, const T *weights, int Bt, int k, T *models, uint8_t *valid, void *stream) {                 \
+    DR_KABSCH_CHECKS(models, valid);                                                                                                \
+    return dr::launch("kabsch_kernel", dr::kabsch_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, weights, Bt, k, models,     \
+                      valid);                                                                                                       \
+  }                                                                                                                                 \
+  int dr_kabsch_bwd_##sfx(const T *samples, const T *weights, const T *grad_models, int Bt, int k, T *grad_samples,                 \
+                          T *grad_weights, void *stream) {                                                                          \
+    DR_KABSCH_CHECKS(grad_models, grad_samples);                                                                                    \
+    return dr::launch("kabsch_bwd_kernel", dr::kabsch_bwd_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, weights,            \
+                      grad_models, Bt, k, grad_samples, grad_weights);                                                              \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
-#define DR_RIGID_MSAC_CHECKS                                                                              \
-  DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                        \
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                         \
-  DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither")
+#define DR_RIGID_SCORE(term, Term, sfx, T)                                                                                         \
+  int dr_rigid_##term##_score_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N,    \
+                                    T *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,           \
+                                    void *stream) {                                                                                 \
+    DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                                                \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither");                           \
+    return dr::launch_rigid_score<T, dr::Term<T>>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters,               \
+                                                  gate_max_iters, stream);                                                          \
+  }
+#define DR_OP(sfx, T) DR_RIGID_SCORE(msac, MsacTerm, sfx, T) DR_RIGID_SCORE(magsac, MagsacTerm, sfx, T)
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
-int dr_rigid_msac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
-                            float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
-                            void *stream) {
-  DR_RIGID_MSAC_CHECKS;
-  return dr::rigid_msac_score_entry<float>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
-}
-int dr_rigid_msac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
-                            int N, double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
-                            void *stream) {
-  DR_RIGID_MSAC_CHECKS;
-  return dr::rigid_msac_score_entry<double>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_registration_update_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P,  \
+                                   int M, int N, int B, double confidence, double eps, int max_iterations, T *best_score,           \
+                                   T *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters,     \
+                                   void *stream) {                                                                                  \
+    DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters,  \
+               "null pointer");                                                                                                     \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes");                                                \
+    return dr::launch("registration_update_kernel", dr::registration_update_kernel<T>, dim3(P), dr::kRUThreads, stream, matches,    \
+                      models, valid, scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask,     \
+                      best_inliers, iters, max_iters);                                                                              \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
-int dr_rigid_magsac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
-                              float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
-                              void *stream) {
-  DR_RIGID_MSAC_CHECKS;
-  return dr::rigid_magsac_score_entry<float>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
-}
-int dr_rigid_magsac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
-                              int N, double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters,
-                              void *stream) {
-  DR_RIGID_MSAC_CHECKS;
-  return dr::rigid_magsac_score_entry<double>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, gate_max_iters, stream);
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_refit_rigid_##sfx(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *model, uint8_t *valid,         \
+                           void *stream) {                                                                                          \
+    DR_REQUIRE(matches && model && valid, "null pointer");                                                                          \
+    DR_REQUIRE(P > 0 && N > 0, "bad sizes");                                                                                        \
+    return dr::launch("refit_rigid_kernel", dr::refit_rigid_kernel<T>, dim3(P), dr::kRFThreads, stream, matches, mask, weights, N,  \
+                      model, valid);                                                                                                \
+  }                                                                                                                                 \
+  int dr_refit_rigid_bwd_##sfx(const T *matches, const uint8_t *mask, const T *weights, const T *grad_model, int P, int N,          \
+                               T *grad_matches, T *grad_weights, void *stream) {                                                    \
+    DR_REQUIRE(matches && grad_model && (grad_matches || grad_weights), "null pointer");                                            \
+    DR_REQUIRE(P > 0 && N > 0 && (long)N * 6 < (1l << 31), "bad sizes");                                                            \
+    return dr::launch("refit_rigid_bwd_kernel", dr::refit_rigid_bwd_kernel<T>, dim3(P), dr::kRFThreads, stream, matches, mask,      \
+                      weights, grad_model, N, grad_matches, grad_weights);                                                          \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
-int dr_registration_irls_f32(const float *matches, const float *thr2, int P, int N, int irls_iters, float *best_score,
-                             float *best_model, int32_t *irls_fits, void *stream) {
-  return dr::registration_irls_entry<float>(matches, thr2, P, N, irls_iters, best_score, best_model, irls_fits, stream);
-}
-int dr_registration_irls_f64(const double *matches, const double *thr2, int P, int N, int irls_iters, double *best_score,
-                             double *best_model, int32_t *irls_fits, void *stream) {
-  return dr::registration_irls_entry<double>(matches, thr2, P, N, irls_iters, best_score, best_model, irls_fits, stream);
-}
-
-#define DR_REGISTRATION_UPDATE_CHECKS                                                                                      \
-  DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters, \
-             "null pointer");                                                                                              \
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes")
-
-int dr_registration_update_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores,
-                               const float *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
-                               float *best_score, float *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
-                               double *max_iters, void *stream) {
-  DR_REGISTRATION_UPDATE_CHECKS;
-  return dr::registration_update_entry<float>(matches, models, valid, scores, thr2, P, M, N, B, confidence, eps, max_iterations,
-                                              best_score, best_model, best_mask, best_inliers, iters, max_iters, stream);
-}
-int dr_registration_update_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores,
-                               const double *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
-                               double *best_score, double *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
-                               double *max_iters, void *stream) {
-  DR_REGISTRATION_UPDATE_CHECKS;
-  return dr::registration_update_entry<double>(matches, models, valid, scores, thr2, P, M, N, B, confidence, eps, max_iterations,
-                                               best_score, best_model, best_mask, best_inliers, iters, max_iters, stream);
-}
-
-int dr_refit_rigid_f32(const float *matches, const uint8_t *mask, const float *weights, int P, int N, float *model, uint8_t *valid,
-                       void *stream) {
-  DR_REQUIRE(matches && model && valid, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0, "bad sizes");
-  return dr::refit_rigid_entry<float>(matches, mask, weights, P, N, model, valid, stream);
-}
-int dr_refit_rigid_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model, uint8_t *valid,
-                       void *stream) {
-  DR_REQUIRE(matches && model && valid, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0, "bad sizes");
-  return dr::refit_rigid_entry<double>(matches, mask, weights, P, N, model, valid, stream);
-}
-
-
-int dr_registration_local_opt_f32(const float *matches, const float *thr2, int P, int N, int lo, int lo_iters, double confidence,
-                                  double eps, int max_iterations, float *best_score, float *best_model, uint8_t *best_mask,
-                                  int32_t *best_inliers, double *max_iters, float *lo_seen, int32_t *lo_refits, void *stream) {
-  return dr::registration_local_opt_entry<float>(matches, thr2, P, N, lo, lo_iters, confidence, eps, max_iterations, best_score,
-                                                 best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, stream);
-}
-int dr_registration_local_opt_f64(const double *matches, const double *thr2, int P, int N, int lo, int lo_iters, double confidence,
-                                  double eps, int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
-                                  int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits, void *stream) {
-  return dr::registration_local_opt_entry<double>(matches, thr2, P, N, lo, lo_iters, confidence, eps, max_iterations, best_score,
-                                                  best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, stream);
-}
-
-#define DR_REFIT_RIGID_BWD_CHECKS                                                                    \
-  DR_REQUIRE(matches && grad_model && (grad_matches || grad_weights), "null pointer");               \
-  DR_REQUIRE(P > 0 && N > 0 && (long)N * 6 < (1l << 31), "bad sizes")
-
-int dr_refit_rigid_bwd_f32(const float *matches, const uint8_t *mask, const float *weights, const float *grad_model, int P, int N,
-                           float *grad_matches, float *grad_weights, void *stream) {
-  DR_REFIT_RIGID_BWD_CHECKS;
-  return dr::refit_rigid_bwd_entry<float>(matches, mask, weights, grad_model, P, N, grad_matches, grad_weights, stream);
-}
-int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const double *weights, const double *grad_model, int P, int N,
-                           double *grad_matches, double *grad_weights, void *stream) {
-  DR_REFIT_RIGID_BWD_CHECKS;
-  return dr::refit_rigid_bwd_entry<double>(matches, mask, weights, grad_model, P, N, grad_matches, grad_weights, stream);
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_registration_local_opt_##sfx(const T *matches, const T *thr2, int P, int N, int lo, int lo_iters, double confidence,       \
+                                      double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask,             \
+                                      int32_t *best_inliers, double *max_iters, T *lo_seen, int32_t *lo_refits, void *stream) {     \
+    DR_REQUIRE(matches && thr2 && best_score && best_model && best_mask && best_inliers && max_iters && lo_seen, "null pointer");   \
+    DR_REQUIRE(P > 0 && N > 0 && max_iterations > 0, "bad sizes");                                                                  \
+    DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");                                              \
+    DR_REQUIRE(lo_iters >= 1, "lo_iters must be at least 1");                                                                       \
+    return dr::launch("registration_local_opt_kernel", dr::registration_local_opt_kernel<T>, dim3(P), dr::kRFThreads, stream,       \
+                      matches, thr2, N, lo == 1 ? 1 : lo_iters, confidence, eps, max_iterations, best_score, best_model, best_mask, \
+                      best_inliers, max_iters, lo_seen, lo_refits);                                                                 \
+  }                                                                                                                                 \
+  int dr_registration_irls_##sfx(const T *matches, const T *thr2, int P, int N, int irls_iters, T *best_score, T *best_model,       \
+                                 int32_t *irls_fits, void *stream) {                                                                \
+    DR_REQUIRE(matches && thr2 && best_score && best_model && irls_fits, "null pointer");                                           \
+    DR_REQUIRE(P > 0 && N > 0, "bad sizes");                                                                                        \
+    DR_REQUIRE(irls_iters >= 1, "irls_iters must be at least 1");                                                                   \
+    return dr::launch("registration_irls_kernel", dr::registration_irls_kernel<T>, dim3(P), dr::kRFThreads, stream, matches, thr2,  \
+                      N, irls_iters, best_score, best_model, irls_fits);                                                            \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"

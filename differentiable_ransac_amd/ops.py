@@ -677,19 +677,24 @@ def kabsch_gather(matches: torch.Tensor, idx: torch.Tensor):
     return models, valid
 
 
-def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
-                     want_inliers: bool = True, gate=None, thr2: Optional[torch.Tensor] = None):
-    """dr_rigid_msac_score: matches [P,N,6], models [P,M,4,4], threshold = inlier DISTANCE (float or [P]) ->
-    (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None).  Invalid slots score
-    -1.  Bit-repeatable (fixed reduction order).  gate = RegistrationState: the blocks of terminated pairs return at once."""
+def _rigid_score(term: str, matches, models, threshold, valid, want_inliers, gate, thr2):
+    """dr_rigid_{msac,magsac}_score: one kernel, two per-point terms"""
     P, N, _ = matches.shape
     M = models.shape[1]
     thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_rigid_msac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+    L.call(f"dr_rigid_{term}_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
     return scores, inliers
+
+
+def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
+                     want_inliers: bool = True, gate=None, thr2: Optional[torch.Tensor] = None):
+    """dr_rigid_msac_score: matches [P,N,6], models [P,M,4,4], threshold = inlier DISTANCE (float or [P]) ->
+    (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None).  Invalid slots score
+    -1.  Bit-repeatable (fixed reduction order).  gate = RegistrationState: the blocks of terminated pairs return at once."""
+    return _rigid_score("msac", matches, models, threshold, valid, want_inliers, gate, thr2)
 
 
 def rigid_magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
@@ -698,14 +703,7 @@ def rigid_magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, v
     read as k sigma_max (k^2 = 11.344866730144373, the 0.99 quantile of chi^2 with 3 degrees of freedom).  With s = d2 / threshold^2,
     u_k = k^2 / 2, c = exp(-u_k): scores [P,M] = sum_n (1 - l(s_n)), l(s) = (1 - exp(-u_k s) - c u_k s) / (1 - c (1 + u_k)) for s < 1,
     else 1; inliers = #{d2_n < threshold^2}.  Invalid slots score -1.  Bit-repeatable; gate as in rigid_msac_score."""
-    P, N, _ = matches.shape
-    M = models.shape[1]
-    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
-    scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
-    inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_rigid_magsac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
-    return scores, inliers
+    return _rigid_score("magsac", matches, models, threshold, valid, want_inliers, gate, thr2)
 
 
 class RegistrationState:
