@@ -220,6 +220,95 @@ __global__ __launch_bounds__(64) void kabsch_gather_kernel(const T *__restrict__
   store_rigid_model(models + (size_t)s * 16, R, t);
 }
 
+// ---- (1b) the same behind a rigidity test of the sample (BatchedRegistration(edge_similarity = ...)) ------------------------------
+// A rigid motion keeps distances, so a sample of inliers has |p_i - p_j| ~ |q_i - q_j| for every pair of its rows.  With
+// sigma = edge_similarity^2 an edge passes iff a2 >= sigma b2 && b2 >= sigma a2, a2 = |p_i - p_j|^2, b2 = |q_i - q_j|^2 in f64 from
+// the stored values (Open3D's CorrespondenceCheckerBasedOnEdgeLength on squares; false for a NaN, true for two coincident rows, which
+// kabsch3 then rejects); a sample passes iff all k (k - 1) / 2 edges do.  A sample with an index out of range is what (1) makes of it
+// (identity, valid = 0) and is not counted; one that fails is the identity with valid = 0 and counts once in rejected[pair] (integer
+// atomics: the same total on every launch); one that passes goes through (1)'s sample_moments and kabsch3 on the same rows in the same
+// order, so its 16 values and its valid byte are (1)'s bit for bit.
+// Mapping: the test is a few loads and compares, the fit some 1800 f64 instructions, and with one lane per sample a wave runs the fit
+// as soon as one of its 64 samples survives (at 1 % survivors: 47 % of the waves).  So a block of 256 samples works in two phases:
+//  1. every lane tests its own sample; a lane whose sample leaves here stores the identity.  The survivors' numbers are compacted into
+//     LDS in ascending order: ballot and prefix count inside the wave, the four wave counts in order across them.
+//  2. lane j < survivors fits survivor j and stores it at that sample's own slot: the waves of phase 2 are full but the last, and a
+//     block without survivors runs no fit at all.  The output is not compacted, only the work; a fit does not depend on its lane.
+constexpr int kCKThreads = 256;
+
+template <typename T>
+__global__ __launch_bounds__(kCKThreads) void kabsch_gather_checked_kernel(const T *__restrict__ matches,
+                                                                           const int32_t *__restrict__ idx, int Bt, int B, int N, int k,
+                                                                           double sigma, T *__restrict__ models,
+                                                                           uint8_t *__restrict__ valid, int32_t *__restrict__ rejected) {
+  __shared__ int s_wcnt[kCKThreads / 64];
+  __shared__ int s_list[kCKThreads];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int s0 = blockIdx.x * kCKThreads, s = s0 + tid;
+  bool pass = false, dropped = false;   // (both false past the end and for an index out of range)
+  if (s < Bt) {
+    const T *base = matches + (size_t)(s / B) * N * 6;
+    const int32_t *gi = idx + (size_t)s * k;
+    bool in_range = true;
+    for (int r = 0; r < k; ++r) in_range = in_range && gi[r] >= 0 && gi[r] < N;
+    if (in_range) {
+      pass = true;
+      for (int i = 0; i + 1 < k; ++i) {
+        const T *xi = base + (size_t)gi[i] * 6;
+        double x[6];
+#pragma unroll
+        for (int d = 0; d < 6; ++d) x[d] = (double)xi[d];
+        for (int j = i + 1; j < k; ++j) {
+          const T *xj = base + (size_t)gi[j] * 6;
+          double a2 = 0.0, b2 = 0.0;
+#pragma unroll
+          for (int d = 0; d < 3; ++d) {
+            const double da = x[d] - (double)xj[d], db = x[3 + d] - (double)xj[3 + d];
+            a2 += da * da;
+            b2 += db * db;
+          }
+          pass = pass && a2 >= sigma * b2 && b2 >= sigma * a2;
+        }
+      }
+      dropped = !pass;
+    }
+    if (!pass) {
+      double R[3][3], t[3];
+      set_identity(R, t);
+      store_rigid_model(models + (size_t)s * 16, R, t);
+      valid[s] = 0;
+    }
+  }
+  const int w0 = s0 + wv * 64;          // the wave's first sample; its samples may belong to several pairs
+  if (rejected && w0 < Bt) {            // (wave-uniform)
+    const int p_last = min(w0 + 63, Bt - 1) / B;
+    for (int p = w0 / B; p <= p_last; ++p) {
+      const int n = __popcll(__ballot(dropped && s / B == p));
+      if (lane == 0 && n) atomicAdd(rejected + p, n);
+    }
+  }
+  const unsigned long long survivors = __ballot(pass);
+  if (lane == 0) s_wcnt[wv] = __popcll(survivors);
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int w = 0; w < kCKThreads / 64; ++w) {
+    before += w < wv ? s_wcnt[w] : 0;
+    total += s_wcnt[w];
+  }
+  if (pass) s_list[before + __popcll(survivors & ((1ull << lane) - 1ull))] = tid;
+  __syncthreads();
+  if (tid < total) {                    // phase 2: (1)'s fit of survivor tid, whose indices are in range
+    const int f = s0 + s_list[tid];
+    const T *base = matches + (size_t)(f / B) * N * 6;
+    const int32_t *gi = idx + (size_t)f * k;
+    double c[6], H[3][3], R[3][3], t[3];
+    sample_moments(k, [&](int r) { return base + (size_t)gi[r] * 6; }, [](int) { return 1.0; }, c, H);
+    valid[f] = kabsch3(H, c, true, R, t);
+    store_rigid_model(models + (size_t)f * 16, R, t);
+  }
+}
+
 // explicit sample tensors [Bt,k,6] with optional weights [Bt,k]: what train mode fits (the straight-through samples of SampleGather).
 // Without weights, on samples = matches[idx], the models and validity of kabsch_gather_kernel bit for bit.
 template <typename T>
@@ -887,6 +976,20 @@ extern "C" {
                "need P, B, N > 0 and 3 <= k <= 8 rows per sample");                                                                 \
     return dr::launch("kabsch_gather_kernel", dr::kabsch_gather_kernel<T>, dim3((P * B + 63) / 64), 64, stream, matches, idx, P * B, \
                       B, N, k, models, valid);                                                                                      \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_kabsch_gather_checked_##sfx(const T *matches, const int32_t *idx, int P, int B, int N, int k, double edge_similarity,      \
+                                     T *models, uint8_t *valid, int32_t *rejected, void *stream) {                                  \
+    DR_REQUIRE(matches && idx && models && valid, "null pointer");                                                                  \
+    DR_REQUIRE(P > 0 && B > 0 && N > 0 && k >= 3 && k <= 8 && (long)P * B <= (1l << 31) - dr::kCKThreads,                           \
+               "need P, B, N > 0 and 3 <= k <= 8 rows per sample");                                                                 \
+    DR_REQUIRE(edge_similarity >= 0.0 && edge_similarity <= 1.0, "edge_similarity must lie in [0, 1]");   /* (false for NaN) */     \
+    return dr::launch("kabsch_gather_checked_kernel", dr::kabsch_gather_checked_kernel<T>,                                          \
+                      dim3((P * B + dr::kCKThreads - 1) / dr::kCKThreads), dr::kCKThreads, stream, matches, idx, P * B, B, N, k,    \
+                      edge_similarity * edge_similarity, models, valid, rejected);                                                  \
   }
 DR_F32_F64(DR_OP)
 #undef DR_OP

@@ -677,6 +677,28 @@ def kabsch_gather(matches: torch.Tensor, idx: torch.Tensor):
     return models, valid
 
 
+def kabsch_gather_checked(matches: torch.Tensor, idx: torch.Tensor, edge_similarity: float, rejected: Optional[torch.Tensor] = None):
+    """dr_kabsch_gather_checked: kabsch_gather behind a rigidity test of every sample.  With sigma = edge_similarity^2 a sample passes
+    iff |p_i - p_j|^2 >= sigma |q_i - q_j|^2 and |q_i - q_j|^2 >= sigma |p_i - p_j|^2 for every pair of its rows (f64; Open3D's
+    CorrespondenceCheckerBasedOnEdgeLength with similarity_threshold = edge_similarity); it then gets kabsch_gather's model and valid
+    bit for bit.  A sample that fails is the identity with valid = 0, no fit is run for it, and it counts once in rejected [P] int32
+    (optional; ADDED to, the caller zeroes it).  A sample with an index out of range is kabsch_gather's (identity, valid = 0) and is
+    not counted.  edge_similarity lies in [0, 1]; at 0 the outputs are kabsch_gather's."""
+    if matches.dim() != 3 or matches.shape[-1] != 6 or idx.dim() != 3 or idx.dtype != torch.int32:
+        raise L.DransacError("kabsch_gather_checked: correspondences [P,N,6] and int32 index sets [P,B,k]")
+    if not 0.0 <= float(edge_similarity) <= 1.0:      # (false for NaN)
+        raise L.DransacError(f"kabsch_gather_checked: edge_similarity must lie in [0, 1], got {edge_similarity!r}")
+    P, N, _ = matches.shape
+    _, B, k = idx.shape
+    if rejected is not None and (rejected.shape != (P,) or rejected.dtype != torch.int32):
+        raise L.DransacError("kabsch_gather_checked: rejected must be [P] int32")
+    models = torch.empty((P, B, 4, 4), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_kabsch_gather_checked_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B),
+           c_int(N), c_int(k), L.c_double(float(edge_similarity)), ptr(models), ptr(valid), ptr(rejected), stream())
+    return models, valid
+
+
 def _rigid_score(term: str, matches, models, threshold, valid, want_inliers, gate, thr2):
     """dr_rigid_{msac,magsac}_score: one kernel, two per-point terms"""
     P, N, _ = matches.shape

@@ -961,6 +961,16 @@ class BatchedRegistration(_SeededDriver):
     Kabsch fits over all points, each kept only where it scores strictly higher; the mask stays the RANSAC winner's.  The result gains
     irls_fits [P].  scoring = "msac" is the path without it: no other launch, allocation or key.
 
+    edge_similarity = a float in (0, 1] (test mode only): every round fits its samples with dr_kabsch_gather_checked in
+    dr_kabsch_gather's place.  A sample is dropped before the fit -- identity, valid = 0, so the score kernel skips it and the update
+    ignores it -- unless sigma |q_i - q_j|^2 <= |p_i - p_j|^2 <= |q_i - q_j|^2 / sigma, sigma = edge_similarity^2, holds for every
+    pair of its rows: a rigid motion keeps distances (Open3D's CorrespondenceCheckerBasedOnEdgeLength, similarity_threshold there).
+    Every sample that passes gives the model it gives without the check, bit for bit, and a dropped draw still counts in `iterations`;
+    nothing else of the round changes and nothing is read back.  The result gains rejected [P] int32, the samples dropped in the rounds
+    the call issued: the fit is not gated on the device, so a pair that has terminated keeps counting while other pairs (or, under
+    device_termination, the remaining rounds) go on.  None is the path without it: no other launch, allocation or key.  With
+    train = True it is refused: a dropped outlier sample is exactly the hypothesis whose loss teaches the logits.
+
     train = True: every round runs (no adaptive stop, as in the reference's train branches), each one ops.SampleGather (the
     straight-through samples of the Gumbel top-k) followed by ops.kabsch, and the call returns dict(models [P, rounds * B, 4, 4],
     keep [P, rounds * B] = the fit's validity) with autograd to the logits, and to `matches` where they require it.  The pose loss on
@@ -968,7 +978,8 @@ class BatchedRegistration(_SeededDriver):
     back to the host."""
 
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
-                 num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64, scoring="msac", irls_iters=10):
+                 num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64, scoring="msac", irls_iters=10,
+                 edge_similarity=None):
         _check_lo(lo, lo_iters)
         if lo and train:
             raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
@@ -980,6 +991,12 @@ class BatchedRegistration(_SeededDriver):
             raise ValueError("scoring='magsac' with train=True is refused: train mode scores nothing")
         if int(irls_iters) < 0:
             raise ValueError(f"irls_iters must be at least 0, got {irls_iters!r}")
+        if edge_similarity is not None:
+            if not 0.0 < float(edge_similarity) <= 1.0:      # (false for NaN)
+                raise ValueError(f"edge_similarity must be None or lie in (0, 1], got {edge_similarity!r}")
+            if train:
+                raise ValueError("edge_similarity with train=True is refused: a rejected outlier sample is exactly the hypothesis "
+                                 "whose loss teaches the logits, and dropping it would remove the training signal")
         if not 3 <= int(num_samples) <= 8:
             raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
         if int(max_iterations) < 1:
@@ -1000,6 +1017,7 @@ class BatchedRegistration(_SeededDriver):
         self.lo_iters = int(lo_iters)
         self.scoring = scoring
         self.irls_iters = int(irls_iters)
+        self.edge_similarity = None if edge_similarity is None else float(edge_similarity)
         self._device_termination = False
 
     @property
@@ -1043,11 +1061,17 @@ class BatchedRegistration(_SeededDriver):
                 lo_refits = torch.zeros(P, device=matches.device, dtype=torch.int32)
             magsac = self.scoring == "magsac"
             score_fn = ops.rigid_magsac_score if magsac else ops.rigid_msac_score
+            rejected = None
+            if self.edge_similarity is not None:
+                rejected = torch.zeros(P, device=matches.device, dtype=torch.int32)
             for r in range(rounds):
                 gate = st if (self._device_termination and r > 0) else None
                 g = None if gumbels is None else gumbels[r]
                 idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
-                models, valid = ops.kabsch_gather(matches, idx)
+                if rejected is None:
+                    models, valid = ops.kabsch_gather(matches, idx)
+                else:
+                    models, valid = ops.kabsch_gather_checked(matches, idx, self.edge_similarity, rejected)
                 scores, _ = score_fn(matches, models, None, valid, want_inliers=False, gate=gate, thr2=thr2)
                 ops.registration_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
                 if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
@@ -1060,8 +1084,11 @@ class BatchedRegistration(_SeededDriver):
                 irls_fits = torch.zeros(P, device=matches.device, dtype=torch.int32)
                 if self.refit and self.irls_iters > 0:
                     ops.registration_irls(st, matches, thr2, self.irls_iters, irls_fits)
-                return dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters,
-                            irls_fits=irls_fits)
+                out = dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters,
+                           irls_fits=irls_fits)
+                if rejected is not None:
+                    out["rejected"] = rejected
+                return out
             if self.refit:
                 cand, cvalid = ops.refit_rigid(matches, st.best_mask)
                 cscore, _ = ops.rigid_msac_score(matches, cand.unsqueeze(1), None, cvalid.unsqueeze(1), want_inliers=False, thr2=thr2)
@@ -1071,4 +1098,6 @@ class BatchedRegistration(_SeededDriver):
             out = dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)
             if self.lo:
                 out["lo_refits"] = lo_refits
+            if rejected is not None:
+                out["rejected"] = rejected
             return out

@@ -378,6 +378,17 @@ int dr_ransac3d_update_f64(const double *pts, const double *models, const uint8_
  *     candidate that does not win.  best_score and best_model [P,16] are rewritten where a candidate won; irls_fits [P] grows by the
  *     fits run.  The mask, the inlier count, iters and max_iters are not arguments: they stay the RANSAC winner's.  DR_EINVAL: a null
  *     pointer, P or N < 1, irls_iters < 1.
+ *   dr_kabsch_gather_checked  dr_kabsch_gather behind a rigidity test of the sample (BatchedRegistration(edge_similarity = ...)): a
+ *     rigid motion keeps distances, so a sample of inliers has |p_i - p_j| ~ |q_i - q_j| for every pair of its rows.  For every pair
+ *     i < j of a sample's k rows, in f64 from the stored values: a2 = |p_i - p_j|^2, b2 = |q_i - q_j|^2, and with
+ *     sigma = edge_similarity^2 the edge passes iff a2 >= sigma b2 && b2 >= sigma a2 (Open3D's
+ *     CorrespondenceCheckerBasedOnEdgeLength with similarity_threshold = edge_similarity, on squares); a NaN coordinate fails the edge,
+ *     two coincident rows pass it (and the fit then rejects the sample as degenerate).  A sample passes iff all k (k - 1) / 2 edges do,
+ *     and then gets exactly dr_kabsch_gather's 16 values and valid byte, bit for bit.  A sample that fails gets the identity and
+ *     valid = 0 without a fit and counts once in rejected[pair]; a sample with an index outside [0, N) gets the identity and valid = 0
+ *     as in dr_kabsch_gather and is not counted.  rejected [P] int32 (NULL = not counted) is ADDED to -- the caller zeroes it -- with
+ *     integer atomics, so a repeated launch gives the same counts.  edge_similarity = 0 passes every sample whose edges are finite:
+ *     the outputs of dr_kabsch_gather byte for byte.  DR_EINVAL: as dr_kabsch_gather, and edge_similarity outside [0, 1] (or NaN).
  *
  * Train mode (ops.kabsch, ops.weighted_kabsch, BatchedRegistration(train=True)).  With weights w >= 0 (1 when NULL), W = sum w:
  * c0 = sum w p / W, c1 = sum w q / W, H = sum w (p - c0)(q - c1)^T.  The backward entries recompute this forward in f64 from their
@@ -432,6 +443,10 @@ int dr_registration_irls_f32(const float *matches, const float *thr2, int P, int
                              float *best_model, int32_t *irls_fits, void *stream);
 int dr_registration_irls_f64(const double *matches, const double *thr2, int P, int N, int irls_iters, double *best_score,
                              double *best_model, int32_t *irls_fits, void *stream);
+int dr_kabsch_gather_checked_f32(const float *matches, const int32_t *idx, int P, int B, int N, int k, double edge_similarity,
+                                 float *models, uint8_t *valid, int32_t *rejected, void *stream);
+int dr_kabsch_gather_checked_f64(const double *matches, const int32_t *idx, int P, int B, int N, int k, double edge_similarity,
+                                 double *models, uint8_t *valid, int32_t *rejected, void *stream);
 int dr_kabsch_f32(const float *samples, const float *weights, int Bt, int k, float *models, uint8_t *valid, void *stream);
 int dr_kabsch_f64(const double *samples, const double *weights, int Bt, int k, double *models, uint8_t *valid, void *stream);
 int dr_kabsch_bwd_f32(const float *samples, const float *weights, const float *grad_models, int Bt, int k, float *grad_samples,
