@@ -4,6 +4,7 @@ torch stream and returns freshly allocated torch tensors; nothing synchronises.
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Tuple
 
 import torch
@@ -370,6 +371,53 @@ def uniform_sample(P: int, B: int, k: int, N: int, seed: int, device) -> torch.T
     """K1u: idx [P,B,k] int32 ~ U{0..N-2} (uniform_sampler.py:15-19 semantics)."""
     idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
     L.call("dr_uniform_sample", *_seed_args(seed), c_int(P), c_int(B), c_int(k), c_int(N), ptr(idx), stream())
+    return idx
+
+
+def prosac_rank(logits: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The ranking PROSAC samples from: order [P,N] int32, the points of every pair by descending logit, ties by ascending index,
+    NaN logits last (-0.0 ranks with 0.0).  None stays None: no order, the sampler reads the identity."""
+    if logits is None:
+        return None
+    # (l + 0.0 turns -0.0 into +0.0: a radix sort would tell their bit patterns apart)
+    key = torch.where(torch.isnan(logits), torch.full_like(logits, float("-inf")), logits + 0.0)
+    return torch.sort(key, dim=1, descending=True, stable=True).indices.to(torch.int32).contiguous()
+
+
+def prosac_growth(N: int, k: int, prosac_draws: int = 200000, device=None) -> torch.Tensor:
+    """PROSAC's growth function as a table, int64 [N - k + 1] on `device` (a CPU device works too): entry i is T'_{k+i}, the draw
+    number up to which the sampler works on the k + i best-ranked points.  T_n = T_N prod_{i<k} (n - i) / (N - i) in f64 (one division
+    and one multiplication per factor, in this order), T'_k = 1, T'_n = 1 + sum_{j=k+1..n} ceil(T_j - T_{j-1}): strictly increasing,
+    and n(t) <= k + t - 1.  T_N = prosac_draws, the number of draws after which the sampler is uniform over all points."""
+    N, k, T_N = int(N), int(k), int(prosac_draws)
+    if k < 1 or N < k or T_N < 1:
+        raise ValueError(f"prosac_growth needs 1 <= k <= N and prosac_draws >= 1, got N={N}, k={k}, prosac_draws={prosac_draws}")
+    n = torch.arange(k, N + 1, device=device, dtype=torch.float64)
+    T = torch.full_like(n, float(T_N))
+    for i in range(k):
+        T = T * ((n - float(i)) / float(N - i))
+    steps = torch.ceil(T[1:] - T[:-1]).to(torch.int64)
+    return torch.cat([torch.ones(1, device=device, dtype=torch.int64), 1 + torch.cumsum(steps, 0)])
+
+
+def prosac_sample(order: Optional[torch.Tensor], growth: torch.Tensor, B: int, k: int, seed=0, t0: int = 0,
+                  P: Optional[int] = None, N: Optional[int] = None, device=None) -> torch.Tensor:
+    """K1p (dr_prosac_sample): draws t0 + 1 .. t0 + B of the PROSAC sampler for every pair -> idx [P,B,k] int32 ascending.
+    order [P,N] int32 from prosac_rank (or None = the identity: pass P, N, device), growth from prosac_growth(N, k, ...);
+    `seed`: int or a DeviceSeed.next() tensor.  Draw 1 is the k best-ranked points; O(B k) work whatever N is."""
+    if order is not None:
+        if order.dtype != torch.int32 or order.dim() != 2:
+            raise L.DransacError("prosac_sample: order is an int32 [P,N] tensor (prosac_rank)")
+        order = order.contiguous()
+        P, N = order.shape
+        device = order.device
+    else:
+        assert P is not None and N is not None and device is not None
+    if growth.dtype != torch.int64 or growth.numel() != N - k + 1:
+        raise L.DransacError("prosac_sample: growth is the int64 [N - k + 1] table of prosac_growth(N, k, ...)")
+    idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
+    L.call("dr_prosac_sample", ptr(order), ptr(growth.contiguous()), *_seed_args(seed), ctypes.c_int64(int(t0)), c_int(P), c_int(B),
+           c_int(N), c_int(k), ptr(idx), stream())
     return idx
 
 

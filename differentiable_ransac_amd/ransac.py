@@ -516,6 +516,25 @@ class _SeededDriver(object):
         self._seeds.on_device(device)
         return self
 
+    # ---- sampling="prosac" (BatchedRANSAC, BatchedRegistration; test mode): ops.prosac_sample draws from the ranking of the logits
+    def _set_prosac_draws(self, prosac_draws):
+        if isinstance(prosac_draws, bool) or not isinstance(prosac_draws, int) or prosac_draws < 1:
+            raise ValueError(f"prosac_draws must be an int of at least 1, got {prosac_draws!r}")
+        self.prosac_draws = prosac_draws
+        self._prosac_tables = {}
+
+    def _prosac_setup(self, logits, N, device):
+        """(order, growth) of a call: the ranking of its logits and the growth table, cached per (N, k, prosac_draws, device)"""
+        if N < self.k:
+            raise ValueError(f"sampling='prosac' needs at least {self.k} points per pair, got {N}")
+        key = (N, self.k, self.prosac_draws, str(device))
+        growth = self._prosac_tables.get(key)
+        if growth is None:
+            growth = ops.prosac_growth(N, self.k, self.prosac_draws, device)
+            if not torch.cuda.is_current_stream_capturing():      # (a table made inside a capture lives in that graph's pool)
+                self._prosac_tables[key] = growth
+        return ops.prosac_rank(logits), growth
+
 
 class BatchedRANSAC(_SeededDriver):
     """The (pair x hypothesis) grid in one go: all P pairs sample, solve, score and select per round with a fixed
@@ -534,7 +553,7 @@ class BatchedRANSAC(_SeededDriver):
 
     def __init__(self, solver="nister", ransac_batch_size=1024, train=False, threshold=0.75, confidence=0.999,
                  max_iterations=5000, tau=1.0, seed=0, weighted=0, keep_masks=False, refit=True, eps=1e-5,
-                 sampling="gumbel", num_samples=None, lo=0, lo_iters=64):
+                 sampling="gumbel", num_samples=None, lo=0, lo_iters=64, prosac_draws=200000):
         # num_samples: points per sample when it is not the solver's minimal count -- 8 with solver="nister" is the reference's
         # `-sam 3` (8-point Gumbel sampler) feeding the five-point estimator (ransac.py:82-83; nister.py:64-65 runs on all rows)
         # sampling: "gumbel" = the reference's sampler (noise for every point of every hypothesis, top-k);
@@ -542,14 +561,19 @@ class BatchedRANSAC(_SeededDriver):
         # (ops.topdown_sample, O(B k log N)); test mode only, no soft weights (weighted=0), no explicit noise.
         # "uniform" = UniformSampler.batch_generate (samplers/uniform_sampler.py:15-19: randint(0, N - 1), with replacement,
         # the last point never drawn) for all pairs in one launch; index sets only, logits ignored.
-        if sampling not in ("gumbel", "topdown", "uniform"):
-            raise ValueError("sampling must be 'gumbel', 'topdown' or 'uniform'")
+        # "prosac" = PROSAC (ops.prosac_sample, O(B k)): the logits are ranked once per call and draw t of a call -- hypothesis
+        # t - 1 counted through its rounds -- takes the point of rank n(t) - 1 and k - 1 points ranked above it, n(t) growing from k to
+        # N over about `prosac_draws` draws (ops.prosac_growth), uniform over all points from there on; draw 1 is the k best-ranked
+        # points.  Test mode only, index sets only, no explicit noise; the adaptive stop stays the driver's own.
+        if sampling not in ("gumbel", "topdown", "uniform", "prosac"):
+            raise ValueError("sampling must be 'gumbel', 'topdown', 'uniform' or 'prosac'")
+        self._set_prosac_draws(prosac_draws)
         # lo (test mode; ignored in train mode, as in the reference): local optimisation of ransac.py:217-257 after every new best
         # model -- 1 = one LSQ refit on its inliers, 2 = up to lo_iters of them (ops.local_optimize, one launch per device round)
         _check_lo(lo, lo_iters)
         self.lo = int(lo)
         self.lo_iters = int(lo_iters)
-        if sampling in ("topdown", "uniform") and (train or weighted):
+        if sampling in ("topdown", "uniform", "prosac") and (train or weighted):
             raise ValueError(f"{sampling} sampling yields index sets only: train mode and weighted=1 need the Gumbel sampler")
         self.sampling = sampling
         self.pipeline = True     # test mode: issue round r+1's sampler/solver on a second stream while round r is scored
@@ -580,6 +604,7 @@ class BatchedRANSAC(_SeededDriver):
         self.eps = eps
         self.fmat = solver in ("f8", "f7")
         self._race_ws = None     # per-call weights of the one-logarithm sampler (written by dr_ransac_init, read by every round)
+        self._prosac = None      # per-call (order, growth) of sampling="prosac" (made by the test-mode set-up, read by every round)
         self._side = None
         self._gap = None         # scratch word of the one-launch dispatch gap in front of the sampler (see __call__)
         # Super-rounds (round 6, test mode).  The loop of ransac.py:55-144 runs `ransac_batch_size` hypotheses per iteration of a
@@ -638,11 +663,12 @@ class BatchedRANSAC(_SeededDriver):
             return F.unsqueeze(2), v.unsqueeze(2)
         return ops.solve_f7(samples)
 
-    def _hypotheses(self, matches, logits, gumbels=None, gate=None, R=1):
+    def _hypotheses(self, matches, logits, gumbels=None, gate=None, R=1, t0=0):
         """hypotheses() + the (seed, noise) pair of the draw when the weighted refit will need row 0's soft weights again
         (returned, not stashed on self: two rounds are in flight on two streams when `pipeline` is on), else None.
         R > 1 (test mode, see `super_hypotheses`): R consecutive batches in one go -> models [P, R * B, S, 3, 3]; explicit noise is the
-        R batches' tensors concatenated along the hypothesis axis."""
+        R batches' tensors concatenated along the hypothesis axis.
+        t0 (sampling="prosac"): the hypotheses the call has drawn before this round; the round's rows are PROSAC draws t0 + 1 ..."""
         B, w, row0, solve_gate = R * self.B, None, None, None
         f32_two_view = matches.dtype == torch.float32 and matches.shape[-1] == 4
         if self.sampling == "uniform" and gumbels is None:
@@ -654,6 +680,16 @@ class BatchedRANSAC(_SeededDriver):
             samples = ops.gather(matches, idx)
         elif self.sampling == "topdown" and gumbels is None:
             idx = ops.topdown_sample(logits, B, self.k, self._seeds.next())
+            samples = ops.gather(matches, idx)
+        elif self.sampling == "prosac":
+            if gumbels is not None:
+                raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
+            if self._prosac is None:      # (hypotheses() outside a call: __call__ ranks once for all its rounds)
+                order, growth = self._prosac_setup(logits, matches.shape[1], matches.device)
+            else:
+                order, growth = self._prosac
+            idx = ops.prosac_sample(order, growth, B, self.k, self._seeds.next(), t0, P=matches.shape[0], N=matches.shape[1],
+                                    device=matches.device)
             samples = ops.gather(matches, idx)
         elif self.train or self.weighted:
             seed = self._seeds.next()
@@ -682,6 +718,9 @@ class BatchedRANSAC(_SeededDriver):
         P, N, _ = matches.shape
         dev, dt = matches.device, matches.dtype
         self._race_ws = None      # (weights of THIS call's logits only: set by the test-mode set-up below, dropped by _finish)
+        self._prosac = None
+        if self.sampling == "prosac" and gumbels is not None:
+            raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
         rounds = max(1, math.ceil(self.max_iterations / self.B))
         if self.train:
             out = []
@@ -744,6 +783,8 @@ class BatchedRANSAC(_SeededDriver):
                                       K2 if use_K else None, dev, dt, seeds=(self._dev_seed, n_batches) if draw else None,
                                       packed=self.device_termination and P == 1, race_logits=race_lg)
             self._race_ws = st.race_ws
+            if self.sampling == "prosac":
+                self._prosac = self._prosac_setup(logits, N, dev)
             # what every round of the call works on (_round, _finish): state, inputs, the masks of the last round (keep_masks) and,
             # for the weighted refit, per pair the row-0 soft weights of the last batch it ran
             c = types.SimpleNamespace(st=st, thr=thr, matches=matches, logits=logits, plan=plan, pre=pre, all_masks=None,
@@ -777,7 +818,7 @@ class BatchedRANSAC(_SeededDriver):
                 g = None
                 if gumbels is not None:
                     g = gumbels[first[r]] if plan[r] == 1 else torch.cat(list(gumbels[first[r]:first[r] + plan[r]]), dim=1)
-                return self._hypotheses(matches, logits, g, gate=gate, R=plan[r])
+                return self._hypotheses(matches, logits, g, gate=gate, R=plan[r], t0=first[r] * self.B)
 
             if self.device_termination:
                 if rounds > 16:
@@ -848,6 +889,7 @@ class BatchedRANSAC(_SeededDriver):
     def _finish(self, c):
         """final refit on the inliers of the best model (ransac.py:148-195) and the result dictionary"""
         self._race_ws = None
+        self._prosac = None
         st = c.st
         if self.refit:
             if self.fmat:
@@ -971,6 +1013,14 @@ class BatchedRegistration(_SeededDriver):
     device_termination, the remaining rounds) go on.  None is the path without it: no other launch, allocation or key.  With
     train = True it is refused: a dropped outlier sample is exactly the hypothesis whose loss teaches the logits.
 
+    sampling = "prosac" (test mode only): the logits are ranked once per call (ops.prosac_rank) and every round draws its index sets
+    with ops.prosac_sample in ops.gumbel_topk's place, round r being PROSAC draws r B + 1 .. (r + 1) B of every pair: draw 1 is the
+    `num_samples` best-ranked points, draw t takes the point of rank n(t) - 1 and points ranked above it, n(t) growing from
+    num_samples to N over about `prosac_draws` draws (ops.prosac_growth; uniform over all points from there on).  O(B k) random words
+    per round instead of O(B N); everything behind the index sets is unchanged, `tau` plays no part, and the adaptive stop stays the
+    driver's own (PROSAC's non-randomness and maximality criteria are not implemented).  Refused with train = True and with explicit
+    `gumbels`.  sampling = "gumbel" is the path without it: no other launch, allocation or key.
+
     train = True: every round runs (no adaptive stop, as in the reference's train branches), each one ops.SampleGather (the
     straight-through samples of the Gumbel top-k) followed by ops.kabsch, and the call returns dict(models [P, rounds * B, 4, 4],
     keep [P, rounds * B] = the fit's validity) with autograd to the logits, and to `matches` where they require it.  The pose loss on
@@ -979,8 +1029,14 @@ class BatchedRegistration(_SeededDriver):
 
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
                  num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64, scoring="msac", irls_iters=10,
-                 edge_similarity=None):
+                 edge_similarity=None, sampling="gumbel", prosac_draws=200000):
         _check_lo(lo, lo_iters)
+        if sampling not in ("gumbel", "prosac"):
+            raise ValueError(f"sampling must be 'gumbel' or 'prosac', got {sampling!r}")
+        if sampling == "prosac" and train:
+            raise ValueError("sampling='prosac' yields index sets only: train mode needs the Gumbel sampler")
+        self._set_prosac_draws(prosac_draws)
+        self.sampling = sampling
         if lo and train:
             raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
         if scoring not in ("msac", "magsac"):
@@ -1041,6 +1097,8 @@ class BatchedRegistration(_SeededDriver):
         P, N, c = matches.shape
         if c != 6:
             raise ValueError("matches must be [P,N,6] = (p, q)")
+        if self.sampling == "prosac" and gumbels is not None:
+            raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
         rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
         if self.train:
             out = []
@@ -1064,10 +1122,17 @@ class BatchedRegistration(_SeededDriver):
             rejected = None
             if self.edge_similarity is not None:
                 rejected = torch.zeros(P, device=matches.device, dtype=torch.int32)
+            prosac = self.sampling == "prosac"
+            if prosac:      # the ranking of this call's logits and the growth table, once for all its rounds
+                order, growth = self._prosac_setup(logits, N, matches.device)
             for r in range(rounds):
                 gate = st if (self._device_termination and r > 0) else None
                 g = None if gumbels is None else gumbels[r]
-                idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
+                if prosac:      # rows of round r = draws r B + 1 .. (r + 1) B (t0 goes by value: a captured call replays it)
+                    idx = ops.prosac_sample(order, growth, self.B, self.k, self._seeds.next(), r * self.B, P=P, N=N,
+                                            device=matches.device)
+                else:
+                    idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
                 if rejected is None:
                     models, valid = ops.kabsch_gather(matches, idx)
                 else:

@@ -96,6 +96,21 @@ int dr_topdown_sample_f64(const double *logits, uint64_t seed, int P, int B, int
  * Philox4x32-7(key = seed, counter = (j, b, p, 1)). */
 int dr_uniform_sample(uint64_t seed, const uint64_t *seed_dev, int P, int B, int k, int N, int32_t *idx, void *stream);
 
+/* K1p  PROSAC sampler (Chum & Matas, CVPR 2005), index sets only: order [P,N] = the points of every pair from the best-ranked
+ * to the worst (NULL = the identity), growth [N-k+1] with growth[i] = T'_{k+i}, the number of draws after which the sampler
+ * has moved on from the k+i best-ranked points (strictly increasing, growth[0] = 1; ops.prosac_growth).  Row b of the launch
+ * is draw t = t0 + b + 1 of every pair:
+ *   t <= T'_N: n = min{ n in [k,N] : T'_n >= t }; the ranks are n-1 and k-1 distinct ranks uniform in [0, n-2]
+ *              (draw 1 is the ranks 0..k-1; the paper's listing starts at n = k+1);
+ *   t >  T'_N: k distinct ranks uniform in [0, N-1].
+ * Distinct ranks by Floyd's algorithm: c out of a pool of s from exactly c words, for i = 0..c-1, j = s-c+i:
+ * r = (word_i * (j+1)) >> 32, take j where r is already chosen, else r (bias <= (j+1) / 2^32).  word_i is word i & 3 of
+ * Philox4x32-7(key = seed, counter = (i >> 2, b, p, 3)).  idx [P,B,k] = order[p, rank], ascending in the point index.
+ * seed_dev != NULL: the key is read from device memory.  Ungated.  DR_EINVAL before any launch for a null idx or growth,
+ * k outside [1, 8], N < k, P or B < 1, t0 < 0. */
+int dr_prosac_sample(const int32_t *order, const int64_t *growth, uint64_t seed, const uint64_t *seed_dev, int64_t t0, int P,
+                     int B, int N, int k, int32_t *idx, void *stream);
+
 /* The per-call key of the batched drivers, advanced on the device (every replay of a captured step then draws fresh hypotheses):
  * state[0] = base, state[1] = number of calls so far -> seeds_out[i] = base * 0x9E3779B97F4A7C15 + calls + i (mod 2^64) for
  * i < n (<= 65 536), calls += n: CONSECUTIVE integers, one per call (ransac.py of this package: `_next_seed`).  n = 1 is the
