@@ -780,22 +780,25 @@ __global__ __launch_bounds__(kBT) void rigid_residual_bwd_kernel(const float *__
 
 }  // namespace dr
 
-template <typename T>
-static int f8_bwd_launch(const T *samples, const T *weights, const T *models, const T *grad_models, int Bt, int n, T *grad_samples,
-                         T *grad_weights, void *stream) {
+// the f32 five-point backward: from the solver's f64 models where the caller kept them (models_f64), else from the f32 ones
+static int fivepoint_bwd_f32_launch(const float *samples, const float *models, const double *models_f64, const uint8_t *valid,
+                                    const float *grad, const int32_t *which, int Bt, float *grad_samples, void *stream) {
+  const dim3 grid((Bt + 63) / 64);
+  if (models_f64)
+    return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<double>, grid, 64, stream, samples, models_f64, valid, grad, Bt,
+                      grad_samples, which);
+  return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<float>, grid, 64, stream, samples, models, valid, grad, Bt,
+                    grad_samples, which);
+}
+
+// Kernel: the instantiation of fivepoint_nm_bwd_kernel for these model (MT) and in-memory (IO) types
+template <auto Kernel, typename MT, typename IO>
+static int nm_bwd_launch(const IO *samples, const IO *weights, const MT *models, const uint8_t *valid, const IO *grad_models, int Bt,
+                         int n, IO *grad_samples, IO *grad_weights, void *stream) {
   const size_t smem = sizeof(double) * 162 * 64;
-  // the attribute is per device: remember which devices of this process have it (one process may drive several GPUs)
-  static bool attr_set[64] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dr::f8_bwd_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL((dr::f8_bwd_kernel<T>), dim3((Bt + 63) / 64), dim3(64), smem, (hipStream_t)stream, samples, weights,
-                     models, grad_models, Bt, n, grad_samples, grad_weights);
-  return dr::check_launch("f8_bwd_kernel");
+  dr::allow_dynamic_lds<Kernel>(smem);
+  return dr::launch_lds("fivepoint_nm_bwd_kernel", Kernel, dim3((Bt + 63) / 64), 64, smem, stream, samples, weights, models, valid,
+                        grad_models, Bt, n, grad_samples, grad_weights);
 }
 
 extern "C" {
@@ -805,13 +808,7 @@ int dr_solve_nister5_bwd_f32(const float *samples, const float *models, const do
                              void *stream) {
   DR_REQUIRE(samples && (models || models_f64) && valid && grad_models && grad_samples, "null pointer");
   DR_REQUIRE(Bt > 0, "need Bt > 0");
-  if (models_f64)
-    hipLaunchKernelGGL((dr::fivepoint_bwd_kernel<double>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                       samples, models_f64, valid, grad_models, Bt, grad_samples, (const int32_t *)nullptr);
-  else
-    hipLaunchKernelGGL((dr::fivepoint_bwd_kernel<float>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                       samples, models, valid, grad_models, Bt, grad_samples, (const int32_t *)nullptr);
-  return dr::check_launch("fivepoint_bwd_kernel");
+  return fivepoint_bwd_f32_launch(samples, models, models_f64, valid, grad_models, nullptr, Bt, grad_samples, stream);
 }
 
 int dr_solve_nister5_bwd_sel_f32(const float *samples, const float *models, const double *models_f64,
@@ -819,13 +816,7 @@ int dr_solve_nister5_bwd_sel_f32(const float *samples, const float *models, cons
                                  float *grad_samples, void *stream) {
   DR_REQUIRE(samples && (models || models_f64) && valid && grad_chosen && which && grad_samples, "null pointer");
   DR_REQUIRE(Bt > 0, "need Bt > 0");
-  if (models_f64)
-    hipLaunchKernelGGL((dr::fivepoint_bwd_kernel<double>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                       samples, models_f64, valid, grad_chosen, Bt, grad_samples, which);
-  else
-    hipLaunchKernelGGL((dr::fivepoint_bwd_kernel<float>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream,
-                       samples, models, valid, grad_chosen, Bt, grad_samples, which);
-  return dr::check_launch("fivepoint_bwd_kernel");
+  return fivepoint_bwd_f32_launch(samples, models, models_f64, valid, grad_chosen, which, Bt, grad_samples, stream);
 }
 
 int dr_solve_nister5_nm_bwd_f32(const float *samples, const float *weights, const float *models, const double *models_f64,
@@ -833,24 +824,11 @@ int dr_solve_nister5_nm_bwd_f32(const float *samples, const float *weights, cons
                                 float *grad_weights, void *stream) {
   DR_REQUIRE(samples && (models || models_f64) && valid && grad_models && grad_samples, "null pointer");
   DR_REQUIRE(Bt > 0 && n > 5, "need Bt > 0 and n > 5 points per sample (minimal samples: dr_solve_nister5_bwd_f32)");
-  const size_t smem = sizeof(double) * 162 * 64;
-  static bool attr_set[64] = {false};   // per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dr::fivepoint_nm_bwd_kernel<double>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dr::fivepoint_nm_bwd_kernel<float>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
   if (models_f64)
-    hipLaunchKernelGGL((dr::fivepoint_nm_bwd_kernel<double>), dim3((Bt + 63) / 64), dim3(64), smem, (hipStream_t)stream,
-                       samples, weights, models_f64, valid, grad_models, Bt, n, grad_samples, grad_weights);
-  else
-    hipLaunchKernelGGL((dr::fivepoint_nm_bwd_kernel<float>), dim3((Bt + 63) / 64), dim3(64), smem, (hipStream_t)stream,
-                       samples, weights, models, valid, grad_models, Bt, n, grad_samples, grad_weights);
-  return dr::check_launch("fivepoint_nm_bwd_kernel");
+    return nm_bwd_launch<dr::fivepoint_nm_bwd_kernel<double>>(samples, weights, models_f64, valid, grad_models, Bt, n, grad_samples,
+                                                              grad_weights, stream);
+  return nm_bwd_launch<dr::fivepoint_nm_bwd_kernel<float>>(samples, weights, models, valid, grad_models, Bt, n, grad_samples,
+                                                           grad_weights, stream);
 }
 
 /* the same with everything f64 in memory (`-sam 3 -fmat 0 -tr 1 -pr 2`; round 6: the f32-I/O kernel rounded samples and gradients) */
@@ -858,68 +836,55 @@ int dr_solve_nister5_nm_bwd_f64(const double *samples, const double *weights, co
                                 const double *grad_models, int Bt, int n, double *grad_samples, double *grad_weights, void *stream) {
   DR_REQUIRE(samples && models && valid && grad_models && grad_samples, "null pointer");
   DR_REQUIRE(Bt > 0 && n > 5, "need Bt > 0 and n > 5 points per sample (minimal samples: dr_solve_nister5_bwd_f64)");
-  const size_t smem = sizeof(double) * 162 * 64;
-  static bool attr_set[64] = {false};   // per device
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dr::fivepoint_nm_bwd_kernel<double, double>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL((dr::fivepoint_nm_bwd_kernel<double, double>), dim3((Bt + 63) / 64), dim3(64), smem, (hipStream_t)stream, samples,
-                     weights, models, valid, grad_models, Bt, n, grad_samples, grad_weights);
-  return dr::check_launch("fivepoint_nm_bwd_kernel");
+  return nm_bwd_launch<dr::fivepoint_nm_bwd_kernel<double, double>>(samples, weights, models, valid, grad_models, Bt, n, grad_samples,
+                                                                    grad_weights, stream);
 }
 
-int dr_solve_f8_bwd_f32(const float *samples, const float *weights, const float *models, const float *grad_models,
-                        int Bt, int n, float *grad_samples, float *grad_weights, void *stream) {
-  DR_REQUIRE(samples && models && grad_models && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8");
-  return f8_bwd_launch<float>(samples, weights, models, grad_models, Bt, n, grad_samples, grad_weights, stream);
-}
-/* f64 in memory as well (`-pr 2 -tr 1`, model_cl.py:164-169): the same kernel, nothing rounded to f32 on the way */
-int dr_solve_f8_bwd_f64(const double *samples, const double *weights, const double *models, const double *grad_models,
-                        int Bt, int n, double *grad_samples, double *grad_weights, void *stream) {
-  DR_REQUIRE(samples && models && grad_models && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8");
-  return f8_bwd_launch<double>(samples, weights, models, grad_models, Bt, n, grad_samples, grad_weights, stream);
-}
+/* f64: in memory as well (`-pr 2 -tr 1`, model_cl.py:164-169): the same kernel, nothing rounded to f32 on the way */
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_solve_f8_bwd_##sfx(const T *samples, const T *weights, const T *models, const T *grad_models, int Bt, int n,               \
+                            T *grad_samples, T *grad_weights, void *stream) {                                                       \
+    DR_REQUIRE(samples && models && grad_models && grad_samples, "null pointer");                                                   \
+    DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8");                                                                         \
+    const size_t smem = sizeof(double) * 162 * 64;                                                                                  \
+    dr::allow_dynamic_lds<dr::f8_bwd_kernel<T>>(smem);                                                                              \
+    return dr::launch_lds("f8_bwd_kernel", dr::f8_bwd_kernel<T>, dim3((Bt + 63) / 64), 64, smem, stream, samples, weights, models,  \
+                          grad_models, Bt, n, grad_samples, grad_weights);                                                          \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
 /* minimal five-point backward, everything f64 in memory (dense gradient [Bt,10,9]) */
 int dr_solve_nister5_bwd_f64(const double *samples, const double *models, const uint8_t *valid, const double *grad_models, int Bt,
                              double *grad_samples, void *stream) {
   DR_REQUIRE(samples && models && valid && grad_models && grad_samples, "null pointer");
   DR_REQUIRE(Bt > 0, "need Bt > 0");
-  hipLaunchKernelGGL((dr::fivepoint_bwd_kernel<double, double>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples,
-                     models, valid, grad_models, Bt, grad_samples, (const int32_t *)nullptr);
-  return dr::check_launch("fivepoint_bwd_kernel");
+  return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<double, double>, dim3((Bt + 63) / 64), 64, stream, samples, models,
+                    valid, grad_models, Bt, grad_samples, nullptr);
 }
 
 int dr_solve_rigid_bwd_f32(const float *samples, const float *models, const float *grad_models, int Bt, int n,
                            int flag, float *grad_samples, void *stream) {
   DR_REQUIRE(samples && models && grad_models && grad_samples, "null pointer");
   DR_REQUIRE(Bt > 0 && n >= 3, "need Bt > 0 and n >= 3");
-  hipLaunchKernelGGL(dr::rigid_bwd_kernel, dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, models,
-                     grad_models, Bt, n, flag, grad_samples);
-  return dr::check_launch("rigid_bwd_kernel");
+  return dr::launch("rigid_bwd_kernel", dr::rigid_bwd_kernel, dim3((Bt + 63) / 64), 64, stream, samples, models, grad_models, Bt, n,
+                    flag, grad_samples);
 }
 
 int dr_msac_score_bwd_f32(const float *matches, const float *models, const float *thr, const float *grad_scores,
                           int P, int M, int N, float *grad_models, void *stream) {
   DR_REQUIRE(matches && models && thr && grad_scores && grad_models, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL(dr::msac_bwd_kernel, dim3((M + dr::kBM - 1) / dr::kBM, 1, P), dim3(dr::kBT), 0,
-                     (hipStream_t)stream, matches, models, thr, grad_scores, M, N, grad_models);
-  return dr::check_launch("msac_bwd_kernel");
+  return dr::launch("msac_bwd_kernel", dr::msac_bwd_kernel, dim3((M + dr::kBM - 1) / dr::kBM, 1, P), dr::kBT, stream, matches, models,
+                    thr, grad_scores, M, N, grad_models);
 }
 
 int dr_rigid_residual_bwd_f32(const float *pts, const float *models, const float *grad_res, int P, int M, int N,
                               float *grad_models, void *stream) {
   DR_REQUIRE(pts && models && grad_res && grad_models, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL(dr::rigid_residual_bwd_kernel, dim3((M + dr::kBM - 1) / dr::kBM, 1, P), dim3(dr::kBT), 0,
-                     (hipStream_t)stream, pts, models, grad_res, M, N, grad_models);
-  return dr::check_launch("rigid_residual_bwd_kernel");
+  return dr::launch("rigid_residual_bwd_kernel", dr::rigid_residual_bwd_kernel, dim3((M + dr::kBM - 1) / dr::kBM, 1, P), dr::kBT, stream,
+                    pts, models, grad_res, M, N, grad_models);
 }
 
 }  // extern "C"

@@ -29,6 +29,37 @@ inline int check_launch(const char *what) {
     }                                    \
   } while (0)
 
+// ---- the C entries (the code below `extern "C" {` of every .hip file) ----
+// Every op is written once: an op whose _f32 and _f64 entries differ only in float / double is a body DR_OP(sfx, T) and DR_F32_F64
+// makes its two symbols; an entry without such a twin is a plain function.  An op's argument checks stand at the top of its body
+// (DR_REQUIRE names the symbol in the message) or of the one template it forwards to, the launch below them.
+#define DR_F32_F64(OP) OP(f32, float) OP(f64, double)
+
+// one launch on the caller's stream -> status; launch_lds: the same with `lds_bytes` of dynamic LDS
+template <typename... Params, typename... Args>
+int launch_lds(const char *name, void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, void *stream, Args... args) {
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, (hipStream_t)stream, args...);
+  return check_launch(name);
+}
+template <typename... Params, typename... Args>
+int launch(const char *name, void (*kernel)(Params...), dim3 grid, dim3 block, void *stream, Args... args) {
+  return launch_lds(name, kernel, grid, block, 0, stream, args...);
+}
+
+// Lets `Kernel` ask for up to `bytes` of dynamic LDS (more than the default 64 KB needs the opt-in).  The attribute is per device: one
+// process may drive several GPUs, so each kernel instantiation remembers the devices that have it.  The call's status is ignored (a
+// launch that asks for too much reports it).
+template <auto Kernel>
+void allow_dynamic_lds(size_t bytes) {
+  static bool done[64] = {false};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  if (dev < 0 || dev >= 64 || !done[dev]) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (dev >= 0 && dev < 64) done[dev] = true;
+  }
+}
+
 // Per-pair gate of the multi-round test-mode drivers (round 5: device-side termination): a pair whose iteration counter has
 // reached its adaptive bound (ransac.py:135-144, kept on the device by dr_ransac_update) has terminated; the kernels of later rounds
 // return at once for its blocks -- nothing about a round is read back by the host, so a whole multi-round call is one HIP graph.

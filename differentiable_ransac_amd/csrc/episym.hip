@@ -315,6 +315,16 @@ static int episym_groups(int P, int M, int per_simd) {
   long g = (wave_models + capacity - 1) / capacity;
   return (int)(g < 1 ? 1 : (g > 16 ? 16 : g));
 }
+
+// one episym_kernel<kMode> launch over the (pair x model) grid; the arguments after `stream` are the kernel's own, less M, N and `groups`
+template <int kMode>
+static int episym_launch(const char *name, int P, int M, int N, void *stream, const float *matches, const uint8_t *mask,
+                         const float *models, const uint8_t *valid, const float *grad_sums, int grad_per_pair, float *out,
+                         const float *grad_scalar, float scalar_scale, float *out2 = nullptr) {
+  const int groups = episym_groups(P, M, 4), per_block = kEMperGroup * groups;
+  return launch(name, episym_kernel<kMode>, dim3((M + per_block - 1) / per_block, 1, P), kET, stream, matches, mask, models, valid,
+                grad_sums, grad_per_pair, M, N, out, groups, grad_scalar, scalar_scale, out2);
+}
 }  // namespace dr
 
 extern "C" {
@@ -323,44 +333,29 @@ int dr_episym_fwd_f32(const float *matches, const uint8_t *mask, const float *mo
                       int N, float *sums, void *stream) {
   DR_REQUIRE(matches && models && sums, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  const int groups = dr::episym_groups(P, M, 4), per_block = dr::kEMperGroup * groups;
-  hipLaunchKernelGGL((dr::episym_kernel<0>), dim3((M + per_block - 1) / per_block, 1, P), dim3(dr::kET), 0,
-                     (hipStream_t)stream, matches, mask, models, valid, (const float *)nullptr, 0, M, N, sums, groups,
-                     (const float *)nullptr, 1.0f);
-  return dr::check_launch("episym_kernel");
+  return dr::episym_launch<0>("episym_kernel", P, M, N, stream, matches, mask, models, valid, nullptr, 0, sums, nullptr, 1.0f);
 }
 
 int dr_episym_bwd_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *valid,
                       const float *grad_sums, int P, int M, int N, float *grad_models, void *stream) {
   DR_REQUIRE(matches && models && grad_sums && grad_models, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  const int groups = dr::episym_groups(P, M, 4), per_block = dr::kEMperGroup * groups;
-  hipLaunchKernelGGL((dr::episym_kernel<1>), dim3((M + per_block - 1) / per_block, 1, P), dim3(dr::kET), 0,
-                     (hipStream_t)stream, matches, mask, models, valid, grad_sums, 0, M, N, grad_models, groups,
-                     (const float *)nullptr, 1.0f);
-  return dr::check_launch("episym_kernel");
+  return dr::episym_launch<1>("episym_kernel", P, M, N, stream, matches, mask, models, valid, grad_sums, 0, grad_models, nullptr, 1.0f);
 }
 
 int dr_episym_bwd_pair_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *valid,
                            const float *grad_pair, int P, int M, int N, float *grad_models, void *stream) {
   DR_REQUIRE(matches && models && grad_pair && grad_models, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  const int groups = dr::episym_groups(P, M, 4), per_block = dr::kEMperGroup * groups;
-  hipLaunchKernelGGL((dr::episym_kernel<1>), dim3((M + per_block - 1) / per_block, 1, P), dim3(dr::kET), 0,
-                     (hipStream_t)stream, matches, mask, models, valid, grad_pair, 1, M, N, grad_models, groups,
-                     (const float *)nullptr, 1.0f);
-  return dr::check_launch("episym_kernel");
+  return dr::episym_launch<1>("episym_kernel", P, M, N, stream, matches, mask, models, valid, grad_pair, 1, grad_models, nullptr, 1.0f);
 }
 
 int dr_episym_bwd_mean_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *valid,
                            const float *coef, const float *grad_mean, int P, int M, int N, float *grad_models, void *stream) {
   DR_REQUIRE(matches && models && coef && grad_mean && grad_models, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  const int groups = dr::episym_groups(P, M, 4), per_block = dr::kEMperGroup * groups;
-  hipLaunchKernelGGL((dr::episym_kernel<1>), dim3((M + per_block - 1) / per_block, 1, P), dim3(dr::kET), 0,
-                     (hipStream_t)stream, matches, mask, models, valid, coef, 1, M, N, grad_models, groups, grad_mean,
-                     1.0f / (float)P);
-  return dr::check_launch("episym_kernel");
+  return dr::episym_launch<1>("episym_kernel", P, M, N, stream, matches, mask, models, valid, coef, 1, grad_models, grad_mean,
+                              1.0f / (float)P);
 }
 
 /* Round 5: MatchLoss (loss.py:107-153) value + gradient in one pass over the (model x point) grid.  dr_match_loss_fused_f32: sums
@@ -371,14 +366,11 @@ int dr_match_loss_fused_f32(const float *matches, const uint8_t *mask, const flo
                             float *sums, float *grad_unscaled, float *per_pair, float *coef, float *mean, void *stream) {
   DR_REQUIRE(matches && models && sums && grad_unscaled && per_pair && coef && mean, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  const int groups = dr::episym_groups(P, M, 4), per_block = dr::kEMperGroup * groups;
-  hipLaunchKernelGGL((dr::episym_kernel<2>), dim3((M + per_block - 1) / per_block, 1, P), dim3(dr::kET), 0, (hipStream_t)stream,
-                     matches, mask, models, valid, (const float *)nullptr, 0, M, N, grad_unscaled, groups, (const float *)nullptr,
-                     1.0f, sums);
-  if (int rc = dr::check_launch("episym_kernel<fused>")) return rc;
-  hipLaunchKernelGGL(dr::match_loss_mean_kernel, dim3(1), dim3(dr::kMeanT), 0, (hipStream_t)stream, sums, mask, valid, P, M, N,
-                     per_pair, coef, mean);
-  return dr::check_launch("match_loss_mean_kernel");
+  if (int rc = dr::episym_launch<2>("episym_kernel<fused>", P, M, N, stream, matches, mask, models, valid, nullptr, 0, grad_unscaled,
+                                    nullptr, 1.0f, sums))
+    return rc;
+  return dr::launch("match_loss_mean_kernel", dr::match_loss_mean_kernel, dim3(1), dr::kMeanT, stream, sums, mask, valid, P, M, N,
+                    per_pair, coef, mean);
 }
 
 int dr_match_loss_scale_f32(const float *grad_unscaled, const float *coef, const float *grad_mean, int P, int M, float *grad_models,
@@ -386,27 +378,24 @@ int dr_match_loss_scale_f32(const float *grad_unscaled, const float *coef, const
   DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");
   DR_REQUIRE(P > 0 && M > 0, "bad sizes");
   const size_t total = (size_t)P * M * 9;
-  hipLaunchKernelGGL(dr::match_loss_scale_kernel, dim3((unsigned)((total + dr::kET - 1) / dr::kET)), dim3(dr::kET), 0,
-                     (hipStream_t)stream, grad_unscaled, coef, grad_mean, 1.0f / (float)P, M * 9, total, grad_models);
-  return dr::check_launch("match_loss_scale_kernel");
+  return dr::launch("match_loss_scale_kernel", dr::match_loss_scale_kernel, dim3((unsigned)((total + dr::kET - 1) / dr::kET)), dr::kET,
+                    stream, grad_unscaled, coef, grad_mean, 1.0f / (float)P, M * 9, total, grad_models);
 }
 
 int dr_match_loss_mean_f32(const float *sums, const uint8_t *mask, const uint8_t *keep, int P, int M, int N,
                            float *per_pair, float *coef, float *mean, void *stream) {
   DR_REQUIRE(sums && per_pair && coef && mean, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0, "bad sizes");
-  hipLaunchKernelGGL(dr::match_loss_mean_kernel, dim3(1), dim3(dr::kMeanT), 0, (hipStream_t)stream, sums, mask, keep, P, M, N,
-                     per_pair, coef, mean);
-  return dr::check_launch("match_loss_mean_kernel");
+  return dr::launch("match_loss_mean_kernel", dr::match_loss_mean_kernel, dim3(1), dr::kMeanT, stream, sums, mask, keep, P, M, N,
+                    per_pair, coef, mean);
 }
 
 int dr_match_loss_pair_f32(const float *sums, const uint8_t *mask, const uint8_t *keep, int P, int M, int N,
                            float *per_pair, float *coef, void *stream) {
   DR_REQUIRE(sums && per_pair && coef, "null pointer");
   DR_REQUIRE(P > 0 && M > 0 && N > 0, "bad sizes");
-  hipLaunchKernelGGL(dr::match_loss_pair_kernel, dim3(P), dim3(dr::kET), 0, (hipStream_t)stream, sums, mask, keep, M, N,
-                     per_pair, coef);
-  return dr::check_launch("match_loss_pair_kernel");
+  return dr::launch("match_loss_pair_kernel", dr::match_loss_pair_kernel, dim3(P), dr::kET, stream, sums, mask, keep, M, N, per_pair,
+                    coef);
 }
 
 }  // extern "C"

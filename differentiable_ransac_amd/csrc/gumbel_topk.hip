@@ -933,19 +933,19 @@ __global__ __launch_bounds__(kRowsPerBlock * 64) void gumbel_topk_stream_kernel(
 }
 
 template <int K>
-static void stream_launch(bool soft, dim3 grid, dim3 block, hipStream_t st, const float *logits, uint64_t seed, int B, int N, int k,
+static int stream_launch(bool soft, dim3 grid, dim3 block, hipStream_t st, const float *logits, uint64_t seed, int B, int N, int k,
                           int32_t *idx, float *y_sel, float *lse, const uint64_t *seed_ptr, const uint32_t *tb = nullptr,
                           const float *Tp = nullptr, int sub = 0) {
   // few rows: four waves per row (one row per block) -- the wave-per-row grid would leave the SIMDs at <= 4 waves each
   const long rows = (long)grid.y * B;
-  if (rows <= 4096 && N >= 4 * 64 * 4 * 4) {
-    const dim3 g2(B, grid.y);
-    if (soft) hipLaunchKernelGGL((gumbel_topk_stream_kernel<K, true, kRowsPerBlock>), g2, block, 0, st, logits, seed, B, N, k, idx, y_sel, lse, seed_ptr);
-    else hipLaunchKernelGGL((gumbel_topk_stream_kernel<K, false, kRowsPerBlock>), g2, block, 0, st, logits, seed, B, N, k, idx, y_sel, lse, seed_ptr, tb, Tp, sub);
-    return;
-  }
-  if (soft) hipLaunchKernelGGL((gumbel_topk_stream_kernel<K, true, 1>), grid, block, 0, st, logits, seed, B, N, k, idx, y_sel, lse, seed_ptr);
-  else hipLaunchKernelGGL((gumbel_topk_stream_kernel<K, false, 1>), grid, block, 0, st, logits, seed, B, N, k, idx, y_sel, lse, seed_ptr, tb, Tp, sub);
+  const bool wide = rows <= 4096 && N >= 4 * 64 * 4 * 4;
+  if (wide) grid = dim3(B, grid.y);
+  const char *name = "gumbel_topk_stream_kernel";
+  if (soft)   // (train mode: no screen, no sub-batches)
+    return launch(name, wide ? gumbel_topk_stream_kernel<K, true, kRowsPerBlock> : gumbel_topk_stream_kernel<K, true, 1>, grid, block, st,
+                  logits, seed, B, N, k, idx, y_sel, lse, seed_ptr, nullptr, nullptr, 0);
+  return launch(name, wide ? gumbel_topk_stream_kernel<K, false, kRowsPerBlock> : gumbel_topk_stream_kernel<K, false, 1>, grid, block, st,
+                logits, seed, B, N, k, idx, y_sel, lse, seed_ptr, tb, Tp, sub);
 }
 
 template <typename T>
@@ -967,18 +967,15 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
   const bool soft = y_sel != nullptr;   // the entry points have checked: y_sel and lse both given, or neither (then no dense outputs)
   if constexpr (sizeof(T) == 4) {
     if (logits && !gumbel && tau == T(1) && (N & 3) == 0 && N <= 4 * 64 * kFastGroups && !y_soft && !ret && !gumbel_out) {
+      const char *name = "gumbel_topk_fast_kernel";
       if (race_ws && !race_ready)
-        hipLaunchKernelGGL(gumbel_race_weights_kernel, dim3(P), dim3(256), 0, st, (const float *)logits, N, P, race_ws);
-      if (soft)   // (train mode: no gate, no sub-batches)
-        hipLaunchKernelGGL((gumbel_topk_fast_kernel<true>), grid, block, 0, st, (const float *)logits, seed, B, N, k, idx,
-                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, PairGate(), 0,
-                           (const float *)race_ws, P);
-      else
-        hipLaunchKernelGGL((gumbel_topk_fast_kernel<false>), grid, block, 0, st, (const float *)logits, seed, B, N, k, idx,
-                           (float *)y_sel, (float *)lse, seed_ptr, gather_src, gather_dst, gate, sub,
-                           (const float *)race_ws, P);
+        if (int rc = launch(name, gumbel_race_weights_kernel, dim3(P), 256, st, (const float *)logits, N, P, race_ws)) return rc;
       if (gathered) *gathered = gather_dst != nullptr;
-      return check_launch("gumbel_topk_fast_kernel");
+      if (soft)   // (train mode: no gate, no sub-batches)
+        return launch(name, gumbel_topk_fast_kernel<true>, grid, block, st, (const float *)logits, seed, B, N, k, idx, (float *)y_sel,
+                      (float *)lse, seed_ptr, gather_src, gather_dst, PairGate(), 0, (const float *)race_ws, P);
+      return launch(name, gumbel_topk_fast_kernel<false>, grid, block, st, (const float *)logits, seed, B, N, k, idx, (float *)y_sel,
+                    (float *)lse, seed_ptr, gather_src, gather_dst, gate, sub, (const float *)race_ws, P);
     }
     // measured against the general two-pass kernel: 50 000 x 2048 rows, k = 3: 226 -> 113 us; 4096 x 32 768 rows, k = 5: 196 -> 178 us;
     // k = 8 lists cost what the second pass costs (256 vs 250 us at N = 20 000) -> the general kernel keeps k > 5
@@ -990,38 +987,29 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
         // workspace: P x N words + P scores + P x 16 partial sums; lambda = 20 + k: P(fewer than k of a row's points reach T) < 1e-7
         float *Tw = reinterpret_cast<float *>(screen_ws + (size_t)P * N);
         float *part = Tw + P;
+        const char *name = "gumbel_topk_stream_kernel";
         if ((long)((N + 1023) / 1024) * N <= (16L << 20)) {   // (row re-reads bounded: beyond, the two-launch form)
-          hipLaunchKernelGGL(gumbel_screen_fused_kernel, dim3((N + 1023) / 1024, P), dim3(1024), 0, st, (const float *)logits, N,
-                             (float)(20 + k), Tw, screen_ws);
+          if (int rc = launch(name, gumbel_screen_fused_kernel, dim3((N + 1023) / 1024, P), 1024, st, (const float *)logits, N,
+                              (float)(20 + k), Tw, screen_ws))
+            return rc;
         } else {
-          hipLaunchKernelGGL(gumbel_screen_part_kernel, dim3(kRowParts, P), dim3(256), 0, st, (const float *)logits, N, part);
-          hipLaunchKernelGGL(gumbel_screen_kernel, dim3((N + 255) / 256, P), dim3(256), 0, st, (const float *)logits, N, (float)(20 + k),
-                             part, Tw, screen_ws);
+          if (int rc = launch(name, gumbel_screen_part_kernel, dim3(kRowParts, P), 256, st, (const float *)logits, N, part)) return rc;
+          if (int rc = launch(name, gumbel_screen_kernel, dim3((N + 255) / 256, P), 256, st, (const float *)logits, N, (float)(20 + k),
+                              part, Tw, screen_ws))
+            return rc;
         }
         tb = screen_ws;
         Tp = Tw;
       }
-      if (k <= 3) stream_launch<3>(soft, grid, block, st, (const float *)logits, seed, B, N, k, idx, (float *)y_sel, (float *)lse, seed_ptr, tb, Tp, sub);
-      else stream_launch<5>(soft, grid, block, st, (const float *)logits, seed, B, N, k, idx, (float *)y_sel, (float *)lse, seed_ptr, tb, Tp, sub);
-      return check_launch("gumbel_topk_stream_kernel");
+      if (k <= 3) return stream_launch<3>(soft, grid, block, st, (const float *)logits, seed, B, N, k, idx, (float *)y_sel, (float *)lse, seed_ptr, tb, Tp, sub);
+      return stream_launch<5>(soft, grid, block, st, (const float *)logits, seed, B, N, k, idx, (float *)y_sel, (float *)lse, seed_ptr, tb, Tp, sub);
     }
   }
-  if (base + cache <= 64 * 1024) {
-    if (soft)
-      hipLaunchKernelGGL((gumbel_topk_kernel<T, true, true>), grid, block, base + cache, st, a, idx, y_sel, lse, y_soft, ret,
-                         gumbel_out);
-    else
-      hipLaunchKernelGGL((gumbel_topk_kernel<T, true, false>), grid, block, base + cache, st, a, idx, y_sel, lse, y_soft,
-                         ret, gumbel_out);
-  } else {
-    if (soft)
-      hipLaunchKernelGGL((gumbel_topk_kernel<T, false, true>), grid, block, base, st, a, idx, y_sel, lse, y_soft, ret,
-                         gumbel_out);
-    else
-      hipLaunchKernelGGL((gumbel_topk_kernel<T, false, false>), grid, block, base, st, a, idx, y_sel, lse, y_soft, ret,
-                         gumbel_out);
-  }
-  return check_launch("gumbel_topk_kernel");
+  const bool cached = base + cache <= 64 * 1024;   // the row's noisy logits fit into LDS next to the candidate lists
+  const auto kernel = cached ? (soft ? gumbel_topk_kernel<T, true, true> : gumbel_topk_kernel<T, true, false>)
+                             : (soft ? gumbel_topk_kernel<T, false, true> : gumbel_topk_kernel<T, false, false>);
+  return launch_lds("gumbel_topk_kernel", kernel, grid, block, cached ? base + cache : base, st, a, idx, y_sel, lse, y_soft, ret,
+                    gumbel_out);
 }
 
 // ---- backward of K1 (+K2):  grad_logits[p,n] = (1/tau) sum_b y_bn (a_bn - sum_m y_bm a_bm), a non-zero only at idx
@@ -1313,13 +1301,11 @@ __global__ void gather_bwd_kernel(const T *__restrict__ matches, const int32_t *
 
 }  // namespace dr
 
+// (the entries have checked the arguments: DR_GUMBEL_BWD_CHECK)
 template <typename T>
-static int gumbel_bwd_impl(const T *logits, const T *gumbel, uint64_t seed, const uint64_t *seed_ptr, T tau,
-                           int P, int B, int N, int k, const int32_t *idx, const T *lse, const T *a_sel,
-                           T *grad_logits, void *stream, const T *grad_samples = nullptr, const T *grad_w = nullptr,
-                           const T *matches4 = nullptr) {
-  DR_REQUIRE(idx && lse && grad_logits && (a_sel || (grad_samples && matches4)), "null pointer");
-  DR_REQUIRE(P > 0 && B > 0 && N > 0 && P <= 65535 && k >= 1 && k <= dr::kMaxK && tau > 0, "bad sizes");
+static int gumbel_bwd_launch(const T *logits, const T *gumbel, uint64_t seed, const uint64_t *seed_ptr, T tau, int P, int B, int N,
+                             int k, const int32_t *idx, const T *lse, const T *a_sel, T *grad_logits, void *stream,
+                             const T *grad_samples = nullptr, const T *grad_w = nullptr, const T *matches4 = nullptr) {
   dr::GumbelArgs<T> a{logits, gumbel, seed, tau, P, B, N, k, seed_ptr};
   const size_t smem = sizeof(T) * 256 * 2;
   const int gx = ((N + 3) / 4 + 255) / 256;
@@ -1330,34 +1316,16 @@ static int gumbel_bwd_impl(const T *logits, const T *gumbel, uint64_t seed, cons
   chunks = (B + rows_per_block - 1) / rows_per_block;
   if (hipMemsetAsync(grad_logits, 0, sizeof(T) * (size_t)P * N, (hipStream_t)stream) != hipSuccess)
     return dr::check_launch("memset");
-  hipLaunchKernelGGL((dr::gumbel_bwd_kernel<T>), dim3(gx, P, chunks), dim3(256), smem, (hipStream_t)stream, a, idx,
-                     lse, a_sel, grad_logits, rows_per_block, grad_samples, grad_w, matches4);
-  return dr::check_launch("gumbel_bwd_kernel");
-}
-static int gumbel_bwd_f32_impl(const float *logits, const float *gumbel, uint64_t seed, const uint64_t *seed_ptr, float tau,
-                               int P, int B, int N, int k, const int32_t *idx, const float *lse, const float *a_sel,
-                               float *grad_logits, void *stream) {
-  return gumbel_bwd_impl<float>(logits, gumbel, seed, seed_ptr, tau, P, B, N, k, idx, lse, a_sel, grad_logits, stream);
+  return dr::launch_lds("gumbel_bwd_kernel", dr::gumbel_bwd_kernel<T>, dim3(gx, P, chunks), 256, smem, stream, a, idx, lse, a_sel,
+                        grad_logits, rows_per_block, grad_samples, grad_w, matches4);
 }
 
 template <typename T>
-static int topdown_impl(const T *logits, uint64_t seed, const uint64_t *seed_ptr, int P, int B, int N, int k, double *cdf_ws,
-                        int32_t *idx, void *stream) {
-  DR_REQUIRE(P > 0 && B > 0 && N > 0 && k > 0 && k <= dr::kMaxK && k <= N && P <= 65535, "bad sizes");
-  DR_REQUIRE(cdf_ws && idx, "null pointer");
-  hipLaunchKernelGGL((dr::softmax_cdf_kernel<T>), dim3(P), dim3(1024), 0, (hipStream_t)stream, logits, N, cdf_ws);
-  if (int rc = dr::check_launch("softmax_cdf_kernel")) return rc;
-  hipLaunchKernelGGL(dr::topdown_sample_kernel, dim3((B + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, cdf_ws, seed, B,
-                     N, k, idx, seed_ptr);
-  return dr::check_launch("topdown_sample_kernel");
-}
-
-static int uniform_impl(uint64_t seed, const uint64_t *seed_ptr, int P, int B, int k, int N, int32_t *idx, void *stream) {
-  DR_REQUIRE(idx, "null pointer");
-  DR_REQUIRE(P > 0 && B > 0 && k > 0 && N > 1 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL(dr::uniform_sample_kernel, dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, seed,
-                     B, k, N, idx, seed_ptr);
-  return dr::check_launch("uniform_sample_kernel");
+static int topdown_launch(const T *logits, uint64_t seed, const uint64_t *seed_ptr, int P, int B, int N, int k, double *cdf_ws,
+                          int32_t *idx, void *stream) {
+  if (int rc = dr::launch("softmax_cdf_kernel", dr::softmax_cdf_kernel<T>, dim3(P), 1024, stream, logits, N, cdf_ws)) return rc;
+  return dr::launch("topdown_sample_kernel", dr::topdown_sample_kernel, dim3((B + 255) / 256, P), 256, stream, cdf_ws, seed, B, N, k,
+                    idx, seed_ptr);
 }
 
 extern "C" {
@@ -1375,50 +1343,60 @@ extern "C" {
 // advances such a seed on the device); it serves the in-kernel noise of given logits (no explicit noise, no dense outputs)
 #define DR_SEED_DEV_CHECK()                                                                                              \
   DR_REQUIRE(!seed_dev || (logits && !gumbel && !y_soft && !ret && !gumbel_out), "a device seed serves the in-kernel noise of given logits only")
-int dr_gumbel_topk_fwd_f32(const float *logits, const float *gumbel, uint64_t seed, const uint64_t *seed_dev, float tau, int P, int B,
-                           int N, int k, int32_t *idx, float *y_sel, float *lse, float *y_soft, float *ret,
-                           float *gumbel_out, void *stream) {
-  DR_GUMBEL_CHECK();
-  DR_SEED_DEV_CHECK();
-  return dr::gumbel_fwd_launch<float>(logits, gumbel, seed, tau, P, B, N, k, idx, y_sel, lse, y_soft, ret, gumbel_out,
-                                      (hipStream_t)stream, seed_dev);
-}
 
-int dr_gumbel_topk_fwd_f64(const double *logits, const double *gumbel, uint64_t seed, const uint64_t *seed_dev, double tau, int P,
-                           int B, int N, int k, int32_t *idx, double *y_sel, double *lse, double *y_soft, double *ret,
-                           double *gumbel_out, void *stream) {
-  DR_GUMBEL_CHECK();
-  DR_SEED_DEV_CHECK();
-  return dr::gumbel_fwd_launch<double>(logits, gumbel, seed, tau, P, B, N, k, idx, y_sel, lse, y_soft, ret,
-                                       gumbel_out, (hipStream_t)stream, seed_dev);
-}
+// the backward entries; `a` = where the row sums come from: a_sel, or grad_samples and the correspondences
+#define DR_GUMBEL_BWD_CHECK(a)                                       \
+  DR_REQUIRE(idx && lse && grad_logits && (a), "null pointer"); \
+  DR_REQUIRE(P > 0 && B > 0 && N > 0 && P <= 65535 && k >= 1 && k <= dr::kMaxK && tau > 0, "bad sizes")
+
+#define DR_TOPDOWN_CHECK()                                                                                  \
+  DR_REQUIRE(P > 0 && B > 0 && N > 0 && k > 0 && k <= dr::kMaxK && k <= N && P <= 65535, "bad sizes"); \
+  DR_REQUIRE(cdf_ws && idx, "null pointer")
+
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_gumbel_topk_fwd_##sfx(const T *logits, const T *gumbel, uint64_t seed, const uint64_t *seed_dev, T tau, int P, int B,      \
+                               int N, int k, int32_t *idx, T *y_sel, T *lse, T *y_soft, T *ret, T *gumbel_out, void *stream) {      \
+    DR_GUMBEL_CHECK();                                                                                                              \
+    DR_SEED_DEV_CHECK();                                                                                                            \
+    return dr::gumbel_fwd_launch<T>(logits, gumbel, seed, tau, P, B, N, k, idx, y_sel, lse, y_soft, ret, gumbel_out,                \
+                                    (hipStream_t)stream, seed_dev);                                                                 \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 int dr_gumbel_topk_bwd_f32(const float *logits, const float *gumbel, uint64_t seed, const uint64_t *seed_dev, float tau, int P, int B,
                            int N, int k, const int32_t *idx, const float *lse, const float *a_sel, float *grad_logits,
                            void *stream) {
   DR_REQUIRE(!seed_dev || (logits && !gumbel), "a device seed serves the in-kernel noise of given logits only");
-  return gumbel_bwd_f32_impl(logits, gumbel, seed, seed_dev, tau, P, B, N, k, idx, lse, a_sel, grad_logits, stream);
+  DR_GUMBEL_BWD_CHECK(a_sel);
+  return gumbel_bwd_launch<float>(logits, gumbel, seed, seed_dev, tau, P, B, N, k, idx, lse, a_sel, grad_logits, stream);
 }
 
 // f64 (`-pr 2 -tr 1`, model_cl.py:164-169): the same kernel in double (general form: two logarithms + an exponential per element)
 int dr_gumbel_topk_bwd_f64(const double *logits, const double *gumbel, uint64_t seed, double tau, int P, int B, int N,
                            int k, const int32_t *idx, const double *lse, const double *a_sel, double *grad_logits,
                            void *stream) {
-  return gumbel_bwd_impl<double>(logits, gumbel, seed, nullptr, tau, P, B, N, k, idx, lse, a_sel, grad_logits, stream);
+  DR_GUMBEL_BWD_CHECK(a_sel);
+  return gumbel_bwd_launch<double>(logits, gumbel, seed, nullptr, tau, P, B, N, k, idx, lse, a_sel, grad_logits, stream);
 }
 
 int dr_topdown_sample_f32(const float *logits, uint64_t seed, const uint64_t *seed_dev, int P, int B, int N, int k, double *cdf_ws,
                           int32_t *idx, void *stream) {
-  return topdown_impl<float>(logits, seed, seed_dev, P, B, N, k, cdf_ws, idx, stream);
+  DR_TOPDOWN_CHECK();
+  return topdown_launch<float>(logits, seed, seed_dev, P, B, N, k, cdf_ws, idx, stream);
 }
 
 int dr_topdown_sample_f64(const double *logits, uint64_t seed, int P, int B, int N, int k, double *cdf_ws, int32_t *idx,
                           void *stream) {
-  return topdown_impl<double>(logits, seed, nullptr, P, B, N, k, cdf_ws, idx, stream);
+  DR_TOPDOWN_CHECK();
+  return topdown_launch<double>(logits, seed, nullptr, P, B, N, k, cdf_ws, idx, stream);
 }
 
 int dr_uniform_sample(uint64_t seed, const uint64_t *seed_dev, int P, int B, int k, int N, int32_t *idx, void *stream) {
-  return uniform_impl(seed, seed_dev, P, B, k, N, idx, stream);
+  DR_REQUIRE(idx, "null pointer");
+  DR_REQUIRE(P > 0 && B > 0 && k > 0 && N > 1 && P <= 65535, "bad sizes");
+  return dr::launch("uniform_sample_kernel", dr::uniform_sample_kernel, dim3((B * k + 255) / 256, P), 256, stream, seed, B, k, N, idx,
+                    seed_dev);
 }
 
 // ---- the same samplers with the Philox key read from device memory (*seed_dev) when the kernel starts: what a captured
@@ -1426,28 +1404,7 @@ int dr_uniform_sample(uint64_t seed, const uint64_t *seed_dev, int P, int B, int
 int dr_seed_next_n(uint64_t *state, uint64_t *seeds_out, int n, void *stream) {
   DR_REQUIRE(state && seeds_out, "null pointer");
   DR_REQUIRE(n >= 1 && n <= 65536, "1 <= n <= 65536 seeds per launch");
-  hipLaunchKernelGGL(dr::seed_next_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, seeds_out, n);
-  return dr::check_launch("seed_next_kernel");
-}
-
-// K1 (index sets only) + K2 in one call: idx [P,B,k] and samples [P,B,k,4] = matches[p, idx] (test mode: the points themselves,
-// ransac.py:65).  One launch when the register kernel serves the shape, sampler + gather launches otherwise.
-static int gumbel_topk_gather_impl(const float *logits, const float *matches, uint64_t seed, const uint64_t *seed_dev, float tau, int P,
-                                   int B, int N, int k, int32_t *idx, float *samples, dr::PairGate gate, void *stream,
-                                   int sub = 0, float *race_ws = nullptr, bool race_ready = false) {
-  const float *y_sel = nullptr, *lse = nullptr, *y_soft = nullptr, *ret = nullptr;
-  DR_REQUIRE(logits && matches && samples, "null pointer");
-  DR_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(samples) & 15) == 0, "16-byte alignment");
-  DR_GUMBEL_CHECK();
-  bool gathered = false;
-  if (int rc = dr::gumbel_fwd_launch<float>(logits, nullptr, seed, tau, P, B, N, k, idx, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                            (hipStream_t)stream, seed_dev, reinterpret_cast<const float4 *>(matches),
-                                            reinterpret_cast<float4 *>(samples), &gathered, nullptr, gate, sub, race_ws, race_ready))
-    return rc;
-  if (gathered) return 0;
-  hipLaunchKernelGGL((dr::gather_fwd_kernel<float>), dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, matches, idx,
-                     (const float *)nullptr, N, B * k, 4, samples);
-  return dr::check_launch("gather_fwd_kernel");
+  return dr::launch("seed_next_kernel", dr::seed_next_kernel, dim3(1), 64, stream, state, seeds_out, n);
 }
 
 // Train mode (round 5): K1 with the soft-max statistics + K2 in one call -- idx, y_sel [P,B,k], lse [P,B] and samples [P,B,k,4] =
@@ -1470,9 +1427,8 @@ int dr_gumbel_topk_gather_soft_f32(const float *logits, const float *matches, ui
                                             reinterpret_cast<float4 *>(samples), &gathered, nullptr, dr::PairGate(), 0, race_ws, false))
     return rc;
   if (gathered) return 0;
-  hipLaunchKernelGGL((dr::gather_fwd_kernel<float>), dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, matches, idx,
-                     (const float *)y_sel, N, B * k, 4, samples);
-  return dr::check_launch("gather_fwd_kernel");
+  return dr::launch("gather_fwd_kernel", dr::gather_fwd_kernel<float>, dim3((B * k + 255) / 256, P), 256, stream, matches, idx, y_sel, N,
+                    B * k, 4, samples);
 }
 
 // ... and its backward in one launch: grad_logits [P,N] from grad_samples [P,B,k,4] (and grad_w [P,B,k] | null, the gradient of the
@@ -1482,11 +1438,14 @@ int dr_gumbel_topk_gather_bwd_f32(const float *logits, const float *matches, uin
                                   int P, int B, int N, int k, const int32_t *idx, const float *lse, const float *grad_samples,
                                   const float *grad_w, float *grad_logits, void *stream) {
   DR_REQUIRE(logits && matches && grad_samples, "null pointer");
-  return gumbel_bwd_impl<float>(logits, nullptr, seed, seed_dev, tau, P, B, N, k, idx, lse, nullptr, grad_logits, stream,
-                                grad_samples, grad_w, matches);
+  DR_GUMBEL_BWD_CHECK(grad_samples && matches);
+  return gumbel_bwd_launch<float>(logits, nullptr, seed, seed_dev, tau, P, B, N, k, idx, lse, nullptr, grad_logits, stream, grad_samples,
+                                  grad_w, matches);
 }
 
-// THE test-mode sampler entry (round 6: `_gated` folded in).  gate_iters / gate_max_iters (optional: a round > 1 of a multi-round
+// THE test-mode sampler entry (round 6: `_gated` folded in): K1 (index sets only) + K2 in one call: idx [P,B,k] and samples [P,B,k,4] =
+// matches[p, idx] (test mode: the points themselves, ransac.py:65).  One launch when the register kernel serves the shape, sampler +
+// gather launches otherwise.  gate_iters / gate_max_iters (optional: a round > 1 of a multi-round
 // call): pairs whose iteration counter has reached its bound are skipped (gate_iters [P] int32, gate_max_iters [P] f64: the state
 // dr_ransac_update keeps; the rows of a skipped pair keep their contents).
 // Only the register-resident kernel (N <= 2048, N % 4 == 0, tau = 1) looks at the gate; other shapes simply run.
@@ -1500,10 +1459,21 @@ int dr_gumbel_topk_gather_f32(const float *logits, const float *matches, uint64_
   DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither");
   DR_REQUIRE(sub >= 0, "sub-batch size");
   DR_REQUIRE((reinterpret_cast<uintptr_t>(race_ws) & 15) == 0, "workspace alignment");
+  const float *y_sel = nullptr, *lse = nullptr, *y_soft = nullptr, *ret = nullptr;
+  DR_REQUIRE(logits && matches && samples, "null pointer");
+  DR_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(samples) & 15) == 0, "16-byte alignment");
+  DR_GUMBEL_CHECK();
   dr::PairGate gate;
   gate.iters = gate_iters;
   gate.max_iters = gate_max_iters;
-  return gumbel_topk_gather_impl(logits, matches, seed, seed_dev, tau, P, B, N, k, idx, samples, gate, stream, sub, race_ws, race_ready != 0);
+  bool gathered = false;
+  if (int rc = dr::gumbel_fwd_launch<float>(logits, nullptr, seed, tau, P, B, N, k, idx, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                            (hipStream_t)stream, seed_dev, reinterpret_cast<const float4 *>(matches),
+                                            reinterpret_cast<float4 *>(samples), &gathered, nullptr, gate, sub, race_ws, race_ready != 0))
+    return rc;
+  if (gathered) return 0;
+  return dr::launch("gather_fwd_kernel", dr::gather_fwd_kernel<float>, dim3((B * k + 255) / 256, P), 256, stream, matches, idx, nullptr,
+                    N, B * k, 4, samples);
 }
 
 // K1, index sets only, in-kernel noise, with an optional screening workspace ((N + 32) * P words, 16-byte aligned): long rows
@@ -1518,42 +1488,22 @@ int dr_gumbel_topk_index_f32(const float *logits, uint64_t seed, const uint64_t 
                                       (hipStream_t)stream, seed_dev, nullptr, nullptr, nullptr, screen_ws);
 }
 
-int dr_gather_fwd_f32(const float *matches, const int32_t *idx, const float *y_sel, int P, int N, int B, int k,
-                      int c, float *samples, void *stream) {
-  DR_REQUIRE(matches && idx && samples, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0 && B > 0 && k > 0 && c > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL((dr::gather_fwd_kernel<float>), dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream,
-                     matches, idx, y_sel, N, B * k, c, samples);
-  return dr::check_launch("gather_fwd_kernel");
-}
-
-int dr_gather_fwd_f64(const double *matches, const int32_t *idx, const double *y_sel, int P, int N, int B, int k,
-                      int c, double *samples, void *stream) {
-  DR_REQUIRE(matches && idx && samples, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0 && B > 0 && k > 0 && c > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL((dr::gather_fwd_kernel<double>), dim3((B * k + 255) / 256, P), dim3(256), 0,
-                     (hipStream_t)stream, matches, idx, y_sel, N, B * k, c, samples);
-  return dr::check_launch("gather_fwd_kernel");
-}
-
-int dr_gather_bwd_f32(const float *matches, const int32_t *idx, const float *y_sel, const float *grad_samples,
-                      const float *grad_w, int P, int N, int B, int k, int c, float *a_sel, float *grad_matches,
-                      void *stream) {
-  DR_REQUIRE(matches && idx && grad_samples && a_sel, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0 && B > 0 && k > 0 && c > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL((dr::gather_bwd_kernel<float>), dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream,
-                     matches, idx, y_sel, grad_samples, grad_w, N, B * k, c, a_sel, grad_matches);
-  return dr::check_launch("gather_bwd_kernel");
-}
-
-int dr_gather_bwd_f64(const double *matches, const int32_t *idx, const double *y_sel, const double *grad_samples,
-                      const double *grad_w, int P, int N, int B, int k, int c, double *a_sel, double *grad_matches,
-                      void *stream) {
-  DR_REQUIRE(matches && idx && grad_samples && a_sel, "null pointer");
-  DR_REQUIRE(P > 0 && N > 0 && B > 0 && k > 0 && c > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL((dr::gather_bwd_kernel<double>), dim3((B * k + 255) / 256, P), dim3(256), 0, (hipStream_t)stream,
-                     matches, idx, y_sel, grad_samples, grad_w, N, B * k, c, a_sel, grad_matches);
-  return dr::check_launch("gather_bwd_kernel");
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_gather_fwd_##sfx(const T *matches, const int32_t *idx, const T *y_sel, int P, int N, int B, int k, int c, T *samples,      \
+                          void *stream) {                                                                                           \
+    DR_REQUIRE(matches && idx && samples, "null pointer");                                                                          \
+    DR_REQUIRE(P > 0 && N > 0 && B > 0 && k > 0 && c > 0 && P <= 65535, "bad sizes");                                               \
+    return dr::launch("gather_fwd_kernel", dr::gather_fwd_kernel<T>, dim3((B * k + 255) / 256, P), 256, stream, matches, idx,       \
+                      y_sel, N, B * k, c, samples);                                                                                 \
+  }                                                                                                                                 \
+  int dr_gather_bwd_##sfx(const T *matches, const int32_t *idx, const T *y_sel, const T *grad_samples, const T *grad_w, int P,      \
+                          int N, int B, int k, int c, T *a_sel, T *grad_matches, void *stream) {                                    \
+    DR_REQUIRE(matches && idx && grad_samples && a_sel, "null pointer");                                                            \
+    DR_REQUIRE(P > 0 && N > 0 && B > 0 && k > 0 && c > 0 && P <= 65535, "bad sizes");                                               \
+    return dr::launch("gather_bwd_kernel", dr::gather_bwd_kernel<T>, dim3((B * k + 255) / 256, P), 256, stream, matches, idx,       \
+                      y_sel, grad_samples, grad_w, N, B * k, c, a_sel, grad_matches);                                               \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"

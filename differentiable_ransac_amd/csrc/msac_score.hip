@@ -899,10 +899,8 @@ int msac_score_launch(const T *matches, const T *models, const uint8_t *valid, c
     if (N <= kSmallMaxN) {   // short rows: a wave per model (BASELINE configs[0])
       const dim3 g((M + kSmallTile - 1) / kSmallTile, 1, P), b(kSmallWaves * 64);
       const float *mt = (const float *)matches, *md = (const float *)models, *th = (const float *)thr;
-      if (N <= 64) hipLaunchKernelGGL(msac_score_kernel_f32_small<1>, g, b, 0, st, mt, md, valid, th, M, N, (float *)scores, masks);
-      else if (N <= 128) hipLaunchKernelGGL(msac_score_kernel_f32_small<2>, g, b, 0, st, mt, md, valid, th, M, N, (float *)scores, masks);
-      else hipLaunchKernelGGL(msac_score_kernel_f32_small<4>, g, b, 0, st, mt, md, valid, th, M, N, (float *)scores, masks);
-      return check_launch("msac_score_kernel_f32_small");
+      const auto kernel = N <= 64 ? msac_score_kernel_f32_small<1> : N <= 128 ? msac_score_kernel_f32_small<2> : msac_score_kernel_f32_small<4>;
+      return launch("msac_score_kernel_f32_small", kernel, g, b, st, mt, md, valid, th, M, N, (float *)scores, masks);
     }
   }
   // (16-byte mask stores: whole rows and a 16-byte aligned base -- a caller may pass a slice of a larger buffer)
@@ -926,24 +924,16 @@ int msac_score_launch(const T *matches, const T *models, const uint8_t *valid, c
   }
   dim3 grid(tiles, ny, P);
   if constexpr (kFast) {
-    if (fast16) {
-      hipLaunchKernelGGL(msac_score_kernel_f32_fast16, grid, dim3(kT16), 0, st, (const float *)matches,
-                         (const float *)models, valid, (const float *)thr, M, N, (float *)scores, masks, masks ? 1 : 0,
-                         cpb, use_atomic, small_grid ? kSmallGridTile : kFastTile, gate);
-      return check_launch("msac_score_kernel");
-    }
-    hipLaunchKernelGGL(msac_score_kernel_f32_fast, grid, dim3(kThreads), 0, st, (const float *)matches,
-                       (const float *)models, valid, (const float *)thr, M, N, (float *)scores, masks, masks ? 1 : 0,
-                       cpb, use_atomic);
+    if (fast16)
+      return launch("msac_score_kernel", msac_score_kernel_f32_fast16, grid, kT16, st, (const float *)matches, (const float *)models,
+                    valid, (const float *)thr, M, N, (float *)scores, masks, masks ? 1 : 0, cpb, use_atomic,
+                    small_grid ? kSmallGridTile : kFastTile, gate);
+    return launch("msac_score_kernel", msac_score_kernel_f32_fast, grid, kThreads, st, (const float *)matches, (const float *)models,
+                  valid, (const float *)thr, M, N, (float *)scores, masks, masks ? 1 : 0, cpb, use_atomic);
   } else {
-    if (masks)
-      hipLaunchKernelGGL((msac_score_kernel<T, true>), grid, dim3(kThreads), 0, st, matches, models, valid, thr, M, N,
-                         scores, masks, cpb, use_atomic);
-    else
-      hipLaunchKernelGGL((msac_score_kernel<T, false>), grid, dim3(kThreads), 0, st, matches, models, valid, thr, M, N,
-                         scores, masks, cpb, use_atomic);
+    return launch("msac_score_kernel", masks ? msac_score_kernel<T, true> : msac_score_kernel<T, false>, grid, kThreads, st, matches,
+                  models, valid, thr, M, N, scores, masks, cpb, use_atomic);
   }
-  return check_launch("msac_score_kernel");
 }
 
 }  // namespace dr
@@ -972,100 +962,50 @@ int dr_msac_score_f64(const double *matches, const double *models, const uint8_t
   return dr::msac_score_launch<double>(matches, models, valid, thr, P, M, N, scores, masks, (hipStream_t)stream);
 }
 
-int dr_select_best_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores,
-                       const float *thr, int P, int M, int N, int32_t *best_idx, float *best_score,
-                       float *best_model, uint8_t *best_mask, int32_t *inliers, void *stream) {
-  DR_REQUIRE(matches && models && scores && thr && best_idx && best_score, "null pointer");
-  DR_REQUIRE(P > 0 && M > 0 && N > 0, "bad sizes");
-  hipLaunchKernelGGL((dr::select_best_kernel<float>), dim3(P), dim3(dr::kThreads), 0, (hipStream_t)stream, matches,
-                     models, valid, scores, thr, M, N, best_idx, best_score, best_model, best_mask, inliers);
-  return dr::check_launch("select_best_kernel");
-}
-
-int dr_refit_accept_f32(const float *matches, const float *cand, const uint8_t *cand_valid, const float *thr, int P, int S,
-                        int N, float *best_score, float *best_model, void *stream) {
-  DR_REQUIRE(P > 0 && S > 0 && N > 0, "bad sizes");
-  DR_REQUIRE(matches && cand && thr && best_score && best_model, "null pointer");
-  hipLaunchKernelGGL((dr::refit_accept_kernel<float>), dim3(P), dim3(dr::kThreads), 0, (hipStream_t)stream, matches, cand,
-                     cand_valid, thr, S, N, best_score, best_model);
-  return dr::check_launch("refit_accept_kernel");
-}
-
-int dr_refit_accept_f64(const double *matches, const double *cand, const uint8_t *cand_valid, const double *thr, int P,
-                        int S, int N, double *best_score, double *best_model, void *stream) {
-  DR_REQUIRE(P > 0 && S > 0 && N > 0, "bad sizes");
-  DR_REQUIRE(matches && cand && thr && best_score && best_model, "null pointer");
-  hipLaunchKernelGGL((dr::refit_accept_kernel<double>), dim3(P), dim3(dr::kThreads), 0, (hipStream_t)stream, matches, cand,
-                     cand_valid, thr, S, N, best_score, best_model);
-  return dr::check_launch("refit_accept_kernel");
-}
-
-int dr_ransac_init_f32(const float *K1, const float *K2, int k_stride, double threshold, int P, int N,
-                       int max_iterations, float *thr, float *best_score, float *best_model, uint8_t *best_mask,
-                       int32_t *best_inliers, int32_t *iters, double *max_iters, uint64_t *seed_state, uint64_t *seeds_out,
-                       int n_seeds, const float *race_logits, float *race_ws, void *stream) {
-  DR_REQUIRE(P > 0 && N > 0 && (k_stride == 0 || k_stride == 9), "bad sizes");
-  DR_REQUIRE((race_logits == nullptr) == (race_ws == nullptr), "race weights: logits and workspace, or neither");
-  DR_REQUIRE(thr && best_score && best_model && best_mask && best_inliers && iters && max_iters && (!K1 == !K2),
-             "null pointer");
-  DR_REQUIRE(!seed_state || (seeds_out && n_seeds >= 1 && n_seeds <= 65536), "seed state: need seeds_out and 1 <= n_seeds <= 65536");
-  hipLaunchKernelGGL((dr::ransac_init_kernel<float>), dim3(P), dim3(256), 0, (hipStream_t)stream, K1, K2, k_stride,
-                     (float)threshold, N, max_iterations, thr, best_score, best_model, best_mask, best_inliers, iters,
-                     max_iters, seed_state, seeds_out, n_seeds, race_logits, race_ws, P);
-  return dr::check_launch("ransac_init_kernel");
-}
-
-int dr_ransac_init_f64(const double *K1, const double *K2, int k_stride, double threshold, int P, int N,
-                       int max_iterations, double *thr, double *best_score, double *best_model, uint8_t *best_mask,
-                       int32_t *best_inliers, int32_t *iters, double *max_iters, uint64_t *seed_state, uint64_t *seeds_out,
-                       int n_seeds, const float *race_logits, float *race_ws, void *stream) {
-  DR_REQUIRE(P > 0 && N > 0 && (k_stride == 0 || k_stride == 9), "bad sizes");
-  DR_REQUIRE((race_logits == nullptr) == (race_ws == nullptr), "race weights: logits and workspace, or neither");
-  DR_REQUIRE(thr && best_score && best_model && best_mask && best_inliers && iters && max_iters && (!K1 == !K2),
-             "null pointer");
-  DR_REQUIRE(!seed_state || (seeds_out && n_seeds >= 1 && n_seeds <= 65536), "seed state: need seeds_out and 1 <= n_seeds <= 65536");
-  hipLaunchKernelGGL((dr::ransac_init_kernel<double>), dim3(P), dim3(256), 0, (hipStream_t)stream, K1, K2, k_stride,
-                     threshold, N, max_iterations, thr, best_score, best_model, best_mask, best_inliers, iters,
-                     max_iters, seed_state, seeds_out, n_seeds, race_logits, race_ws, P);
-  return dr::check_launch("ransac_init_kernel");
-}
-
-int dr_ransac_update_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores,
-                         const float *thr, int P, int M, int N, int B, int k, double confidence, double eps,
-                         int max_iterations, float *best_score, float *best_model, uint8_t *best_mask,
-                         int32_t *best_inliers, int32_t *iters, double *max_iters, int sub_models, void *stream) {
-  DR_REQUIRE(matches && models && scores && thr && best_score && best_model && best_mask && best_inliers && iters &&
-                 max_iters, "null pointer");
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && k > 0, "bad sizes");
-  DR_REQUIRE(sub_models >= 0 && (sub_models == 0 || (M + sub_models - 1) / sub_models <= dr::kUpdMaxSub), "sub-batches per launch");
-  hipLaunchKernelGGL((dr::ransac_update_kernel<float>), dim3(P), dim3(dr::kUpdThreads), 0, (hipStream_t)stream,
-                     matches, models, valid, scores, thr, M, N, B, k, confidence, eps, max_iterations, best_score,
-                     best_model, best_mask, best_inliers, iters, max_iters, sub_models);
-  return dr::check_launch("ransac_update_kernel");
-}
-
-int dr_ransac_update_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores,
-                         const double *thr, int P, int M, int N, int B, int k, double confidence, double eps,
-                         int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
-                         int32_t *best_inliers, int32_t *iters, double *max_iters, int sub_models, void *stream) {
-  DR_REQUIRE(matches && models && scores && thr && best_score && best_model && best_mask && best_inliers && iters &&
-                 max_iters, "null pointer");
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && k > 0, "bad sizes");
-  DR_REQUIRE(sub_models >= 0 && (sub_models == 0 || (M + sub_models - 1) / sub_models <= dr::kUpdMaxSub), "sub-batches per launch");
-  hipLaunchKernelGGL((dr::ransac_update_kernel<double>), dim3(P), dim3(dr::kUpdThreads), 0, (hipStream_t)stream,
-                     matches, models, valid, scores, thr, M, N, B, k, confidence, eps, max_iterations, best_score,
-                     best_model, best_mask, best_inliers, iters, max_iters, sub_models);
-  return dr::check_launch("ransac_update_kernel");
-}
-
-int dr_select_best_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores,
-                       const double *thr, int P, int M, int N, int32_t *best_idx, double *best_score,
-                       double *best_model, uint8_t *best_mask, int32_t *inliers, void *stream) {
-  DR_REQUIRE(matches && models && scores && thr && best_idx && best_score, "null pointer");
-  DR_REQUIRE(P > 0 && M > 0 && N > 0, "bad sizes");
-  hipLaunchKernelGGL((dr::select_best_kernel<double>), dim3(P), dim3(dr::kThreads), 0, (hipStream_t)stream, matches,
-                     models, valid, scores, thr, M, N, best_idx, best_score, best_model, best_mask, inliers);
-  return dr::check_launch("select_best_kernel");
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_select_best_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr, int P, int M,    \
+                           int N, int32_t *best_idx, T *best_score, T *best_model, uint8_t *best_mask, int32_t *inliers,            \
+                           void *stream) {                                                                                          \
+    DR_REQUIRE(matches && models && scores && thr && best_idx && best_score, "null pointer");                                       \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0, "bad sizes");                                                                               \
+    return dr::launch("select_best_kernel", dr::select_best_kernel<T>, dim3(P), dr::kThreads, stream, matches, models, valid,       \
+                      scores, thr, M, N, best_idx, best_score, best_model, best_mask, inliers);                                     \
+  }                                                                                                                                 \
+  int dr_refit_accept_##sfx(const T *matches, const T *cand, const uint8_t *cand_valid, const T *thr, int P, int S, int N,          \
+                            T *best_score, T *best_model, void *stream) {                                                           \
+    DR_REQUIRE(P > 0 && S > 0 && N > 0, "bad sizes");                                                                               \
+    DR_REQUIRE(matches && cand && thr && best_score && best_model, "null pointer");                                                 \
+    return dr::launch("refit_accept_kernel", dr::refit_accept_kernel<T>, dim3(P), dr::kThreads, stream, matches, cand, cand_valid,  \
+                      thr, S, N, best_score, best_model);                                                                           \
+  }                                                                                                                                 \
+  int dr_ransac_init_##sfx(const T *K1, const T *K2, int k_stride, double threshold, int P, int N, int max_iterations, T *thr,      \
+                           T *best_score, T *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,                 \
+                           double *max_iters, uint64_t *seed_state, uint64_t *seeds_out, int n_seeds, const float *race_logits,     \
+                           float *race_ws, void *stream) {                                                                          \
+    DR_REQUIRE(P > 0 && N > 0 && (k_stride == 0 || k_stride == 9), "bad sizes");                                                    \
+    DR_REQUIRE((race_logits == nullptr) == (race_ws == nullptr), "race weights: logits and workspace, or neither");                 \
+    DR_REQUIRE(thr && best_score && best_model && best_mask && best_inliers && iters && max_iters && (!K1 == !K2),                  \
+               "null pointer");                                                                                                     \
+    DR_REQUIRE(!seed_state || (seeds_out && n_seeds >= 1 && n_seeds <= 65536),                                                      \
+               "seed state: need seeds_out and 1 <= n_seeds <= 65536");                                                             \
+    return dr::launch("ransac_init_kernel", dr::ransac_init_kernel<T>, dim3(P), 256, stream, K1, K2, k_stride, (T)threshold, N,     \
+                      max_iterations, thr, best_score, best_model, best_mask, best_inliers, iters, max_iters, seed_state,           \
+                      seeds_out, n_seeds, race_logits, race_ws, P);                                                                 \
+  }                                                                                                                                 \
+  int dr_ransac_update_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr, int P, int M,  \
+                             int N, int B, int k, double confidence, double eps, int max_iterations, T *best_score, T *best_model,  \
+                             uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters, int sub_models,          \
+                             void *stream) {                                                                                        \
+    DR_REQUIRE(matches && models && scores && thr && best_score && best_model && best_mask && best_inliers && iters && max_iters,   \
+               "null pointer");                                                                                                     \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && k > 0, "bad sizes");                                                             \
+    DR_REQUIRE(sub_models >= 0 && (sub_models == 0 || (M + sub_models - 1) / sub_models <= dr::kUpdMaxSub),                         \
+               "sub-batches per launch");                                                                                           \
+    return dr::launch("ransac_update_kernel", dr::ransac_update_kernel<T>, dim3(P), dr::kUpdThreads, stream, matches, models,       \
+                      valid, scores, thr, M, N, B, k, confidence, eps, max_iterations, best_score, best_model, best_mask,           \
+                      best_inliers, iters, max_iters, sub_models);                                                                  \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"

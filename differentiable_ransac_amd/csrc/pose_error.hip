@@ -429,98 +429,39 @@ __global__ __launch_bounds__(kPoseThreads) void recover_pose_mask_kernel(const T
   }
 }
 
-template <typename T>
-int pose_error_launch(const T *matches, const T *models, const T *gt_R, const T *gt_t, int P, int M, int N,
-                      double dist_thr, T *err_R, T *err_t, int32_t *which, int32_t *votes, hipStream_t st, int svd = 0) {
-  dim3 grid((M + kPoseTile - 1) / kPoseTile, P);
-  hipLaunchKernelGGL((pose_error_kernel<T>), grid, dim3(kPoseThreads), 0, st, matches, models, gt_R, gt_t, M, N, dist_thr,
-                     err_R, err_t, which, votes, svd);
-  return check_launch("pose_error_kernel");
-}
-
-template <typename T>
-int pose_error_bwd_launch(const T *models, const T *gt_R, const T *gt_t, const int32_t *which, const T *g_err_R,
-                          const T *g_err_t, int P, int M, T *grad_models, hipStream_t st) {
-  const size_t total = (size_t)P * M;
-  hipLaunchKernelGGL((pose_error_bwd_kernel<T>), dim3((unsigned)((total + 63) / 64)), dim3(64), 0, st, models, gt_R, gt_t,
-                     which, g_err_R, g_err_t, P, M, grad_models);
-  return check_launch("pose_error_bwd_kernel");
-}
-
 }  // namespace dr
 
 extern "C" {
 
-int dr_pose_error_fwd_f32(const float *matches, const float *models, const float *gt_R, const float *gt_t, int P, int M,
-                          int N, double distance_threshold, float *err_R, float *err_t, int32_t *which, int32_t *votes,
-                          void *stream) {
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  DR_REQUIRE(matches && models && gt_R && gt_t && err_R && err_t && which, "null pointer");
-  return dr::pose_error_launch<float>(matches, models, gt_R, gt_t, P, M, N, distance_threshold, err_R, err_t, which, votes,
-                                      (hipStream_t)stream);
-}
+#define DR_POSE_ERROR_FWD(name, svd, sfx, T)                                                                                       \
+  int dr_##name##_fwd_##sfx(const T *matches, const T *models, const T *gt_R, const T *gt_t, int P, int M, int N,                   \
+                            double distance_threshold, T *err_R, T *err_t, int32_t *which, int32_t *votes, void *stream) {          \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    DR_REQUIRE(matches && models && gt_R && gt_t && err_R && err_t && which, "null pointer");                                       \
+    return dr::launch("pose_error_kernel", dr::pose_error_kernel<T>, dim3((M + dr::kPoseTile - 1) / dr::kPoseTile, P),              \
+                      dr::kPoseThreads, stream, matches, models, gt_R, gt_t, M, N, distance_threshold, err_R, err_t, which, votes,  \
+                      svd);                                                                                                         \
+  }
 
-int dr_pose_error_fwd_f64(const double *matches, const double *models, const double *gt_R, const double *gt_t, int P,
-                          int M, int N, double distance_threshold, double *err_R, double *err_t, int32_t *which,
-                          int32_t *votes, void *stream) {
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  DR_REQUIRE(matches && models && gt_R && gt_t && err_R && err_t && which, "null pointer");
-  return dr::pose_error_launch<double>(matches, models, gt_R, gt_t, P, M, N, distance_threshold, err_R, err_t, which,
-                                       votes, (hipStream_t)stream);
-}
-
-int dr_pose_error_svd_fwd_f32(const float *matches, const float *models, const float *gt_R, const float *gt_t, int P, int M,
-                              int N, double distance_threshold, float *err_R, float *err_t, int32_t *which, int32_t *votes,
-                              void *stream) {
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  DR_REQUIRE(matches && models && gt_R && gt_t && err_R && err_t && which, "null pointer");
-  return dr::pose_error_launch<float>(matches, models, gt_R, gt_t, P, M, N, distance_threshold, err_R, err_t, which, votes,
-                                      (hipStream_t)stream, 1);
-}
-
-int dr_pose_error_svd_fwd_f64(const double *matches, const double *models, const double *gt_R, const double *gt_t, int P,
-                              int M, int N, double distance_threshold, double *err_R, double *err_t, int32_t *which,
-                              int32_t *votes, void *stream) {
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  DR_REQUIRE(matches && models && gt_R && gt_t && err_R && err_t && which, "null pointer");
-  return dr::pose_error_launch<double>(matches, models, gt_R, gt_t, P, M, N, distance_threshold, err_R, err_t, which,
-                                       votes, (hipStream_t)stream, 1);
-}
-
-int dr_pose_error_bwd_f32(const float *models, const float *gt_R, const float *gt_t, const int32_t *which,
-                          const float *grad_err_R, const float *grad_err_t, int P, int M, float *grad_models,
-                          void *stream) {
-  DR_REQUIRE(P > 0 && M > 0, "bad sizes");
-  DR_REQUIRE(models && gt_R && gt_t && which && grad_err_R && grad_err_t && grad_models, "null pointer");
-  return dr::pose_error_bwd_launch<float>(models, gt_R, gt_t, which, grad_err_R, grad_err_t, P, M, grad_models,
-                                          (hipStream_t)stream);
-}
-
-int dr_pose_error_bwd_f64(const double *models, const double *gt_R, const double *gt_t, const int32_t *which,
-                          const double *grad_err_R, const double *grad_err_t, int P, int M, double *grad_models,
-                          void *stream) {
-  DR_REQUIRE(P > 0 && M > 0, "bad sizes");
-  DR_REQUIRE(models && gt_R && gt_t && which && grad_err_R && grad_err_t && grad_models, "null pointer");
-  return dr::pose_error_bwd_launch<double>(models, gt_R, gt_t, which, grad_err_R, grad_err_t, P, M, grad_models,
-                                           (hipStream_t)stream);
-}
-
-int dr_recover_pose_mask_f32(const float *matches, const float *models, int P, int M, int N, double distance_threshold,
-                             int32_t *which, uint8_t *mask, void *stream) {
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  DR_REQUIRE(matches && models && mask, "null pointer");
-  hipLaunchKernelGGL((dr::recover_pose_mask_kernel<float>), dim3(M, P), dim3(dr::kPoseThreads), 0, (hipStream_t)stream, matches,
-                     models, M, N, distance_threshold, which, mask);
-  return dr::check_launch("recover_pose_mask_kernel");
-}
-
-int dr_recover_pose_mask_f64(const double *matches, const double *models, int P, int M, int N, double distance_threshold,
-                             int32_t *which, uint8_t *mask, void *stream) {
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  DR_REQUIRE(matches && models && mask, "null pointer");
-  hipLaunchKernelGGL((dr::recover_pose_mask_kernel<double>), dim3(M, P), dim3(dr::kPoseThreads), 0, (hipStream_t)stream, matches,
-                     models, M, N, distance_threshold, which, mask);
-  return dr::check_launch("recover_pose_mask_kernel");
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  DR_POSE_ERROR_FWD(pose_error, 0, sfx, T)                                                                                          \
+  DR_POSE_ERROR_FWD(pose_error_svd, 1, sfx, T)                                                                                      \
+  int dr_pose_error_bwd_##sfx(const T *models, const T *gt_R, const T *gt_t, const int32_t *which, const T *grad_err_R,             \
+                              const T *grad_err_t, int P, int M, T *grad_models, void *stream) {                                    \
+    DR_REQUIRE(P > 0 && M > 0, "bad sizes");                                                                                        \
+    DR_REQUIRE(models && gt_R && gt_t && which && grad_err_R && grad_err_t && grad_models, "null pointer");                         \
+    const size_t total = (size_t)P * M;                                                                                             \
+    return dr::launch("pose_error_bwd_kernel", dr::pose_error_bwd_kernel<T>, dim3((unsigned)((total + 63) / 64)), 64, stream,       \
+                      models, gt_R, gt_t, which, grad_err_R, grad_err_t, P, M, grad_models);                                        \
+  }                                                                                                                                 \
+  int dr_recover_pose_mask_##sfx(const T *matches, const T *models, int P, int M, int N, double distance_threshold,                 \
+                                 int32_t *which, uint8_t *mask, void *stream) {                                                     \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    DR_REQUIRE(matches && models && mask, "null pointer");                                                                          \
+    return dr::launch("recover_pose_mask_kernel", dr::recover_pose_mask_kernel<T>, dim3(M, P), dr::kPoseThreads, stream, matches,   \
+                      models, M, N, distance_threshold, which, mask);                                                               \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"

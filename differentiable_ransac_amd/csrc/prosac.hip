@@ -97,9 +97,8 @@ int dr_prosac_sample(const int32_t *order, const int64_t *growth, uint64_t seed,
   DR_REQUIRE(N >= k, "N must be at least k");
   DR_REQUIRE(P >= 1 && B >= 1 && P <= 65535, "bad sizes");
   DR_REQUIRE(t0 >= 0, "t0 must not be negative");
-  hipLaunchKernelGGL(dr::prosac_sample_kernel, dim3((B + 255) / 256, P), dim3(256), 0, (hipStream_t)stream, order, growth, seed,
-                     seed_dev, t0, B, N, k, idx);
-  return dr::check_launch("prosac_sample_kernel");
+  return dr::launch("prosac_sample_kernel", dr::prosac_sample_kernel, dim3((B + 255) / 256, P), 256, stream, order, growth, seed,
+                    seed_dev, t0, B, N, k, idx);
 }
 
 }  // extern "C"

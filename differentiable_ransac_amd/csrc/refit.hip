@@ -226,31 +226,17 @@ template <typename T>
 int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *models,
                  uint8_t *valid, hipStream_t st) {
   const size_t smem = sizeof(double) * kRefitLdsDoubles;
-  static bool attr_e = false, attr_p = false, attr_f = false;
   if (fundamental) {
-    if (!attr_f) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&refit_fundamental_kernel<T>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      attr_f = true;
-    }
-    hipLaunchKernelGGL((refit_fundamental_kernel<T>), dim3(P), dim3(kRefT), smem, st, matches, mask, weights, N, models, valid);
-  } else if (P >= kRefitPairFinishMinPairs) {
-    const size_t smem_p = std::max(smem, sizeof(double) * (size_t)kNisterPairDoubles);   // the solver's workspace, overlaid
-    if (!attr_p) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&refit_essential_kernel<T, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_p);
-      attr_p = true;
-    }
-    hipLaunchKernelGGL((refit_essential_kernel<T, true>), dim3(P), dim3(kRefT), smem_p, st, matches, mask, N, models, valid);
-  } else {
-    if (!attr_e) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&refit_essential_kernel<T, false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-      attr_e = true;
-    }
-    hipLaunchKernelGGL((refit_essential_kernel<T, false>), dim3(P), dim3(kRefT), smem, st, matches, mask, N, models, valid);
+    allow_dynamic_lds<refit_fundamental_kernel<T>>(smem);
+    return launch_lds("refit_kernel", refit_fundamental_kernel<T>, dim3(P), kRefT, smem, st, matches, mask, weights, N, models, valid);
   }
-  return check_launch("refit_kernel");
+  if (P >= kRefitPairFinishMinPairs) {
+    const size_t smem_p = std::max(smem, sizeof(double) * (size_t)kNisterPairDoubles);   // the solver's workspace, overlaid
+    allow_dynamic_lds<refit_essential_kernel<T, true>>(smem_p);
+    return launch_lds("refit_kernel", refit_essential_kernel<T, true>, dim3(P), kRefT, smem_p, st, matches, mask, N, models, valid);
+  }
+  allow_dynamic_lds<refit_essential_kernel<T, false>>(smem);
+  return launch_lds("refit_kernel", refit_essential_kernel<T, false>, dim3(P), kRefT, smem, st, matches, mask, N, models, valid);
 }
 
 
@@ -366,83 +352,50 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 
   }
 }
 
-template <typename T, int kMode>
-static void local_opt_go(int P, hipStream_t st, const T *matches, const T *thr, int N, int iters, int k, double confidence,
-                         double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask, int32_t *best_inliers,
-                         double *max_iters, T *lo_seen, int32_t *lo_refits) {
+template <typename T, int kMode, typename... Args>
+int local_opt_go(int P, void *stream, Args... args) {
   constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
   const size_t smem = sizeof(double) * (((kWs + 3) & ~3) + 90 + 2);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&local_opt_kernel<T, kMode>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr = true;
-  }
-  hipLaunchKernelGGL((local_opt_kernel<T, kMode>), dim3(P), dim3(kRefT), smem, st, matches, thr, N, iters, k, confidence, eps,
-                     max_iterations, best_score, best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits);
+  allow_dynamic_lds<local_opt_kernel<T, kMode>>(smem);
+  return launch_lds("local_opt_kernel", local_opt_kernel<T, kMode>, dim3(P), kRefT, smem, stream, args...);
 }
 
-template <typename T>
-int local_opt_launch(const T *matches, const T *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
-                     double confidence, double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask,
-                     int32_t *best_inliers, double *max_iters, T *lo_seen, int32_t *lo_refits, hipStream_t st) {
-  DR_REQUIRE(matches && thr && best_score && best_model && best_mask && best_inliers && max_iters && lo_seen, "null pointer");
-  DR_REQUIRE(P > 0 && N >= (fundamental ? 8 : 5) && k > 0, "bad sizes");
-  DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");
-  DR_REQUIRE(lo == 1 || lo_iters >= 1, "lo_iters must be at least 1");
-  const int iters = lo == 1 ? 1 : lo_iters;
-  if (fundamental)
-    local_opt_go<T, 0>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
-                       best_inliers, max_iters, lo_seen, lo_refits);
-  else if (P >= kRefitPairFinishMinPairs)
-    local_opt_go<T, 2>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
-                       best_inliers, max_iters, lo_seen, lo_refits);
-  else
-    local_opt_go<T, 1>(P, st, matches, thr, N, iters, k, confidence, eps, max_iterations, best_score, best_model, best_mask,
-                       best_inliers, max_iters, lo_seen, lo_refits);
-  return check_launch("local_opt_kernel");
+// args: the kernel's own argument list
+template <typename T, typename... Args>
+int local_opt_launch(bool fundamental, int P, void *stream, Args... args) {
+  if (fundamental) return local_opt_go<T, 0>(P, stream, args...);
+  if (P >= kRefitPairFinishMinPairs) return local_opt_go<T, 2>(P, stream, args...);
+  return local_opt_go<T, 1>(P, stream, args...);
 }
 
 }  // namespace dr
 
 extern "C" {
 
-int dr_refit_essential_f32(const float *matches, const uint8_t *mask, int P, int N, float *models, uint8_t *valid,
-                           void *stream) {
-  DR_REQUIRE(matches && models && valid, "null pointer");
-  DR_REQUIRE(P > 0 && N >= 5, "bad sizes");
-  return dr::refit_launch<float>(false, matches, mask, nullptr, P, N, models, valid, (hipStream_t)stream);
-}
-int dr_refit_essential_f64(const double *matches, const uint8_t *mask, int P, int N, double *models, uint8_t *valid,
-                           void *stream) {
-  DR_REQUIRE(matches && models && valid, "null pointer");
-  DR_REQUIRE(P > 0 && N >= 5, "bad sizes");
-  return dr::refit_launch<double>(false, matches, mask, nullptr, P, N, models, valid, (hipStream_t)stream);
-}
-int dr_refit_fundamental_f32(const float *matches, const uint8_t *mask, const float *weights, int P, int N, float *models,
-                             uint8_t *valid, void *stream) {
-  DR_REQUIRE(matches && models && valid, "null pointer");
-  DR_REQUIRE(P > 0 && N >= 8, "bad sizes");
-  return dr::refit_launch<float>(true, matches, mask, weights, P, N, models, valid, (hipStream_t)stream);
-}
-int dr_refit_fundamental_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *models,
-                             uint8_t *valid, void *stream) {
-  DR_REQUIRE(matches && models && valid, "null pointer");
-  DR_REQUIRE(P > 0 && N >= 8, "bad sizes");
-  return dr::refit_launch<double>(true, matches, mask, weights, P, N, models, valid, (hipStream_t)stream);
-}
-
-int dr_local_opt_f32(const float *matches, const float *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
-                     double confidence, double eps, int max_iterations, float *best_score, float *best_model, uint8_t *best_mask,
-                     int32_t *best_inliers, double *max_iters, float *lo_seen, int32_t *lo_refits, void *stream) {
-  return dr::local_opt_launch<float>(matches, thr, P, N, fundamental, lo, lo_iters, k, confidence, eps, max_iterations, best_score,
-                                     best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, (hipStream_t)stream);
-}
-int dr_local_opt_f64(const double *matches, const double *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,
-                     double confidence, double eps, int max_iterations, double *best_score, double *best_model, uint8_t *best_mask,
-                     int32_t *best_inliers, double *max_iters, double *lo_seen, int32_t *lo_refits, void *stream) {
-  return dr::local_opt_launch<double>(matches, thr, P, N, fundamental, lo, lo_iters, k, confidence, eps, max_iterations, best_score,
-                                      best_model, best_mask, best_inliers, max_iters, lo_seen, lo_refits, (hipStream_t)stream);
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_refit_essential_##sfx(const T *matches, const uint8_t *mask, int P, int N, T *models, uint8_t *valid, void *stream) {      \
+    DR_REQUIRE(matches && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(P > 0 && N >= 5, "bad sizes");                                                                                       \
+    return dr::refit_launch<T>(false, matches, mask, nullptr, P, N, models, valid, (hipStream_t)stream);                            \
+  }                                                                                                                                 \
+  int dr_refit_fundamental_##sfx(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *models, uint8_t *valid,  \
+                                 void *stream) {                                                                                    \
+    DR_REQUIRE(matches && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(P > 0 && N >= 8, "bad sizes");                                                                                       \
+    return dr::refit_launch<T>(true, matches, mask, weights, P, N, models, valid, (hipStream_t)stream);                             \
+  }                                                                                                                                 \
+  int dr_local_opt_##sfx(const T *matches, const T *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,                \
+                         double confidence, double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask,       \
+                         int32_t *best_inliers, double *max_iters, T *lo_seen, int32_t *lo_refits, void *stream) {                  \
+    DR_REQUIRE(matches && thr && best_score && best_model && best_mask && best_inliers && max_iters && lo_seen, "null pointer");    \
+    DR_REQUIRE(P > 0 && N >= (fundamental ? 8 : 5) && k > 0, "bad sizes");                                                          \
+    DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");                                              \
+    DR_REQUIRE(lo == 1 || lo_iters >= 1, "lo_iters must be at least 1");                                                            \
+    return dr::local_opt_launch<T>(fundamental != 0, P, stream, matches, thr, N, lo == 1 ? 1 : lo_iters, k, confidence, eps,       \
+                                   max_iterations, best_score, best_model, best_mask, best_inliers, max_iters, lo_seen,            \
+                                   lo_refits);                                                                                      \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"

@@ -943,13 +943,6 @@ __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *
   }
 }
 
-// one launch on the caller's stream -> status
-template <typename... Params, typename... Args>
-int launch(const char *name, void (*kernel)(Params...), dim3 grid, int threads, void *stream, Args... args) {
-  hipLaunchKernelGGL(kernel, grid, dim3(threads), 0, (hipStream_t)stream, args...);
-  return check_launch(name);
-}
-
 template <typename T, typename Term>
 int launch_rigid_score(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
                        int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
@@ -961,10 +954,6 @@ int launch_rigid_score(const T *matches, const T *models, const uint8_t *valid, 
 }
 
 }  // namespace dr
-
-// ---- the C entries: every op is written once, DR_F32_F64 makes its _f32 and _f64 symbols; an op's argument checks stand at the top of
-// its body (DR_REQUIRE names the symbol in the message), the launch below them
-#define DR_F32_F64(OP) OP(f32, float) OP(f64, double)
 
 extern "C" {
 

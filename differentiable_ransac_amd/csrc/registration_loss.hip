@@ -187,32 +187,15 @@ __global__ __launch_bounds__(256) void registration_gt_mask_kernel(const T *__re
   if (tid == 0) count[p] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
 }
 
+// the loss value (and, kGrad, its unscaled gradient) per model, then the means
 template <typename T, bool kGrad>
-int registration_loss_entry(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2, int P, int M,
-                            int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) {
-  hipLaunchKernelGGL((registration_loss_kernel<T, kGrad>), dim3((M + 63) / 64, P), dim3(64), 0, (hipStream_t)stream, matches, mask,
-                     models, keep, thr2, M, N, sums, grad_unscaled);
-  if (int rc = check_launch("registration_loss_kernel")) return rc;
-  hipLaunchKernelGGL((registration_loss_mean_kernel<T>), dim3(1), dim3(kRLMeanT), 0, (hipStream_t)stream, sums, mask, keep, P, M, N,
-                     per_pair, coef, mean);
-  return check_launch("registration_loss_mean_kernel");
-}
-
-template <typename T>
-int registration_loss_scale_entry(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,
-                                  void *stream) {
-  const size_t total = (size_t)P * M * 16;
-  hipLaunchKernelGGL((registration_loss_scale_kernel<T>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     grad_unscaled, coef, grad_mean, T(1) / (T)P, (size_t)M * 16, total, grad_models);
-  return check_launch("registration_loss_scale_kernel");
-}
-
-template <typename T>
-int registration_gt_mask_entry(const T *matches, const T *gt_pose, const T *thr2, int P, int N, uint8_t *mask, int32_t *count,
-                               void *stream) {
-  hipLaunchKernelGGL((registration_gt_mask_kernel<T>), dim3(P), dim3(256), 0, (hipStream_t)stream, matches, gt_pose, thr2, N, mask,
-                     count);
-  return check_launch("registration_gt_mask_kernel");
+int registration_loss_launch(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2, int P, int M,
+                             int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) {
+  if (int rc = launch("registration_loss_kernel", registration_loss_kernel<T, kGrad>, dim3((M + 63) / 64, P), 64, stream, matches, mask,
+                      models, keep, thr2, M, N, sums, grad_unscaled))
+    return rc;
+  return launch("registration_loss_mean_kernel", registration_loss_mean_kernel<T>, dim3(1), kRLMeanT, stream, sums, mask, keep, P, M, N,
+                per_pair, coef, mean);
 }
 
 }  // namespace dr
@@ -222,35 +205,39 @@ extern "C" {
 #define DR_REGISTRATION_LOSS_SIZES \
   DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535 && (long)P * M < (1l << 22), "need P, M, N > 0, P <= 65535 and P M < 2^22")
 
-#define DR_REGISTRATION_LOSS_ENTRIES(T, sfx)                                                                                             \
-  int dr_registration_loss_fused_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,    \
-                                       int P, int M, int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) { \
-    DR_REQUIRE(matches && models && thr2 && sums && grad_unscaled && per_pair && coef && mean, "null pointer");                       \
-    DR_REGISTRATION_LOSS_SIZES;                                                                                                        \
-    return dr::registration_loss_entry<T, true>(matches, mask, models, keep, thr2, P, M, N, sums, grad_unscaled, per_pair, coef,       \
-                                                mean, stream);                                                                         \
-  }                                                                                                                                    \
-  int dr_registration_loss_fwd_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,      \
-                                     int P, int M, int N, T *sums, T *per_pair, T *coef, T *mean, void *stream) {                      \
-    DR_REQUIRE(matches && models && thr2 && sums && per_pair && coef && mean, "null pointer");                                        \
-    DR_REGISTRATION_LOSS_SIZES;                                                                                                        \
-    return dr::registration_loss_entry<T, false>(matches, mask, models, keep, thr2, P, M, N, sums, (T *)nullptr, per_pair, coef,       \
-                                                 mean, stream);                                                                        \
-  }                                                                                                                                    \
-  int dr_registration_loss_scale_##sfx(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,       \
-                                       void *stream) {                                                                                 \
-    DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");                                                    \
-    DR_REQUIRE(P > 0 && M > 0 && (long)P * M < (1l << 22), "need P, M > 0 and P M < 2^22");                                            \
-    return dr::registration_loss_scale_entry<T>(grad_unscaled, coef, grad_mean, P, M, grad_models, stream);                            \
-  }                                                                                                                                    \
-  int dr_registration_gt_mask_##sfx(const T *matches, const T *gt_pose, const T *thr2, int P, int N, uint8_t *mask, int32_t *count,   \
-                                    void *stream) {                                                                                    \
-    DR_REQUIRE(matches && gt_pose && thr2 && mask && count, "null pointer");                                                          \
-    DR_REQUIRE(P > 0 && N > 0, "need P, N > 0");                                                                                       \
-    return dr::registration_gt_mask_entry<T>(matches, gt_pose, thr2, P, N, mask, count, stream);                                       \
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_registration_loss_fused_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,  \
+                                       int P, int M, int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean,               \
+                                       void *stream) {                                                                              \
+    DR_REQUIRE(matches && models && thr2 && sums && grad_unscaled && per_pair && coef && mean, "null pointer");                     \
+    DR_REGISTRATION_LOSS_SIZES;                                                                                                     \
+    return dr::registration_loss_launch<T, true>(matches, mask, models, keep, thr2, P, M, N, sums, grad_unscaled, per_pair, coef,   \
+                                                 mean, stream);                                                                     \
+  }                                                                                                                                 \
+  int dr_registration_loss_fwd_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,    \
+                                     int P, int M, int N, T *sums, T *per_pair, T *coef, T *mean, void *stream) {                   \
+    DR_REQUIRE(matches && models && thr2 && sums && per_pair && coef && mean, "null pointer");                                      \
+    DR_REGISTRATION_LOSS_SIZES;                                                                                                     \
+    return dr::registration_loss_launch<T, false>(matches, mask, models, keep, thr2, P, M, N, sums, (T *)nullptr, per_pair, coef,   \
+                                                  mean, stream);                                                                    \
+  }                                                                                                                                 \
+  int dr_registration_loss_scale_##sfx(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,     \
+                                       void *stream) {                                                                              \
+    DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");                                                  \
+    DR_REQUIRE(P > 0 && M > 0 && (long)P * M < (1l << 22), "need P, M > 0 and P M < 2^22");                                         \
+    const size_t total = (size_t)P * M * 16;                                                                                        \
+    return dr::launch("registration_loss_scale_kernel", dr::registration_loss_scale_kernel<T>,                                      \
+                      dim3((unsigned)((total + 255) / 256)), 256, stream, grad_unscaled, coef, grad_mean, T(1) / (T)P,              \
+                      (size_t)M * 16, total, grad_models);                                                                          \
+  }                                                                                                                                 \
+  int dr_registration_gt_mask_##sfx(const T *matches, const T *gt_pose, const T *thr2, int P, int N, uint8_t *mask,                 \
+                                    int32_t *count, void *stream) {                                                                 \
+    DR_REQUIRE(matches && gt_pose && thr2 && mask && count, "null pointer");                                                        \
+    DR_REQUIRE(P > 0 && N > 0, "need P, N > 0");                                                                                    \
+    return dr::launch("registration_gt_mask_kernel", dr::registration_gt_mask_kernel<T>, dim3(P), 256, stream, matches, gt_pose,    \
+                      thr2, N, mask, count);                                                                                        \
   }
-
-DR_REGISTRATION_LOSS_ENTRIES(float, f32)
-DR_REGISTRATION_LOSS_ENTRIES(double, f64)
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"

@@ -321,34 +321,23 @@ static inline bool fivepoint_two_phase(int Bt, int fb_cost_pct) {
 template <typename T>
 int nister_launch(const T *samples, const T *weights, int Bt, int n, T *models, uint8_t *valid, hipStream_t st,
                   double *models64 = nullptr, int path = 0, PairGate gate = PairGate(), int per_pair = 1) {
-  static bool attr_set[64] = {false};   // per device: one process may drive several GPUs
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&nister5_kernel<T>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(double) * kFiveWs * 64));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
   if (n == 5) {
     // minimal samples: two lanes per sample; LDS per 32-sample block: 100 doubles per sample for the constraint solve,
     // later basis + B(z) / candidate queue + root-search workspace (36.5 KiB => four blocks per CU, one per SIMD)
     const size_t smem = sizeof(double) * kNisterPairDoubles;
     if (path == 2 || (path == 0 && fivepoint_two_phase(Bt, kFbCostNister))) {
       static_assert(70 * 64 <= kNisterPairDoubles, "front stage: rows 0-6 of 64 right blocks");
-      hipLaunchKernelGGL((nister5_fb_kernel<T>), dim3((Bt + 63) / 64), dim3(64), smem, st, samples, weights, Bt, models, valid,
-                         models64, gate, per_pair);
-      return check_launch("nister5_fb_kernel");
+      return launch_lds("nister5_fb_kernel", nister5_fb_kernel<T>, dim3((Bt + 63) / 64), 64, smem, st, samples, weights, Bt, models,
+                        valid, models64, gate, per_pair);
     }
     const int spb = samples_per_block(Bt);
-    hipLaunchKernelGGL((nister5_pair_kernel<T>), dim3((Bt + spb - 1) / spb), dim3(64), smem, st, samples, weights, Bt, models,
-                       valid, models64, spb, gate, per_pair);
-    return check_launch("nister5_pair_kernel");
+    return launch_lds("nister5_pair_kernel", nister5_pair_kernel<T>, dim3((Bt + spb - 1) / spb), 64, smem, st, samples, weights, Bt,
+                      models, valid, models64, spb, gate, per_pair);
   }
   // n > 5 fallback (refit): one lane per sample, A^T A + eigenvectors in LDS (162 doubles)
   const size_t smem = sizeof(double) * kFiveWs * 64;
-  hipLaunchKernelGGL((nister5_kernel<T>), dim3((Bt + 63) / 64), dim3(64), smem, st, samples, weights, Bt, n, models,
-                     valid);
-  return check_launch("nister5_kernel");
+  allow_dynamic_lds<nister5_kernel<T>>(smem);
+  return launch_lds("nister5_kernel", nister5_kernel<T>, dim3((Bt + 63) / 64), 64, smem, st, samples, weights, Bt, n, models, valid);
 }
 
 template <typename T>
@@ -362,15 +351,13 @@ int stewenius_launch(const T *samples, int Bt, T *models, uint8_t *valid, hipStr
     constexpr int kBack = (SturmWs<10>::kDoubles > FinishQueue::kDoubles ? SturmWs<10>::kDoubles : FinishQueue::kDoubles) + 60 * 32;
     constexpr int kFb = 70 * 64 > kBack ? 70 * 64 : kBack;
     static_assert(kFb * sizeof(double) <= 40960, "four blocks per CU");
-    hipLaunchKernelGGL((stewenius5_fb_kernel<T>), dim3((Bt + 63) / 64), dim3(64), sizeof(double) * kFb, st, samples, Bt, models,
-                       valid, gate, per_pair);
-    return check_launch("stewenius5_fb_kernel");
+    return launch_lds("stewenius5_fb_kernel", stewenius5_fb_kernel<T>, dim3((Bt + 63) / 64), 64, sizeof(double) * kFb, st, samples,
+                      Bt, models, valid, gate, per_pair);
   }
   const size_t smem = sizeof(double) * kDoubles;
   const int spb = samples_per_block(Bt);
-  hipLaunchKernelGGL((stewenius5_pair_kernel<T>), dim3((Bt + spb - 1) / spb), dim3(64), smem, st, samples, Bt, models, valid, spb,
-                     gate, per_pair);
-  return check_launch("stewenius5_pair_kernel");
+  return launch_lds("stewenius5_pair_kernel", stewenius5_pair_kernel<T>, dim3((Bt + spb - 1) / spb), 64, smem, st, samples, Bt,
+                    models, valid, spb, gate, per_pair);
 }
 
 // ---- test hook: the real-root search of the two-lanes-per-sample kernels on given degree-10 polynomials -------------------
@@ -438,11 +425,9 @@ int dr_debug_real_roots10(const double *coef, int n, int method, double *roots, 
   constexpr int kD = dr::RootWs<10>::kDoubles > dr::SturmWs<10>::kDoubles ? dr::RootWs<10>::kDoubles : dr::SturmWs<10>::kDoubles;
   const size_t smem = sizeof(double) * kD;
   if (method == 1)   // (the Sturm search's own workspace, 19.7 KB: eight blocks per CU fit when the kernel is built for two waves per SIMD)
-    hipLaunchKernelGGL((dr::debug_roots10_kernel<1>), dim3((n + 31) / 32), dim3(64), sizeof(double) * dr::SturmWs<10>::kDoubles,
-                       (hipStream_t)stream, coef, n, roots, counts);
-  else
-    hipLaunchKernelGGL((dr::debug_roots10_kernel<0>), dim3((n + 31) / 32), dim3(64), smem, (hipStream_t)stream, coef, n, roots, counts);
-  return dr::check_launch("debug_roots10_kernel");
+    return dr::launch_lds("debug_roots10_kernel", dr::debug_roots10_kernel<1>, dim3((n + 31) / 32), 64,
+                          sizeof(double) * dr::SturmWs<10>::kDoubles, stream, coef, n, roots, counts);
+  return dr::launch_lds("debug_roots10_kernel", dr::debug_roots10_kernel<0>, dim3((n + 31) / 32), 64, smem, stream, coef, n, roots, counts);
 }
 
 int dr_solve_stewenius5_f32(const float *samples, int Bt, float *models, uint8_t *valid, int path, int per_pair,

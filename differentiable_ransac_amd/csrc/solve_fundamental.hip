@@ -188,37 +188,28 @@ __global__ __launch_bounds__(64) void f7_kernel(const T *__restrict__ samples, i
     }
 }
 
-template <typename T>
-int f8_launch(const T *samples, const T *weights, int Bt, int n, T *models, uint8_t *valid, hipStream_t st) {
-  const size_t smem = (n == 8) ? 0 : sizeof(double) * kF8Ws * 64;
-  static bool attr_set[64] = {false};   // per device: one process may drive several GPUs
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&f8_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(sizeof(double) * kF8Ws * 64));
-    if (dev >= 0 && dev < 64) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL((f8_kernel<T, false>), dim3((Bt + 63) / 64), dim3(64), smem, st, samples, weights, Bt, n, models, valid);
-  return check_launch("f8_kernel");
-}
-
 }  // namespace dr
 
 extern "C" {
 
-int dr_solve_f8_f32(const float *samples, const float *weights, int Bt, int n, float *models, uint8_t *valid,
-                    void *stream) {
-  DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8 points per sample");
-  return dr::f8_launch<float>(samples, weights, Bt, n, models, valid, (hipStream_t)stream);
-}
-int dr_solve_f8_f64(const double *samples, const double *weights, int Bt, int n, double *models, uint8_t *valid,
-                    void *stream) {
-  DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8 points per sample");
-  return dr::f8_launch<double>(samples, weights, Bt, n, models, valid, (hipStream_t)stream);
-}
+// (n == 8 solves in registers; more points per sample need the per-lane LDS workspace)
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_solve_f8_##sfx(const T *samples, const T *weights, int Bt, int n, T *models, uint8_t *valid, void *stream) {               \
+    DR_REQUIRE(samples && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8 points per sample");                                                       \
+    const size_t ws = sizeof(double) * dr::kF8Ws * 64;                                                                              \
+    dr::allow_dynamic_lds<dr::f8_kernel<T, false>>(ws);                                                                             \
+    return dr::launch_lds("f8_kernel", dr::f8_kernel<T, false>, dim3((Bt + 63) / 64), 64, n == 8 ? 0 : ws, stream, samples,         \
+                          weights, Bt, n, models, valid, 0, nullptr, 0, 0, nullptr);                                                \
+  }                                                                                                                                 \
+  int dr_solve_f7_##sfx(const T *samples, int Bt, T *models, uint8_t *valid, void *stream) {                                        \
+    DR_REQUIRE(samples && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(Bt > 0, "need Bt > 0");                                                                                              \
+    return dr::launch("f7_kernel", dr::f7_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, Bt, models, valid);                 \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
 // K1u + K2 + K3f8 in one launch: P x B minimal samples of eight correspondences drawn by UniformSampler's rule (indices in
 // [0, N - 2]: the same index sets dr_uniform_sample draws for this seed), solved by the 8-point kernel; idx [P,B,8] may be NULL
 int dr_solve_f8_uniform_f32(const float *matches, uint64_t seed, const uint64_t *seed_dev, int P, int B, int N, int32_t *idx,
@@ -226,24 +217,8 @@ int dr_solve_f8_uniform_f32(const float *matches, uint64_t seed, const uint64_t 
   DR_REQUIRE(matches && models && valid, "null pointer");
   DR_REQUIRE(P > 0 && B > 0 && N > 1 && (long)P * B < (1l << 31), "bad sizes");
   const int Bt = P * B;
-  hipLaunchKernelGGL((dr::f8_kernel<float, true>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, matches,
-                     (const float *)nullptr, Bt, 8, models, valid, seed, seed_dev, B, N, idx);
-  return dr::check_launch("f8_kernel");
-}
-
-int dr_solve_f7_f32(const float *samples, int Bt, float *models, uint8_t *valid, void *stream) {
-  DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(Bt > 0, "need Bt > 0");
-  hipLaunchKernelGGL((dr::f7_kernel<float>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, Bt,
-                     models, valid);
-  return dr::check_launch("f7_kernel");
-}
-int dr_solve_f7_f64(const double *samples, int Bt, double *models, uint8_t *valid, void *stream) {
-  DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(Bt > 0, "need Bt > 0");
-  hipLaunchKernelGGL((dr::f7_kernel<double>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples, Bt,
-                     models, valid);
-  return dr::check_launch("f7_kernel");
+  return dr::launch("f8_kernel", dr::f8_kernel<float, true>, dim3((Bt + 63) / 64), 64, stream, matches, nullptr, Bt, 8, models, valid,
+                    seed, seed_dev, B, N, idx);
 }
 
 }  // extern "C"

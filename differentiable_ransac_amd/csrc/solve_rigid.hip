@@ -341,9 +341,8 @@ int rigid_residual_launch(const T *pts, const T *models, T threshold, int P, int
       const int cpb = 1;
       const int use_atomic = ny > 1 || sums_zeroed;   // (pre-zeroed sums are added to, never stored over)
       if (use_atomic && !sums_zeroed && hipMemsetAsync(res_sum, 0, sizeof(T) * (size_t)P * M, st) != hipSuccess) return check_launch("memset");
-      hipLaunchKernelGGL((rigid_residual_kernel_f32_pk<kPts>), dim3(tiles, ny, P), dim3(kR16Threads), 0, st, (const float *)pts,
-                         (const float *)models, (float)threshold, M, N, (float *)res_sum, masks, cpb, use_atomic, tile);
-      return check_launch("rigid_residual_kernel_f32_pk");
+      return launch("rigid_residual_kernel_f32_pk", rigid_residual_kernel_f32_pk<kPts>, dim3(tiles, ny, P), kR16Threads, st,
+                    (const float *)pts, (const float *)models, (float)threshold, M, N, (float *)res_sum, masks, cpb, use_atomic, tile);
     }
   }
   const int tiles = (M + kRModels - 1) / kRModels;
@@ -357,13 +356,8 @@ int rigid_residual_launch(const T *pts, const T *models, T threshold, int P, int
   if (use_atomic && !sums_zeroed && hipMemsetAsync(res_sum, 0, sizeof(T) * (size_t)P * M, st) != hipSuccess)
     return check_launch("memset");
   dim3 grid(tiles, ny, P);
-  if (masks)
-    hipLaunchKernelGGL((rigid_residual_kernel<T, true>), grid, dim3(kRThreads), 0, st, pts, models, threshold, M, N,
-                       res_sum, masks, cpb, use_atomic);
-  else
-    hipLaunchKernelGGL((rigid_residual_kernel<T, false>), grid, dim3(kRThreads), 0, st, pts, models, threshold, M, N,
-                       res_sum, masks, cpb, use_atomic);
-  return check_launch("rigid_residual_kernel");
+  return launch("rigid_residual_kernel", masks ? rigid_residual_kernel<T, true> : rigid_residual_kernel<T, false>, grid, kRThreads, st,
+                pts, models, threshold, M, N, res_sum, masks, cpb, use_atomic);
 }
 
 // ---- K6 of the 3-D path: per-pair arg-min of the residual sums, "is it better", best model and best mask on the device ----
@@ -454,9 +448,8 @@ int ransac3d_update_launch(const T *pts, const T *models, const uint8_t *valid, 
   int nblk = 1;
   if (best_mask) nblk = max(1, min((N + 511) / 512, max(1, 1024 / P)));
   const int ppb = (N + nblk - 1) / nblk;
-  hipLaunchKernelGGL((ransac3d_update_kernel<T>), dim3(nblk, P), dim3(kU3Threads), 0, st, pts, models, valid, res, threshold, M,
-                     N, ppb, best_res_in, best_model_in, best_res_out, best_model_out, best_mask, best_idx);
-  return check_launch("ransac3d_update_kernel");
+  return launch("ransac3d_update_kernel", ransac3d_update_kernel<T>, dim3(nblk, P), kU3Threads, st, pts, models, valid, res,
+                threshold, M, N, ppb, best_res_in, best_model_in, best_res_out, best_model_out, best_mask, best_idx);
 }
 
 // ---- K5: chosen[p,b] = the valid slot closest (Frobenius) to gt[p] -----------------------------------------
@@ -531,22 +524,16 @@ __global__ void select_closest_bwd_kernel(const T *__restrict__ grad_chosen, con
 
 extern "C" {
 
-int dr_solve_rigid_f32(const float *samples, const float *weights, int Bt, int n, int flag, float *models, float *R,
-                       float *t, float *scale, uint8_t *valid, void *stream) {
-  DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(Bt > 0 && n >= 3, "need Bt > 0 and n >= 3 correspondences per sample");
-  hipLaunchKernelGGL((dr::rigid_kernel<float>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples,
-                     weights, Bt, n, flag, models, R, t, scale, valid);
-  return dr::check_launch("rigid_kernel");
-}
-int dr_solve_rigid_f64(const double *samples, const double *weights, int Bt, int n, int flag, double *models,
-                       double *R, double *t, double *scale, uint8_t *valid, void *stream) {
-  DR_REQUIRE(samples && models && valid, "null pointer");
-  DR_REQUIRE(Bt > 0 && n >= 3, "need Bt > 0 and n >= 3 correspondences per sample");
-  hipLaunchKernelGGL((dr::rigid_kernel<double>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, samples,
-                     weights, Bt, n, flag, models, R, t, scale, valid);
-  return dr::check_launch("rigid_kernel");
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_solve_rigid_##sfx(const T *samples, const T *weights, int Bt, int n, int flag, T *models, T *R, T *t, T *scale,            \
+                           uint8_t *valid, void *stream) {                                                                          \
+    DR_REQUIRE(samples && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(Bt > 0 && n >= 3, "need Bt > 0 and n >= 3 correspondences per sample");                                              \
+    return dr::launch("rigid_kernel", dr::rigid_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, weights, Bt, n, flag, models, \
+                      R, t, scale, valid, nullptr, 0, 0, nullptr);                                                                  \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 // K2 + K3r in one launch (test mode of the 3-D driver): samples are read through the index sets, and (optionally) the residual
 // sums of the round are cleared on the way, so that dr_rigid_residual_acc_f32 needs no memset launch
@@ -555,9 +542,8 @@ int dr_solve_rigid_gather_f32(const float *matches, const int32_t *idx, int P, i
   DR_REQUIRE(matches && idx && models && valid, "null pointer");
   DR_REQUIRE(P > 0 && B > 0 && N > 0 && k >= 3 && (long)P * B < (1l << 31), "need P, B, N > 0 and k >= 3 correspondences per sample");
   const int Bt = P * B;
-  hipLaunchKernelGGL((dr::rigid_kernel<float>), dim3((Bt + 63) / 64), dim3(64), 0, (hipStream_t)stream, matches,
-                     (const float *)nullptr, Bt, k, flag, models, R, t, scale, valid, idx, B, N, zero_sums);
-  return dr::check_launch("rigid_kernel");
+  return dr::launch("rigid_kernel", dr::rigid_kernel<float>, dim3((Bt + 63) / 64), 64, stream, matches, nullptr, Bt, k, flag,
+                    models, R, t, scale, valid, idx, B, N, zero_sums);
 }
 
 // dr_rigid_residual_f32 with the sums ADDED to res_sum, which the caller (or dr_solve_rigid_gather_f32) has cleared
@@ -576,60 +562,32 @@ int dr_rigid_residual_f64(const double *pts, const double *models, double thresh
   return dr::rigid_residual_launch<double>(pts, models, threshold, P, M, N, res_sum, masks, (hipStream_t)stream);
 }
 
-int dr_ransac3d_update_f32(const float *pts, const float *models, const uint8_t *valid, const float *res, float threshold,
-                           int P, int M, int N, const float *best_res_in, const float *best_model_in, float *best_res_out,
-                           float *best_model_out, uint8_t *best_mask, int32_t *best_idx, void *stream) {
-  DR_REQUIRE(pts && models && res && best_res_out && best_model_out, "null pointer");
-  DR_REQUIRE((best_res_in == nullptr) == (best_model_in == nullptr), "first round: pass NULL for BOTH input states");
-  DR_REQUIRE(best_res_in != best_res_out && best_model_in != best_model_out, "the state is ping-ponged: in and out must differ");
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  return dr::ransac3d_update_launch<float>(pts, models, valid, res, threshold, P, M, N, best_res_in, best_model_in,
-                                           best_res_out, best_model_out, best_mask, best_idx, (hipStream_t)stream);
-}
-int dr_ransac3d_update_f64(const double *pts, const double *models, const uint8_t *valid, const double *res, double threshold,
-                           int P, int M, int N, const double *best_res_in, const double *best_model_in, double *best_res_out,
-                           double *best_model_out, uint8_t *best_mask, int32_t *best_idx, void *stream) {
-  DR_REQUIRE(pts && models && res && best_res_out && best_model_out, "null pointer");
-  DR_REQUIRE((best_res_in == nullptr) == (best_model_in == nullptr), "first round: pass NULL for BOTH input states");
-  DR_REQUIRE(best_res_in != best_res_out && best_model_in != best_model_out, "the state is ping-ponged: in and out must differ");
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");
-  return dr::ransac3d_update_launch<double>(pts, models, valid, res, threshold, P, M, N, best_res_in, best_model_in,
-                                            best_res_out, best_model_out, best_mask, best_idx, (hipStream_t)stream);
-}
-
-int dr_select_closest_f32(const float *models, const uint8_t *valid, const float *gt, int P, int B, int S,
-                          float *chosen, int32_t *which, uint8_t *keep, void *stream) {
-  DR_REQUIRE(models && gt && chosen && which, "null pointer");
-  DR_REQUIRE(P > 0 && B > 0 && S > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL((dr::select_closest_kernel<float>), dim3((B + 255) / 256, P), dim3(256), 0, (hipStream_t)stream,
-                     models, valid, gt, B, S, chosen, which, keep);
-  return dr::check_launch("select_closest_kernel");
-}
-int dr_select_closest_f64(const double *models, const uint8_t *valid, const double *gt, int P, int B, int S,
-                          double *chosen, int32_t *which, uint8_t *keep, void *stream) {
-  DR_REQUIRE(models && gt && chosen && which, "null pointer");
-  DR_REQUIRE(P > 0 && B > 0 && S > 0 && P <= 65535, "bad sizes");
-  hipLaunchKernelGGL((dr::select_closest_kernel<double>), dim3((B + 255) / 256, P), dim3(256), 0,
-                     (hipStream_t)stream, models, valid, gt, B, S, chosen, which, keep);
-  return dr::check_launch("select_closest_kernel");
-}
-int dr_select_closest_bwd_f32(const float *grad_chosen, const int32_t *which, int P, int B, int S, float *grad_models,
-                              void *stream) {
-  DR_REQUIRE(P > 0 && B > 0 && S > 0, "bad sizes");
-  DR_REQUIRE(grad_chosen && which && grad_models, "null pointer");
-  const size_t total = (size_t)P * B * S * 9;
-  hipLaunchKernelGGL((dr::select_closest_bwd_kernel<float>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, grad_chosen, which, total, S, grad_models);
-  return dr::check_launch("select_closest_bwd_kernel");
-}
-int dr_select_closest_bwd_f64(const double *grad_chosen, const int32_t *which, int P, int B, int S, double *grad_models,
-                              void *stream) {
-  DR_REQUIRE(P > 0 && B > 0 && S > 0, "bad sizes");
-  DR_REQUIRE(grad_chosen && which && grad_models, "null pointer");
-  const size_t total = (size_t)P * B * S * 9;
-  hipLaunchKernelGGL((dr::select_closest_bwd_kernel<double>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, grad_chosen, which, total, S, grad_models);
-  return dr::check_launch("select_closest_bwd_kernel");
-}
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_ransac3d_update_##sfx(const T *pts, const T *models, const uint8_t *valid, const T *res, T threshold, int P, int M,        \
+                               int N, const T *best_res_in, const T *best_model_in, T *best_res_out, T *best_model_out,             \
+                               uint8_t *best_mask, int32_t *best_idx, void *stream) {                                               \
+    DR_REQUIRE(pts && models && res && best_res_out && best_model_out, "null pointer");                                             \
+    DR_REQUIRE((best_res_in == nullptr) == (best_model_in == nullptr), "first round: pass NULL for BOTH input states");             \
+    DR_REQUIRE(best_res_in != best_res_out && best_model_in != best_model_out, "the state is ping-ponged: in and out must differ"); \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    return dr::ransac3d_update_launch<T>(pts, models, valid, res, threshold, P, M, N, best_res_in, best_model_in, best_res_out,     \
+                                         best_model_out, best_mask, best_idx, (hipStream_t)stream);                                 \
+  }                                                                                                                                 \
+  int dr_select_closest_##sfx(const T *models, const uint8_t *valid, const T *gt, int P, int B, int S, T *chosen, int32_t *which,   \
+                              uint8_t *keep, void *stream) {                                                                        \
+    DR_REQUIRE(models && gt && chosen && which, "null pointer");                                                                    \
+    DR_REQUIRE(P > 0 && B > 0 && S > 0 && P <= 65535, "bad sizes");                                                                 \
+    return dr::launch("select_closest_kernel", dr::select_closest_kernel<T>, dim3((B + 255) / 256, P), 256, stream, models, valid,  \
+                      gt, B, S, chosen, which, keep);                                                                               \
+  }                                                                                                                                 \
+  int dr_select_closest_bwd_##sfx(const T *grad_chosen, const int32_t *which, int P, int B, int S, T *grad_models, void *stream) {  \
+    DR_REQUIRE(P > 0 && B > 0 && S > 0, "bad sizes");                                                                               \
+    DR_REQUIRE(grad_chosen && which && grad_models, "null pointer");                                                                \
+    const size_t total = (size_t)P * B * S * 9;                                                                                     \
+    return dr::launch("select_closest_bwd_kernel", dr::select_closest_bwd_kernel<T>, dim3((unsigned)((total + 255) / 256)), 256,    \
+                      stream, grad_chosen, which, total, S, grad_models);                                                           \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
 
 }  // extern "C"
