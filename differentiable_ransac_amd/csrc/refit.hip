@@ -9,6 +9,7 @@
 // The ragged inlier sets never leave the device.
 #include <algorithm>
 #include "fivepoint_device.hpp"
+#include "magsac_device.hpp"
 #include "ransac_device.hpp"
 
 namespace dr {
@@ -44,7 +45,8 @@ __device__ __forceinline__ void gram_accumulate(const T *__restrict__ mt, const 
                      ((double)mt[4 * n + 2] - mu[2]) * r2, ((double)mt[4 * n + 3] - mu[3]) * r2,
                      wt ? (double)wt[n] : 1.0, row);   // weights scale the ROWS (fundamental_matrix_estimator.py:243-244)
     else
-      epipolar_row_5pt((double)mt[4 * n], (double)mt[4 * n + 1], (double)mt[4 * n + 2], (double)mt[4 * n + 3], 1.0, row);
+      epipolar_row_5pt((double)mt[4 * n], (double)mt[4 * n + 1], (double)mt[4 * n + 2], (double)mt[4 * n + 3],
+                       wt ? (double)wt[n] : 1.0, row);   // (1.0: the unweighted row, bit for bit)
     int q = 0;
 #pragma unroll
     for (int i = 0; i < 9; ++i)
@@ -81,17 +83,18 @@ __device__ __forceinline__ void gram_accumulate(const T *__restrict__ mt, const 
 // chain anyway) keep the light one-sample form -- 256 registers, 4.6 KB of LDS; same-box A/B of the per-pair loop: 0.208-0.211 ms
 // per pair with it, 0.214-0.217 with the heavy form -- batched calls take the fast one.
 // (register budget of the light form: 256 per lane, waves_per_eu(2, 2), although one wave per pair does the work)
-// One pair, the whole block: the 10 candidates of the five-point solver on the rows mt [N,4] selected by mk (NULL = all) ->
-// models [10,9], valid [10].  Waves 1-3 return after the Gram matrix, wave 0 solves (a caller that goes on puts a barrier behind).
+// One pair, the whole block: the 10 candidates of the five-point solver on the rows mt [N,4] selected by mk (NULL = all), row n
+// scaled by wt[n] (NULL = unweighted) -> models [10,9], valid [10].  Waves 1-3 return after the Gram matrix, wave 0 solves (a caller that goes on puts a barrier behind).
 // lds: the block's dynamic LDS -- [192] five-point workspace, then gram[81] + red[4], wave partials, Jacobi (kRefitLdsDoubles),
 // or the solver's whole workspace with kPairFinish (kmax(kRefitLdsDoubles, kNisterPairDoubles)).
 template <typename T, bool kPairFinish>
-__device__ __forceinline__ void refit_essential_pair(const T *__restrict__ mt, const uint8_t *__restrict__ mk, int N, double *lds,
+__device__ __forceinline__ void refit_essential_pair(const T *__restrict__ mt, const uint8_t *__restrict__ mk,
+                                                     const T *__restrict__ wt, int N, double *lds,
                                                      T *__restrict__ models, uint8_t *__restrict__ valid) {
   double *gram = lds + 192;   // [0,162): the one five-point workspace slot all lanes share (identical values)
   double *red = gram + 81;
   const double mu[4] = {0, 0, 0, 0};
-  gram_accumulate<false, T>(mt, mk, static_cast<const T *>(nullptr), N, mu, 1.0, 1.0, gram, red);
+  gram_accumulate<false, T>(mt, mk, wt, N, mu, 1.0, 1.0, gram, red);
   if (threadIdx.x >= 64) return;
   // the rest is one latency-bound wave per pair, usually running next to the scoring kernel of the same call (8 VALU-bound
   // waves per SIMD): raise its issue priority so that it proceeds at its own pace and the scoring waves fill the gaps
@@ -133,7 +136,8 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kPairFini
                                                                 T *__restrict__ models, uint8_t *__restrict__ valid) {
   extern __shared__ __align__(16) double lds[];
   const int p = blockIdx.x;
-  refit_essential_pair<T, kPairFinish>(matches + (size_t)p * N * 4, mask ? mask + (size_t)p * N : nullptr, N, lds,
+  refit_essential_pair<T, kPairFinish>(matches + (size_t)p * N * 4, mask ? mask + (size_t)p * N : nullptr,
+                                       static_cast<const T *>(nullptr), N, lds,
                                        models + (size_t)p * 90, valid + (size_t)p * 10);
 }
 
@@ -294,7 +298,7 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 
     if constexpr (kF)
       refit_fundamental_pair<T>(mt, mk, static_cast<const T *>(nullptr), N, lds, cand, cvalid);
     else
-      refit_essential_pair<T, kMode == 2>(mt, mk, N, lds, cand, cvalid);
+      refit_essential_pair<T, kMode == 2>(mt, mk, static_cast<const T *>(nullptr), N, lds, cand, cvalid);
     __syncthreads();
     ++refits;
     T cb = -INFINITY;
@@ -368,6 +372,122 @@ int local_opt_launch(bool fundamental, int P, void *stream, Args... args) {
   return local_opt_go<T, 1>(P, stream, args...);
 }
 
+// ---- K7m IRLS polish of the pair state under the two-view MAGSAC++ loss (BatchedRANSAC(scoring = "magsac")), one 256-thread
+// block per pair: local_opt_kernel's sibling, same modes.  Up to `iters` times from the pair's (best_model, best_score): the weights
+// w(s_n) of magsac_device.hpp under the current model, sqrt(w_n) into the pair's row of weights_ws (the refit bodies scale the ROWS, so
+// the Gram matrix is sum_n w_n row_n row_n^T); the refit of this file over ALL points with those weights (F: the Hartley normalisation
+// stays unweighted over all points; E: the five-point solver on the weighted Gram matrix); the MAGSAC++ score over all points of every
+// valid, finite candidate, first arg-max; taken only on a STRICTLY higher score.  The loop ends before a fit when fewer than 8 (F) /
+// 5 (E) points have s < 1 (s and w in f64 for either type), on no valid finite candidate, on a candidate that does not win, and at the step limit.  irls_fits[p] += fits
+// run.  best_mask, best_inliers, iters and max_iters are neither read nor written.  Sums go lane, wave butterfly, the four waves in
+// order: no atomics, no read-back, a repeated launch gives the same bits.
+// (one wave per SIMD in every mode: under local_opt_kernel's two-wave budget the light final stage spills 836 B per lane here)
+template <typename T, int kMode>
+__global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) void magsac_irls_kernel(
+    const T *__restrict__ matches, const T *__restrict__ thr, int N, int iters, T *__restrict__ best_score, T *__restrict__ best_model,
+    T *__restrict__ weights_ws, int32_t *__restrict__ irls_fits) {
+  constexpr bool kF = kMode == 0;
+  constexpr int kS = kF ? 1 : 10;                 // candidates per refit
+  constexpr int kMinRows = kF ? 8 : 5;            // rows the LSQ solve needs
+  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
+  constexpr int kCand = (kWs + 3) & ~3;           // (32-byte aligned)
+  extern __shared__ __align__(16) double lds[];   // [kWs] refit workspace | candidates [kS][9] (T) | their valid flags
+  T *cand = reinterpret_cast<T *>(lds + kCand);
+  uint8_t *cvalid = reinterpret_cast<uint8_t *>(lds + kCand + 90);
+  __shared__ T s_part[kRefT / kWave];
+  __shared__ int s_cnt[kRefT / kWave];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const T *mt = matches + (size_t)p * N * 4;
+  T *wt = weights_ws + (size_t)p * N;
+  T bs = best_score[p];
+  T bm[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) bm[q] = best_model[(size_t)p * 9 + q];
+  const Magsac4Term<T> term(thr[p]);
+  const Magsac4Term<double> termd((double)thr[p]);
+  bool taken = false;
+  int fits = 0;
+  for (int it = 0; it < iters; ++it) {
+    __syncthreads();   // (the state and the previous pass's s_cnt / s_part have been read; the refit's LDS is free)
+    int cnt = 0;
+    // the weights in f64 whatever T is (the refit is f64 inside): with f32 residuals at a cutoff of 1e-3 the weights are off by
+    // ~1e-3 relative and the fitted model by more than its own output rounding
+    double bd[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) bd[q] = (double)bm[q];
+    for (int n = tid; n < N; n += kRefT) {
+      const T *q = mt + (size_t)n * 4;
+      const double s = termd.ratio(sampson_d2<double>(bd, (double)q[0], (double)q[1], (double)q[2], (double)q[3]));
+      const bool in = termd.inlier(s);
+      wt[n] = in ? (T)sqrt(termd.weight(s)) : T(0);
+      cnt += in;
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();   // (also orders the weights before the refit's reads)
+    if (s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] < kMinRows) break;   // block-uniform, like every exit below
+    if constexpr (kF)
+      refit_fundamental_pair<T>(mt, static_cast<const uint8_t *>(nullptr), wt, N, lds, cand, cvalid);
+    else
+      refit_essential_pair<T, kMode == 2>(mt, static_cast<const uint8_t *>(nullptr), wt, N, lds, cand, cvalid);
+    __syncthreads();
+    ++fits;
+    T cb = -INFINITY;
+    int which = -1;
+    for (int c = 0; c < kS; ++c) {
+      if (!cvalid[c]) continue;   // block-uniform
+      T m[9];
+      bool finite = true, nonzero = false;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) {
+        m[q] = cand[c * 9 + q];
+        finite = finite && is_finite(m[q]);
+        nonzero = nonzero || (m[q] != T(0));
+      }
+      T acc = T(0);
+      for (int n = tid; n < N; n += kRefT) {
+        const T *q = mt + (size_t)n * 4;
+        acc += term.contrib(sampson_d2<T>(m, q[0], q[1], q[2], q[3]));
+      }
+      acc = wave_sum(acc);
+      if (lane == 0) s_part[wv] = acc;
+      __syncthreads();
+      const T sc = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+      __syncthreads();
+      if (finite && nonzero && sc > cb) { cb = sc; which = c; }   // strict: the first maximum wins
+    }
+    if (which < 0 || !(cb > bs)) break;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) bm[q] = cand[which * 9 + q];
+    bs = cb;
+    taken = true;
+  }
+  if (tid == 0) {
+    if (taken) {
+      best_score[p] = bs;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) best_model[(size_t)p * 9 + q] = bm[q];
+    }
+    irls_fits[p] += fits;
+  }
+}
+
+template <typename T, int kMode, typename... Args>
+int magsac_irls_go(int P, void *stream, Args... args) {
+  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
+  const size_t smem = sizeof(double) * (((kWs + 3) & ~3) + 90 + 2);
+  allow_dynamic_lds<magsac_irls_kernel<T, kMode>>(smem);
+  return launch_lds("magsac_irls_kernel", magsac_irls_kernel<T, kMode>, dim3(P), kRefT, smem, stream, args...);
+}
+
+// args: the kernel's own argument list; the modes are chosen as refit_launch chooses
+template <typename T, typename... Args>
+int magsac_irls_launch(bool fundamental, int P, void *stream, Args... args) {
+  if (fundamental) return magsac_irls_go<T, 0>(P, stream, args...);
+  if (P >= kRefitPairFinishMinPairs) return magsac_irls_go<T, 2>(P, stream, args...);
+  return magsac_irls_go<T, 1>(P, stream, args...);
+}
+
 }  // namespace dr
 
 extern "C" {
@@ -394,6 +514,14 @@ extern "C" {
     return dr::local_opt_launch<T>(fundamental != 0, P, stream, matches, thr, N, lo == 1 ? 1 : lo_iters, k, confidence, eps,       \
                                    max_iterations, best_score, best_model, best_mask, best_inliers, max_iters, lo_seen,            \
                                    lo_refits);                                                                                      \
+  }                                                                                                                                 \
+  int dr_magsac_irls_##sfx(const T *matches, const T *thr, int P, int N, int fundamental, int irls_iters, T *best_score,            \
+                           T *best_model, T *weights_ws, int32_t *irls_fits, void *stream) {                                        \
+    DR_REQUIRE(matches && thr && best_score && best_model && weights_ws && irls_fits, "null pointer");                              \
+    DR_REQUIRE(P > 0 && N > 0, "bad sizes");   /* (below 8 / 5 points the kernel ends before its first fit: a no-op polish) */       \
+    DR_REQUIRE(irls_iters >= 1, "irls_iters must be at least 1");                                                                   \
+    return dr::magsac_irls_launch<T>(fundamental != 0, P, stream, matches, thr, N, irls_iters, best_score, best_model, weights_ws,  \
+                                     irls_fits);                                                                                    \
   }
 DR_F32_F64(DR_OP)
 #undef DR_OP

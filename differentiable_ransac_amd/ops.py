@@ -92,6 +92,58 @@ def msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, want_mask
     return scores, masks
 
 
+def magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None, gate=None,
+                 want_inliers: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """dr_magsac_score: matches [P,N,4], models [P,M,3,3] (or [P,M,9]), threshold as msac_score takes it (float or [P]; the cutoff is
+    (1.5 thr)^2, read as (k sigma_max)^2 with k^2 = chi2.ppf(0.99, 4)) -> (scores [P,M] = sum_n (1 - l(s_n)), inliers [P,M] int32 =
+    #{s_n < 1} | None); include/dransac.h states l.  msac_score's slot rules (invalid: exactly 0, non-finite or all-zero model: NaN),
+    no mask rows.  Bit-repeatable.  gate = RansacState: the blocks of terminated pairs return at once."""
+    if matches.dim() != 3 or matches.shape[-1] != 4:
+        raise L.DransacError("magsac_score: correspondences are [P,N,4]")
+    P, N, _ = matches.shape
+    if models.dim() not in (3, 4) or models.shape[0] != P or models.shape[2:].numel() != 9:
+        raise L.DransacError("magsac_score: models are [P,M,3,3] (or [P,M,9])")
+    if models.dtype != matches.dtype or models.device != matches.device:
+        raise L.DransacError("magsac_score: models must have the correspondences' dtype and device")
+    M = models.shape[1]
+    if valid is not None and (valid.shape != (P, M) or valid.dtype not in (torch.bool, torch.uint8)):
+        raise L.DransacError("magsac_score: valid is [P,M] bool")
+    thr = _thr_tensor(threshold, P, matches)
+    scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
+    inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
+    L.call(f"dr_magsac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(thr), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
+    return scores, inliers
+
+
+def magsac_irls(state: "RansacState", matches, thr, fundamental: bool, irls_iters: int, irls_fits: torch.Tensor,
+                weights_ws: torch.Tensor) -> None:
+    """dr_magsac_irls: the IRLS polish under the two-view MAGSAC++ loss, in place on state.best_model / state.best_score: up to
+    irls_iters times the weights w(s) under the current model, the row-weighted refit over all points (F: LSQ 8-point, E: five-point
+    on the weighted Gram matrix) and the candidates' MAGSAC++ scores, the best taken only where it is strictly higher.  thr [P] as
+    ransac_init returns it; irls_fits [P] int32 grows by the fits run; weights_ws [P,N] (matches' dtype) is workspace.  Mask, inlier
+    count and counters of the state are left alone.  One launch, no synchronisation."""
+    tensors = (matches, thr, irls_fits, weights_ws, state.best_score, state.best_model)
+    if any(t is None or not t.is_cuda for t in tensors):
+        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    if matches.dim() != 3 or matches.shape[-1] != 4:
+        raise L.DransacError("magsac_irls: correspondences are [P,N,4]")
+    P, N, _ = matches.shape
+    dt = matches.dtype
+    if thr.shape != (P,) or thr.dtype != dt or not thr.is_contiguous():
+        raise L.DransacError("magsac_irls: thr must be a contiguous [P] tensor of the matches' dtype")
+    if (state.best_score.shape != (P,) or state.best_score.dtype != dt or state.best_model.shape != (P, 3, 3)
+            or state.best_model.dtype != dt):
+        raise L.DransacError("magsac_irls: the state's best_score [P] / best_model [P,3,3] must have the matches' dtype")
+    if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
+        raise L.DransacError("magsac_irls: irls_fits must be [P] int32")
+    if weights_ws.shape != (P, N) or weights_ws.dtype != matches.dtype or not weights_ws.is_contiguous():
+        raise L.DransacError("magsac_irls: weights_ws must be a contiguous [P,N] tensor of the matches' dtype")
+    L.call(f"dr_magsac_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), c_int(P), c_int(N),
+           c_int(1 if fundamental else 0), c_int(int(irls_iters)), ptr(state.best_score), ptr(state.best_model), ptr(weights_ws),
+           ptr(irls_fits), stream())
+
+
 def select_best(matches: torch.Tensor, models: torch.Tensor, scores: torch.Tensor, threshold,
                 valid: Optional[torch.Tensor] = None):
     """Per pair: (best_idx [P] int32, best_score [P], best_model [P,3,3], best_mask [P,N] bool, inliers [P] int32)."""

@@ -553,7 +553,26 @@ class BatchedRANSAC(_SeededDriver):
 
     def __init__(self, solver="nister", ransac_batch_size=1024, train=False, threshold=0.75, confidence=0.999,
                  max_iterations=5000, tau=1.0, seed=0, weighted=0, keep_masks=False, refit=True, eps=1e-5,
-                 sampling="gumbel", num_samples=None, lo=0, lo_iters=64, prosac_draws=200000):
+                 sampling="gumbel", num_samples=None, lo=0, lo_iters=64, prosac_draws=200000, scoring="msac", irls_iters=10):
+        # scoring (test mode): "msac" = the reference's MSACScore (ops.msac_score); "magsac" = the two-view MAGSAC++ score
+        # (ops.magsac_score) in its place -- dr_ransac_update, super-rounds and device_termination as they are -- and, with
+        # refit=True and irls_iters > 0, the IRLS polish under that loss (ops.magsac_irls, up to irls_iters weighted refits) in the place
+        # of the final refit and its acceptance step; the result gains irls_fits [P].  mask and inliers stay dr_ransac_update's.
+        if scoring not in ("msac", "magsac"):
+            raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
+        if isinstance(irls_iters, bool) or not isinstance(irls_iters, int) or irls_iters < 0:
+            raise ValueError(f"irls_iters must be an int of at least 0, got {irls_iters!r}")
+        if scoring == "magsac":
+            if train:
+                raise ValueError("scoring='magsac' is a test-mode score: train mode scores nothing")
+            if lo:
+                raise ValueError("scoring='magsac' needs lo=0: the local optimisation (dr_local_opt) scores its refits with MSAC")
+            if weighted:
+                raise ValueError("scoring='magsac' needs weighted=0: its polish computes its own row weights")
+            if keep_masks:
+                raise ValueError("scoring='magsac' needs keep_masks=False: the MAGSAC++ scoring launch writes no mask rows")
+        self.scoring = scoring
+        self.irls_iters = irls_iters
         # num_samples: points per sample when it is not the solver's minimal count -- 8 with solver="nister" is the reference's
         # `-sam 3` (8-point Gumbel sampler) feeding the five-point estimator (ransac.py:82-83; nister.py:64-65 runs on all rows)
         # sampling: "gumbel" = the reference's sampler (noise for every point of every hypothesis, top-k);
@@ -761,7 +780,7 @@ class BatchedRANSAC(_SeededDriver):
             # on a side stream and joins before the final scoring -- and it is issued FIRST, before the state set-up (round 5; see the
             # note on dispatch order below).
             pre = None
-            if self.refit and not self.fmat:
+            if self.refit and not self.fmat and self.scoring == "msac":
                 if self._side is None:
                     self._side = torch.cuda.Stream(device=dev)
                 self._side.wait_stream(torch.cuda.current_stream())
@@ -876,9 +895,12 @@ class BatchedRANSAC(_SeededDriver):
             w0 = ops.soft_weights_row0(c.logits, self.k, self.tau, row0[1], row0[0])
             c.last_w = torch.where((c.st.iters.double() < c.st.max_iters)[:, None], w0, c.last_w)
         flat, valid = models.reshape(P, -1, 3, 3), valid.reshape(P, -1)
-        scores, masks = ops.msac_score(c.matches, flat, c.thr, want_masks=self.keep_masks, valid=valid, gate=gate)
-        if self.keep_masks:
-            c.all_masks = masks
+        if self.scoring == "magsac":
+            scores, _ = ops.magsac_score(c.matches, flat, c.thr, valid=valid, gate=gate)
+        else:
+            scores, masks = ops.msac_score(c.matches, flat, c.thr, want_masks=self.keep_masks, valid=valid, gate=gate)
+            if self.keep_masks:
+                c.all_masks = masks
         # dr_ransac_update's sub_models: the round's models are plan[r] batches of B x S
         ops.ransac_update(c.st, c.matches, flat, valid, scores, c.thr, self.B, self.stop_k, self.confidence, self.eps,
                           sub_models=self.B * self.S if c.plan[r] > 1 else 0)
@@ -891,7 +913,14 @@ class BatchedRANSAC(_SeededDriver):
         self._race_ws = None
         self._prosac = None
         st = c.st
-        if self.refit:
+        irls_fits = None
+        if self.scoring == "magsac":
+            P, N, _ = c.matches.shape
+            irls_fits = torch.zeros(P, device=c.matches.device, dtype=torch.int32)
+            if self.refit and self.irls_iters > 0:
+                ops.magsac_irls(st, c.matches, c.thr, self.fmat, self.irls_iters, irls_fits,
+                                torch.empty((P, N), device=c.matches.device, dtype=c.matches.dtype))
+        elif self.refit:
             if self.fmat:
                 F, fvalid = ops.refit_fundamental(c.matches, st.best_mask, c.last_w)   # (weighted) LSQ on the inliers of the best mask
                 cand, cvalid = F.unsqueeze(1), fvalid.unsqueeze(1)
@@ -907,6 +936,8 @@ class BatchedRANSAC(_SeededDriver):
                    masks=c.all_masks, packed=st.packed)
         if c.lo_refits is not None:
             out["lo_refits"] = c.lo_refits
+        if irls_fits is not None:
+            out["irls_fits"] = irls_fits
         return out
 
 

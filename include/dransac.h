@@ -647,6 +647,38 @@ int dr_local_opt_f64(const double *matches, const double *thr, int P, int N, int
                      void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * K4m / K7m two-view MAGSAC++: the score in dr_msac_score's place and the IRLS polish in the final refit's.
+ *     d2 = K4's squared Sampson distance; thr2 = (1.5 thr)^2 with thr the [P] tensor of dr_ransac_init, K4's and K6's own cutoff, read
+ *     as (k sigma_max)^2: k^2 = chi2.ppf(0.99, 4) = 13.276704135987622 (the residual has 4 degrees of freedom), the noise scale
+ *     uniform in [0, sigma_max].  With s = d2 / thr2, u = u_k s, u_k = k^2 / 2 = 6.638352067993811,
+ *     Gamma_k = Gamma(3/2, u_k) = 0.0036112606177586, Gamma_0 = Gamma(3/2) = sqrt(pi) / 2, rho_1 = gamma(5/2, u_k) = 1.3015316073311318:
+ *       weight  w(s) = (Gamma(3/2, u) - Gamma_k) / (Gamma_0 - Gamma_k)                 for s < 1, else 0
+ *       loss    l(s) = (u Gamma(3/2, u) + gamma(5/2, u) - u Gamma_k) / rho_1           for s < 1, else 1
+ *       score        = sum_n (1 - l(s_n)) in [0, N];  inliers = #{s_n < 1};  a non-finite d2 contributes nothing.
+ *     Evaluated in closed form, F = Gamma_0 erfc(sqrt u):  Gamma(3/2, u) = F + sqrt(u) exp(-u),
+ *     rho(u) = u (F - Gamma_k) - (3/2) Gamma(3/2, u) + 3 sqrt(pi) / 4,  l = rho / rho_1.
+ *   dr_magsac_score   dr_msac_score's arguments with the mask pointer replaced by inliers [P,M] int32 (NULL = not counted); both types
+ *     take the gate pair.  K4's slot rules, so that dr_ransac_update runs unchanged: an invalid slot gets score exactly 0 and 0
+ *     inliers without being evaluated, a non-finite or all-zero model a NaN score (0 inliers), the outputs of a gated pair keep their
+ *     contents.  No [P,M,N] tensor, no atomics, fixed reduction order: a repeated launch gives the same bits.
+ *   dr_magsac_irls    on the per-pair state of dr_ransac_update, in place, one cooperative block per pair (fundamental != 0: F).  Up to
+ *     irls_iters times from (best_model, best_score): w(s_n) under the current model for every point, sqrt(w_n) into the pair's row of
+ *     weights_ws [P,N] (workspace); the K7 refit over ALL points with these row weights (F: Hartley LSQ 8-point, normalisation
+ *     unweighted; E: the five-point solver on the weighted Gram matrix, f64 inside); the MAGSAC++ score over all points of every valid,
+ *     finite candidate, first arg-max; taken only on a STRICTLY higher score.  Ends before a fit when fewer than 8 (F) / 5 (E) points
+ *     have s < 1 (so always when N is below that: the state is left as it is), on no valid finite candidate, on a candidate that does not win, at the step limit.  irls_fits[p] grows by the fits
+ *     run.  best_mask, best_inliers, iters and max_iters are not touched.  No atomics, no read-back: capturable.
+ * ------------------------------------------------------------------------------------------ */
+int dr_magsac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr, int P, int M, int N,
+                        float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream);
+int dr_magsac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr, int P, int M, int N,
+                        double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream);
+int dr_magsac_irls_f32(const float *matches, const float *thr, int P, int N, int fundamental, int irls_iters, float *best_score,
+                       float *best_model, float *weights_ws, int32_t *irls_fits, void *stream);
+int dr_magsac_irls_f64(const double *matches, const double *thr, int P, int N, int fundamental, int irls_iters, double *best_score,
+                       double *best_model, double *weights_ws, int32_t *irls_fits, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * the training loss right after the path -- MatchLoss (loss.py:107-153) on batch_episym
  * (cv_utils.py:680-695).  sums [P,M] = sum over the points with mask[p,n] != 0 (NULL = all points) of
  * min(ys, 1), ys = (x2^T M x1)^2 (1/((Mx1)_0^2+(Mx1)_1^2+1e-15) + 1/((M^T x2)_0^2+(M^T x2)_1^2+1e-15)).
