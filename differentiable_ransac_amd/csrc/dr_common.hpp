@@ -182,6 +182,16 @@ __device__ __forceinline__ float wave_sum_lane63(float v) {
   v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2, 3
   return v;
 }
+// the same tree on integers (a count only lane 63 consumes)
+__device__ __forceinline__ int wave_sum_lane63(int v) {
+  v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);
+  v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);
+  v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);
+  v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);
+  return v;
+}
 
 // Maximum over the 64 lanes by DPP, broadcast to every lane through an SGPR (v_readlane of lane 63).
 // f64 variant: the two halves travel through DPP separately; total valid in lane 63 only.

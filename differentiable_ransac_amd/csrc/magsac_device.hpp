@@ -1,6 +1,8 @@
-// The two-view MAGSAC++ term, shared by the scoring kernel (magsac_score.hip) and the IRLS polish (refit.hip).
+// The two-view MAGSAC++ term, shared by the scoring kernels (magsac_score.hip) and the IRLS polish (refit.hip): the
+// constants, the closed forms and Magsac4Term, which has SampsonMsacTerm's interface (ransac_device.hpp: the distance, the cutoff
+// and the block score pass live there).
 //
-// d2 = the squared Sampson distance of K4; thr2 = (1.5 thr)^2, K4's and K6's own cutoff, read as (k sigma_max)^2 with
+// d2 = the squared Sampson distance of K4 (sampson_d2); thr2 = (1.5 thr)^2, K4's and K6's own cutoff, read as (k sigma_max)^2 with
 // k^2 = chi2.ppf(0.99, 4) = 13.276704135987622 (the residual has 4 degrees of freedom), the noise scale uniform in [0, sigma_max].
 // With s = d2 / thr2, u = u_k s, u_k = k^2 / 2, Gamma_k = Gamma(3/2, u_k), Gamma_0 = Gamma(3/2) = sqrt(pi) / 2, rho_1 = gamma(5/2, u_k):
 //   weight  w(s) = (Gamma(3/2, u) - Gamma_k) / (Gamma_0 - Gamma_k)                       for s < 1, else 0
@@ -29,26 +31,10 @@ __device__ __forceinline__ double magsac4_exp(double x) { return exp(x); }
 __device__ __forceinline__ float magsac4_sqrt(float x) { return sqrtf(x); }
 __device__ __forceinline__ double magsac4_sqrt(double x) { return sqrt(x); }
 
-// squared Sampson distance: sampson_s's expression without the threshold
-template <typename T>
-__device__ __forceinline__ T sampson_d2(const T m[9], T x1, T y1, T x2, T y2) {
-  const T a0 = fma(x2, m[0], fma(y2, m[3], m[6]));
-  const T a1 = fma(x2, m[1], fma(y2, m[4], m[7]));
-  const T a2 = fma(x2, m[2], fma(y2, m[5], m[8]));
-  const T b0 = fma(x1, m[0], fma(y1, m[1], m[2]));
-  const T b1 = fma(x1, m[3], fma(y1, m[4], m[5]));
-  const T r = fma(x1, a0, fma(y1, a1, a2));
-  const T jj = fma(a0, a0, fma(a1, a1, fma(b0, b0, b1 * b1)));
-  return (r * r) * fast_rcp(jj);
-}
-
 template <typename T>
 struct Magsac4Term {
-  T inv;      // 1 / thr2, thr2 = (1.5 thr)^2 as K4 and K6 form it
-  __device__ __forceinline__ explicit Magsac4Term(T thr) {
-    const T t = T(1.5) * thr;
-    inv = T(1) / (t * t);
-  }
+  T inv;      // 1 / thr2, thr2 = (1.5 thr)^2: the MSAC term's cutoff
+  __device__ __forceinline__ explicit Magsac4Term(T thr) : inv(SampsonMsacTerm<T>(thr).inv) {}
   __device__ __forceinline__ T ratio(T d2) const { return d2 * inv; }                 // s
   __device__ __forceinline__ static bool inlier(T s) { return s < T(1); }             // (false for NaN): the term's and the count's test
   // Gamma(3/2, u_k s) and F - Gamma_k of the closed form

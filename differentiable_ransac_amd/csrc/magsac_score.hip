@@ -4,8 +4,9 @@
 // Mapping: K4's skeleton.  One block = (pair p, tile of 32 model slots); a lane owns 8 CONSECUTIVE points of a 2048-point chunk in VGPRs
 // and the block walks ALL chunks of the row itself, so a (pair, model) is owned by one block.  The model index is wave-uniform: the nine
 // coefficients arrive through the scalar cache.  f32 evaluates the Sampson part two points at a time (v_pk_fma_f32), as K4's fast
-// kernels do.  One compare, s < 1, serves the term and the count.  Slots the solver marked invalid are never evaluated (score exactly 0,
-// count 0); a non-finite or all-zero model scores NaN (count 0); the blocks of a gated pair return at once.
+// kernels do (sampson_d2_pair of ransac_device.hpp, theirs).  One compare, s < 1, serves the term and the count.  Slots the solver marked
+// invalid are never evaluated (score exactly 0, count 0); a non-finite or all-zero model scores NaN (count 0) (model_kind); the blocks
+// of a gated pair return at once.
 // Rows of at most 256 points take a wave per model (1, 2 or 4 consecutive points per lane), where the first mapping would idle lanes.
 // Reduction order, fixed: a lane's points in order, the DPP wave tree, the chunks in order onto the wave's LDS partial, the four waves in
 // order.  No atomics, no [P,M,N] tensor: a repeated launch gives the same bits.
@@ -16,56 +17,23 @@ namespace dr {
 constexpr int kMgThreads = 256, kMgPts = 8, kMgChunk = kMgThreads * kMgPts, kMgTile = 32;
 constexpr int kMgWaveMaxN = 256, kMgWaves = 4, kMgPerWave = 4, kMgWaveTile = kMgWaves * kMgPerWave;
 
-typedef float mg_v2f __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ mg_v2f mg_splat(float a) { return (mg_v2f){a, a}; }
-
-// integer sum over the 64 lanes by DPP only, valid in LANE 63 ONLY (dr_common.hpp's float tree on integers: only lane 63 consumes the
-// count, so the ds_bpermute butterfly of wave_sum is not needed)
-__device__ __forceinline__ int wave_isum_lane63(int v) {
-  v += __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true);          // quad_perm [1,0,3,2]
-  v += __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true);          // quad_perm [2,3,0,1]
-  v += __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true);         // row_half_mirror
-  v += __builtin_amdgcn_mov_dpp(v, 0x140, 0xF, 0xF, true);         // row_mirror: row sums
-  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xA, 0xF, false);  // row_bcast:15 -> rows 1, 3
-  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xC, 0xF, false);  // row_bcast:31 -> rows 2, 3
-  return v;
-}
-
 // d2 of the lane's 8 points under model m (wave-uniform)
 __device__ __forceinline__ void magsac_d2_8(const float (&x1)[kMgPts], const float (&y1)[kMgPts], const float (&x2)[kMgPts],
                                             const float (&y2)[kMgPts], const float (&m)[9], float (&d2)[kMgPts]) {
+  v2f ms[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) ms[q] = splat(m[q]);
 #pragma unroll
   for (int j = 0; j < kMgPts; j += 2) {
-    const mg_v2f X1 = {x1[j], x1[j + 1]}, Y1 = {y1[j], y1[j + 1]}, X2 = {x2[j], x2[j + 1]}, Y2 = {y2[j], y2[j + 1]};
-    const mg_v2f a0 = X2 * mg_splat(m[0]) + (Y2 * mg_splat(m[3]) + mg_splat(m[6]));
-    const mg_v2f a1 = X2 * mg_splat(m[1]) + (Y2 * mg_splat(m[4]) + mg_splat(m[7]));
-    const mg_v2f a2 = X2 * mg_splat(m[2]) + (Y2 * mg_splat(m[5]) + mg_splat(m[8]));
-    const mg_v2f b0 = X1 * mg_splat(m[0]) + (Y1 * mg_splat(m[1]) + mg_splat(m[2]));
-    const mg_v2f b1 = X1 * mg_splat(m[3]) + (Y1 * mg_splat(m[4]) + mg_splat(m[5]));
-    const mg_v2f r = X1 * a0 + (Y1 * a1 + a2);
-    const mg_v2f jj = a0 * a0 + (a1 * a1 + (b0 * b0 + b1 * b1));
-    const mg_v2f rr = r * r;
-    d2[j] = rr[0] * __builtin_amdgcn_rcpf(jj[0]);
-    d2[j + 1] = rr[1] * __builtin_amdgcn_rcpf(jj[1]);
+    const v2f d = sampson_d2_pair((v2f){x1[j], x1[j + 1]}, (v2f){y1[j], y1[j + 1]}, (v2f){x2[j], x2[j + 1]}, (v2f){y2[j], y2[j + 1]}, ms);
+    d2[j] = d[0];
+    d2[j + 1] = d[1];
   }
 }
 __device__ __forceinline__ void magsac_d2_8(const double (&x1)[kMgPts], const double (&y1)[kMgPts], const double (&x2)[kMgPts],
                                             const double (&y2)[kMgPts], const double (&m)[9], double (&d2)[kMgPts]) {
 #pragma unroll
   for (int j = 0; j < kMgPts; ++j) d2[j] = sampson_d2<double>(m, x1[j], y1[j], x2[j], y2[j]);
-}
-
-// 0 = invalid slot (not evaluated), 1 = evaluated, 2 = non-finite or all-zero model (NaN score)
-template <typename T>
-__device__ __forceinline__ int magsac_slot_kind(const T *__restrict__ m9, bool live) {
-  if (!live) return 0;
-  bool finite = true, nonzero = false;
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    finite = finite && is_finite(m9[q]);
-    nonzero = nonzero || (m9[q] != T(0));
-  }
-  return (finite && nonzero) ? 1 : 2;
 }
 
 template <typename T>
@@ -87,7 +55,7 @@ __global__ __launch_bounds__(kMgThreads) void magsac_score_kernel(const T *__res
     (&part[0][0])[tid] = T(0);
     (&pcnt[0][0])[tid] = 0;
   }
-  if (tid < mcount) kind[tid] = magsac_slot_kind<T>(md + tid * 9, !valid || valid[(size_t)p * M + m0 + tid] != 0);
+  if (tid < mcount) kind[tid] = model_kind<T>(md + tid * 9, !valid || valid[(size_t)p * M + m0 + tid] != 0);
   __syncthreads();
   for (int c0 = 0; c0 < N; c0 += kMgChunk) {
     const int n0 = c0 + tid * kMgPts;
@@ -108,7 +76,7 @@ __global__ __launch_bounds__(kMgThreads) void magsac_score_kernel(const T *__res
     }
 #pragma unroll 1
     for (int ml = 0; ml < mcount; ++ml) {
-      if (__builtin_amdgcn_readfirstlane(kind[ml]) != 1) continue;   // block-uniform
+      if (__builtin_amdgcn_readfirstlane(kind[ml]) != kModelScored) continue;   // block-uniform
       T m[9];
 #pragma unroll
       for (int q = 0; q < 9; ++q) m[q] = md[ml * 9 + q];
@@ -124,7 +92,7 @@ __global__ __launch_bounds__(kMgThreads) void magsac_score_kernel(const T *__res
         cnt += in;
       }
       acc = wave_sum_lane63(acc);
-      if (inliers) cnt = wave_isum_lane63(cnt);
+      if (inliers) cnt = wave_sum_lane63(cnt);
       if (lane == 63) {   // the wave's own LDS words: the chunks accumulate in order
         part[wv][ml] += acc;
         pcnt[wv][ml] += cnt;
@@ -136,8 +104,8 @@ __global__ __launch_bounds__(kMgThreads) void magsac_score_kernel(const T *__res
     const int k = kind[tid];
     const T v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
     const size_t slot = (size_t)p * M + m0 + tid;
-    scores[slot] = k == 1 ? v : (k == 2 ? T(NAN) : T(0));
-    if (inliers) inliers[slot] = k == 1 ? pcnt[0][tid] + pcnt[1][tid] + pcnt[2][tid] + pcnt[3][tid] : 0;
+    scores[slot] = k == kModelScored ? v : (k == kModelNan ? T(NAN) : T(0));
+    if (inliers) inliers[slot] = k == kModelScored ? pcnt[0][tid] + pcnt[1][tid] + pcnt[2][tid] + pcnt[3][tid] : 0;
   }
 }
 
@@ -171,10 +139,10 @@ __global__ __launch_bounds__(kMgWaves * 64) void magsac_score_wave_kernel(const 
     T m[9];
 #pragma unroll
     for (int q = 0; q < 9; ++q) m[q] = models[slot * 9 + q];
-    const int k = magsac_slot_kind<T>(m, !valid || valid[slot] != 0);
+    const int k = model_kind<T>(m, !valid || valid[slot] != 0);
     T acc = T(0);
     int cnt = 0;
-    if (k == 1) {
+    if (k == kModelScored) {
 #pragma unroll
       for (int j = 0; j < kPtsS; ++j) {
         const T s = term.ratio(sampson_d2<T>(m, x1[j], y1[j], x2[j], y2[j]));
@@ -184,9 +152,9 @@ __global__ __launch_bounds__(kMgWaves * 64) void magsac_score_wave_kernel(const 
       }
     }
     acc = wave_sum_lane63(acc);
-    if (inliers) cnt = wave_isum_lane63(cnt);
+    if (inliers) cnt = wave_sum_lane63(cnt);
     if (lane == 63) {
-      scores[slot] = k == 1 ? acc : (k == 2 ? T(NAN) : T(0));
+      scores[slot] = k == kModelScored ? acc : (k == kModelNan ? T(NAN) : T(0));
       if (inliers) inliers[slot] = cnt;
     }
   }

@@ -76,8 +76,7 @@ __global__ __launch_bounds__(kThreads) void msac_score_kernel(const T *__restric
   const int m0 = blockIdx.x * kModelsPerBlock;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int mcount = min(kModelsPerBlock, M - m0);
-  const T t = T(1.5) * thr[p];
-  const T inv_thr2 = T(1) / (t * t);
+  const T inv_thr2 = SampsonMsacTerm<T>(thr[p]).inv;
   const T *mt = matches + (size_t)p * N * 4;
   const T *md = models + ((size_t)p * M + m0) * 9;
   const bool row_aligned = (N % 8) == 0 && (reinterpret_cast<uintptr_t>(masks) % 8) == 0;
@@ -162,7 +161,6 @@ __global__ __launch_bounds__(kThreads) void msac_score_kernel(const T *__restric
 // The variants measured and dropped in rounds 1-3 (non-temporal stores, LDS quad-sum reduction, contiguous zero-run fill,
 // real SGPR pairs, hand-placed scalar prefetch, per-half rendezvous, register budgets for 3 / 5 / 6 waves, 32- / 128-slot
 // tiles, ...) are kept as scratch/k4_dropped_variants.patch; their numbers are in profiles/r3_k4_counters_p128.md.
-typedef float v2f __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // 16-byte store at (wave-uniform 64-bit base) + (per-lane unsigned 32-bit offset): the SGPR-base form of global_store, so that
@@ -175,8 +173,6 @@ __device__ __forceinline__ void mask_row_store_saddr(const uint8_t *base_uniform
   const u32x4 v = {a, b, c, d};
   asm volatile("global_store_dwordx4 %0, %1, %2" : : "v"(off), "v"(v), "s"(bs) : "memory");
 }
-
-__device__ __forceinline__ v2f splat(float a) { return (v2f){a, a}; }
 
 constexpr int kFastTile = 64;   // model slots per block in the f32 fast paths (two 32-bit validity words)
 
@@ -193,8 +189,7 @@ __global__ __launch_bounds__(kThreads) void msac_score_kernel_f32_fast(const flo
   const int m0 = blockIdx.x * kFastTile;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int mcount = min(kFastTile, M - m0);
-  const float t = 1.5f * thr[p];
-  const float inv_thr2 = 1.0f / (t * t);
+  const float inv_thr2 = SampsonMsacTerm<float>(thr[p]).inv;
   const float *mt = matches + (size_t)p * N * 4;
   const float *md = models + ((size_t)p * M + m0) * 9;
   const bool row_aligned = (N % 8) == 0 && (reinterpret_cast<uintptr_t>(masks) % 8) == 0;
@@ -343,18 +338,7 @@ __global__ __launch_bounds__(kThreads) void msac_score_kernel_f32_fast(const flo
 // packed FMA ([0, 1]; NaN -> 0): inlier <=> term > 0 <=> bit 5 of its top byte (biased exponent 64..127) is set.
 // ms[q] = the model coefficient q in both halves (an SGPR broadcast through op_sel, or a VGPR pair).
 __device__ __forceinline__ v2f msac_pair_term(v2f x1, v2f y1, v2f x2, v2f y2, const v2f (&ms)[9], float inv_thr2) {
-  const v2f a0 = x2 * ms[0] + (y2 * ms[3] + ms[6]);
-  const v2f a1 = x2 * ms[1] + (y2 * ms[4] + ms[7]);
-  const v2f a2 = x2 * ms[2] + (y2 * ms[5] + ms[8]);
-  const v2f b0 = x1 * ms[0] + (y1 * ms[1] + ms[2]);
-  const v2f b1 = x1 * ms[3] + (y1 * ms[4] + ms[5]);
-  const v2f r = x1 * a0 + (y1 * a1 + a2);
-  const v2f jj = a0 * a0 + (a1 * a1 + (b0 * b0 + b1 * b1));
-  const v2f rr = r * r;
-  v2f rc;
-  rc[0] = __builtin_amdgcn_rcpf(jj[0]);
-  rc[1] = __builtin_amdgcn_rcpf(jj[1]);
-  const v2f pq = rr * rc;
+  const v2f pq = sampson_d2_pair(x1, y1, x2, y2, ms);
   const v2f one = splat(1.0f), ith = splat(inv_thr2);
   v2f c;
   asm("v_pk_fma_f32 %0, %1, %2, %3 neg_lo:[1,0,0] neg_hi:[1,0,0] clamp" : "=v"(c) : "v"(pq), "v"(ith), "v"(one));
@@ -414,8 +398,7 @@ __global__ __launch_bounds__(kT16) void msac_score_kernel_f32_fast16(const float
   const int m0 = (blockIdx.x * kHalves + half) * tile_slots;
   const int tid = threadIdx.x % kH16, lane = tid & 63, wv = threadIdx.x >> 6;
   const int mcount = max(0, min(tile_slots, M - m0));
-  const float t = 1.5f * thr[p];
-  const float inv_thr2 = 1.0f / (t * t);
+  const float inv_thr2 = SampsonMsacTerm<float>(thr[p]).inv;
   const float *mt = matches + (size_t)p * N * 4;
   const float *md = models + ((size_t)p * M + m0) * 9;
   for (int i = threadIdx.x; i < (kT16 / kWave) * kTile; i += kT16) (&part[0][0])[i] = 0.f;
@@ -560,8 +543,7 @@ __global__ __launch_bounds__(kSmallWaves * 64) void msac_score_kernel_f32_small(
                                                                                uint8_t *__restrict__ masks) {
   const int p = blockIdx.z;
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const float t = 1.5f * thr[p];
-  const float inv_thr2 = 1.0f / (t * t);
+  const float inv_thr2 = SampsonMsacTerm<float>(thr[p]).inv;
   const float4 *mt = reinterpret_cast<const float4 *>(matches) + (size_t)p * N;
   const int n0 = lane * kPtsS;
   const int nvalid = min(kPtsS, max(0, N - n0));
@@ -659,8 +641,9 @@ __global__ __launch_bounds__(kThreads) void select_best_kernel(const T *__restri
 
 // ---- K7 acceptance: score the (few) refit candidates of every pair and keep the best of them if it beats the RANSAC
 // result (ransac.py:173-185: `scores = score(points, models); if scores.max() > best_score: best_model, best_score =
-// ...`; the mask is left as it is, like there).  One block per pair, a wave per candidate in turn: replaces an MSAC launch,
-// select_best and four torch kernels (50 us of device time per call) by one launch.
+// ...`; the mask is left as it is, like there).  One block per pair, the candidates in turn, each scored by the whole block
+// (score_partial under SampsonMsacTerm, ransac_device.hpp: the local optimisation's pass): replaces an MSAC launch, select_best and
+// four torch kernels (50 us of device time per call) by one launch.
 template <typename T>
 __global__ __launch_bounds__(kThreads) void refit_accept_kernel(const T *__restrict__ matches, const T *__restrict__ cand,
                                                                const uint8_t *__restrict__ cvalid, const T *__restrict__ thr,
@@ -670,31 +653,26 @@ __global__ __launch_bounds__(kThreads) void refit_accept_kernel(const T *__restr
   __shared__ T s_best;
   __shared__ int s_which;
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const T t = T(1.5) * thr[p];
-  const T inv_thr2 = T(1) / (t * t);
+  const SampsonMsacTerm<T> term(thr[p]);
   if (tid == 0) { s_best = best_score[p]; s_which = -1; }
   __syncthreads();
   for (int c = 0; c < S; ++c) {
     if (cvalid && !cvalid[(size_t)p * S + c]) continue;   // block-uniform
     T m[9];
-    bool finite = true, nonzero = false;
 #pragma unroll
-    for (int q = 0; q < 9; ++q) {
-      m[q] = cand[((size_t)p * S + c) * 9 + q];
-      finite = finite && is_finite(m[q]);
-      nonzero = nonzero || (m[q] != T(0));
-    }
+    for (int q = 0; q < 9; ++q) m[q] = cand[((size_t)p * S + c) * 9 + q];
     // an all-zero candidate competes no more than a non-finite one: dr_msac_score gives it a NaN score (the reference's 0/0),
     // while the sum below would be 0 and could beat a negative best_score
-    finite = finite && nonzero;
-    T acc = msac_partial<T, kThreads>(matches + (size_t)p * N * 4, m, N, inv_thr2);
+    const int kind = model_kind<T>(m, true);
+    // block_score's pass with thread 0 as the only reader of the partials: it alone decides (the state stays in LDS)
+    T acc = score_partial<T, kThreads>(matches + (size_t)p * N * 4, m, N, term);
     acc = wave_sum(acc);
     if (lane == 0) s_part[wv] = acc;
     __syncthreads();
     if (tid == 0) {
       T sc = T(0);
       for (int w = 0; w < kThreads / kWave; ++w) sc += s_part[w];
-      if (finite && sc > s_best) { s_best = sc; s_which = c; }   // strict: the first maximum wins, like torch.argmax
+      if (kind == kModelScored && sc > s_best) { s_best = sc; s_which = c; }   // strict: the first maximum wins, like torch.argmax
     }
     __syncthreads();
   }

@@ -7,7 +7,9 @@
 // cooperatively (three passes for F: centroid, mean distances, Gram), then wave 0 takes the eigenvectors it needs from a
 // wave-cooperative Jacobi eigen-decomposition (F: the smallest one, E: the four smallest) and, for E, runs the five-point pipeline.
 // The ragged inlier sets never leave the device.
-#include <algorithm>
+// Behind it, on the same two fit bodies (refit_fundamental_pair, refit_essential_pair): K7b, the local optimisation, and K7m, the
+// MAGSAC++ IRLS polish.  What those two share is PairRefit (LDS layout, candidate arg-max); all four entries launch
+// through pair_mode / pair_launch.  The terms, the model classification and the block score pass are ransac_device.hpp's.
 #include "fivepoint_device.hpp"
 #include "magsac_device.hpp"
 #include "ransac_device.hpp"
@@ -55,7 +57,7 @@ __device__ __forceinline__ void gram_accumulate(const T *__restrict__ mt, const 
   }
   // 45 partial sums per thread: reduced inside each wave by DPP (no LDS traffic), one LDS slot per (wave, entry), ONE
   // barrier, then 45 threads add the four wave partials (was: 45 x (wave butterfly over ds_bpermute + two barriers))
-  double *part = gram + 96;   // [4][45] behind gram[81] + red[4] (+ padding); see the LDS sizes at the launch sites
+  double *part = gram + 96;   // [4][45] behind gram[81] + red[4] (+ padding); kRefitLdsDoubles
 #pragma unroll
   for (int q = 0; q < 45; ++q) {
     const double s = wave_sum_lane63(acc[q]);
@@ -226,47 +228,78 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                             weights ? weights + (size_t)p * N : nullptr, N, lds, models + (size_t)p * 9, valid + p);
 }
 
-template <typename T>
-int refit_launch(bool fundamental, const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *models,
-                 uint8_t *valid, hipStream_t st) {
-  const size_t smem = sizeof(double) * kRefitLdsDoubles;
-  if (fundamental) {
-    allow_dynamic_lds<refit_fundamental_kernel<T>>(smem);
-    return launch_lds("refit_kernel", refit_fundamental_kernel<T>, dim3(P), kRefT, smem, st, matches, mask, weights, N, models, valid);
-  }
-  if (P >= kRefitPairFinishMinPairs) {
-    const size_t smem_p = std::max(smem, sizeof(double) * (size_t)kNisterPairDoubles);   // the solver's workspace, overlaid
-    allow_dynamic_lds<refit_essential_kernel<T, true>>(smem_p);
-    return launch_lds("refit_kernel", refit_essential_kernel<T, true>, dim3(P), kRefT, smem_p, st, matches, mask, N, models, valid);
-  }
-  allow_dynamic_lds<refit_essential_kernel<T, false>>(smem);
-  return launch_lds("refit_kernel", refit_essential_kernel<T, false>, dim3(P), kRefT, smem, st, matches, mask, N, models, valid);
-}
+// ---- The pair scaffold: what the per-pair kernels of this file share.  kMode: 0 = F, 1 = E with the light final stage, 2 = E with the
+// wave-cooperative one (launches of at least kRefitPairFinishMinPairs pairs: see refit_essential_pair).
+// PairMode: the constants and the dynamic LDS of a block, [kWs] refit workspace | candidates [kS][9] (T) | their valid flags (the last
+// two for the kernels that fit and score in one launch).
+template <int kMode>
+struct PairMode {
+  static constexpr bool kF = kMode == 0;
+  static constexpr int kS = kF ? 1 : 10;                 // candidates per refit
+  static constexpr int kMinRows = kF ? 8 : 5;            // rows the LSQ solve needs
+  static constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
+  static constexpr int kCand = (kWs + 3) & ~3;           // (32-byte aligned)
+  static constexpr size_t lds_bytes(bool candidates) { return sizeof(double) * (candidates ? kCand + 90 + 2 : kWs); }
+};
 
+// PairRefit: the block's candidate slots and the choice among them.  The fit itself (refit_fundamental_pair / refit_essential_pair into
+// cand / cvalid, then a barrier) is written out in the two kernels, with their null mask or weight pointer as a typed literal: behind
+// a shared fit(mt, mk, wt, N) member the refit bodies compiled differently in EVERY kernel of the file (LOG 21).
+template <typename T, int kMode>
+struct PairRefit : PairMode<kMode> {
+  using PairMode<kMode>::kCand;
+  double *lds;
+  T *cand;
+  uint8_t *cvalid;
+  __device__ __forceinline__ explicit PairRefit(double *lds_)
+      : lds(lds_), cand(reinterpret_cast<T *>(lds_ + kCand)), cvalid(reinterpret_cast<uint8_t *>(lds_ + kCand + 90)) {}
+  // first arg-max (strict: like torch.argmax) of the scores under `term`, over all N points, of the valid candidates that
+  // model_kind(..., zero_is_nan) calls scored -> its slot (-1: none) and score cb.  Block-uniform.
+  template <typename Term>
+  __device__ __forceinline__ int best_candidate(const T *__restrict__ mt, int N, const Term &term, bool zero_is_nan, T *s_part,
+                                                T &cb) const {
+    cb = -INFINITY;
+    int which = -1;
+    for (int c = 0; c < PairMode<kMode>::kS; ++c) {
+      if (!cvalid[c]) continue;
+      T m[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) m[q] = cand[c * 9 + q];
+      const int kind = model_kind<T>(m, true, zero_is_nan);
+      const T sc = block_score<T, kRefT>(mt, m, N, term, s_part);
+      if (kind == kModelScored && sc > cb) { cb = sc; which = c; }
+    }
+    return which;
+  }
+};
+
+// The launcher of the per-pair kernels.  pair_mode: the kMode of a launch; pair_launch: Kernel, one block per pair, with kMode's dynamic
+// LDS (opted in); pair_family_launch (below the kernels): a kernel family K<T, kMode> at the launch's mode.
+inline int pair_mode(bool fundamental, int P) { return fundamental ? 0 : (P >= kRefitPairFinishMinPairs ? 2 : 1); }
+template <auto Kernel, int kMode, bool kCandidates, typename... Args>
+int pair_launch(const char *name, int P, void *stream, Args... args) {
+  constexpr size_t smem = PairMode<kMode>::lds_bytes(kCandidates);
+  allow_dynamic_lds<Kernel>(smem);
+  return launch_lds(name, Kernel, dim3(P), kRefT, smem, stream, args...);
+}
 
 // ---- K7b local optimisation (RANSAC.localOptimization, ransac.py:217-257, lo = 1 / 2), one 256-thread block per pair, once per
 // device round right behind dr_ransac_update.  A pair whose (best_score, best_model) still equals its snapshot lo_seen[p] (bit
 // for bit: only a replacement by dr_ransac_update changes them, and the snapshot starts as NaN) returns at once.  Otherwise, up
 // to `iters` times: the refit of this file on the best mask (F: LSQ 8-point, unweighted; E: the five-point solver on the
-// selected rows, f64 inside), the MSAC scores of its valid, finite candidates (refit_accept_kernel's rule, first arg-max), and,
-// if that score is >= the best (ransac.py:252: ties are taken), the new best score / model and -- with dr_ransac_update's
-// predicate -- mask and inlier count.  The loop stops early when a refit loses or leaves the mask as it was (the next refit
-// would see the same rows: same model, same outcome).  Then max_iters from the new inlier count (ransac.py:135-142) and the
-// snapshot.  The refit's candidates live in LDS behind the refit workspace.
-// kMode: 0 = F, 1 = E with the light final stage, 2 = E with the wave-cooperative one (chosen per launch like refit_launch)
+// selected rows, f64 inside), the MSAC scores of its valid, finite candidates (first arg-max; an all-zero candidate is not excluded
+// here, unlike in refit_accept_kernel), and, if that score is >= the best (ransac.py:252: ties are taken), the new best score / model
+// and -- with dr_ransac_update's predicate -- mask and inlier count.  The loop stops early when a refit loses or leaves the mask as it
+// was (the next refit would see the same rows: same model, same outcome).  Then max_iters from the new inlier count
+// (ransac.py:135-142) and the snapshot.
 template <typename T, int kMode>
 __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 1 ? 2 : 1, kMode == 1 ? 2 : 1))) void local_opt_kernel(
     const T *__restrict__ matches, const T *__restrict__ thr, int N, int iters, int k, double confidence, double eps,
     int max_iterations, T *__restrict__ best_score, T *__restrict__ best_model, uint8_t *__restrict__ best_mask,
     int32_t *__restrict__ best_inliers, double *__restrict__ max_iters, T *__restrict__ lo_seen, int32_t *__restrict__ lo_refits) {
-  constexpr bool kF = kMode == 0;
-  constexpr int kS = kF ? 1 : 10;                 // candidates per refit
-  constexpr int kMinRows = kF ? 8 : 5;            // rows the LSQ solve needs
-  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
-  constexpr int kCand = (kWs + 3) & ~3;           // (32-byte aligned)
-  extern __shared__ __align__(16) double lds[];   // [kWs] refit workspace | candidates [kS][9] (T) | their valid flags
-  T *cand = reinterpret_cast<T *>(lds + kCand);
-  uint8_t *cvalid = reinterpret_cast<uint8_t *>(lds + kCand + 90);
+  extern __shared__ __align__(16) double lds[];
+  const PairRefit<T, kMode> pair(lds);
+  constexpr int kMinRows = PairMode<kMode>::kMinRows;
   __shared__ T s_part[kRefT / kWave];
   __shared__ int s_cnt[kRefT / kWave], s_chg[kRefT / kWave];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -282,8 +315,7 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 
     same = same && same_bits(bm[q], seen[1 + q]);
   }
   if (same) return;   // block-uniform: no replacement since the last visit
-  const T t = T(1.5) * thr[p];
-  const T inv_thr2 = T(1) / (t * t);
+  const SampsonMsacTerm<T> term(thr[p]);
   // the current inlier count, from the mask itself
   int cnt = 0;
   for (int n = tid; n < N; n += kRefT) cnt += mk[n] != 0;
@@ -295,40 +327,22 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 
   int refits = 0;
   for (int it = 0; run && it < iters && inl >= kMinRows; ++it) {
     __syncthreads();   // (the previous pass's s_cnt / s_chg have been read; the refit's LDS is free)
-    if constexpr (kF)
-      refit_fundamental_pair<T>(mt, mk, static_cast<const T *>(nullptr), N, lds, cand, cvalid);
+    if constexpr (kMode == 0)
+      refit_fundamental_pair<T>(mt, mk, static_cast<const T *>(nullptr), N, lds, pair.cand, pair.cvalid);
     else
-      refit_essential_pair<T, kMode == 2>(mt, mk, static_cast<const T *>(nullptr), N, lds, cand, cvalid);
+      refit_essential_pair<T, kMode == 2>(mt, mk, static_cast<const T *>(nullptr), N, lds, pair.cand, pair.cvalid);
     __syncthreads();
     ++refits;
-    T cb = -INFINITY;
-    int which = -1;
-    for (int c = 0; c < kS; ++c) {
-      if (!cvalid[c]) continue;   // block-uniform
-      T m[9];
-      bool finite = true;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) {
-        m[q] = cand[c * 9 + q];
-        finite = finite && is_finite(m[q]);
-      }
-      T acc = msac_partial<T, kRefT>(mt, m, N, inv_thr2);
-      acc = wave_sum(acc);
-      if (lane == 0) s_part[wv] = acc;
-      __syncthreads();
-      T sc = T(0);
-      for (int w = 0; w < kRefT / kWave; ++w) sc += s_part[w];   // refit_accept_kernel's order
-      __syncthreads();
-      if (finite && sc > cb) { cb = sc; which = c; }            // strict: the first maximum wins, like torch.argmax
-    }
+    T cb;
+    const int which = pair.best_candidate(mt, N, term, false, s_part, cb);
     if (which < 0 || !(cb >= bs)) break;                         // ransac.py:252-257
 #pragma unroll
-    for (int q = 0; q < 9; ++q) bm[q] = cand[which * 9 + q];
+    for (int q = 0; q < 9; ++q) bm[q] = pair.cand[which * 9 + q];
     bs = cb;
     int c2 = 0, chg = 0;
     for (int n = tid; n < N; n += kRefT) {
       const T *q = mt + (size_t)n * 4;
-      const uint8_t in = sampson_s<T>(bm, q[0], q[1], q[2], q[3], inv_thr2) < T(0);
+      const uint8_t in = term.inlier(term.ratio(sampson_d2<T>(bm, q[0], q[1], q[2], q[3])));
       chg |= in != mk[n];
       mk[n] = in;
       c2 += in;
@@ -356,29 +370,13 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(kMode == 
   }
 }
 
-template <typename T, int kMode, typename... Args>
-int local_opt_go(int P, void *stream, Args... args) {
-  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
-  const size_t smem = sizeof(double) * (((kWs + 3) & ~3) + 90 + 2);
-  allow_dynamic_lds<local_opt_kernel<T, kMode>>(smem);
-  return launch_lds("local_opt_kernel", local_opt_kernel<T, kMode>, dim3(P), kRefT, smem, stream, args...);
-}
-
-// args: the kernel's own argument list
-template <typename T, typename... Args>
-int local_opt_launch(bool fundamental, int P, void *stream, Args... args) {
-  if (fundamental) return local_opt_go<T, 0>(P, stream, args...);
-  if (P >= kRefitPairFinishMinPairs) return local_opt_go<T, 2>(P, stream, args...);
-  return local_opt_go<T, 1>(P, stream, args...);
-}
-
 // ---- K7m IRLS polish of the pair state under the two-view MAGSAC++ loss (BatchedRANSAC(scoring = "magsac")), one 256-thread
-// block per pair: local_opt_kernel's sibling, same modes.  Up to `iters` times from the pair's (best_model, best_score): the weights
+// block per pair: local_opt_kernel's sibling on the same scaffold.  Up to `iters` times from the pair's (best_model, best_score): the weights
 // w(s_n) of magsac_device.hpp under the current model, sqrt(w_n) into the pair's row of weights_ws (the refit bodies scale the ROWS, so
 // the Gram matrix is sum_n w_n row_n row_n^T); the refit of this file over ALL points with those weights (F: the Hartley normalisation
 // stays unweighted over all points; E: the five-point solver on the weighted Gram matrix); the MAGSAC++ score over all points of every
-// valid, finite candidate, first arg-max; taken only on a STRICTLY higher score.  The loop ends before a fit when fewer than 8 (F) /
-// 5 (E) points have s < 1 (s and w in f64 for either type), on no valid finite candidate, on a candidate that does not win, and at the step limit.  irls_fits[p] += fits
+// valid candidate that is finite and not all zero, first arg-max; taken only on a STRICTLY higher score.  The loop ends before a fit when fewer than 8 (F) /
+// 5 (E) points have s < 1 (s and w in f64 for either type), on no such candidate, on a candidate that does not win, and at the step limit.  irls_fits[p] += fits
 // run.  best_mask, best_inliers, iters and max_iters are neither read nor written.  Sums go lane, wave butterfly, the four waves in
 // order: no atomics, no read-back, a repeated launch gives the same bits.
 // (one wave per SIMD in every mode: under local_opt_kernel's two-wave budget the light final stage spills 836 B per lane here)
@@ -386,14 +384,8 @@ template <typename T, int kMode>
 __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) void magsac_irls_kernel(
     const T *__restrict__ matches, const T *__restrict__ thr, int N, int iters, T *__restrict__ best_score, T *__restrict__ best_model,
     T *__restrict__ weights_ws, int32_t *__restrict__ irls_fits) {
-  constexpr bool kF = kMode == 0;
-  constexpr int kS = kF ? 1 : 10;                 // candidates per refit
-  constexpr int kMinRows = kF ? 8 : 5;            // rows the LSQ solve needs
-  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
-  constexpr int kCand = (kWs + 3) & ~3;           // (32-byte aligned)
-  extern __shared__ __align__(16) double lds[];   // [kWs] refit workspace | candidates [kS][9] (T) | their valid flags
-  T *cand = reinterpret_cast<T *>(lds + kCand);
-  uint8_t *cvalid = reinterpret_cast<uint8_t *>(lds + kCand + 90);
+  extern __shared__ __align__(16) double lds[];
+  const PairRefit<T, kMode> pair(lds);
   __shared__ T s_part[kRefT / kWave];
   __shared__ int s_cnt[kRefT / kWave];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -425,40 +417,18 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     cnt = wave_sum(cnt);
     if (lane == 0) s_cnt[wv] = cnt;
     __syncthreads();   // (also orders the weights before the refit's reads)
-    if (s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] < kMinRows) break;   // block-uniform, like every exit below
-    if constexpr (kF)
-      refit_fundamental_pair<T>(mt, static_cast<const uint8_t *>(nullptr), wt, N, lds, cand, cvalid);
+    if (s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3] < PairMode<kMode>::kMinRows) break;   // block-uniform, like every exit below
+    if constexpr (kMode == 0)
+      refit_fundamental_pair<T>(mt, static_cast<const uint8_t *>(nullptr), wt, N, lds, pair.cand, pair.cvalid);
     else
-      refit_essential_pair<T, kMode == 2>(mt, static_cast<const uint8_t *>(nullptr), wt, N, lds, cand, cvalid);
+      refit_essential_pair<T, kMode == 2>(mt, static_cast<const uint8_t *>(nullptr), wt, N, lds, pair.cand, pair.cvalid);
     __syncthreads();
     ++fits;
-    T cb = -INFINITY;
-    int which = -1;
-    for (int c = 0; c < kS; ++c) {
-      if (!cvalid[c]) continue;   // block-uniform
-      T m[9];
-      bool finite = true, nonzero = false;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) {
-        m[q] = cand[c * 9 + q];
-        finite = finite && is_finite(m[q]);
-        nonzero = nonzero || (m[q] != T(0));
-      }
-      T acc = T(0);
-      for (int n = tid; n < N; n += kRefT) {
-        const T *q = mt + (size_t)n * 4;
-        acc += term.contrib(sampson_d2<T>(m, q[0], q[1], q[2], q[3]));
-      }
-      acc = wave_sum(acc);
-      if (lane == 0) s_part[wv] = acc;
-      __syncthreads();
-      const T sc = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
-      __syncthreads();
-      if (finite && nonzero && sc > cb) { cb = sc; which = c; }   // strict: the first maximum wins
-    }
+    T cb;
+    const int which = pair.best_candidate(mt, N, term, true, s_part, cb);
     if (which < 0 || !(cb > bs)) break;
 #pragma unroll
-    for (int q = 0; q < 9; ++q) bm[q] = cand[which * 9 + q];
+    for (int q = 0; q < 9; ++q) bm[q] = pair.cand[which * 9 + q];
     bs = cb;
     taken = true;
   }
@@ -472,20 +442,24 @@ __global__ __launch_bounds__(kRefT) __attribute__((amdgpu_waves_per_eu(1, 1))) v
   }
 }
 
-template <typename T, int kMode, typename... Args>
-int magsac_irls_go(int P, void *stream, Args... args) {
-  constexpr int kWs = kMode == 2 ? kmax(kRefitLdsDoubles, kNisterPairDoubles) : kRefitLdsDoubles;
-  const size_t smem = sizeof(double) * (((kWs + 3) & ~3) + 90 + 2);
-  allow_dynamic_lds<magsac_irls_kernel<T, kMode>>(smem);
-  return launch_lds("magsac_irls_kernel", magsac_irls_kernel<T, kMode>, dim3(P), kRefT, smem, stream, args...);
-}
-
-// args: the kernel's own argument list; the modes are chosen as refit_launch chooses
-template <typename T, typename... Args>
-int magsac_irls_launch(bool fundamental, int P, void *stream, Args... args) {
-  if (fundamental) return magsac_irls_go<T, 0>(P, stream, args...);
-  if (P >= kRefitPairFinishMinPairs) return magsac_irls_go<T, 2>(P, stream, args...);
-  return magsac_irls_go<T, 1>(P, stream, args...);
+template <typename T, int kMode>
+struct LocalOpt {
+  static constexpr auto kernel = &local_opt_kernel<T, kMode>;
+  static constexpr const char *kName = "local_opt_kernel";
+};
+template <typename T, int kMode>
+struct MagsacIrls {
+  static constexpr auto kernel = &magsac_irls_kernel<T, kMode>;
+  static constexpr const char *kName = "magsac_irls_kernel";
+};
+// args: the kernel's own argument list
+template <template <typename, int> class K, typename T, typename... Args>
+int pair_family_launch(bool fundamental, int P, void *stream, Args... args) {
+  switch (pair_mode(fundamental, P)) {
+    case 0: return pair_launch<K<T, 0>::kernel, 0, true>(K<T, 0>::kName, P, stream, args...);
+    case 2: return pair_launch<K<T, 2>::kernel, 2, true>(K<T, 2>::kName, P, stream, args...);
+    default: return pair_launch<K<T, 1>::kernel, 1, true>(K<T, 1>::kName, P, stream, args...);
+  }
 }
 
 }  // namespace dr
@@ -493,16 +467,21 @@ int magsac_irls_launch(bool fundamental, int P, void *stream, Args... args) {
 extern "C" {
 
 #define DR_OP(sfx, T)                                                                                                              \
-  int dr_refit_essential_##sfx(const T *matches, const uint8_t *mask, int P, int N, T *models, uint8_t *valid, void *stream) {      \
-    DR_REQUIRE(matches && models && valid, "null pointer");                                                                         \
-    DR_REQUIRE(P > 0 && N >= 5, "bad sizes");                                                                                       \
-    return dr::refit_launch<T>(false, matches, mask, nullptr, P, N, models, valid, (hipStream_t)stream);                            \
-  }                                                                                                                                 \
   int dr_refit_fundamental_##sfx(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *models, uint8_t *valid,  \
                                  void *stream) {                                                                                    \
     DR_REQUIRE(matches && models && valid, "null pointer");                                                                         \
     DR_REQUIRE(P > 0 && N >= 8, "bad sizes");                                                                                       \
-    return dr::refit_launch<T>(true, matches, mask, weights, P, N, models, valid, (hipStream_t)stream);                             \
+    return dr::pair_launch<dr::refit_fundamental_kernel<T>, 0, false>("refit_kernel", P, stream, matches, mask, weights, N, models, \
+                                                                      valid);                                                       \
+  }                                                                                                                                 \
+  int dr_refit_essential_##sfx(const T *matches, const uint8_t *mask, int P, int N, T *models, uint8_t *valid, void *stream) {      \
+    DR_REQUIRE(matches && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(P > 0 && N >= 5, "bad sizes");                                                                                       \
+    if (dr::pair_mode(false, P) == 2)                                                                                               \
+      return dr::pair_launch<dr::refit_essential_kernel<T, true>, 2, false>("refit_kernel", P, stream, matches, mask, N, models,    \
+                                                                            valid);                                                 \
+    return dr::pair_launch<dr::refit_essential_kernel<T, false>, 1, false>("refit_kernel", P, stream, matches, mask, N, models,     \
+                                                                           valid);                                                  \
   }                                                                                                                                 \
   int dr_local_opt_##sfx(const T *matches, const T *thr, int P, int N, int fundamental, int lo, int lo_iters, int k,                \
                          double confidence, double eps, int max_iterations, T *best_score, T *best_model, uint8_t *best_mask,       \
@@ -511,17 +490,17 @@ extern "C" {
     DR_REQUIRE(P > 0 && N >= (fundamental ? 8 : 5) && k > 0, "bad sizes");                                                          \
     DR_REQUIRE(lo == 1 || lo == 2, "lo must be 1 (one refit) or 2 (iterated refits)");                                              \
     DR_REQUIRE(lo == 1 || lo_iters >= 1, "lo_iters must be at least 1");                                                            \
-    return dr::local_opt_launch<T>(fundamental != 0, P, stream, matches, thr, N, lo == 1 ? 1 : lo_iters, k, confidence, eps,       \
-                                   max_iterations, best_score, best_model, best_mask, best_inliers, max_iters, lo_seen,            \
-                                   lo_refits);                                                                                      \
+    return dr::pair_family_launch<dr::LocalOpt, T>(fundamental != 0, P, stream, matches, thr, N, lo == 1 ? 1 : lo_iters, k,         \
+                                                   confidence, eps, max_iterations, best_score, best_model, best_mask,              \
+                                                   best_inliers, max_iters, lo_seen, lo_refits);                                    \
   }                                                                                                                                 \
   int dr_magsac_irls_##sfx(const T *matches, const T *thr, int P, int N, int fundamental, int irls_iters, T *best_score,            \
                            T *best_model, T *weights_ws, int32_t *irls_fits, void *stream) {                                        \
     DR_REQUIRE(matches && thr && best_score && best_model && weights_ws && irls_fits, "null pointer");                              \
     DR_REQUIRE(P > 0 && N > 0, "bad sizes");   /* (below 8 / 5 points the kernel ends before its first fit: a no-op polish) */       \
     DR_REQUIRE(irls_iters >= 1, "irls_iters must be at least 1");                                                                   \
-    return dr::magsac_irls_launch<T>(fundamental != 0, P, stream, matches, thr, N, irls_iters, best_score, best_model, weights_ws,  \
-                                     irls_fits);                                                                                    \
+    return dr::pair_family_launch<dr::MagsacIrls, T>(fundamental != 0, P, stream, matches, thr, N, irls_iters, best_score,          \
+                                                     best_model, weights_ws, irls_fits);                                            \
   }
 DR_F32_F64(DR_OP)
 #undef DR_OP
