@@ -1,0 +1,568 @@
+// Plane-induced homographies (ransac.BatchedHomography): models from minimal samples of four matches by a closed form, its reverse
+// pass for train mode, the MSAC score and inlier count of every model against every point under the symmetric transfer error, the
+// per-pair state step with the adaptive stop, and the normalised DLT refit over the rows a mask selects.
+//   matches [P,N,4] = (x1, y1, x2, y2) in the caller's coordinates (pixels; no K).  A model is the row-major 3x3 H, x2 ~ H x1, stored
+//   with unit Frobenius norm and det H > 0 (det(-H) = -det H: the sign is canonical, and under it a point seen in front of both
+//   cameras has a positive third coordinate in both directions).
+//   Residual: y = H (x1, 1), z = adj(H) (x2, 1), d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2; a point with y_w <= 0 or z_w <= 0, or
+//   a non-finite d2, is an outlier and contributes nothing.  The threshold is a DISTANCE and enters as thr2 = threshold^2 per pair:
+//   inlier <=> d2 < thr2; MSAC score = sum_n max(0, 1 - d2_n / thr2).
+#include "homography_device.hpp"
+#include "solver_common.hpp"
+
+namespace dr {
+
+// ---- (1) four matches -> H, closed form ------------------------------------------------------------------------------------------
+// Per image: c = the centroid of the four points, q_i = x_i - c, s = sqrt(2) / mean |q_i|, p_i = (s q_i, 1).  The four orientation
+// determinants D_3 = [q0 q1 q2], D_0 = [q3 q1 q2], D_1 = [q0 q3 q2], D_2 = [q0 q1 q3] ([a b c] = det of the three points with a row
+// of ones: twice the signed area) are the cofactors of the 3x3 solve [p0 p1 p2] lambda = p3 -- lambda_i = D_i / D_3, unchanged by
+// the similarity (c, s) -- and the sample's validity test: every one non-zero, each with the same sign in both images.  They are taken
+// on the centred, unscaled q: for integer coordinates every product and sum is exact, so three collinear points give exactly 0.
+// A = [lambda_0 p0 | lambda_1 p1 | lambda_2 p2] maps the projective basis (e0, e1, e2, (1, 1, 1)) to the four points, so
+// H = T2^-1 A2 adj(A1) T1 up to scale; then unit norm and det > 0.  All f64, all in registers.
+struct H4Image {
+  double q[4][2], r[4], nz[3], D[4], lam[3], A[9];      // nz = (cx, cy, s); A row-major
+};
+
+__device__ __forceinline__ double tri(const double (&q)[4][2], int i, int j, int k) {
+  return q[i][0] * (q[j][1] - q[k][1]) - q[j][0] * (q[i][1] - q[k][1]) + q[k][0] * (q[i][1] - q[j][1]);
+}
+
+__device__ __forceinline__ void tri_bwd(const double (&q)[4][2], int i, int j, int k, double g, double (&gq)[4][2]) {
+  gq[i][0] += g * (q[j][1] - q[k][1]);
+  gq[j][0] -= g * (q[i][1] - q[k][1]);
+  gq[k][0] += g * (q[i][1] - q[j][1]);
+  gq[i][1] += g * (q[k][0] - q[j][0]);
+  gq[j][1] += g * (q[i][0] - q[k][0]);
+  gq[k][1] += g * (q[j][0] - q[i][0]);
+}
+
+__device__ __forceinline__ void h4_image(const double (&x)[4][2], H4Image &im) {
+  im.nz[0] = 0.25 * (x[0][0] + x[1][0] + x[2][0] + x[3][0]);
+  im.nz[1] = 0.25 * (x[0][1] + x[1][1] + x[2][1] + x[3][1]);
+  double md = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    im.q[i][0] = x[i][0] - im.nz[0];
+    im.q[i][1] = x[i][1] - im.nz[1];
+    im.r[i] = sqrt(im.q[i][0] * im.q[i][0] + im.q[i][1] * im.q[i][1]);
+    md += im.r[i];
+  }
+  im.nz[2] = M_SQRT2 / (0.25 * md);
+  im.D[0] = tri(im.q, 3, 1, 2);
+  im.D[1] = tri(im.q, 0, 3, 2);
+  im.D[2] = tri(im.q, 0, 1, 3);
+  im.D[3] = tri(im.q, 0, 1, 2);
+  const double rd = 1.0 / im.D[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    im.lam[c] = im.D[c] * rd;
+    im.A[c] = im.lam[c] * (im.nz[2] * im.q[c][0]);
+    im.A[3 + c] = im.lam[c] * (im.nz[2] * im.q[c][1]);
+    im.A[6 + c] = im.lam[c];
+  }
+}
+
+// -> valid; H canonical (identity when not valid); M = A2 adj(A1), nrm = |T2^-1 M T1|_F, sigma: kept for the reverse pass
+template <typename RowFn>
+__device__ __forceinline__ bool homography4_fwd(RowFn row, bool usable, H4Image (&im)[2], double (&M)[9], double (&H)[9], double &nrm,
+                                                double &sigma) {
+  double x[2][4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const auto *r = row(i);
+#pragma unroll
+    for (int d = 0; d < 4; ++d) x[d >> 1][i][d & 1] = (double)r[d];
+  }
+  h4_image(x[0], im[0]);
+  h4_image(x[1], im[1]);
+  bool ok = usable;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    ok = ok && ((im[0].D[t] > 0.0 && im[1].D[t] > 0.0) || (im[0].D[t] < 0.0 && im[1].D[t] < 0.0));      // (false for NaN)
+  double B[9];
+  adjugate3(im[0].A, B);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+      M[3 * i + j] = im[1].A[3 * i] * B[j] + im[1].A[3 * i + 1] * B[3 + j] + im[1].A[3 * i + 2] * B[6 + j];
+  denormalise_h(M, im[0].nz, im[1].nz, H);
+  return canonical_h(H, ok, nrm, sigma);
+}
+
+template <typename T>
+__device__ __forceinline__ void store_h(T *__restrict__ dst, const double (&H)[9]) {
+#pragma unroll
+  for (int q = 0; q < 9; ++q) dst[q] = (T)H[q];
+}
+
+// rows read through the index sets: one lane = one sample (a bad index reads row 0, valid = 0)
+template <typename T>
+__global__ __launch_bounds__(64) void homography4_gather_kernel(const T *__restrict__ matches, const int32_t *__restrict__ idx, int Bt,
+                                                                int B, int N, T *__restrict__ models, uint8_t *__restrict__ valid) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= Bt) return;
+  const T *base = matches + (size_t)(s / B) * N * 4;
+  const int32_t *gi = idx + (size_t)s * 4;
+  bool in_range = true;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) in_range = in_range && gi[r] >= 0 && gi[r] < N;
+  H4Image im[2];
+  double M[9], H[9], nrm, sigma;
+  valid[s] = homography4_fwd([&](int r) { return base + (size_t)(in_range ? gi[r] : 0) * 4; }, in_range, im, M, H, nrm, sigma);
+  store_h(models + (size_t)s * 9, H);
+}
+
+// explicit sample tensors [Bt,4,4]: what train mode fits.  On samples = matches[idx] the bits of the gather kernel.
+template <typename T>
+__global__ __launch_bounds__(64) void homography4_kernel(const T *__restrict__ samples, int Bt, T *__restrict__ models,
+                                                         uint8_t *__restrict__ valid) {
+  const int s = blockIdx.x * 64 + threadIdx.x;
+  if (s >= Bt) return;
+  const T *base = samples + (size_t)s * 16;
+  H4Image im[2];
+  double M[9], H[9], nrm, sigma;
+  valid[s] = homography4_fwd([&](int r) { return base + r * 4; }, true, im, M, H, nrm, sigma);
+  store_h(models + (size_t)s * 9, H);
+}
+
+// ---- (1c) the reverse pass of (1): gH -> the gradient of the 16 sample values ------------------------------------------------------
+// The forward is recomputed in f64 from the sample (no stored model).  Backwards through it:
+//   H = sigma H0 / |H0|         g0 = (sigma / |H0|) (gH - H <H, gH>)        (so a multiple of H in gH passes nothing on)
+//   H0 = T2^-1 (M T1)           gM, and the direct gradients of (c1, s1) and (c2, s2)
+//   M = A2 adj(A1)              gA2 = gM adj(A1)^T;  adj(A)'s rows are a1 x a2, a2 x a0, a0 x a1 of A's columns: cross-product rule
+//   a_c = lambda_c (s q_c, 1)   g lambda, gs, gq;  lambda_c = D_c / D_3 -> gD;  D = orientation determinants -> gq
+//   s = sqrt(2) / mean |q_i|,  q_i = x_i - c,  c = mean x_i
+// one image's part: gA (row-major), the direct gradient gnz of (cx, cy, s) -> gx[4][2]
+__device__ __forceinline__ void h4_image_bwd(const H4Image &im, const double (&gA)[9], const double (&gnz)[3], double (&gx)[4][2]) {
+  double gq[4][2], gD[4], gs = gnz[2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) gq[i][0] = gq[i][1] = 0.0;
+  const double s = im.nz[2], rd = 1.0 / im.D[3];
+  gD[3] = 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double g0 = gA[c], g1 = gA[3 + c], g2 = gA[6 + c];
+    const double glam = g0 * (s * im.q[c][0]) + g1 * (s * im.q[c][1]) + g2;
+    gs += im.lam[c] * (g0 * im.q[c][0] + g1 * im.q[c][1]);
+    gq[c][0] += s * im.lam[c] * g0;
+    gq[c][1] += s * im.lam[c] * g1;
+    gD[c] = glam * rd;
+    gD[3] -= glam * im.lam[c] * rd;
+  }
+  tri_bwd(im.q, 3, 1, 2, gD[0], gq);
+  tri_bwd(im.q, 0, 3, 2, gD[1], gq);
+  tri_bwd(im.q, 0, 1, 3, gD[2], gq);
+  tri_bwd(im.q, 0, 1, 2, gD[3], gq);
+  const double md = 0.25 * (im.r[0] + im.r[1] + im.r[2] + im.r[3]);
+  const double gmd = -gs * s / md;
+  double sum0 = 0.0, sum1 = 0.0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const double ri = im.r[i] > 0.0 ? 0.25 * gmd / im.r[i] : 0.0;      // (a point on the centroid: |q| is not differentiable, pass 0)
+    gq[i][0] += ri * im.q[i][0];
+    gq[i][1] += ri * im.q[i][1];
+    sum0 += gq[i][0];
+    sum1 += gq[i][1];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    gx[i][0] = gq[i][0] + 0.25 * (gnz[0] - sum0);
+    gx[i][1] = gq[i][1] + 0.25 * (gnz[1] - sum1);
+  }
+}
+
+__device__ __forceinline__ void cross_acc(const double *a, const double *b, double *out) {      // out += a x b
+  out[0] += a[1] * b[2] - a[2] * b[1];
+  out[1] += a[2] * b[0] - a[0] * b[2];
+  out[2] += a[0] * b[1] - a[1] * b[0];
+}
+
+// every output element is written; exact zeros for a sample without a valid model or with a non-finite derivative
+template <typename T>
+__global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict__ samples, const T *__restrict__ grad_models, int Bt,
+                                                             T *__restrict__ grad_samples) {
+  const int smp = blockIdx.x * 64 + threadIdx.x;
+  if (smp >= Bt) return;
+  const T *base = samples + (size_t)smp * 16;
+  H4Image im[2];
+  double M[9], H[9], nrm, sigma;
+  bool ok = homography4_fwd([&](int r) { return base + r * 4; }, true, im, M, H, nrm, sigma);
+  double g0[9], dot = 0.0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    g0[q] = (double)grad_models[(size_t)smp * 9 + q];
+    dot += H[q] * g0[q];
+  }
+  const double sc = sigma / nrm;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) g0[q] = sc * (g0[q] - H[q] * dot);
+  // H0 = T2^-1 G, G = M T1
+  const double s1 = im[0].nz[2], cx1 = im[0].nz[0], cy1 = im[0].nz[1];
+  const double s2 = im[1].nz[2], cx2 = im[1].nz[0], cy2 = im[1].nz[1], r2 = 1.0 / s2;
+  double G[9], gG[9], gnz1[3] = {0.0, 0.0, 0.0}, gnz2[3] = {0.0, 0.0, 0.0}, gM[9];
+  double gr2 = 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    G[3 * i] = M[3 * i] * s1;
+    G[3 * i + 1] = M[3 * i + 1] * s1;
+    G[3 * i + 2] = M[3 * i + 2] - s1 * (M[3 * i] * cx1 + M[3 * i + 1] * cy1);
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    gG[j] = r2 * g0[j];
+    gG[3 + j] = r2 * g0[3 + j];
+    gG[6 + j] = cx2 * g0[j] + cy2 * g0[3 + j] + g0[6 + j];
+    gr2 += g0[j] * G[j] + g0[3 + j] * G[3 + j];
+    gnz2[0] += g0[j] * G[6 + j];
+    gnz2[1] += g0[3 + j] * G[6 + j];
+  }
+  gnz2[2] = -gr2 * r2 * r2;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const double m0 = M[3 * i], m1 = M[3 * i + 1], g2 = gG[3 * i + 2];
+    gM[3 * i] = s1 * (gG[3 * i] - g2 * cx1);
+    gM[3 * i + 1] = s1 * (gG[3 * i + 1] - g2 * cy1);
+    gM[3 * i + 2] = g2;
+    gnz1[2] += gG[3 * i] * m0 + gG[3 * i + 1] * m1 - g2 * (m0 * cx1 + m1 * cy1);
+    gnz1[0] -= s1 * g2 * m0;
+    gnz1[1] -= s1 * g2 * m1;
+  }
+  // M = A2 B, B = adj(A1)
+  double Bm[9], gA2[9], gB[9], gA1[9];
+  adjugate3(im[0].A, Bm);
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      gA2[3 * i + k] = gM[3 * i] * Bm[3 * k] + gM[3 * i + 1] * Bm[3 * k + 1] + gM[3 * i + 2] * Bm[3 * k + 2];
+      gB[3 * i + k] = im[1].A[i] * gM[k] + im[1].A[3 + i] * gM[3 + k] + im[1].A[6 + i] * gM[6 + k];      // (A2^T gM)[i][k]
+    }
+  double a[3][3], ga[3][3];      // columns of A1 and their gradients
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+      a[c][r] = im[0].A[3 * r + c];
+      ga[c][r] = 0.0;
+    }
+  cross_acc(a[2], &gB[0], ga[1]);      // row 0 = a1 x a2
+  cross_acc(&gB[0], a[1], ga[2]);
+  cross_acc(a[0], &gB[3], ga[2]);      // row 1 = a2 x a0
+  cross_acc(&gB[3], a[2], ga[0]);
+  cross_acc(a[1], &gB[6], ga[0]);      // row 2 = a0 x a1
+  cross_acc(&gB[6], a[0], ga[1]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int r = 0; r < 3; ++r) gA1[3 * r + c] = ga[c][r];
+  double gx1[4][2], gx2[4][2];
+  h4_image_bwd(im[0], gA1, gnz1, gx1);
+  h4_image_bwd(im[1], gA2, gnz2, gx2);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ok = ok && is_finite(gx1[i][0]) && is_finite(gx1[i][1]) && is_finite(gx2[i][0]) && is_finite(gx2[i][1]);
+  T *gs = grad_samples + (size_t)smp * 16;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    gs[4 * i] = ok ? (T)gx1[i][0] : T(0);
+    gs[4 * i + 1] = ok ? (T)gx1[i][1] : T(0);
+    gs[4 * i + 2] = ok ? (T)gx2[i][0] : T(0);
+    gs[4 * i + 3] = ok ? (T)gx2[i][1] : T(0);
+  }
+}
+
+// ---- (2) MSAC score and inlier count of every model against every point ---------------------------------------------------------------
+// rigid_score_kernel's mapping: one block = (pair, tile of kHSModels model slots) and walks ALL the pair's points in chunks of
+// kHSChunk.  A lane keeps kHSPts points of the chunk in registers across the tile -- point c0 + 256 j + tid, so one load
+// instruction of a wave reads 64 consecutive points --; the model is wave-uniform: its nine values are read through a uniform
+// address, the sign rule, adj(H) and the slot's kind are worked out from them once per (model, chunk), and a slot that is not valid
+// is left before anything of it is loaded.  Per point: twelve fma, two reciprocals, one compare for the term and the count.
+// The sum of a (pair, model) is reduced in one fixed order -- a lane's points in order, the wave butterfly, chunk after chunk into
+// the wave's LDS slot, the four slots in order -- with no atomics: a repeated launch gives the same bits.  No [P,M,N] tensor.
+// Slots: valid = 0 scores exactly 0 (0 inliers) and is never evaluated; a non-finite model or det == 0 scores NaN (0 inliers).
+constexpr int kHSThreads = 256, kHSPts = 8, kHSChunk = kHSThreads * kHSPts, kHSModels = 16;
+
+template <typename T>
+struct alignas(4 * sizeof(T)) Match4 {
+  T v[4];
+};
+
+template <typename T>
+__global__ __launch_bounds__(kHSThreads) void homography_score_kernel(const T *__restrict__ matches, const T *__restrict__ models,
+                                                                      const uint8_t *__restrict__ valid, const T *__restrict__ thr2,
+                                                                      int M, int N, T *__restrict__ scores,
+                                                                      int32_t *__restrict__ inliers) {
+  __shared__ T part[kHSThreads / 64][kHSModels];
+  __shared__ int pcnt[kHSThreads / 64][kHSModels];
+  const int p = blockIdx.y, m0 = blockIdx.x * kHSModels;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int mcount = min(kHSModels, M - m0);
+  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
+  const T *md = models + ((size_t)p * M + m0) * 9;
+  const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
+  const T t2 = thr2[p], inv = T(1) / t2;
+  if (tid < (kHSThreads / 64) * kHSModels) {
+    (&part[0][0])[tid] = T(0);
+    (&pcnt[0][0])[tid] = 0;
+  }
+  __syncthreads();
+  for (int c0 = 0; c0 < N; c0 += kHSChunk) {
+    Match4<T> x[kHSPts];
+#pragma unroll
+    for (int j = 0; j < kHSPts; ++j) {
+      const int n = c0 + j * kHSThreads + tid;
+      x[j] = pt[n < N ? n : N - 1];      // (a slot past the end re-reads the last row and is gated below)
+    }
+    for (int ml = 0; ml < mcount; ++ml) {
+      if (vd && !vd[ml]) continue;       // (wave-uniform)
+      ScoredH<T> s;
+      prepare_h(md + ml * 9, true, s);
+      if (s.kind != kModelScored) continue;
+      T acc = T(0);
+      int cnt = 0;
+#pragma unroll
+      for (int j = 0; j < kHSPts; ++j) {
+        T d2;
+        const bool in = transfer_inlier(s, x[j].v, t2, d2) && (c0 + j * kHSThreads + tid < N);
+        acc += in ? msac_gain(d2, inv) : T(0);
+        cnt += in ? 1 : 0;
+      }
+      acc = wave_sum(acc);
+      cnt = wave_sum(cnt);
+      if (lane == 0) {
+        part[wv][ml] += acc;
+        pcnt[wv][ml] += cnt;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < mcount) {
+    ScoredH<T> s;
+    prepare_h(md + tid * 9, !vd || vd[tid], s);
+    T v = T(0);
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kHSThreads / 64; ++w) {
+      v += part[w][tid];
+      n += pcnt[w][tid];
+    }
+    scores[(size_t)p * M + m0 + tid] = s.kind == kModelScored ? v : (s.kind == kModelNan ? T(NAN) : T(0));
+    if (inliers) inliers[(size_t)p * M + m0 + tid] = s.kind == kModelScored ? n : 0;
+  }
+}
+
+// ---- (3) the state step: registration_update_kernel's sibling for 3x3 models and 4-column matches ------------------------------------
+// One block per pair, the only writer of the pair's state.  A terminated pair returns at once.  The first arg-max over valid,
+// non-NaN scores replaces the state only on a STRICTLY higher score; mask and inlier count of a new best come from transfer_inlier,
+// the score kernel's expression, so the count is the mask's count; the bound from adaptive_max_iters with sample size 4; iters += B.
+constexpr int kHUThreads = 256;
+
+template <typename T>
+__global__ __launch_bounds__(kHUThreads) void homography_update_kernel(
+    const T *__restrict__ matches, const T *__restrict__ models, const uint8_t *__restrict__ valid, const T *__restrict__ scores,
+    const T *__restrict__ thr2, int M, int N, int B, double confidence, double eps, int max_iterations, T *__restrict__ best_score,
+    T *__restrict__ best_model, uint8_t *__restrict__ best_mask, int32_t *__restrict__ best_inliers, int32_t *__restrict__ iters,
+    double *__restrict__ max_iters) {
+  __shared__ T s_val[kHUThreads / 64];
+  __shared__ int s_idx[kHUThreads / 64];
+  __shared__ int s_cnt[kHUThreads / 64];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int it = iters[p];
+  if ((double)it >= max_iters[p]) return;      // this pair has terminated (uniform across the block)
+  const T bs = best_score[p];
+  T bv;
+  int bi;
+  // (its barrier comes after every thread has read iters / max_iters / best_score above: thread 0 may write them below)
+  block_arg_best<T, kHUThreads, true>(scores + (size_t)p * M, valid ? valid + (size_t)p * M : nullptr, M, s_val, s_idx, bv, bi);
+  if (bi != 0x7fffffff && bv > bs) {           // (block-uniform)
+    const T *win = models + ((size_t)p * M + bi) * 9;
+    ScoredH<T> s;
+    prepare_h(win, true, s);
+    const T t2 = thr2[p];
+    const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
+    int cnt = 0;
+    for (int n = tid; n < N; n += kHUThreads) {
+      const Match4<T> x = pt[n];
+      T d2;
+      const bool in = s.kind == kModelScored && transfer_inlier(s, x.v, t2, d2);
+      best_mask[(size_t)p * N + n] = in;
+      cnt += in;
+    }
+    cnt = wave_sum(cnt);
+    if (lane == 0) s_cnt[wv] = cnt;
+    __syncthreads();
+    if (tid < 9) best_model[(size_t)p * 9 + tid] = win[tid];
+    if (tid == 0) {
+      int inl = 0;
+#pragma unroll
+      for (int w = 0; w < kHUThreads / 64; ++w) inl += s_cnt[w];
+      best_inliers[p] = inl;
+      best_score[p] = bv;
+      max_iters[p] = adaptive_max_iters(inl, N, 4, confidence, eps, max_iterations);
+    }
+  }
+  if (tid == 0) iters[p] = it + B;
+}
+
+// ---- (4) normalised DLT over the rows a mask selects: one 256-thread block per pair, f64, fixed-order sums -----------------------------
+// Three passes of thread n over rows n, n + 256, ...: the count and the coordinate sums (the centroids), the distance sums (the
+// scales s_i = sqrt(2) / mean distance: Hartley's transforms of the selected rows, unweighted), the Gram matrix.  With X = (x, y, 1)
+// and (u, v) the normalised points, the two DLT rows of a match are a = (0, -X, v X) and b = (X, 0, -u X), so
+//   sum w (a a^T + b b^T) = [[S, 0, -Su], [0, S, -Sv], [-Su, -Sv, Sq]],   S = sum w X X^T, Su = sum w u X X^T, Sv = sum w v X X^T,
+//   Sq = sum w (u^2 + v^2) X X^T:  24 sums instead of 45.  Sums go lane, wave butterfly, the four waves in order (no atomics).
+// Wave 0 then takes the smallest eigenvector with jacobi_eig9_wave, denormalises and canonicalises; valid = 0 (identity) below four
+// rows and for a non-finite or singular result.
+constexpr int kHRThreads = 256;
+
+template <int K>
+__device__ __forceinline__ void h_block_sum(double (&v)[K], double *s_part, double *s_tot) {      // s_part [4][K], s_tot [K]
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const double w = wave_sum(v[i]);
+    if (lane == 0) s_part[wv * K + i] = w;
+  }
+  __syncthreads();
+  if (tid < K) {
+    double a = s_part[tid];
+#pragma unroll
+    for (int w = 1; w < kHRThreads / 64; ++w) a += s_part[w * K + tid];
+    s_tot[tid] = a;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < K; ++i) v[i] = s_tot[i];
+  __syncthreads();      // (the buffers are reused)
+}
+
+template <typename T>
+__global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                                      const T *__restrict__ weights, int N, T *__restrict__ model,
+                                                                      uint8_t *__restrict__ valid) {
+  __shared__ double s_part[(kHRThreads / 64) * 24], s_tot[24], gram[81], Vl[81], cs[18];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+  double a[5] = {0, 0, 0, 0, 0};
+  for (int n = tid; n < N; n += kHRThreads) {
+    if (mk && !mk[n]) continue;
+    const Match4<T> x = pt[n];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) a[d] += (double)x.v[d];
+    a[4] += 1.0;
+  }
+  h_block_sum<5>(a, s_part, s_tot);
+  const double rows = a[4], rn = 1.0 / rows;
+  const double mu[4] = {a[0] * rn, a[1] * rn, a[2] * rn, a[3] * rn};
+  double dd[2] = {0, 0};
+  for (int n = tid; n < N; n += kHRThreads) {
+    if (mk && !mk[n]) continue;
+    const Match4<T> x = pt[n];
+    const double q0 = (double)x.v[0] - mu[0], q1 = (double)x.v[1] - mu[1], q2 = (double)x.v[2] - mu[2], q3 = (double)x.v[3] - mu[3];
+    dd[0] += sqrt(q0 * q0 + q1 * q1);
+    dd[1] += sqrt(q2 * q2 + q3 * q3);
+  }
+  h_block_sum<2>(dd, s_part, s_tot);
+  const double nz1[3] = {mu[0], mu[1], M_SQRT2 * rows / dd[0]}, nz2[3] = {mu[2], mu[3], M_SQRT2 * rows / dd[1]};
+  double g[24];
+#pragma unroll
+  for (int q = 0; q < 24; ++q) g[q] = 0.0;
+  for (int n = tid; n < N; n += kHRThreads) {
+    if (mk && !mk[n]) continue;
+    const Match4<T> m = pt[n];
+    const double w = wt ? (double)wt[n] : 1.0;
+    const double x = ((double)m.v[0] - nz1[0]) * nz1[2], y = ((double)m.v[1] - nz1[1]) * nz1[2];
+    const double u = ((double)m.v[2] - nz2[0]) * nz2[2], v = ((double)m.v[3] - nz2[1]) * nz2[2];
+    const double xx[6] = {w * x * x, w * x * y, w * x, w * y * y, w * y, w};
+    const double q2 = u * u + v * v;
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+      g[e] += xx[e];
+      g[6 + e] += u * xx[e];
+      g[12 + e] += v * xx[e];
+      g[18 + e] += q2 * xx[e];
+    }
+  }
+  h_block_sum<24>(g, s_part, s_tot);      // (s_tot keeps the 24 totals)
+  if (tid < 81) {
+    const int r = tid / 9, c = tid - 9 * r, br = r / 3, bc = c / 3, i = r - 3 * br, j = c - 3 * bc;
+    const int lo = min(i, j), hi = max(i, j), e = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);      // (i, j) -> entry of the symmetric 3x3
+    const int bl = min(br, bc), bh = max(br, bc);
+    double v = 0.0;
+    if (bl == bh) v = bl == 2 ? s_tot[18 + e] : s_tot[e];
+    else if (bh == 2) v = bl == 0 ? -s_tot[6 + e] : -s_tot[12 + e];
+    gram[tid] = v;
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+  jacobi_eig9_wave(gram, Vl, cs, tid);
+  double ev[1][9];
+  smallest_eigvecs9_lds<1>(gram, Vl, ev);
+  double H[9], nrm, sigma;
+  denormalise_h(ev[0], nz1, nz2, H);
+  const bool ok = canonical_h(H, rows >= 4.0, nrm, sigma);
+  if (tid == 0) {
+    store_h(model + (size_t)p * 9, H);
+    valid[p] = ok;
+  }
+}
+
+}  // namespace dr
+
+extern "C" {
+
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_homography4_gather_##sfx(const T *matches, const int32_t *idx, int P, int B, int N, T *models, uint8_t *valid,             \
+                                  void *stream) {                                                                                   \
+    DR_REQUIRE(matches && idx && models && valid, "null pointer");                                                                  \
+    DR_REQUIRE(P > 0 && B > 0 && N > 0 && (long)P * B < (1l << 31), "need P, B, N > 0");                                            \
+    return dr::launch("homography4_gather_kernel", dr::homography4_gather_kernel<T>, dim3((P * B + 63) / 64), 64, stream, matches,  \
+                      idx, P * B, B, N, models, valid);                                                                             \
+  }                                                                                                                                 \
+  int dr_homography4_##sfx(const T *samples, int Bt, T *models, uint8_t *valid, void *stream) {                                     \
+    DR_REQUIRE(samples && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(Bt > 0, "need Bt > 0");                                                                                              \
+    return dr::launch("homography4_kernel", dr::homography4_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, Bt, models,       \
+                      valid);                                                                                                       \
+  }                                                                                                                                 \
+  int dr_homography4_bwd_##sfx(const T *samples, const T *grad_models, int Bt, T *grad_samples, void *stream) {                     \
+    DR_REQUIRE(samples && grad_models && grad_samples, "null pointer");                                                             \
+    DR_REQUIRE(Bt > 0, "need Bt > 0");                                                                                              \
+    return dr::launch("homography4_bwd_kernel", dr::homography4_bwd_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples,           \
+                      grad_models, Bt, grad_samples);                                                                               \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_homography_score_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N,        \
+                                T *scores, int32_t *inliers, void *stream) {                                                        \
+    DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                                                \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    return dr::launch("homography_score_kernel", dr::homography_score_kernel<T>, dim3((M + dr::kHSModels - 1) / dr::kHSModels, P),  \
+                      dr::kHSThreads, stream, matches, models, valid, thr2, M, N, scores, inliers);                                 \
+  }                                                                                                                                 \
+  int dr_homography_update_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P,    \
+                                 int M, int N, int B, double confidence, double eps, int max_iterations, T *best_score,             \
+                                 T *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters,       \
+                                 void *stream) {                                                                                    \
+    DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters,  \
+               "null pointer");                                                                                                     \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes");                                                \
+    return dr::launch("homography_update_kernel", dr::homography_update_kernel<T>, dim3(P), dr::kHUThreads, stream, matches,        \
+                      models, valid, scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask,     \
+                      best_inliers, iters, max_iters);                                                                              \
+  }                                                                                                                                 \
+  int dr_refit_homography_##sfx(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *model, uint8_t *valid,    \
+                                void *stream) {                                                                                     \
+    DR_REQUIRE(matches && model && valid, "null pointer");                                                                          \
+    DR_REQUIRE(P > 0 && N > 0, "bad sizes");                                                                                        \
+    return dr::launch("refit_homography_kernel", dr::refit_homography_kernel<T>, dim3(P), dr::kHRThreads, stream, matches, mask,    \
+                      weights, N, model, valid);                                                                                    \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
+}  // extern "C"

@@ -1240,6 +1240,134 @@ def weighted_kabsch(matches, weights=None, mask=None):
     return _WeightedKabsch.apply(matches, weights, mask)
 
 
+# ------------------------------------------------------------------------------------------ plane-induced homographies
+# matches [P,N,4] = (x1, y1, x2, y2) in the caller's coordinates (pixels), models [.,3,3] = H with x2 ~ H x1, unit Frobenius norm and
+# det > 0.  d2 = the symmetric transfer error; `threshold` is a DISTANCE: inlier iff d2 < threshold^2 (thr2_tensor).
+def _check_matches4(name: str, matches: torch.Tensor) -> None:
+    if matches.dim() != 3 or matches.shape[-1] != 4:
+        raise L.DransacError(f"{name}: matches [P,N,4] = (x1, y1, x2, y2)")
+
+
+def homography4_gather(matches: torch.Tensor, idx: torch.Tensor):
+    """dr_homography4_gather: matches [P,N,4], idx [P,B,4] int32 -> (models [P,B,3,3], valid [P,B] bool): the closed-form homography of
+    every four-point sample; a sample with three collinear points, with an orientation that differs between the images, or without a
+    finite non-singular model is the identity with valid = 0."""
+    _check_matches4("homography4_gather", matches)
+    if idx.dim() != 3 or idx.shape[-1] != 4 or idx.dtype != torch.int32 or idx.shape[0] != matches.shape[0]:
+        raise L.DransacError("homography4_gather: int32 index sets [P,B,4]")
+    P, N, _ = matches.shape
+    B = idx.shape[1]
+    models = torch.empty((P, B, 3, 3), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_homography4_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B),
+           c_int(N), ptr(models), ptr(valid), stream())
+    return models, valid
+
+
+def homography_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
+                     want_inliers: bool = True, thr2: Optional[torch.Tensor] = None):
+    """dr_homography_score: matches [P,N,4], models [P,M,3,3], threshold = inlier DISTANCE (float or [P]) ->
+    (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None).  A slot with valid = 0
+    scores exactly 0; a non-finite model or one with det == 0 scores NaN; a model of negative determinant scores like its negation.
+    Bit-repeatable (fixed reduction order)."""
+    _check_matches4("homography_score", matches)
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    if models.shape != (P, M, 3, 3) or models.dtype != matches.dtype:
+        raise L.DransacError("homography_score: models [P,M,3,3] of the matches' dtype")
+    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
+    scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
+    inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
+    L.call(f"dr_homography_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), stream())
+    return scores, inliers
+
+
+class HomographyState:
+    """Per-pair state of a BatchedHomography call, on the device: best_score [P] (0), best_model [P,3,3] (identity), best_mask [P,N],
+    best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch."""
+
+    def __init__(self, P: int, N: int, max_iterations: int, device, dtype):
+        self.best_score = torch.zeros(P, device=device, dtype=dtype)
+        self.best_model = torch.eye(3, device=device, dtype=dtype).repeat(P, 1, 1)
+        self.best_mask = torch.zeros(P, N, device=device, dtype=torch.bool)
+        self.best_inliers = torch.zeros(P, device=device, dtype=torch.int32)
+        self.iters = torch.zeros(P, device=device, dtype=torch.int32)
+        self.max_iters = torch.full((P,), float(max_iterations), device=device, dtype=torch.float64)
+        self.max_iterations = int(max_iterations)
+
+
+def homography_update(state: HomographyState, matches, models, valid, scores, threshold, B: int, confidence: float = 0.999,
+                      eps: float = 1e-5, thr2: Optional[torch.Tensor] = None) -> None:
+    """dr_homography_update, in place on `state`: per pair with iters < max_iters the first arg-max of scores [P,M] over valid, non-NaN
+    slots replaces the state if score > best_score (mask and inlier count recomputed with the score kernel's expression,
+    max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 4))); iters += B."""
+    _check_matches4("homography_update", matches)
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
+    L.call(f"dr_homography_update_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(scores.contiguous()), ptr(thr2), c_int(P), c_int(M), c_int(N), c_int(int(B)), L.c_double(confidence), L.c_double(eps),
+           c_int(state.max_iterations), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
+           ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
+
+
+def refit_homography(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
+    """dr_refit_homography: the normalised DLT over the rows mask [P,N] selects (None = all), weights [P,N] (optional) multiplying a
+    row's terms in the Gram matrix -> (model [P,3,3], valid [P] bool); valid = 0 (identity) below four rows or for a non-finite or
+    singular result."""
+    _check_matches4("refit_homography", matches)
+    P, N, _ = matches.shape
+    if weights is not None and weights.shape != (P, N):
+        raise L.DransacError("refit weights are [P,N], one per point")
+    if mask is not None and mask.shape != (P, N):
+        raise L.DransacError("the refit mask is [P,N], one flag per point")
+    model = torch.empty((P, 3, 3), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_refit_homography_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
+           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(model), ptr(valid),
+           stream())
+    return model, valid
+
+
+class _Homography4(torch.autograd.Function):
+    """dr_homography4 / dr_homography4_bwd: the backward recomputes the closed form from the samples, so no model is saved"""
+
+    @staticmethod
+    def forward(ctx, samples):
+        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+        s, Bt, _ = _flat_samples(samples, 4)
+        models = torch.empty((Bt, 3, 3), device=s.device, dtype=s.dtype)
+        valid = torch.empty((Bt,), device=s.device, dtype=torch.bool)
+        L.call(f"dr_homography4_{L.suffix(s.dtype)}", ptr(s), c_int(Bt), ptr(models), ptr(valid), stream())
+        ctx.save_for_backward(s)
+        ctx.sshape = samples.shape
+        lead = samples.shape[:-2]
+        valid = valid.reshape(lead)
+        ctx.mark_non_differentiable(valid)
+        return models.reshape(*lead, 3, 3), valid
+
+    @staticmethod
+    def backward(ctx, g_models, _gv):
+        if g_models is None:
+            return None
+        (s,) = ctx.saved_tensors
+        gs = torch.empty_like(s)
+        L.call(f"dr_homography4_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(g_models.to(s.dtype).reshape(-1, 3, 3).contiguous()),
+               c_int(s.shape[0]), ptr(gs), stream())
+        return gs.reshape(ctx.sshape)
+
+
+def homography4(samples):
+    """samples [..., 4, 4] = four (x1, y1, x2, y2) rows -> (models [..., 3, 3], keep [...] bool): the closed-form homography of every
+    sample with autograd to `samples` in f32 and f64 (dr_homography4, dr_homography4_bwd).  On samples = matches[idx] the models of
+    homography4_gather bit for bit.  A sample without a valid model (keep = 0: the identity), or with a non-finite derivative, passes
+    exact zeros back."""
+    if samples.dim() < 3 or samples.shape[-2:] != (4, 4):
+        raise L.DransacError("homography4: samples [..., 4, 4], four matches per sample")
+    return _Homography4.apply(samples)
+
+
 class _MsacScore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, matches, models, thr, want_masks):

@@ -1197,3 +1197,103 @@ class BatchedRegistration(_SeededDriver):
             if rejected is not None:
                 out["rejected"] = rejected
             return out
+
+
+class BatchedHomography(_SeededDriver):
+    """Robust plane-induced homographies of image pairs: matches [P,N,4] = (x1, y1, x2, y2) in the caller's own coordinates (pixels;
+    there is no K), logits [P,N] -> in test mode (the default) dict(model [P,3,3] = H with x2 ~ H x1, unit Frobenius norm and
+    det H > 0, mask [P,N], score [P], inliers [P], iterations [P]).  The model for planar scenes and pure rotations, where the E and F
+    solvers of BatchedRANSAC degenerate.
+
+    One round = K1 Gumbel top-k (index sets of 4 points) -> dr_homography4_gather (the closed-form model of every sample; a sample
+    with three collinear points or an orientation that differs between the images is dropped: identity, valid = 0) ->
+    dr_homography_score (MSAC score of every model against every point under the symmetric transfer error) -> dr_homography_update
+    (first arg-max, strictly-better test, mask, adaptive stop with sample size 4, all per-pair state on the device).  The host reads
+    back "does any pair continue?" after each round.  With `refit`, the normalised DLT on the best mask (dr_refit_homography) replaces
+    the model where it scores strictly higher; the mask stays the RANSAC winner's.
+
+    `threshold` is a DISTANCE in the matches' units: a point is an inlier iff d2 < threshold^2, d2 = |x2 - H x1|^2 + |x1 - H^-1 x2|^2
+    after the perspective divisions; a point that H or H^-1 sends behind the camera is an outlier.
+
+    sampling = "prosac" (test mode only): ops.prosac_sample in ops.gumbel_topk's place, round r being PROSAC draws r B + 1 .. (r + 1) B
+    of every pair, as in BatchedRegistration.  Refused with train = True and with explicit `gumbels`.
+
+    train = True: every round runs (no adaptive stop), each one ops.SampleGather followed by ops.homography4, and the call returns
+    dict(models [P, rounds * B, 3, 3], keep [P, rounds * B] = the sample's validity) with autograd to the logits, and to `matches`
+    where they require it.  `refit` and `confidence` play no part and nothing is read back.
+
+    Not here: local optimisation, MAGSAC++ scoring, device_termination, super-rounds, samples of more than 4 points."""
+
+    k = 4
+
+    def __init__(self, ransac_batch_size=1024, threshold=3.0, confidence=0.999, max_iterations=5000, tau=1.0, seed=0, refit=True,
+                 eps=1e-5, train=False, sampling="gumbel", prosac_draws=200000):
+        if sampling not in ("gumbel", "prosac"):
+            raise ValueError(f"sampling must be 'gumbel' or 'prosac', got {sampling!r}")
+        if sampling == "prosac" and train:
+            raise ValueError("sampling='prosac' yields index sets only: train mode needs the Gumbel sampler")
+        self._set_prosac_draws(prosac_draws)
+        self.sampling = sampling
+        if int(max_iterations) < 1:
+            raise ValueError(f"max_iterations must be at least 1, got {max_iterations!r}")
+        if int(ransac_batch_size) < 1:
+            raise ValueError(f"ransac_batch_size must be at least 1, got {ransac_batch_size!r}")
+        self.B = int(ransac_batch_size)
+        self.threshold = threshold
+        self.confidence = confidence
+        self.max_iterations = int(max_iterations)
+        self.tau = tau
+        self._seeds = _Seeds(seed)
+        self.refit = refit
+        self.eps = eps
+        self.train = bool(train)
+
+    @property
+    def rounds(self):
+        """rounds a call can run at most"""
+        return max(1, math.ceil(self.max_iterations / self.B))
+
+    def __call__(self, matches, logits, gumbels=None):
+        """`gumbels` (optional, list of [P,B,N] tensors, one per round) replaces the in-kernel noise: parity runs."""
+        if matches.dim() != 3 or matches.shape[-1] != 4:
+            raise ValueError("matches must be [P,N,4] = (x1, y1, x2, y2)")
+        P, N, _ = matches.shape
+        if self.sampling == "prosac" and gumbels is not None:
+            raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
+        rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
+        if self.train:
+            if logits.dtype != matches.dtype:      # (the straight-through weights are read in the matches' type)
+                raise ValueError(f"train mode needs logits of the matches' dtype, got {logits.dtype} and {matches.dtype}")
+            out = []
+            for r in range(rounds):
+                g = None if gumbels is None else gumbels[r]
+                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
+                out.append(ops.homography4(samples))
+            return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
+        with torch.no_grad():
+            matches = matches.contiguous()
+            st = ops.HomographyState(P, N, self.max_iterations, matches.device, matches.dtype)
+            thr2 = ops.thr2_tensor(self.threshold, P, matches)
+            prosac = self.sampling == "prosac"
+            if prosac:      # the ranking of this call's logits and the growth table, once for all its rounds
+                order, growth = self._prosac_setup(logits, N, matches.device)
+            for r in range(rounds):
+                g = None if gumbels is None else gumbels[r]
+                if prosac:      # rows of round r = draws r B + 1 .. (r + 1) B
+                    idx = ops.prosac_sample(order, growth, self.B, self.k, self._seeds.next(), r * self.B, P=P, N=N,
+                                            device=matches.device)
+                else:
+                    idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
+                models, valid = ops.homography4_gather(matches, idx)
+                scores, _ = ops.homography_score(matches, models, None, valid, want_inliers=False, thr2=thr2)
+                ops.homography_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
+                if r + 1 < rounds and not bool((st.iters.double() < st.max_iters).any()):
+                    break
+            model, score = st.best_model, st.best_score
+            if self.refit:
+                cand, cvalid = ops.refit_homography(matches, st.best_mask)
+                cscore, _ = ops.homography_score(matches, cand.unsqueeze(1), None, cvalid.unsqueeze(1), want_inliers=False, thr2=thr2)
+                take = cscore[:, 0] > score          # (an invalid candidate scores 0, a NaN never compares higher)
+                model = torch.where(take[:, None, None], cand, model)
+                score = torch.where(take, cscore[:, 0], score)
+            return dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)

@@ -474,6 +474,62 @@ int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const dou
                            double *grad_matches, double *grad_weights, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Plane-induced homographies (ransac.BatchedHomography).  Not a restatement of upstream code.  matches [P,N,4] = (x1, y1, x2, y2) in
+ * the caller's coordinates (pixels; there is no K).  A model [.,9] is the row-major 3x3 H with x2 ~ H x1, stored with unit Frobenius
+ * norm and det H > 0.  Residual: y = H (x1, 1), z = adj(H) (x2, 1), d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2 (the symmetric
+ * transfer error); a point with y_w <= 0 or z_w <= 0 under the det > 0 sign, or with a non-finite d2, is an outlier and contributes
+ * nothing.  The threshold is a DISTANCE and enters as thr2 [P] = threshold^2: inlier iff d2 < thr2, MSAC score =
+ * sum_n max(0, 1 - d2_n / thr2).
+ *
+ *   dr_homography4_gather   idx [P,B,4] int32 -> models [P,B,9], valid [P,B]: the closed form, f64 inside, one lane per sample.  Per
+ *     image q_i = x_i - centroid, s = sqrt(2) / mean |q_i|, p_i = (s q_i, 1); D_3 = [q0 q1 q2], D_0 = [q3 q1 q2], D_1 = [q0 q3 q2],
+ *     D_2 = [q0 q1 q3] (orientation determinants), lambda_i = D_i / D_3, A = [lambda_0 p0 | lambda_1 p1 | lambda_2 p2];
+ *     H = T2^-1 A2 adj(A1) T1, then unit norm and det > 0.  valid = 0, model = identity: an index outside [0, N), a D that is zero or
+ *     whose sign differs between the images (three collinear points, a sample point sent through infinity), a non-finite or singular H.
+ *   dr_homography4          the same on explicit samples [Bt,4,4]; on samples = matches[idx] the same bits.
+ *   dr_homography4_bwd      grad_models [Bt,9] -> grad_samples [Bt,4,4]: the reverse pass of the closed form, through the
+ *     normalisation and the unit-norm scaling (a multiple of H in grad_models passes nothing on); the forward is recomputed in f64.
+ *     A sample without a valid model, or with a non-finite derivative, gets exact zeros.  Every element is written.
+ *   dr_homography_score     models [P,M,9], valid [P,M] or NULL -> scores [P,M], inliers [P,M] int32 (or NULL).  A slot with
+ *     valid = 0 scores exactly 0 (0 inliers) and is never evaluated; a non-finite model or one with det == 0 scores NaN (0 inliers).
+ *     The det > 0 sign is applied here: a model of negative determinant scores like its negation.  f32 computes in f32 (two
+ *     v_rcp_f32 per model and point), f64 in f64.  No [P,M,N] tensor, no atomics, one fixed reduction order: a repeated launch gives
+ *     the same bits.  P <= 65535.
+ *   dr_homography_update    the state step: for every pair with iters < max_iters, the first arg-max of scores over valid, non-NaN
+ *     slots replaces the state only if score > best_score (strict) -- best_score, best_model [P,9], best_mask [P,N] and best_inliers
+ *     (the mask's count, by dr_homography_score's expression), max_iters = min(max_iterations, adaptive_iteration_number(inliers, N,
+ *     4)) in f64 -- and iters += B.  No qualifying slot: only iters moves.  Terminated pairs are untouched.
+ *   dr_refit_homography     the normalised DLT over the rows mask [P,N] selects (NULL = all), weights [P,N] (optional) multiplying a
+ *     row's terms in the Gram matrix -> model [P,9], valid [P].  Hartley's transforms come from the selected rows, unweighted; the 9x9
+ *     Gram matrix of the two DLT rows per point is summed in f64 in one fixed order; its smallest eigenvector (Jacobi) is denormalised,
+ *     scaled to unit norm and given det > 0.  valid = 0, model = identity: fewer than four rows, a non-finite or singular result.
+ * ------------------------------------------------------------------------------------------ */
+int dr_homography4_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, float *models, uint8_t *valid,
+                              void *stream);
+int dr_homography4_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, double *models, uint8_t *valid,
+                              void *stream);
+int dr_homography4_f32(const float *samples, int Bt, float *models, uint8_t *valid, void *stream);
+int dr_homography4_f64(const double *samples, int Bt, double *models, uint8_t *valid, void *stream);
+int dr_homography4_bwd_f32(const float *samples, const float *grad_models, int Bt, float *grad_samples, void *stream);
+int dr_homography4_bwd_f64(const double *samples, const double *grad_models, int Bt, double *grad_samples, void *stream);
+int dr_homography_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
+                            float *scores, int32_t *inliers, void *stream);
+int dr_homography_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
+                            int N, double *scores, int32_t *inliers, void *stream);
+int dr_homography_update_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores,
+                             const float *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
+                             float *best_score, float *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
+                             double *max_iters, void *stream);
+int dr_homography_update_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores,
+                             const double *thr2, int P, int M, int N, int B, double confidence, double eps, int max_iterations,
+                             double *best_score, double *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters,
+                             double *max_iters, void *stream);
+int dr_refit_homography_f32(const float *matches, const uint8_t *mask, const float *weights, int P, int N, float *model,
+                            uint8_t *valid, void *stream);
+int dr_refit_homography_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model,
+                            uint8_t *valid, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The training loss of the registration path (loss.RegistrationLoss).  Not a restatement of upstream code: RANSACLayer3D's own loss
  * (model_cl.py:586-589) is the mean squared residual over ALL points, which dr_rigid_residual already reproduces.  matches, models,
  * thr2 as above; mask [P,N] (the ground-truth inliers; NULL = all points), keep [P,M] (NULL = all models).  With r = R p + t - q:
