@@ -8,6 +8,7 @@
 //   a non-finite d2, is an outlier and contributes nothing.  The threshold is a DISTANCE and enters as thr2 = threshold^2 per pair:
 //   inlier <=> d2 < thr2; MSAC score = sum_n max(0, 1 - d2_n / thr2).
 #include "homography_device.hpp"
+#include "pair_state_device.hpp"
 #include "solver_common.hpp"
 
 namespace dr {
@@ -272,175 +273,24 @@ __global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict
   }
 }
 
-// ---- (2) MSAC score and inlier count of every model against every point ---------------------------------------------------------------
-// rigid_score_kernel's mapping: one block = (pair, tile of kHSModels model slots) and walks ALL the pair's points in chunks of
-// kHSChunk.  A lane keeps kHSPts points of the chunk in registers across the tile -- point c0 + 256 j + tid, so one load
-// instruction of a wave reads 64 consecutive points --; the model is wave-uniform: its nine values are read through a uniform
-// address, the sign rule, adj(H) and the slot's kind are worked out from them once per (model, chunk), and a slot that is not valid
-// is left before anything of it is loaded.  Per point: twelve fma, two reciprocals, one compare for the term and the count.
-// The sum of a (pair, model) is reduced in one fixed order -- a lane's points in order, the wave butterfly, chunk after chunk into
-// the wave's LDS slot, the four slots in order -- with no atomics: a repeated launch gives the same bits.  No [P,M,N] tensor.
-// Slots: valid = 0 scores exactly 0 (0 inliers) and is never evaluated; a non-finite model or det == 0 scores NaN (0 inliers).
-constexpr int kHSThreads = 256, kHSPts = 8, kHSChunk = kHSThreads * kHSPts, kHSModels = 16;
-
-template <typename T>
-struct alignas(4 * sizeof(T)) Match4 {
-  T v[4];
-};
-
-template <typename T>
-__global__ __launch_bounds__(kHSThreads) void homography_score_kernel(const T *__restrict__ matches, const T *__restrict__ models,
-                                                                      const uint8_t *__restrict__ valid, const T *__restrict__ thr2,
-                                                                      int M, int N, T *__restrict__ scores,
-                                                                      int32_t *__restrict__ inliers) {
-  __shared__ T part[kHSThreads / 64][kHSModels];
-  __shared__ int pcnt[kHSThreads / 64][kHSModels];
-  const int p = blockIdx.y, m0 = blockIdx.x * kHSModels;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int mcount = min(kHSModels, M - m0);
-  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
-  const T *md = models + ((size_t)p * M + m0) * 9;
-  const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
-  const T t2 = thr2[p], inv = T(1) / t2;
-  if (tid < (kHSThreads / 64) * kHSModels) {
-    (&part[0][0])[tid] = T(0);
-    (&pcnt[0][0])[tid] = 0;
-  }
-  __syncthreads();
-  for (int c0 = 0; c0 < N; c0 += kHSChunk) {
-    Match4<T> x[kHSPts];
-#pragma unroll
-    for (int j = 0; j < kHSPts; ++j) {
-      const int n = c0 + j * kHSThreads + tid;
-      x[j] = pt[n < N ? n : N - 1];      // (a slot past the end re-reads the last row and is gated below)
-    }
-    for (int ml = 0; ml < mcount; ++ml) {
-      if (vd && !vd[ml]) continue;       // (wave-uniform)
-      ScoredH<T> s;
-      prepare_h(md + ml * 9, true, s);
-      if (s.kind != kModelScored) continue;
-      T acc = T(0);
-      int cnt = 0;
-#pragma unroll
-      for (int j = 0; j < kHSPts; ++j) {
-        T d2;
-        const bool in = transfer_inlier(s, x[j].v, t2, d2) && (c0 + j * kHSThreads + tid < N);
-        acc += in ? msac_gain(d2, inv) : T(0);
-        cnt += in ? 1 : 0;
-      }
-      acc = wave_sum(acc);
-      cnt = wave_sum(cnt);
-      if (lane == 0) {
-        part[wv][ml] += acc;
-        pcnt[wv][ml] += cnt;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < mcount) {
-    ScoredH<T> s;
-    prepare_h(md + tid * 9, !vd || vd[tid], s);
-    T v = T(0);
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < kHSThreads / 64; ++w) {
-      v += part[w][tid];
-      n += pcnt[w][tid];
-    }
-    scores[(size_t)p * M + m0 + tid] = s.kind == kModelScored ? v : (s.kind == kModelNan ? T(NAN) : T(0));
-    if (inliers) inliers[(size_t)p * M + m0 + tid] = s.kind == kModelScored ? n : 0;
-  }
-}
-
-// ---- (3) the state step: registration_update_kernel's sibling for 3x3 models and 4-column matches ------------------------------------
-// One block per pair, the only writer of the pair's state.  A terminated pair returns at once.  The first arg-max over valid,
-// non-NaN scores replaces the state only on a STRICTLY higher score; mask and inlier count of a new best come from transfer_inlier,
-// the score kernel's expression, so the count is the mask's count; the bound from adaptive_max_iters with sample size 4; iters += B.
-constexpr int kHUThreads = 256;
-
-template <typename T>
-__global__ __launch_bounds__(kHUThreads) void homography_update_kernel(
-    const T *__restrict__ matches, const T *__restrict__ models, const uint8_t *__restrict__ valid, const T *__restrict__ scores,
-    const T *__restrict__ thr2, int M, int N, int B, double confidence, double eps, int max_iterations, T *__restrict__ best_score,
-    T *__restrict__ best_model, uint8_t *__restrict__ best_mask, int32_t *__restrict__ best_inliers, int32_t *__restrict__ iters,
-    double *__restrict__ max_iters) {
-  __shared__ T s_val[kHUThreads / 64];
-  __shared__ int s_idx[kHUThreads / 64];
-  __shared__ int s_cnt[kHUThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int it = iters[p];
-  if ((double)it >= max_iters[p]) return;      // this pair has terminated (uniform across the block)
-  const T bs = best_score[p];
-  T bv;
-  int bi;
-  // (its barrier comes after every thread has read iters / max_iters / best_score above: thread 0 may write them below)
-  block_arg_best<T, kHUThreads, true>(scores + (size_t)p * M, valid ? valid + (size_t)p * M : nullptr, M, s_val, s_idx, bv, bi);
-  if (bi != 0x7fffffff && bv > bs) {           // (block-uniform)
-    const T *win = models + ((size_t)p * M + bi) * 9;
-    ScoredH<T> s;
-    prepare_h(win, true, s);
-    const T t2 = thr2[p];
-    const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
-    int cnt = 0;
-    for (int n = tid; n < N; n += kHUThreads) {
-      const Match4<T> x = pt[n];
-      T d2;
-      const bool in = s.kind == kModelScored && transfer_inlier(s, x.v, t2, d2);
-      best_mask[(size_t)p * N + n] = in;
-      cnt += in;
-    }
-    cnt = wave_sum(cnt);
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    if (tid < 9) best_model[(size_t)p * 9 + tid] = win[tid];
-    if (tid == 0) {
-      int inl = 0;
-#pragma unroll
-      for (int w = 0; w < kHUThreads / 64; ++w) inl += s_cnt[w];
-      best_inliers[p] = inl;
-      best_score[p] = bv;
-      max_iters[p] = adaptive_max_iters(inl, N, 4, confidence, eps, max_iterations);
-    }
-  }
-  if (tid == 0) iters[p] = it + B;
-}
+// ---- (2), (3) the MSAC score of every model against every point and the state step are pair_state_device.hpp's pair_score_kernel and
+// pair_update_kernel under HomographyGeom and TransferMsacTerm (homography_device.hpp)
 
 // ---- (4) normalised DLT over the rows a mask selects: one 256-thread block per pair, f64, fixed-order sums -----------------------------
 // Three passes of thread n over rows n, n + 256, ...: the count and the coordinate sums (the centroids), the distance sums (the
 // scales s_i = sqrt(2) / mean distance: Hartley's transforms of the selected rows, unweighted), the Gram matrix.  With X = (x, y, 1)
 // and (u, v) the normalised points, the two DLT rows of a match are a = (0, -X, v X) and b = (X, 0, -u X), so
 //   sum w (a a^T + b b^T) = [[S, 0, -Su], [0, S, -Sv], [-Su, -Sv, Sq]],   S = sum w X X^T, Su = sum w u X X^T, Sv = sum w v X X^T,
-//   Sq = sum w (u^2 + v^2) X X^T:  24 sums instead of 45.  Sums go lane, wave butterfly, the four waves in order (no atomics).
+//   Sq = sum w (u^2 + v^2) X X^T:  24 sums instead of 45.  Sums by block_sum_f64: lane, wave butterfly, the four waves in order.
 // Wave 0 then takes the smallest eigenvector with jacobi_eig9_wave, denormalises and canonicalises; valid = 0 (identity) below four
 // rows and for a non-finite or singular result.
-constexpr int kHRThreads = 256;
-
-template <int K>
-__device__ __forceinline__ void h_block_sum(double (&v)[K], double *s_part, double *s_tot) {      // s_part [4][K], s_tot [K]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    const double w = wave_sum(v[i]);
-    if (lane == 0) s_part[wv * K + i] = w;
-  }
-  __syncthreads();
-  if (tid < K) {
-    double a = s_part[tid];
-#pragma unroll
-    for (int w = 1; w < kHRThreads / 64; ++w) a += s_part[w * K + tid];
-    s_tot[tid] = a;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < K; ++i) v[i] = s_tot[i];
-  __syncthreads();      // (the buffers are reused)
-}
+constexpr int kHRThreads = kPairThreads;
 
 template <typename T>
 __global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
                                                                       const T *__restrict__ weights, int N, T *__restrict__ model,
                                                                       uint8_t *__restrict__ valid) {
-  __shared__ double s_part[(kHRThreads / 64) * 24], s_tot[24], gram[81], Vl[81], cs[18];
+  __shared__ double s_part[(kHRThreads / 64) * 24], s_tot[24], gram[81], Vl[81], cs[18];      // s_part: [4][K] of the three sums in turn
   const int p = blockIdx.x, tid = threadIdx.x;
   const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
   const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
@@ -453,7 +303,7 @@ __global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *_
     for (int d = 0; d < 4; ++d) a[d] += (double)x.v[d];
     a[4] += 1.0;
   }
-  h_block_sum<5>(a, s_part, s_tot);
+  block_sum_f64<5>(a, reinterpret_cast<double(*)[5]>(s_part));
   const double rows = a[4], rn = 1.0 / rows;
   const double mu[4] = {a[0] * rn, a[1] * rn, a[2] * rn, a[3] * rn};
   double dd[2] = {0, 0};
@@ -464,7 +314,7 @@ __global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *_
     dd[0] += sqrt(q0 * q0 + q1 * q1);
     dd[1] += sqrt(q2 * q2 + q3 * q3);
   }
-  h_block_sum<2>(dd, s_part, s_tot);
+  block_sum_f64<2>(dd, reinterpret_cast<double(*)[2]>(s_part));
   const double nz1[3] = {mu[0], mu[1], M_SQRT2 * rows / dd[0]}, nz2[3] = {mu[2], mu[3], M_SQRT2 * rows / dd[1]};
   double g[24];
 #pragma unroll
@@ -485,7 +335,9 @@ __global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *_
       g[18 + e] += q2 * xx[e];
     }
   }
-  h_block_sum<24>(g, s_part, s_tot);      // (s_tot keeps the 24 totals)
+  block_partials_f64<24>(g, reinterpret_cast<double(*)[24]>(s_part));
+  if (tid < 24) s_tot[tid] = block_total_f64<24>(reinterpret_cast<double(*)[24]>(s_part), tid);      // (the Gram matrix picks its totals by
+  __syncthreads();                                                                                  // a run-time index: they stay in LDS)
   if (tid < 81) {
     const int r = tid / 9, c = tid - 9 * r, br = r / 3, bc = c / 3, i = r - 3 * br, j = c - 3 * bc;
     const int lo = min(i, j), hi = max(i, j), e = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);      // (i, j) -> entry of the symmetric 3x3
@@ -541,8 +393,8 @@ DR_F32_F64(DR_OP)
                                 T *scores, int32_t *inliers, void *stream) {                                                        \
     DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                                                \
     DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
-    return dr::launch("homography_score_kernel", dr::homography_score_kernel<T>, dim3((M + dr::kHSModels - 1) / dr::kHSModels, P),  \
-                      dr::kHSThreads, stream, matches, models, valid, thr2, M, N, scores, inliers);                                 \
+    return dr::launch_pair_score<T, dr::HomographyGeom, dr::TransferMsacTerm<T>>(matches, models, valid, thr2, P, M, N, scores,     \
+                                                                                 inliers, nullptr, nullptr, stream);                \
   }                                                                                                                                 \
   int dr_homography_update_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P,    \
                                  int M, int N, int B, double confidence, double eps, int max_iterations, T *best_score,             \
@@ -551,9 +403,9 @@ DR_F32_F64(DR_OP)
     DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters,  \
                "null pointer");                                                                                                     \
     DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes");                                                \
-    return dr::launch("homography_update_kernel", dr::homography_update_kernel<T>, dim3(P), dr::kHUThreads, stream, matches,        \
-                      models, valid, scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask,     \
-                      best_inliers, iters, max_iters);                                                                              \
+    return dr::launch("pair_update_kernel", dr::pair_update_kernel<T, dr::HomographyGeom>, dim3(P), dr::kPairThreads, stream,       \
+                      matches, models, valid, scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model,       \
+                      best_mask, best_inliers, iters, max_iters);                                                                   \
   }                                                                                                                                 \
   int dr_refit_homography_##sfx(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *model, uint8_t *valid,    \
                                 void *stream) {                                                                                     \

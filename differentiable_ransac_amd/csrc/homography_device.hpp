@@ -1,8 +1,9 @@
 // What the homography kernels (homography.hip) share.
 //   ScoredH / prepare_h     a model slot as the score and update kernels evaluate it: the det > 0 sign applied, adj(H), its kind
-//   transfer_inlier         the symmetric transfer error of one point and its inlier decision -- ONE text for the score kernel, the
-//                           update kernel's mask and its count, every product an explicit fma, so that -ffp-contract has nothing to
-//                           decide and the three round alike
+//   transfer_d2             the symmetric transfer error of one point -- ONE text for the score kernel, the state step's mask and its
+//                           count, every product an explicit fma, so that -ffp-contract has nothing to decide and the three round alike
+//   TransferMsacTerm        the MSAC term on it
+//   HomographyGeom          the family's policy for pair_state_device.hpp's score kernel and state step
 //   canonical_h             unit Frobenius norm, det > 0; false for a non-finite or singular matrix (solver and refit)
 //   denormalise_h           T2^-1 M T1 for the two similarity normalisations (solver and refit)
 #pragma once
@@ -48,10 +49,10 @@ __device__ __forceinline__ void prepare_h(const T *__restrict__ m9, bool live, S
   s.kind = !live ? kModelSkipped : ((finite && is_finite(det) && det != T(0)) ? kModelScored : kModelNan);
 }
 
-// d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2, y = H (x1, 1), z = adj(H) (x2, 1); -> inlier: both third coordinates positive and
-// d2 < thr2 (false for a NaN or infinite d2).  x = (x1, y1, x2, y2).  Two reciprocals (v_rcp_f32 in f32).
+// d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2, y = H (x1, 1), z = adj(H) (x2, 1); -> are both third coordinates positive (a point
+// behind a camera is an outlier whatever its d2).  x = (x1, y1, x2, y2).  Two reciprocals (v_rcp_f32 in f32).
 template <typename T>
-__device__ __forceinline__ bool transfer_inlier(const ScoredH<T> &s, const T (&x)[4], T thr2, T &d2) {
+__device__ __forceinline__ bool transfer_d2(const ScoredH<T> &s, const T (&x)[4], T &d2) {
   const T yx = fma(s.h[0], x[0], fma(s.h[1], x[1], s.h[2]));
   const T yy = fma(s.h[3], x[0], fma(s.h[4], x[1], s.h[5]));
   const T yw = fma(s.h[6], x[0], fma(s.h[7], x[1], s.h[8]));
@@ -62,15 +63,80 @@ __device__ __forceinline__ bool transfer_inlier(const ScoredH<T> &s, const T (&x
   const T e0 = fma(-yx, ry, x[2]), e1 = fma(-yy, ry, x[3]);
   const T f0 = fma(-zx, rz, x[0]), f1 = fma(-zy, rz, x[1]);
   d2 = fma(e0, e0, fma(e1, e1, fma(f0, f0, f1 * f1)));
-  return yw > T(0) && zw > T(0) && d2 < thr2;
+  return yw > T(0) && zw > T(0);
 }
 
-// the MSAC term of an inlier: 1 - d2 / thr2, never below 0 (d2 < thr2 and d2 * inv >= 1 can meet by one rounding of inv)
+// MSAC on it: an inlier (d2 < thr2, false for a NaN or infinite d2) adds 1 - d2 / thr2, never below 0 (d2 < thr2 and d2 * inv >= 1
+// can meet by one rounding of inv)
 template <typename T>
-__device__ __forceinline__ T msac_gain(T d2, T inv) {
-  const T sv = fma(-d2, inv, T(1));
-  return sv > T(0) ? sv : T(0);
-}
+struct TransferMsacTerm {
+  T t2, inv;
+  __device__ __forceinline__ explicit TransferMsacTerm(T thr2) : t2(thr2), inv(T(1) / thr2) {}
+  __device__ __forceinline__ bool inlier(T d2) const { return d2 < t2; }
+  __device__ __forceinline__ T contrib(T d2, bool live = true) const {
+    const T sv = fma(-d2, inv, T(1));
+    return (live && inlier(d2) && sv > T(0)) ? sv : T(0);
+  }
+};
+
+template <typename T>
+struct alignas(4 * sizeof(T)) Match4 {
+  T v[4];
+};
+
+// The homography family as pair_state_device.hpp's kernels see it.  A lane's chunk is points c0 + 256 j + tid, so one load instruction
+// of a wave reads 64 consecutive points; a slot past the end re-reads the last row and is not live.  Per (model, chunk) the sign rule,
+// adj(H) and the slot's kind are worked out once; per point: twelve fma, two reciprocals, one compare for the term and the count.
+// Slots: valid = 0 scores exactly 0 (0 inliers) and is never evaluated; a non-finite model or det == 0 scores NaN (0 inliers).  The
+// state step replaces the state only on a strictly higher score, in the first round too.
+struct HomographyGeom {
+  static constexpr int kModel = 9, kWidth = 4, kSample = 4;
+  static constexpr bool kFirstRoundTakes = false;
+  template <typename T>
+  using Slot = ScoredH<T>;
+  template <typename T>
+  struct Point : Match4<T> {
+    static __device__ __forceinline__ Point load(const T *matches, size_t row) {
+      return Point{reinterpret_cast<const Match4<T> *>(matches)[row]};
+    }
+  };
+  template <typename T>
+  struct Chunk {
+    Match4<T> x[8];
+    int n0, N;
+    __device__ __forceinline__ void load(const T *pt, int c0, int tid, int rowN) {
+      n0 = c0 + tid;
+      N = rowN;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int n = n0 + j * 256;
+        x[j] = reinterpret_cast<const Match4<T> *>(pt)[n < N ? n : N - 1];
+      }
+    }
+    __device__ __forceinline__ bool live(int j) const { return n0 + j * 256 < N; }
+    __device__ __forceinline__ const T (&point(int j) const)[4] { return x[j].v; }
+  };
+  template <typename T>
+  static __device__ __forceinline__ int prepare(const T *__restrict__ m9, Slot<T> &s) {
+    prepare_h(m9, true, s);
+    return s.kind;
+  }
+  template <typename T>
+  static __device__ __forceinline__ int kind(const T *__restrict__ m9, bool live) {
+    ScoredH<T> s;
+    prepare_h(m9, live, s);
+    return s.kind;
+  }
+  template <typename T>
+  static __device__ __forceinline__ T dead_score(int kind) { return kind == kModelNan ? T(NAN) : T(0); }
+  template <typename T>
+  static __device__ __forceinline__ bool d2(const Slot<T> &s, const T (&x)[4], T &out) { return transfer_d2(s, x, out); }
+  template <typename T>
+  static __device__ __forceinline__ bool inlier(const Slot<T> &s, const T (&x)[4], T thr2) {
+    T d2;
+    return transfer_d2(s, x, d2) && d2 < thr2;
+  }
+};
 
 __device__ __forceinline__ double det3(const double (&h)[9]) {
   return h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]);

@@ -7,6 +7,7 @@
 // Unlike dr_solve_rigid (the reference's estimate_model, kept for parity with its training branch: cov^T cov with flag, the
 // row-sum translation of rigid...:66) this is the least-squares rigid fit: R = V diag(1, 1, det(V U^T)) U^T of H = U S V^T,
 // t = c1 - R c0.
+#include "pair_state_device.hpp"
 #include "rigid_device.hpp"
 #include "solver_common.hpp"
 
@@ -369,16 +370,8 @@ __global__ __launch_bounds__(64) void kabsch_bwd_kernel(const T *__restrict__ sa
   }
 }
 
-// ---- (2) score and inlier count of every model against every point, under a per-point term ----------------------------------------
-// The mapping of rigid_residual_kernel: a lane owns 8 consecutive points in registers, the model is wave-uniform.  One block =
-// (pair, tile of kSModels models) and walks ALL the pair's points chunk by chunk, so the sum of a (pair, model) is reduced in one
-// fixed order -- lane, wave butterfly, chunk after chunk into the wave's LDS slot, the four slots in order -- and a repeated launch
-// gives the same bits (scores are compared strictly downstream).  No [P,M,N] tensor, no floating-point atomics.
-// A term is built from thr2 once per block and has inlier(d2) and contrib(d2), the point's part of the score: 0 where it adds nothing,
-// so 0 for a NaN distance too, and 0 for a slot past the end of the row (`live` false; the gate joins the term's own predicate).
-// Only the tile kernel has such slots; block_score walks existing rows and relies on the default live = true.
-constexpr int kSThreads = 256, kSPts = 8, kSChunk = kSThreads * kSPts, kSModels = 16;
-
+// ---- (2) score and inlier count of every model against every point: pair_state_device.hpp's pair_score_kernel under RigidGeom and one
+// of the two terms below.  block_score walks existing rows with the same terms and relies on their default live = true.
 // MSAC: max(0, 1 - d2 / thr2).  The contribution and the count keep their own predicates (sv > 0 and d2 < thr2 can differ by a rounding)
 template <typename T>
 struct MsacTerm {
@@ -434,143 +427,10 @@ struct MagsacTerm {
   }
 };
 
-// the kernel of (2) for either term
-template <typename T, typename Term>
-__global__ __launch_bounds__(kSThreads) void rigid_score_kernel(const T *__restrict__ pts, const T *__restrict__ models,
-                                                                const uint8_t *__restrict__ valid, const T *__restrict__ thr2, int M,
-                                                                int N, T *__restrict__ scores, int32_t *__restrict__ inliers,
-                                                                PairGate gate) {
-  __shared__ T part[kSThreads / 64][kSModels];
-  __shared__ int pcnt[kSThreads / 64][kSModels];
-  const int p = blockIdx.y, m0 = blockIdx.x * kSModels;
-  if (gate.closed(p)) return;   // a terminated pair of a multi-round call (block-uniform): its scores keep their contents
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int mcount = min(kSModels, M - m0);
-  const T *pt = pts + (size_t)p * N * 6;
-  const T *md = models + ((size_t)p * M + m0) * 16;
-  const uint8_t *vd = valid ? valid + (size_t)p * M + m0 : nullptr;
-  const Term term(thr2[p]);
-  if (tid < (kSThreads / 64) * kSModels) {
-    (&part[0][0])[tid] = T(0);
-    (&pcnt[0][0])[tid] = 0;
-  }
-  __syncthreads();
-  for (int c0 = 0; c0 < N; c0 += kSChunk) {
-    const int n0 = c0 + tid * kSPts;
-    T x[kSPts][6];
-    const int nvalid = load_points8(pt, n0, N, x);
-    for (int ml = 0; ml < mcount; ++ml) {
-      if (vd && !vd[ml]) continue;   // (wave-uniform)
-      T m[12];
-#pragma unroll
-      for (int q = 0; q < 12; ++q) m[q] = md[ml * 16 + q];
-      T acc = T(0);
-      int cnt = 0;
-#pragma unroll
-      for (int j = 0; j < kSPts; ++j) {
-        const T d2 = rigid_d2<T>(m, x[j]);
-        const bool live = j < nvalid;
-        acc += term.contrib(d2, live);
-        cnt += (live && term.inlier(d2)) ? 1 : 0;
-      }
-      acc = wave_sum(acc);
-      cnt = wave_sum(cnt);
-      if (lane == 0) {
-        part[wv][ml] += acc;
-        pcnt[wv][ml] += cnt;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < mcount) {
-    const bool ok = !vd || vd[tid];
-    T v = T(0);
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < kSThreads / 64; ++w) {
-      v += part[w][tid];
-      n += pcnt[w][tid];
-    }
-    scores[(size_t)p * M + m0 + tid] = ok ? v : T(-1);
-    if (inliers) inliers[(size_t)p * M + m0 + tid] = ok ? n : 0;
-  }
-}
-
-// ---- (3) the state step of dr_ransac_update for 4x4 models and 6-column points -------------------------------------------------
-// One block per pair: the block is the only writer of the pair's state (no ping-pong needed).  Terminated pairs return at once.
-constexpr int kRUThreads = 256;
-
-template <typename T>
-__global__ __launch_bounds__(kRUThreads) void registration_update_kernel(
-    const T *__restrict__ pts, const T *__restrict__ models, const uint8_t *__restrict__ valid, const T *__restrict__ scores,
-    const T *__restrict__ thr2, int M, int N, int B, double confidence, double eps, int max_iterations,
-    T *__restrict__ best_score, T *__restrict__ best_model, uint8_t *__restrict__ best_mask, int32_t *__restrict__ best_inliers,
-    int32_t *__restrict__ iters, double *__restrict__ max_iters) {
-  __shared__ T s_val[kRUThreads / 64];
-  __shared__ int s_idx[kRUThreads / 64];
-  __shared__ int s_cnt[kRUThreads / 64];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int it = iters[p];
-  if ((double)it >= max_iters[p]) return;   // this pair has terminated (uniform across the block)
-  const T bs = best_score[p];
-  T bv;
-  int bi;
-  // (its barrier comes after every thread has read iters / max_iters / best_score above: thread 0 may write them below)
-  block_arg_best<T, kRUThreads, true>(scores + (size_t)p * M, valid ? valid + (size_t)p * M : nullptr, M, s_val, s_idx, bv, bi);
-  const bool have = bi != 0x7fffffff;              // (a -inf score of a valid model has an index too)
-  const bool better = have && (bv > bs || it == 0);
-  if (better) {
-    T m[12];
-#pragma unroll
-    for (int q = 0; q < 12; ++q) m[q] = models[((size_t)p * M + bi) * 16 + q];
-    const T t2 = thr2[p];
-    int cnt = 0;
-    for (int n = tid; n < N; n += kRUThreads) {
-      const T *xp = pts + ((size_t)p * N + n) * 6;
-      T x[6];
-#pragma unroll
-      for (int d = 0; d < 6; ++d) x[d] = xp[d];
-      const bool in = rigid_d2<T>(m, x) < t2;
-      best_mask[(size_t)p * N + n] = in;
-      cnt += in;
-    }
-    cnt = wave_sum(cnt);
-    if (lane == 0) s_cnt[wv] = cnt;
-    __syncthreads();
-    if (tid < 16) best_model[(size_t)p * 16 + tid] = models[((size_t)p * M + bi) * 16 + tid];
-    if (tid == 0) {
-      int inl = 0;
-#pragma unroll
-      for (int w = 0; w < kRUThreads / 64; ++w) inl += s_cnt[w];
-      best_inliers[p] = inl;
-      best_score[p] = bv;
-      max_iters[p] = adaptive_max_iters(inl, N, 3, confidence, eps, max_iterations);
-    }
-  }
-  if (tid == 0) iters[p] = it + B;
-}
+// ---- (3) the state step is pair_update_kernel under RigidGeom
 
 // ---- (4) Kabsch refit over the rows a mask selects: one block per pair, f64, two passes, fixed-order reduction ---------------
-constexpr int kRFThreads = 256;
-
-template <int K>
-__device__ __forceinline__ void block_sum_f64(double *v, double (*s)[K]) {   // v: K sums, s: shared [kRFThreads / 64][K]
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    const double w = wave_sum(v[i]);
-    if (lane == 0) s[wv][i] = w;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < K; ++i) {
-    double a = s[0][i];
-#pragma unroll
-    for (int w = 1; w < kRFThreads / 64; ++w) a += s[w][i];
-    v[i] = a;
-  }
-  __syncthreads();   // (the buffer may be reused)
-}
+constexpr int kRFThreads = kPairThreads;
 
 template <typename T>
 __device__ __forceinline__ void load_row(const T *pt, int n, T (&x)[6]) {
@@ -943,16 +803,6 @@ __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *
   }
 }
 
-template <typename T, typename Term>
-int launch_rigid_score(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,
-                       int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {
-  PairGate gate;
-  gate.iters = gate_iters;
-  gate.max_iters = gate_max_iters;
-  return launch("rigid_score_kernel", rigid_score_kernel<T, Term>, dim3((M + kSModels - 1) / kSModels, P), kSThreads, stream, matches,
-                models, valid, thr2, M, N, scores, inliers, gate);
-}
-
 }  // namespace dr
 
 extern "C" {
@@ -1009,8 +859,8 @@ DR_F32_F64(DR_OP)
     DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                                                \
     DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
     DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither");                           \
-    return dr::launch_rigid_score<T, dr::Term<T>>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters,               \
-                                                  gate_max_iters, stream);                                                          \
+    return dr::launch_pair_score<T, dr::RigidGeom, dr::Term<T>>(matches, models, valid, thr2, P, M, N, scores, inliers, gate_iters, \
+                                                                gate_max_iters, stream);                                            \
   }
 #define DR_OP(sfx, T) DR_RIGID_SCORE(msac, MsacTerm, sfx, T) DR_RIGID_SCORE(magsac, MagsacTerm, sfx, T)
 DR_F32_F64(DR_OP)
@@ -1024,7 +874,7 @@ DR_F32_F64(DR_OP)
     DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters,  \
                "null pointer");                                                                                                     \
     DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes");                                                \
-    return dr::launch("registration_update_kernel", dr::registration_update_kernel<T>, dim3(P), dr::kRUThreads, stream, matches,    \
+    return dr::launch("pair_update_kernel", dr::pair_update_kernel<T, dr::RigidGeom>, dim3(P), dr::kPairThreads, stream, matches,   \
                       models, valid, scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask,     \
                       best_inliers, iters, max_iters);                                                                              \
   }

@@ -29,6 +29,54 @@ __device__ __forceinline__ int load_points8(const T *pt, int n0, int N, T (&x)[8
   return min(8, max(0, N - n0));
 }
 
+// The rigid family as pair_state_device.hpp's kernels see it.  Residual: d2 = |q - (R p + t)|^2 (rigid_d2); every point may count.
+// A lane's chunk is 8 CONSECUTIVE points (load_points8: zeros past the end, live = j < nvalid).  Nothing of a model is classified:
+// a slot with valid = 0 scores -1 (0 inliers), every other one is evaluated as it stands, so a NaN model scores 0.  The state step
+// takes the first round's best whatever it scores.
+struct RigidGeom {
+  static constexpr int kModel = 16, kWidth = 6, kSample = 3;
+  static constexpr bool kFirstRoundTakes = true;
+  template <typename T>
+  struct Slot {
+    T m[12];
+  };
+  template <typename T>
+  struct Point {
+    T v[6];
+    static __device__ __forceinline__ Point load(const T *matches, size_t row) {
+      Point x;
+#pragma unroll
+      for (int d = 0; d < 6; ++d) x.v[d] = matches[row * 6 + d];
+      return x;
+    }
+  };
+  template <typename T>
+  struct Chunk {
+    T x[8][6];
+    int nvalid;
+    __device__ __forceinline__ void load(const T *pt, int c0, int tid, int N) { nvalid = load_points8(pt, c0 + tid * 8, N, x); }
+    __device__ __forceinline__ bool live(int j) const { return j < nvalid; }
+    __device__ __forceinline__ const T (&point(int j) const)[6] { return x[j]; }
+  };
+  template <typename T>
+  static __device__ __forceinline__ int prepare(const T *__restrict__ m16, Slot<T> &s) {
+#pragma unroll
+    for (int q = 0; q < 12; ++q) s.m[q] = m16[q];
+    return kModelScored;
+  }
+  template <typename T>
+  static __device__ __forceinline__ int kind(const T *, bool live) { return live ? kModelScored : kModelSkipped; }
+  template <typename T>
+  static __device__ __forceinline__ T dead_score(int) { return T(-1); }
+  template <typename T>
+  static __device__ __forceinline__ bool d2(const Slot<T> &s, const T (&x)[6], T &out) {
+    out = rigid_d2<T>(s.m, x);
+    return true;
+  }
+  template <typename T>
+  static __device__ __forceinline__ bool inlier(const Slot<T> &s, const T (&x)[6], T thr2) { return rigid_d2<T>(s.m, x) < thr2; }
+};
+
 template <typename T>
 __device__ __forceinline__ void store_rigid_model(T *__restrict__ m, const double (&R)[3][3], const double (&t)[3]) {
 #pragma unroll

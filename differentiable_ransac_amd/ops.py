@@ -799,16 +799,58 @@ def kabsch_gather_checked(matches: torch.Tensor, idx: torch.Tensor, edge_similar
     return models, valid
 
 
-def _rigid_score(term: str, matches, models, threshold, valid, want_inliers, gate, thr2):
-    """dr_rigid_{msac,magsac}_score: one kernel, two per-point terms"""
+# ---- what the families with their per-pair state on the device share (this one and the homographies below): one state class, and one
+# helper each for "score every model", "update the state" and "refit over mask / weights"; a family names its C entry and model side
+class _PairState:
+    """best_score [P] (0), best_model [P,side,side] (identity), best_mask [P,N], best_inliers [P] int32, iters [P] int32,
+    max_iters [P] f64 (= max_iterations).  Allocated and filled with torch (capturable)."""
+
+    def __init__(self, side: int, P: int, N: int, max_iterations: int, device, dtype):
+        self.best_score = torch.zeros(P, device=device, dtype=dtype)
+        self.best_model = torch.eye(side, device=device, dtype=dtype).repeat(P, 1, 1)
+        self.best_mask = torch.zeros(P, N, device=device, dtype=torch.bool)
+        self.best_inliers = torch.zeros(P, device=device, dtype=torch.int32)
+        self.iters = torch.zeros(P, device=device, dtype=torch.int32)
+        self.max_iters = torch.full((P,), float(max_iterations), device=device, dtype=torch.float64)
+        self.max_iterations = int(max_iterations)
+
+
+def _pair_score(entry: str, matches, models, threshold, valid, want_inliers, thr2, gated: bool = False, gate=None):
+    """dr_<entry>_{f32,f64}: (scores [P,M], inliers [P,M] int32 | None) of models [P,M,.,.]; a `gated` entry takes the gate's pointers"""
     P, N, _ = matches.shape
     M = models.shape[1]
     thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_rigid_{term}_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *(_gate_args(gate) if gated else ()), stream())
     return scores, inliers
+
+
+def _pair_update(entry: str, state: _PairState, matches, models, valid, scores, threshold, B: int, confidence, eps, thr2) -> None:
+    """dr_<entry>_{f32,f64}: the state step, in place on `state`"""
+    P, N, _ = matches.shape
+    M = models.shape[1]
+    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+           ptr(scores.contiguous()), ptr(thr2), c_int(P), c_int(M), c_int(N), c_int(int(B)), L.c_double(confidence), L.c_double(eps),
+           c_int(state.max_iterations), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
+           ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
+
+
+def _pair_refit(entry: str, side: int, matches, mask, weights):
+    """dr_<entry>_{f32,f64}: the fit over the rows mask [P,N] selects, under weights [P,N] -> (model [P,side,side], valid [P] bool)"""
+    P, N, _ = matches.shape
+    if weights is not None and weights.shape != (P, N):
+        raise L.DransacError("refit weights are [P,N], one per point")
+    if mask is not None and mask.shape != (P, N):
+        raise L.DransacError("the refit mask is [P,N], one flag per point")
+    model = torch.empty((P, side, side), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
+           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(model), ptr(valid),
+           stream())
+    return model, valid
 
 
 def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
@@ -816,7 +858,7 @@ def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, val
     """dr_rigid_msac_score: matches [P,N,6], models [P,M,4,4], threshold = inlier DISTANCE (float or [P]) ->
     (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None).  Invalid slots score
     -1.  Bit-repeatable (fixed reduction order).  gate = RegistrationState: the blocks of terminated pairs return at once."""
-    return _rigid_score("msac", matches, models, threshold, valid, want_inliers, gate, thr2)
+    return _pair_score("rigid_msac_score", matches, models, threshold, valid, want_inliers, thr2, True, gate)
 
 
 def rigid_magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
@@ -825,21 +867,15 @@ def rigid_magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, v
     read as k sigma_max (k^2 = 11.344866730144373, the 0.99 quantile of chi^2 with 3 degrees of freedom).  With s = d2 / threshold^2,
     u_k = k^2 / 2, c = exp(-u_k): scores [P,M] = sum_n (1 - l(s_n)), l(s) = (1 - exp(-u_k s) - c u_k s) / (1 - c (1 + u_k)) for s < 1,
     else 1; inliers = #{d2_n < threshold^2}.  Invalid slots score -1.  Bit-repeatable; gate as in rigid_msac_score."""
-    return _rigid_score("magsac", matches, models, threshold, valid, want_inliers, gate, thr2)
+    return _pair_score("rigid_magsac_score", matches, models, threshold, valid, want_inliers, thr2, True, gate)
 
 
-class RegistrationState:
+class RegistrationState(_PairState):
     """Per-pair state of a BatchedRegistration call, on the device: best_score [P], best_model [P,4,4] (identity), best_mask [P,N],
     best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch (capturable)."""
 
     def __init__(self, P: int, N: int, max_iterations: int, device, dtype):
-        self.best_score = torch.zeros(P, device=device, dtype=dtype)
-        self.best_model = torch.eye(4, device=device, dtype=dtype).repeat(P, 1, 1)
-        self.best_mask = torch.zeros(P, N, device=device, dtype=torch.bool)
-        self.best_inliers = torch.zeros(P, device=device, dtype=torch.int32)
-        self.iters = torch.zeros(P, device=device, dtype=torch.int32)
-        self.max_iters = torch.full((P,), float(max_iterations), device=device, dtype=torch.float64)
-        self.max_iterations = int(max_iterations)
+        super().__init__(4, P, N, max_iterations, device, dtype)
 
 
 def registration_update(state: RegistrationState, matches, models, valid, scores, threshold, B: int,
@@ -847,13 +883,7 @@ def registration_update(state: RegistrationState, matches, models, valid, scores
     """dr_registration_update, in place on `state`: per pair with iters < max_iters the first arg-max of scores [P,M] over valid,
     non-NaN models replaces the state if score > best_score or iters == 0 (mask and inlier count recomputed with the DISTANCE
     `threshold`, max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 3))); iters += B."""
-    P, N, _ = matches.shape
-    M = models.shape[1]
-    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
-    L.call(f"dr_registration_update_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(scores.contiguous()), ptr(thr2), c_int(P), c_int(M), c_int(N), c_int(int(B)), L.c_double(confidence), L.c_double(eps),
-           c_int(state.max_iterations), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
-           ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
+    _pair_update("registration_update", state, matches, models, valid, scores, threshold, B, confidence, eps, thr2)
 
 
 def registration_local_optimize(state: RegistrationState, matches, thr2, lo: int, lo_iters: int, confidence: float = 0.999,
@@ -897,17 +927,7 @@ def registration_irls(state: RegistrationState, matches, thr2, irls_iters: int, 
 def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
     """dr_refit_rigid: the Kabsch fit over the rows mask [P,N] selects (None = all), weights [P,N] (optional) multiplying a row's
     term in the means and in H -> (model [P,4,4], valid [P] bool); valid = 0 below three rows or for a degenerate selection."""
-    P, N, _ = matches.shape
-    if weights is not None and weights.shape != (P, N):
-        raise L.DransacError("refit weights are [P,N], one per point")
-    if mask is not None and mask.shape != (P, N):
-        raise L.DransacError("the refit mask is [P,N], one flag per point")
-    model = torch.empty((P, 4, 4), device=matches.device, dtype=matches.dtype)
-    valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_refit_rigid_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
-           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(model), ptr(valid),
-           stream())
-    return model, valid
+    return _pair_refit("refit_rigid", 4, matches, mask, weights)
 
 
 def _kabsch_fwd(samples: torch.Tensor, weights: Optional[torch.Tensor]):
@@ -1271,30 +1291,17 @@ def homography_score(matches: torch.Tensor, models: torch.Tensor, threshold, val
     scores exactly 0; a non-finite model or one with det == 0 scores NaN; a model of negative determinant scores like its negation.
     Bit-repeatable (fixed reduction order)."""
     _check_matches4("homography_score", matches)
-    P, N, _ = matches.shape
-    M = models.shape[1]
-    if models.shape != (P, M, 3, 3) or models.dtype != matches.dtype:
+    if models.shape != (matches.shape[0], models.shape[1], 3, 3) or models.dtype != matches.dtype:
         raise L.DransacError("homography_score: models [P,M,3,3] of the matches' dtype")
-    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
-    scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
-    inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_homography_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), stream())
-    return scores, inliers
+    return _pair_score("homography_score", matches, models, threshold, valid, want_inliers, thr2)
 
 
-class HomographyState:
+class HomographyState(_PairState):
     """Per-pair state of a BatchedHomography call, on the device: best_score [P] (0), best_model [P,3,3] (identity), best_mask [P,N],
     best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch."""
 
     def __init__(self, P: int, N: int, max_iterations: int, device, dtype):
-        self.best_score = torch.zeros(P, device=device, dtype=dtype)
-        self.best_model = torch.eye(3, device=device, dtype=dtype).repeat(P, 1, 1)
-        self.best_mask = torch.zeros(P, N, device=device, dtype=torch.bool)
-        self.best_inliers = torch.zeros(P, device=device, dtype=torch.int32)
-        self.iters = torch.zeros(P, device=device, dtype=torch.int32)
-        self.max_iters = torch.full((P,), float(max_iterations), device=device, dtype=torch.float64)
-        self.max_iterations = int(max_iterations)
+        super().__init__(3, P, N, max_iterations, device, dtype)
 
 
 def homography_update(state: HomographyState, matches, models, valid, scores, threshold, B: int, confidence: float = 0.999,
@@ -1303,13 +1310,7 @@ def homography_update(state: HomographyState, matches, models, valid, scores, th
     slots replaces the state if score > best_score (mask and inlier count recomputed with the score kernel's expression,
     max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 4))); iters += B."""
     _check_matches4("homography_update", matches)
-    P, N, _ = matches.shape
-    M = models.shape[1]
-    thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
-    L.call(f"dr_homography_update_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(scores.contiguous()), ptr(thr2), c_int(P), c_int(M), c_int(N), c_int(int(B)), L.c_double(confidence), L.c_double(eps),
-           c_int(state.max_iterations), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
-           ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
+    _pair_update("homography_update", state, matches, models, valid, scores, threshold, B, confidence, eps, thr2)
 
 
 def refit_homography(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
@@ -1317,17 +1318,7 @@ def refit_homography(matches: torch.Tensor, mask: Optional[torch.Tensor] = None,
     row's terms in the Gram matrix -> (model [P,3,3], valid [P] bool); valid = 0 (identity) below four rows or for a non-finite or
     singular result."""
     _check_matches4("refit_homography", matches)
-    P, N, _ = matches.shape
-    if weights is not None and weights.shape != (P, N):
-        raise L.DransacError("refit weights are [P,N], one per point")
-    if mask is not None and mask.shape != (P, N):
-        raise L.DransacError("the refit mask is [P,N], one flag per point")
-    model = torch.empty((P, 3, 3), device=matches.device, dtype=matches.dtype)
-    valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_refit_homography_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
-           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(model), ptr(valid),
-           stream())
-    return model, valid
+    return _pair_refit("refit_homography", 3, matches, mask, weights)
 
 
 class _Homography4(torch.autograd.Function):

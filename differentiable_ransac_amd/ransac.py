@@ -1005,7 +1005,105 @@ class BatchedRANSAC3D(_SeededDriver):
             return dict(model=best_model, residual=best, mask=best_mask, masks=masks)
 
 
-class BatchedRegistration(_SeededDriver):
+class _PairStateDriver(_SeededDriver):
+    """What BatchedRegistration and BatchedHomography share: the constructor's common checks and attributes, the index sets of a round
+    (Gumbel top-k or PROSAC, one seed per round), the train loop (ops.SampleGather -> the family's differentiable fit) and the test
+    loop on a per-pair state on the device (draw -> fit -> score -> update -> _after_update -> read-back of "does any pair continue?"),
+    and the final refit, taken where it scores strictly higher.  A family sets `k`, `_columns` / `_shape_error`, `_State` and the ops
+    `_fit`, `_fit_train`, `_score`, `_update`, `_refit`; what else it does hangs on _begin, _after_update, _stop_after and _finish."""
+
+    def __init__(self, ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws):
+        if sampling not in ("gumbel", "prosac"):
+            raise ValueError(f"sampling must be 'gumbel' or 'prosac', got {sampling!r}")
+        if sampling == "prosac" and train:
+            raise ValueError("sampling='prosac' yields index sets only: train mode needs the Gumbel sampler")
+        self._set_prosac_draws(prosac_draws)
+        self.sampling = sampling
+        if int(max_iterations) < 1:
+            raise ValueError(f"max_iterations must be at least 1, got {max_iterations!r}")
+        if int(ransac_batch_size) < 1:
+            raise ValueError(f"ransac_batch_size must be at least 1, got {ransac_batch_size!r}")
+        self.B = int(ransac_batch_size)
+        self.threshold = threshold
+        self.confidence = confidence
+        self.max_iterations = int(max_iterations)
+        self.tau = tau
+        self._seeds = _Seeds(seed)
+        self.refit = refit
+        self.eps = eps
+        self.train = bool(train)
+
+    @property
+    def rounds(self):
+        """rounds a call can run at most"""
+        return max(1, math.ceil(self.max_iterations / self.B))
+
+    def __call__(self, matches, logits, gumbels=None):
+        """`gumbels` (optional, list of [P,B,N] tensors, one per round) replaces the in-kernel noise: parity runs."""
+        if matches.dim() != 3 or matches.shape[-1] != self._columns:
+            raise ValueError(self._shape_error)
+        if self.sampling == "prosac" and gumbels is not None:
+            raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
+        rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
+        if self.train:
+            self._check_train(matches, logits)
+            out = []
+            for r in range(rounds):
+                g = None if gumbels is None else gumbels[r]
+                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
+                out.append(self._fit_train(samples))
+            return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
+        with torch.no_grad():
+            c = self._begin(matches, rounds)
+            c.order = c.growth = None
+            if self.sampling == "prosac":      # the ranking of this call's logits and the growth table, once for all its rounds
+                c.order, c.growth = self._prosac_setup(logits, c.N, c.matches.device)
+            for r in range(rounds):
+                idx = self._draw(c, r, logits, None if gumbels is None else gumbels[r])
+                models, valid = self._fit(c, idx)
+                scores = self._score(c, r, models, valid)
+                self._update(c.st, c.matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=c.thr2)
+                self._after_update(c)
+                if self._stop_after(c, r, rounds):
+                    break
+            return self._finish(c)
+
+    def _check_train(self, matches, logits):
+        pass
+
+    def _begin(self, matches, rounds):
+        """the state of a test-mode call: c.matches (contiguous), c.P, c.N, c.st, c.thr2"""
+        P, N, _ = matches.shape
+        matches = matches.contiguous()
+        st = self._State(P, N, self.max_iterations, matches.device, matches.dtype)
+        return types.SimpleNamespace(matches=matches, P=P, N=N, st=st, thr2=ops.thr2_tensor(self.threshold, P, matches))
+
+    def _draw(self, c, r, logits, g):
+        """the index sets of round r; under PROSAC its rows are draws r B + 1 .. (r + 1) B (t0 goes by value: a captured call replays it)"""
+        if self.sampling == "prosac":
+            return ops.prosac_sample(c.order, c.growth, self.B, self.k, self._seeds.next(), r * self.B, P=c.P, N=c.N,
+                                     device=c.matches.device)
+        return ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
+
+    def _after_update(self, c):
+        pass
+
+    def _stop_after(self, c, r, rounds):
+        """the read-back after round r: has every pair terminated"""
+        return r + 1 < rounds and not bool((c.st.iters.double() < c.st.max_iters).any())
+
+    def _finish(self, c):
+        model, score = c.st.best_model, c.st.best_score
+        if self.refit:
+            cand, cvalid = self._refit(c.matches, c.st.best_mask)
+            cscore = self._score(c, None, cand.unsqueeze(1), cvalid.unsqueeze(1))
+            take = cscore[:, 0] > score          # (an invalid candidate scores -1 or 0, a NaN never compares higher: neither wins)
+            model = torch.where(take[:, None, None], cand, model)
+            score = torch.where(take, cscore[:, 0], score)
+        return dict(model=model, mask=c.st.best_mask, score=score, inliers=c.st.best_inliers, iterations=c.st.iters)
+
+
+class BatchedRegistration(_PairStateDriver):
     """Robust rigid registration of point-cloud pairs: matches [P,N,6] = (p, q), logits [P,N] -> in test mode (the default)
     dict(model [P,4,4] = [[R, t], [0, 0, 0, 1]] with q ~ R p + t, mask [P,N], score [P], inliers [P], iterations [P]).
 
@@ -1062,12 +1160,7 @@ class BatchedRegistration(_SeededDriver):
                  num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64, scoring="msac", irls_iters=10,
                  edge_similarity=None, sampling="gumbel", prosac_draws=200000):
         _check_lo(lo, lo_iters)
-        if sampling not in ("gumbel", "prosac"):
-            raise ValueError(f"sampling must be 'gumbel' or 'prosac', got {sampling!r}")
-        if sampling == "prosac" and train:
-            raise ValueError("sampling='prosac' yields index sets only: train mode needs the Gumbel sampler")
-        self._set_prosac_draws(prosac_draws)
-        self.sampling = sampling
+        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws)
         if lo and train:
             raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
         if scoring not in ("msac", "magsac"):
@@ -1086,31 +1179,13 @@ class BatchedRegistration(_SeededDriver):
                                  "whose loss teaches the logits, and dropping it would remove the training signal")
         if not 3 <= int(num_samples) <= 8:
             raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
-        if int(max_iterations) < 1:
-            raise ValueError(f"max_iterations must be at least 1, got {max_iterations!r}")
-        if int(ransac_batch_size) < 1:
-            raise ValueError(f"ransac_batch_size must be at least 1, got {ransac_batch_size!r}")
-        self.B = int(ransac_batch_size)
         self.k = int(num_samples)
-        self.threshold = threshold
-        self.confidence = confidence
-        self.max_iterations = int(max_iterations)
-        self.tau = tau
-        self._seeds = _Seeds(seed)
-        self.refit = refit
-        self.eps = eps
-        self.train = bool(train)
         self.lo = int(lo)
         self.lo_iters = int(lo_iters)
         self.scoring = scoring
         self.irls_iters = int(irls_iters)
         self.edge_similarity = None if edge_similarity is None else float(edge_similarity)
         self._device_termination = False
-
-    @property
-    def rounds(self):
-        """rounds a call can run at most"""
-        return max(1, math.ceil(self.max_iterations / self.B))
 
     @property
     def device_termination(self):
@@ -1123,83 +1198,62 @@ class BatchedRegistration(_SeededDriver):
                              "(raise ransac_batch_size or lower max_iterations)")
         self._device_termination = bool(on)
 
-    def __call__(self, matches, logits, gumbels=None):
-        """`gumbels` (optional, list of [P,B,N] tensors, one per round) replaces the in-kernel noise: parity runs."""
-        P, N, c = matches.shape
-        if c != 6:
-            raise ValueError("matches must be [P,N,6] = (p, q)")
-        if self.sampling == "prosac" and gumbels is not None:
-            raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
-        rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
-        if self.train:
-            out = []
-            for r in range(rounds):
-                g = None if gumbels is None else gumbels[r]
-                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
-                out.append(ops.kabsch(samples))
-            return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
+    _columns, _shape_error = 6, "matches must be [P,N,6] = (p, q)"
+    _State = ops.RegistrationState
+    _fit_train = staticmethod(ops.kabsch)
+    _update = staticmethod(ops.registration_update)
+    _refit = staticmethod(ops.refit_rigid)
+
+    def _begin(self, matches, rounds):
         if self._device_termination and rounds > 16:      # (max_iterations / ransac_batch_size assigned after the switch)
             raise ValueError("device_termination issues every round: at most 16 rounds per call")
-        with torch.no_grad():
-            matches = matches.contiguous()
-            st = ops.RegistrationState(P, N, self.max_iterations, matches.device, matches.dtype)
-            thr2 = ops.thr2_tensor(self.threshold, P, matches)
-            lo_seen = lo_refits = None
+        c = super()._begin(matches, rounds)
+        c.lo_seen = c.lo_refits = c.rejected = None
+        if self.lo:
+            c.lo_seen = torch.full((c.P, 17), float("nan"), device=matches.device, dtype=matches.dtype)
+            c.lo_refits = torch.zeros(c.P, device=matches.device, dtype=torch.int32)
+        if self.edge_similarity is not None:
+            c.rejected = torch.zeros(c.P, device=matches.device, dtype=torch.int32)
+        return c
+
+    def _fit(self, c, idx):
+        if c.rejected is None:
+            return ops.kabsch_gather(c.matches, idx)
+        return ops.kabsch_gather_checked(c.matches, idx, self.edge_similarity, c.rejected)
+
+    def _score(self, c, r, models, valid):
+        """round r's models under the driver's scoring, gated on the device from the second round on; r = None: a refit candidate (MSAC)"""
+        if r is None:
+            return ops.rigid_msac_score(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
+        score_fn = ops.rigid_magsac_score if self.scoring == "magsac" else ops.rigid_msac_score
+        gate = c.st if (self._device_termination and r > 0) else None
+        return score_fn(c.matches, models, None, valid, want_inliers=False, gate=gate, thr2=c.thr2)[0]
+
+    def _after_update(self, c):
+        if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
+            ops.registration_local_optimize(c.st, c.matches, c.thr2, self.lo, self.lo_iters, self.confidence, self.eps,
+                                            self.max_iterations, c.lo_seen, c.lo_refits)
+
+    def _stop_after(self, c, r, rounds):
+        return not self._device_termination and super()._stop_after(c, r, rounds)
+
+    def _finish(self, c):
+        if self.scoring == "magsac":      # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
+            irls_fits = torch.zeros(c.P, device=c.matches.device, dtype=torch.int32)
+            if self.refit and self.irls_iters > 0:
+                ops.registration_irls(c.st, c.matches, c.thr2, self.irls_iters, irls_fits)
+            out = dict(model=c.st.best_model, mask=c.st.best_mask, score=c.st.best_score, inliers=c.st.best_inliers,
+                       iterations=c.st.iters, irls_fits=irls_fits)
+        else:
+            out = super()._finish(c)
             if self.lo:
-                lo_seen = torch.full((P, 17), float("nan"), device=matches.device, dtype=matches.dtype)
-                lo_refits = torch.zeros(P, device=matches.device, dtype=torch.int32)
-            magsac = self.scoring == "magsac"
-            score_fn = ops.rigid_magsac_score if magsac else ops.rigid_msac_score
-            rejected = None
-            if self.edge_similarity is not None:
-                rejected = torch.zeros(P, device=matches.device, dtype=torch.int32)
-            prosac = self.sampling == "prosac"
-            if prosac:      # the ranking of this call's logits and the growth table, once for all its rounds
-                order, growth = self._prosac_setup(logits, N, matches.device)
-            for r in range(rounds):
-                gate = st if (self._device_termination and r > 0) else None
-                g = None if gumbels is None else gumbels[r]
-                if prosac:      # rows of round r = draws r B + 1 .. (r + 1) B (t0 goes by value: a captured call replays it)
-                    idx = ops.prosac_sample(order, growth, self.B, self.k, self._seeds.next(), r * self.B, P=P, N=N,
-                                            device=matches.device)
-                else:
-                    idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
-                if rejected is None:
-                    models, valid = ops.kabsch_gather(matches, idx)
-                else:
-                    models, valid = ops.kabsch_gather_checked(matches, idx, self.edge_similarity, rejected)
-                scores, _ = score_fn(matches, models, None, valid, want_inliers=False, gate=gate, thr2=thr2)
-                ops.registration_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
-                if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
-                    ops.registration_local_optimize(st, matches, thr2, self.lo, self.lo_iters, self.confidence, self.eps,
-                                                    self.max_iterations, lo_seen, lo_refits)
-                if not self._device_termination and r + 1 < rounds and not bool((st.iters.double() < st.max_iters).any()):
-                    break
-            model, score = st.best_model, st.best_score
-            if magsac:      # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
-                irls_fits = torch.zeros(P, device=matches.device, dtype=torch.int32)
-                if self.refit and self.irls_iters > 0:
-                    ops.registration_irls(st, matches, thr2, self.irls_iters, irls_fits)
-                out = dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters,
-                           irls_fits=irls_fits)
-                if rejected is not None:
-                    out["rejected"] = rejected
-                return out
-            if self.refit:
-                cand, cvalid = ops.refit_rigid(matches, st.best_mask)
-                cscore, _ = ops.rigid_msac_score(matches, cand.unsqueeze(1), None, cvalid.unsqueeze(1), want_inliers=False, thr2=thr2)
-                take = cscore[:, 0] > score          # (an invalid candidate scores -1 and never wins)
-                model = torch.where(take[:, None, None], cand, model)
-                score = torch.where(take, cscore[:, 0], score)
-            out = dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)
-            if self.lo:
-                out["lo_refits"] = lo_refits
-            if rejected is not None:
-                out["rejected"] = rejected
-            return out
+                out["lo_refits"] = c.lo_refits
+        if c.rejected is not None:
+            out["rejected"] = c.rejected
+        return out
 
 
-class BatchedHomography(_SeededDriver):
+class BatchedHomography(_PairStateDriver):
     """Robust plane-induced homographies of image pairs: matches [P,N,4] = (x1, y1, x2, y2) in the caller's own coordinates (pixels;
     there is no K), logits [P,N] -> in test mode (the default) dict(model [P,3,3] = H with x2 ~ H x1, unit Frobenius norm and
     det H > 0, mask [P,N], score [P], inliers [P], iterations [P]).  The model for planar scenes and pure rotations, where the E and F
@@ -1228,72 +1282,20 @@ class BatchedHomography(_SeededDriver):
 
     def __init__(self, ransac_batch_size=1024, threshold=3.0, confidence=0.999, max_iterations=5000, tau=1.0, seed=0, refit=True,
                  eps=1e-5, train=False, sampling="gumbel", prosac_draws=200000):
-        if sampling not in ("gumbel", "prosac"):
-            raise ValueError(f"sampling must be 'gumbel' or 'prosac', got {sampling!r}")
-        if sampling == "prosac" and train:
-            raise ValueError("sampling='prosac' yields index sets only: train mode needs the Gumbel sampler")
-        self._set_prosac_draws(prosac_draws)
-        self.sampling = sampling
-        if int(max_iterations) < 1:
-            raise ValueError(f"max_iterations must be at least 1, got {max_iterations!r}")
-        if int(ransac_batch_size) < 1:
-            raise ValueError(f"ransac_batch_size must be at least 1, got {ransac_batch_size!r}")
-        self.B = int(ransac_batch_size)
-        self.threshold = threshold
-        self.confidence = confidence
-        self.max_iterations = int(max_iterations)
-        self.tau = tau
-        self._seeds = _Seeds(seed)
-        self.refit = refit
-        self.eps = eps
-        self.train = bool(train)
+        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws)
 
-    @property
-    def rounds(self):
-        """rounds a call can run at most"""
-        return max(1, math.ceil(self.max_iterations / self.B))
+    _columns, _shape_error = 4, "matches must be [P,N,4] = (x1, y1, x2, y2)"
+    _State = ops.HomographyState
+    _fit_train = staticmethod(ops.homography4)
+    _update = staticmethod(ops.homography_update)
+    _refit = staticmethod(ops.refit_homography)
 
-    def __call__(self, matches, logits, gumbels=None):
-        """`gumbels` (optional, list of [P,B,N] tensors, one per round) replaces the in-kernel noise: parity runs."""
-        if matches.dim() != 3 or matches.shape[-1] != 4:
-            raise ValueError("matches must be [P,N,4] = (x1, y1, x2, y2)")
-        P, N, _ = matches.shape
-        if self.sampling == "prosac" and gumbels is not None:
-            raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
-        rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
-        if self.train:
-            if logits.dtype != matches.dtype:      # (the straight-through weights are read in the matches' type)
-                raise ValueError(f"train mode needs logits of the matches' dtype, got {logits.dtype} and {matches.dtype}")
-            out = []
-            for r in range(rounds):
-                g = None if gumbels is None else gumbels[r]
-                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
-                out.append(ops.homography4(samples))
-            return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
-        with torch.no_grad():
-            matches = matches.contiguous()
-            st = ops.HomographyState(P, N, self.max_iterations, matches.device, matches.dtype)
-            thr2 = ops.thr2_tensor(self.threshold, P, matches)
-            prosac = self.sampling == "prosac"
-            if prosac:      # the ranking of this call's logits and the growth table, once for all its rounds
-                order, growth = self._prosac_setup(logits, N, matches.device)
-            for r in range(rounds):
-                g = None if gumbels is None else gumbels[r]
-                if prosac:      # rows of round r = draws r B + 1 .. (r + 1) B
-                    idx = ops.prosac_sample(order, growth, self.B, self.k, self._seeds.next(), r * self.B, P=P, N=N,
-                                            device=matches.device)
-                else:
-                    idx = ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
-                models, valid = ops.homography4_gather(matches, idx)
-                scores, _ = ops.homography_score(matches, models, None, valid, want_inliers=False, thr2=thr2)
-                ops.homography_update(st, matches, models, valid, scores, None, self.B, self.confidence, self.eps, thr2=thr2)
-                if r + 1 < rounds and not bool((st.iters.double() < st.max_iters).any()):
-                    break
-            model, score = st.best_model, st.best_score
-            if self.refit:
-                cand, cvalid = ops.refit_homography(matches, st.best_mask)
-                cscore, _ = ops.homography_score(matches, cand.unsqueeze(1), None, cvalid.unsqueeze(1), want_inliers=False, thr2=thr2)
-                take = cscore[:, 0] > score          # (an invalid candidate scores 0, a NaN never compares higher)
-                model = torch.where(take[:, None, None], cand, model)
-                score = torch.where(take, cscore[:, 0], score)
-            return dict(model=model, mask=st.best_mask, score=score, inliers=st.best_inliers, iterations=st.iters)
+    def _check_train(self, matches, logits):
+        if logits.dtype != matches.dtype:      # (the straight-through weights are read in the matches' type)
+            raise ValueError(f"train mode needs logits of the matches' dtype, got {logits.dtype} and {matches.dtype}")
+
+    def _fit(self, c, idx):
+        return ops.homography4_gather(c.matches, idx)
+
+    def _score(self, c, r, models, valid):
+        return ops.homography_score(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
