@@ -8,7 +8,9 @@ one the library binds to -- one runtime per process, shared streams and allocati
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
+import re
 import threading
 from ctypes import c_char_p, c_double, c_float, c_int, c_uint64, c_void_p
 from typing import Optional
@@ -26,6 +28,52 @@ class DransacError(RuntimeError):
     pass
 
 
+class c_pointer(c_void_p):
+    """The argtype of every `T *` parameter: NULL (None), what ptr() / stream() return (a c_void_p), or a ctypes array or pointer
+    (a host buffer).  Unlike c_void_p it refuses a Python int: an argument list shifted by one slot raises, it does not launch."""
+
+    @staticmethod
+    def from_param(v):      # runs once per pointer of every launch: the identity test first (what ptr() returns), no bound method
+        if v.__class__ is c_void_p or v is None or isinstance(v, (c_void_p, ctypes.Array, ctypes._Pointer)):
+            return v
+        raise TypeError(f"a pointer slot takes None, a c_void_p (ptr(), stream()) or a ctypes array / pointer, not {type(v).__name__}")
+
+
+_SCALARS = {"int": c_int, "int64_t": ctypes.c_int64, "uint64_t": c_uint64, "float": c_float, "double": c_double}
+_UNTYPED = ("dr_version", "dr_last_error")      # int (void) and const char *(void): typed by hand in lib()
+
+
+def parse_header(src: str) -> dict:
+    """{entry: [argtype, ...]} of every `int dr_*(...)` declaration of a header text; a parameter type outside
+    pointers / int / int64_t / uint64_t / float / double is an error, never a guess"""
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    out = {}
+    for name, params in re.findall(r"\bint\s+(dr_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        if name in _UNTYPED:
+            continue
+        out[name] = argtypes = []
+        for prm in params.split(","):
+            ctype = " ".join(re.match(r"(.*?)\w*$", " ".join(prm.split())).group(1).split())   # the parameter less its name
+            if ctype.endswith("*"):
+                argtypes.append(c_pointer)
+            elif ctype in _SCALARS:
+                argtypes.append(_SCALARS[ctype])
+            else:
+                raise DransacError(f"{name}: parameter `{' '.join(prm.split())}` has a type the binding does not know")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def entries() -> dict:
+    """parse_header of include/dransac.h: the binding of the library is derived from its header"""
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise DransacError(f"{HEADER_PATH} cannot be read ({e.strerror}): the C entries are bound from this header") from None
+
+
 def lib() -> ctypes.CDLL:
     global _lib
     if _lib is None:
@@ -33,9 +81,14 @@ def lib() -> ctypes.CDLL:
             raise DransacError(
                 f"{LIB_PATH} not found: build it with `python -m differentiable_ransac_amd.build` "
                 "(there is deliberately no CPU fallback)")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.dr_last_error.restype = c_char_p
-        _lib.dr_version.restype = c_int
+        handle = ctypes.CDLL(LIB_PATH)
+        handle.dr_last_error.restype = c_char_p
+        handle.dr_version.restype = c_int
+        for name, argtypes in entries().items():
+            fn = getattr(handle, name, None)        # (DRANSAC_LIB may name an older build: call() refuses what it lacks)
+            if fn is not None:
+                fn.restype, fn.argtypes = c_int, argtypes
+        _lib = handle
     return _lib
 
 
@@ -111,8 +164,18 @@ def scalar(dtype: torch.dtype, v: float):
 
 
 def call(name: str, *args) -> None:
-    fn = getattr(lib(), name)
-    fn.restype = c_int
+    """One C entry with the argument list the header declares: Python ints / floats / bools by value (or ready-made ctypes values),
+    ptr() / stream() / None in the pointer slots.  A list that does not fit raises before the C function is entered."""
+    fn = getattr(lib(), name, None)
+    argtypes = None if fn is None else fn.argtypes
+    if argtypes is None or len(args) != len(argtypes):      # (ctypes itself lets a cdecl call pass surplus arguments)
+        _reset()
+        if name not in entries():
+            raise DransacError(f"{name} is not an entry that {HEADER_PATH} declares")
+        if argtypes is None:
+            raise DransacError(f"{name} is declared in {HEADER_PATH}, but {LIB_PATH} does not export it")
+        raise DransacError(f"{name} takes {len(argtypes)} arguments, {len(args)} given (the first one that does not fit is "
+                           f"argument {min(len(args), len(argtypes)) + 1})")
     dev = _launch_device()
     _ctx.devs = set()
     try:
@@ -121,10 +184,12 @@ def call(name: str, *args) -> None:
                 status = fn(*args)
         else:
             status = fn(*args)
+    except (TypeError, ctypes.ArgumentError) as e:      # "argument 3: TypeError: ..." (positions count from 1)
+        raise DransacError(f"{name}: {e}") from None
     finally:
         _ctx.keep = []                         # the launch is enqueued on the tensors' stream: stream order protects them now
     check(status, name)
 
 
-__all__ = ["lib", "check", "ptr", "stream", "suffix", "scalar", "call", "DransacError", "LIB_PATH", "HEADER_PATH",
-           "c_int", "c_uint64", "c_float", "c_double", "c_void_p"]
+__all__ = ["lib", "check", "ptr", "stream", "suffix", "scalar", "call", "entries", "parse_header", "c_pointer", "DransacError",
+           "LIB_PATH", "HEADER_PATH", "c_int", "c_uint64", "c_float", "c_double", "c_void_p"]

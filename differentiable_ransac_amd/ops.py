@@ -4,13 +4,12 @@ torch stream and returns freshly allocated torch tensors; nothing synchronises.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Optional, Tuple
 
 import torch
 
 from . import _lib as L
-from ._lib import c_int, c_uint64, ptr, stream
+from ._lib import ptr, stream
 
 # Round 6: the exponential-race form of the index-only sampler (one logarithm per element; dr_gumbel_topk_gather_f32's race_ws).
 # Same top-k up to the rounding of near-ties; False = the two-logarithm form of rounds 1-5.
@@ -50,8 +49,8 @@ def _seed_args(seed):
     """the (seed by value, seed on the device) argument pair of a sampler entry: an int goes by value, a DeviceSeed.next() tensor
     by pointer (read when the kernel starts)"""
     if _dev_seed(seed):
-        return c_uint64(0), ptr(seed)
-    return c_uint64(seed & (2 ** 64 - 1)), ptr(None)
+        return 0, ptr(seed)
+    return seed & (2 ** 64 - 1), ptr(None)
 
 
 def _thr_tensor(threshold, P: int, like: torch.Tensor) -> torch.Tensor:
@@ -84,11 +83,11 @@ def msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, want_mask
     if matches.dtype == torch.float32:
         # gate (a later round of a multi-round call): the blocks of terminated pairs (gate = RansacState) return at once, their
         # scores are never looked at (dr_ransac_update skips such pairs)
-        L.call("dr_msac_score_f32", ptr(matches), ptr(models), ptr(v), ptr(thr), c_int(P), c_int(M), c_int(N), ptr(scores),
-               ptr(masks), *_gate_args(gate), stream())
+        L.call("dr_msac_score_f32", ptr(matches), ptr(models), ptr(v), ptr(thr), P, M, N, ptr(scores), ptr(masks), *_gate_args(gate),
+               stream())
         return scores, masks
-    L.call(f"dr_msac_score_{L.suffix(matches.dtype)}", ptr(matches), ptr(models), ptr(v), ptr(thr), c_int(P), c_int(M), c_int(N),
-           ptr(scores), ptr(masks), stream())
+    L.call(f"dr_msac_score_{L.suffix(matches.dtype)}", ptr(matches), ptr(models), ptr(v), ptr(thr), P, M, N, ptr(scores), ptr(masks),
+           stream())
     return scores, masks
 
 
@@ -111,8 +110,8 @@ def magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: 
     thr = _thr_tensor(threshold, P, matches)
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_magsac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(thr), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *_gate_args(gate), stream())
+    L.call(f"dr_magsac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid), ptr(thr),
+           P, M, N, ptr(scores), ptr(inliers), *_gate_args(gate), stream())
     return scores, inliers
 
 
@@ -139,9 +138,8 @@ def magsac_irls(state: "RansacState", matches, thr, fundamental: bool, irls_iter
         raise L.DransacError("magsac_irls: irls_fits must be [P] int32")
     if weights_ws.shape != (P, N) or weights_ws.dtype != matches.dtype or not weights_ws.is_contiguous():
         raise L.DransacError("magsac_irls: weights_ws must be a contiguous [P,N] tensor of the matches' dtype")
-    L.call(f"dr_magsac_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), c_int(P), c_int(N),
-           c_int(1 if fundamental else 0), c_int(int(irls_iters)), ptr(state.best_score), ptr(state.best_model), ptr(weights_ws),
-           ptr(irls_fits), stream())
+    L.call(f"dr_magsac_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), P, N, bool(fundamental), int(irls_iters),
+           ptr(state.best_score), ptr(state.best_model), ptr(weights_ws), ptr(irls_fits), stream())
 
 
 def select_best(matches: torch.Tensor, models: torch.Tensor, scores: torch.Tensor, threshold,
@@ -157,8 +155,8 @@ def select_best(matches: torch.Tensor, models: torch.Tensor, scores: torch.Tenso
     best_mask = torch.empty((P, N), device=dev, dtype=torch.bool)
     inliers = torch.empty((P,), device=dev, dtype=torch.int32)
     L.call(f"dr_select_best_{L.suffix(dt)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(scores.contiguous()), ptr(thr), c_int(P), c_int(M), c_int(N), ptr(best_idx), ptr(best_score),
-           ptr(best_model), ptr(best_mask), ptr(inliers), stream())
+           ptr(scores.contiguous()), ptr(thr), P, M, N, ptr(best_idx), ptr(best_score), ptr(best_model), ptr(best_mask), ptr(inliers),
+           stream())
     return best_idx, best_score, best_model, best_mask, inliers
 
 
@@ -218,10 +216,9 @@ def ransac_init(P: int, N: int, max_iterations: int, threshold: float, K1: Optio
             if K1.shape[0] != P or K2.shape != K1.shape:
                 raise ValueError("K1/K2 must be [3,3] or [P,3,3]")
             k_stride = 9
-    L.call(f"dr_ransac_init_{L.suffix(dtype)}", ptr(K1), ptr(K2), c_int(k_stride), L.c_double(float(threshold)),
-           c_int(P), c_int(N), c_int(max_iterations), ptr(thr), ptr(st.best_score), ptr(st.best_model),
-           ptr(st.best_mask), ptr(st.best_inliers), ptr(st.iters), ptr(st.max_iters), ptr(seed_state), ptr(st.seeds),
-           c_int(n_seeds), ptr(race_logits), ptr(st.race_ws), stream())
+    L.call(f"dr_ransac_init_{L.suffix(dtype)}", ptr(K1), ptr(K2), k_stride, float(threshold), P, N, max_iterations, ptr(thr),
+           ptr(st.best_score), ptr(st.best_model), ptr(st.best_mask), ptr(st.best_inliers), ptr(st.iters), ptr(st.max_iters),
+           ptr(seed_state), ptr(st.seeds), n_seeds, ptr(race_logits), ptr(st.race_ws), stream())
     return st, thr
 
 
@@ -235,10 +232,9 @@ def ransac_update(state: RansacState, matches, models, valid, scores, thr, B: in
     if sub_models and M > sub_models * 512:
         raise L.DransacError("ransac_update: at most 512 sub-batches per launch")
     L.call(f"dr_ransac_update_{L.suffix(matches.dtype)}", ptr(matches), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(scores.contiguous()), ptr(thr), c_int(P), c_int(M), c_int(N), c_int(B), c_int(k),
-           L.c_double(confidence), L.c_double(eps), c_int(state.max_iterations), ptr(state.best_score),
+           ptr(scores.contiguous()), ptr(thr), P, M, N, B, k, confidence, eps, state.max_iterations, ptr(state.best_score),
            ptr(state.best_model), ptr(state.best_mask), ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters),
-           c_int(int(sub_models)), stream())
+           int(sub_models), stream())
 
 
 # ------------------------------------------------------------------------------------------ K1 / K1u / K2
@@ -259,10 +255,10 @@ def local_optimize(state: RansacState, matches, thr, fundamental: bool, lo: int,
     if lo_refits is not None and (lo_refits.shape != (P,) or lo_refits.dtype != torch.int32):
         raise L.DransacError("local_optimize: lo_refits must be [P] int32")
     mi = state.max_iterations if max_iterations is None else max_iterations
-    L.call(f"dr_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), c_int(P), c_int(N),
-           c_int(1 if fundamental else 0), c_int(int(lo)), c_int(int(lo_iters)), c_int(int(k)), L.c_double(confidence),
-           L.c_double(eps), c_int(int(mi)), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
-           ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits), stream())
+    L.call(f"dr_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), P, N, bool(fundamental), int(lo),
+           int(lo_iters), int(k), confidence, eps, int(mi), ptr(state.best_score), ptr(state.best_model),
+           ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits),
+           stream())
 
 
 class DeviceSeed:
@@ -280,14 +276,14 @@ class DeviceSeed:
 
     def next(self) -> torch.Tensor:
         out = torch.empty(1, dtype=torch.int64, device=self.state.device)
-        L.call("dr_seed_next_n", ptr(self.state), ptr(out), c_int(1), stream())
+        L.call("dr_seed_next_n", ptr(self.state), ptr(out), 1, stream())
         return out
 
     def next_block(self, n: int) -> torch.Tensor:
         """the seeds of the next n calls from ONE launch (a multi-round call draws one per batch) as one [n] tensor of CONSECUTIVE
         integers: seeds[i:i + 1] is what next() would have returned for call i"""
         out = torch.empty(n, dtype=torch.int64, device=self.state.device)
-        L.call("dr_seed_next_n", ptr(self.state), ptr(out), c_int(n), stream())
+        L.call("dr_seed_next_n", ptr(self.state), ptr(out), n, stream())
         return out
 
     def next_n(self, n: int):
@@ -325,8 +321,7 @@ def gumbel_topk(logits: Optional[torch.Tensor], B: int, k: int, tau: float = 1.0
             and N > 2048 and N % 4 == 0 and k <= 5 and (B >= 64 if screen is None else screen)):
         # long rows, index sets only: the screened one-pass kernel (dr_gumbel_topk_index_f32; same index sets, bit for bit)
         ws = torch.empty(((N + 32) * P,), device=device, dtype=torch.int32)
-        L.call("dr_gumbel_topk_index_f32", ptr(logits), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k),
-               ptr(idx), ptr(ws), stream())
+        L.call("dr_gumbel_topk_index_f32", ptr(logits), *_seed_args(seed), tau, P, B, N, k, ptr(idx), ptr(ws), stream())
         return dict(idx=idx, y_sel=None, lse=None)
     y_sel = torch.empty((P, B, k), device=device, dtype=dtype) if soft else None
     lse = torch.empty((P, B), device=device, dtype=dtype) if soft else None
@@ -335,8 +330,8 @@ def gumbel_topk(logits: Optional[torch.Tensor], B: int, k: int, tau: float = 1.0
     noise = torch.empty((P, B, N), device=device, dtype=dtype) if want_noise else None
     if _dev_seed(seed) and (gumbel is not None or dense or want_noise or logits is None):
         raise L.DransacError("a device seed serves the in-kernel noise of given logits only (no explicit noise / dense outputs)")
-    L.call(f"dr_gumbel_topk_fwd_{L.suffix(dtype)}", ptr(logits), ptr(gumbel), *_seed_args(seed), L.scalar(dtype, tau), c_int(P),
-           c_int(B), c_int(N), c_int(k), ptr(idx), ptr(y_sel), ptr(lse), ptr(y_soft), ptr(ret), ptr(noise), stream())
+    L.call(f"dr_gumbel_topk_fwd_{L.suffix(dtype)}", ptr(logits), ptr(gumbel), *_seed_args(seed), tau, P, B, N, k, ptr(idx), ptr(y_sel),
+           ptr(lse), ptr(y_soft), ptr(ret), ptr(noise), stream())
     out = dict(idx=idx, y_sel=y_sel, lse=lse)
     if dense:
         out.update(y_soft=y_soft, ret=ret)
@@ -370,9 +365,8 @@ def gumbel_topk_gather(matches: torch.Tensor, logits: torch.Tensor, B: int, k: i
     ready = race_ws is not None and N <= 2048 and N % 4 == 0 and tau == 1.0
     want_race = not ready and (race_form_pays(P, B, N, tau) if race is None else race) and N <= 2048 and N % 4 == 0 and tau == 1.0
     rws = race_ws if ready else (torch.empty((P, N + 32), device=logits.device, dtype=torch.float32) if want_race else None)
-    L.call("dr_gumbel_topk_gather_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B), c_int(N),
-           c_int(k), ptr(idx), ptr(samples), *_gate_args(gate), c_int(0 if sub >= B else int(sub)), ptr(rws),
-           c_int(1 if ready else 0), stream())
+    L.call("dr_gumbel_topk_gather_f32", ptr(logits), ptr(matches), *_seed_args(seed), tau, P, B, N, k, ptr(idx), ptr(samples),
+           *_gate_args(gate), 0 if sub >= B else int(sub), ptr(rws), ready, stream())
     return idx, samples
 
 
@@ -384,12 +378,11 @@ def gumbel_topk_bwd(logits, gumbel, seed, tau, idx, lse, a_sel):
     if logits.dtype == torch.float64:
         if _dev_seed(seed):
             raise L.DransacError("gumbel_topk_bwd: device seeds serve f32 only")
-        L.call("dr_gumbel_topk_bwd_f64", ptr(logits.contiguous()), ptr(gumbel), c_uint64(seed & (2 ** 64 - 1)),
-               L.c_double(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(lse.contiguous()),
-               ptr(a_sel.to(torch.float64).contiguous()), ptr(grad), stream())
+        L.call("dr_gumbel_topk_bwd_f64", ptr(logits.contiguous()), ptr(gumbel), seed & (2 ** 64 - 1), tau, P, B, N, k, ptr(idx),
+               ptr(lse.contiguous()), ptr(a_sel.to(torch.float64).contiguous()), ptr(grad), stream())
         return grad
-    L.call("dr_gumbel_topk_bwd_f32", ptr(logits.contiguous()), ptr(None if _dev_seed(seed) else gumbel), *_seed_args(seed),
-           L.c_float(tau), c_int(P), c_int(B), c_int(N), c_int(k), ptr(idx), ptr(lse), ptr(a_sel.contiguous()), ptr(grad), stream())
+    L.call("dr_gumbel_topk_bwd_f32", ptr(logits.contiguous()), ptr(None if _dev_seed(seed) else gumbel), *_seed_args(seed), tau, P, B,
+           N, k, ptr(idx), ptr(lse), ptr(a_sel.contiguous()), ptr(grad), stream())
     return grad
 
 
@@ -409,20 +402,18 @@ def topdown_sample(logits: Optional[torch.Tensor], B: int, k: int, seed: int = 0
     ws = torch.empty((P, N), device=device, dtype=torch.float64)
     idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
     if sfx == "f32":
-        L.call("dr_topdown_sample_f32", ptr(logits), *_seed_args(seed), c_int(P), c_int(B), c_int(N), c_int(k), ptr(ws), ptr(idx),
-               stream())
+        L.call("dr_topdown_sample_f32", ptr(logits), *_seed_args(seed), P, B, N, k, ptr(ws), ptr(idx), stream())
         return idx
     if _dev_seed(seed):
         raise L.DransacError("device seeds: f32 logits")
-    L.call("dr_topdown_sample_f64", ptr(logits), _seed_args(seed)[0], c_int(P), c_int(B), c_int(N), c_int(k), ptr(ws), ptr(idx),
-           stream())
+    L.call("dr_topdown_sample_f64", ptr(logits), _seed_args(seed)[0], P, B, N, k, ptr(ws), ptr(idx), stream())
     return idx
 
 
 def uniform_sample(P: int, B: int, k: int, N: int, seed: int, device) -> torch.Tensor:
     """K1u: idx [P,B,k] int32 ~ U{0..N-2} (uniform_sampler.py:15-19 semantics)."""
     idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
-    L.call("dr_uniform_sample", *_seed_args(seed), c_int(P), c_int(B), c_int(k), c_int(N), ptr(idx), stream())
+    L.call("dr_uniform_sample", *_seed_args(seed), P, B, k, N, ptr(idx), stream())
     return idx
 
 
@@ -468,8 +459,7 @@ def prosac_sample(order: Optional[torch.Tensor], growth: torch.Tensor, B: int, k
     if growth.dtype != torch.int64 or growth.numel() != N - k + 1:
         raise L.DransacError("prosac_sample: growth is the int64 [N - k + 1] table of prosac_growth(N, k, ...)")
     idx = torch.empty((P, B, k), device=device, dtype=torch.int32)
-    L.call("dr_prosac_sample", ptr(order), ptr(growth.contiguous()), *_seed_args(seed), ctypes.c_int64(int(t0)), c_int(P), c_int(B),
-           c_int(N), c_int(k), ptr(idx), stream())
+    L.call("dr_prosac_sample", ptr(order), ptr(growth.contiguous()), *_seed_args(seed), int(t0), P, B, N, k, ptr(idx), stream())
     return idx
 
 
@@ -478,8 +468,8 @@ def gather(matches: torch.Tensor, idx: torch.Tensor, y_sel: Optional[torch.Tenso
     P, N, c = matches.shape
     _, B, k = idx.shape
     out = torch.empty((P, B, k, c), device=matches.device, dtype=matches.dtype)
-    L.call(f"dr_gather_fwd_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx), ptr(y_sel), c_int(P),
-           c_int(N), c_int(B), c_int(k), c_int(c), ptr(out), stream())
+    L.call(f"dr_gather_fwd_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx), ptr(y_sel), P, N, B, k, c, ptr(out),
+           stream())
     return out
 
 
@@ -490,8 +480,7 @@ def gather_bwd(matches, idx, y_sel, grad_samples, grad_w=None, want_grad_matches
     gm = torch.zeros_like(matches) if want_grad_matches else None
     dt = matches.dtype
     L.call(f"dr_gather_bwd_{L.suffix(dt)}", ptr(matches.contiguous()), ptr(idx), ptr(y_sel), ptr(grad_samples.to(dt).contiguous()),
-           ptr(None if grad_w is None else grad_w.to(dt).contiguous()), c_int(P), c_int(N), c_int(B), c_int(k), c_int(c),
-           ptr(a_sel), ptr(gm), stream())
+           ptr(None if grad_w is None else grad_w.to(dt).contiguous()), P, N, B, k, c, ptr(a_sel), ptr(gm), stream())
     return a_sel, gm
 
 
@@ -522,8 +511,8 @@ class SampleGather(torch.autograd.Function):
             # reciprocal per element), where its weights prologue pays
             rws = (torch.empty((P, N + 32), device=logits.device, dtype=torch.float32)
                    if K1_RACE_SOFT and race_form_pays(P, B, N, tau) else None)
-            L.call("dr_gumbel_topk_gather_soft_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B),
-                   c_int(N), c_int(k), ptr(r["idx"]), ptr(r["y_sel"]), ptr(r["lse"]), ptr(samples), ptr(rws), stream())
+            L.call("dr_gumbel_topk_gather_soft_f32", ptr(logits), ptr(matches), *_seed_args(seed), tau, P, B, N, k, ptr(r["idx"]),
+                   ptr(r["y_sel"]), ptr(r["lse"]), ptr(samples), ptr(rws), stream())
         else:
             r = gumbel_topk(logits, B, k, tau, gumbel, seed)
             samples = gather(matches, r["idx"], r["y_sel"])
@@ -545,9 +534,8 @@ class SampleGather(torch.autograd.Function):
         if ctx.fused and not ctx.needs_input_grad[0]:
             P, B, k = idx.shape
             gl = torch.empty_like(logits)
-            L.call("dr_gumbel_topk_gather_bwd_f32", ptr(logits), ptr(matches), *_seed_args(seed), L.c_float(tau), c_int(P), c_int(B),
-                   c_int(logits.shape[1]), c_int(k), ptr(idx), ptr(lse), ptr(g_samples.contiguous()),
-                   ptr(None if g_w is None else g_w.contiguous()), ptr(gl), stream())
+            L.call("dr_gumbel_topk_gather_bwd_f32", ptr(logits), ptr(matches), *_seed_args(seed), tau, P, B, logits.shape[1], k,
+                   ptr(idx), ptr(lse), ptr(g_samples.contiguous()), ptr(None if g_w is None else g_w.contiguous()), ptr(gl), stream())
             return None, gl, None, None, None, None, None
         a_sel, gm = gather_bwd(matches, idx, y_sel, g_samples, g_w, want_grad_matches=ctx.needs_input_grad[0])
         gl = gumbel_topk_bwd(logits, gumbel if has_noise else None, seed, tau, idx, lse, a_sel)
@@ -584,10 +572,10 @@ def solve_nister5(samples: torch.Tensor, weights: Optional[torch.Tensor] = None,
         raise L.DransacError("an explicit five-point kernel path exists for f32 minimal samples only")
     rows, st = _solver_gate(gate, s, n)
     if s.dtype == torch.float32:
-        L.call("dr_solve_nister5_f32", ptr(s), ptr(w), c_int(Bt), c_int(n), ptr(models), ptr(None), ptr(valid), c_int(path), c_int(rows),
-               *_gate_args(st), stream())
+        L.call("dr_solve_nister5_f32", ptr(s), ptr(w), Bt, n, ptr(models), ptr(None), ptr(valid), path, rows, *_gate_args(st),
+               stream())
     else:
-        L.call(f"dr_solve_nister5_{L.suffix(s.dtype)}", ptr(s), ptr(w), c_int(Bt), c_int(n), ptr(models), ptr(valid), stream())
+        L.call(f"dr_solve_nister5_{L.suffix(s.dtype)}", ptr(s), ptr(w), Bt, n, ptr(models), ptr(valid), stream())
     return models.reshape(*lead, 10, 3, 3), valid.reshape(*lead, 10)
 
 
@@ -601,8 +589,7 @@ def solve_nister5_hp(samples: torch.Tensor, weights: Optional[torch.Tensor] = No
     m64 = torch.empty((Bt, 10, 3, 3), device=s.device, dtype=torch.float64)
     valid = torch.empty((Bt, 10), device=s.device, dtype=torch.bool)
     w = None if weights is None else weights.reshape(Bt, n).to(s.dtype).contiguous()
-    L.call("dr_solve_nister5_f32", ptr(s), ptr(w), c_int(Bt), c_int(5), ptr(models), ptr(m64), ptr(valid), c_int(path), c_int(0),
-           ptr(None), ptr(None), stream())
+    L.call("dr_solve_nister5_f32", ptr(s), ptr(w), Bt, 5, ptr(models), ptr(m64), ptr(valid), path, 0, ptr(None), ptr(None), stream())
     return models.reshape(*lead, 10, 3, 3), m64.reshape(*lead, 10, 3, 3), valid.reshape(*lead, 10)
 
 
@@ -619,7 +606,7 @@ def debug_real_roots10(coef: torch.Tensor, method: int = 1):
     n = coef.shape[0]
     roots = torch.zeros((n, 2, 10), device=coef.device, dtype=torch.float64)
     counts = torch.zeros((n, 2), device=coef.device, dtype=torch.int32)
-    L.call("dr_debug_real_roots10", ptr(coef), c_int(n), c_int(method), ptr(roots), ptr(counts), stream())
+    L.call("dr_debug_real_roots10", ptr(coef), n, method, ptr(roots), ptr(counts), stream())
     return roots, counts
 
 
@@ -635,9 +622,9 @@ def solve_stewenius5(samples: torch.Tensor, path: int = 0, gate=None):
         raise L.DransacError("an explicit five-point kernel path exists for f32 minimal samples only")
     rows, st = _solver_gate(gate, s, n)
     if s.dtype == torch.float32:
-        L.call("dr_solve_stewenius5_f32", ptr(s), c_int(Bt), ptr(models), ptr(valid), c_int(path), c_int(rows), *_gate_args(st), stream())
+        L.call("dr_solve_stewenius5_f32", ptr(s), Bt, ptr(models), ptr(valid), path, rows, *_gate_args(st), stream())
     else:
-        L.call(f"dr_solve_stewenius5_{L.suffix(s.dtype)}", ptr(s), c_int(Bt), ptr(models), ptr(valid), stream())
+        L.call(f"dr_solve_stewenius5_{L.suffix(s.dtype)}", ptr(s), Bt, ptr(models), ptr(valid), stream())
     return models.reshape(*lead, 10, 3, 3), valid.reshape(*lead, 10)
 
 
@@ -648,7 +635,7 @@ def solve_f8(samples: torch.Tensor, weights: Optional[torch.Tensor] = None):
     models = torch.empty((Bt, 3, 3), device=s.device, dtype=s.dtype)
     valid = torch.empty((Bt,), device=s.device, dtype=torch.bool)
     w = None if weights is None else weights.reshape(Bt, n).to(s.dtype).contiguous()
-    L.call(f"dr_solve_f8_{L.suffix(s.dtype)}", ptr(s), ptr(w), c_int(Bt), c_int(n), ptr(models), ptr(valid), stream())
+    L.call(f"dr_solve_f8_{L.suffix(s.dtype)}", ptr(s), ptr(w), Bt, n, ptr(models), ptr(valid), stream())
     return models.reshape(*lead, 3, 3), valid.reshape(lead)
 
 
@@ -661,8 +648,8 @@ def solve_f8_uniform(matches: torch.Tensor, B: int, seed):
     idx = torch.empty((P, B, 8), device=matches.device, dtype=torch.int32)
     models = torch.empty((P, B, 3, 3), device=matches.device, dtype=torch.float32)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call("dr_solve_f8_uniform_f32", ptr(matches.contiguous()), *_seed_args(seed), c_int(P), c_int(B), c_int(N), ptr(idx),
-           ptr(models), ptr(valid), stream())
+    L.call("dr_solve_f8_uniform_f32", ptr(matches.contiguous()), *_seed_args(seed), P, B, N, ptr(idx), ptr(models), ptr(valid),
+           stream())
     return idx, models, valid
 
 
@@ -673,7 +660,7 @@ def solve_f7(samples: torch.Tensor):
     lead = samples.shape[:-2]
     models = torch.empty((Bt, 4, 3, 3), device=s.device, dtype=s.dtype)
     valid = torch.empty((Bt, 4), device=s.device, dtype=torch.bool)
-    L.call(f"dr_solve_f7_{L.suffix(s.dtype)}", ptr(s), c_int(Bt), ptr(models), ptr(valid), stream())
+    L.call(f"dr_solve_f7_{L.suffix(s.dtype)}", ptr(s), Bt, ptr(models), ptr(valid), stream())
     return models.reshape(*lead, 4, 3, 3), valid.reshape(*lead, 4)
 
 
@@ -688,8 +675,8 @@ def solve_rigid(samples: torch.Tensor, weights: Optional[torch.Tensor] = None, f
     scale = torch.empty((Bt,), device=dev, dtype=dt)
     valid = torch.empty((Bt,), device=dev, dtype=torch.bool)
     w = None if weights is None else weights.reshape(Bt, n).to(dt).contiguous()
-    L.call(f"dr_solve_rigid_{L.suffix(dt)}", ptr(s), ptr(w), c_int(Bt), c_int(n), c_int(1 if flag else 0), ptr(model),
-           ptr(R), ptr(t), ptr(scale), ptr(valid), stream())
+    L.call(f"dr_solve_rigid_{L.suffix(dt)}", ptr(s), ptr(w), Bt, n, bool(flag), ptr(model), ptr(R), ptr(t), ptr(scale), ptr(valid),
+           stream())
     return (model.reshape(*lead, 4, 4), R.reshape(*lead, 3, 3), t.reshape(*lead, 3), scale.reshape(lead),
             valid.reshape(lead))
 
@@ -704,8 +691,8 @@ def solve_rigid_gather(matches: torch.Tensor, idx: torch.Tensor, flag: bool = Tr
     _, B, k = idx.shape
     model = torch.empty((P, B, 4, 4), device=matches.device, dtype=torch.float32)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call("dr_solve_rigid_gather_f32", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B), c_int(N), c_int(k),
-           c_int(1 if flag else 0), ptr(model), ptr(None), ptr(None), ptr(None), ptr(valid), ptr(zero_sums), stream())
+    L.call("dr_solve_rigid_gather_f32", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, k, bool(flag), ptr(model),
+           ptr(None), ptr(None), ptr(None), ptr(valid), ptr(zero_sums), stream())
     return model, valid
 
 
@@ -719,16 +706,16 @@ def rigid_residual(pts: torch.Tensor, models: torch.Tensor, threshold: float = 0
     if res is not None:
         if pts.dtype != torch.float32 or res.shape != (P, M) or res.dtype != torch.float32:
             raise L.DransacError("rigid_residual: res must be an f32 [P,M] tensor of zeros")
-        L.call("dr_rigid_residual_f32", ptr(pts.contiguous()), ptr(models.contiguous()), L.c_float(threshold), c_int(P),
-               c_int(M), c_int(N), ptr(res), ptr(masks), c_int(1), stream())
+        L.call("dr_rigid_residual_f32", ptr(pts.contiguous()), ptr(models.contiguous()), threshold, P, M, N, ptr(res), ptr(masks), 1,
+               stream())
         return res, masks
     res = torch.empty((P, M), device=pts.device, dtype=pts.dtype)
     if pts.dtype == torch.float32:
-        L.call("dr_rigid_residual_f32", ptr(pts.contiguous()), ptr(models.contiguous()), L.c_float(threshold), c_int(P), c_int(M),
-               c_int(N), ptr(res), ptr(masks), c_int(0), stream())
+        L.call("dr_rigid_residual_f32", ptr(pts.contiguous()), ptr(models.contiguous()), threshold, P, M, N, ptr(res), ptr(masks), 0,
+               stream())
     else:
-        L.call(f"dr_rigid_residual_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()),
-               L.scalar(pts.dtype, threshold), c_int(P), c_int(M), c_int(N), ptr(res), ptr(masks), stream())
+        L.call(f"dr_rigid_residual_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()), threshold, P, M, N,
+               ptr(res), ptr(masks), stream())
     return res, masks
 
 
@@ -747,9 +734,8 @@ def ransac3d_update(pts: torch.Tensor, models: torch.Tensor, valid: Optional[tor
     idx = torch.empty((P,), device=pts.device, dtype=torch.int32)
     mk = None if best_mask is None else best_mask.view(torch.uint8)
     L.call(f"dr_ransac3d_update_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(res.contiguous()), L.scalar(pts.dtype, threshold), c_int(P), c_int(M), c_int(N),
-           ptr(None if best_res is None else best_res.contiguous()), ptr(None if best_model is None else best_model.contiguous()),
-           ptr(out_res), ptr(out_model), ptr(mk), ptr(idx), stream())
+           ptr(res.contiguous()), threshold, P, M, N, ptr(None if best_res is None else best_res.contiguous()),
+           ptr(None if best_model is None else best_model.contiguous()), ptr(out_res), ptr(out_model), ptr(mk), ptr(idx), stream())
     return out_res, out_model, idx
 
 
@@ -772,8 +758,8 @@ def kabsch_gather(matches: torch.Tensor, idx: torch.Tensor):
     _, B, k = idx.shape
     models = torch.empty((P, B, 4, 4), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_kabsch_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B),
-           c_int(N), c_int(k), ptr(models), ptr(valid), stream())
+    L.call(f"dr_kabsch_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, k, ptr(models),
+           ptr(valid), stream())
     return models, valid
 
 
@@ -794,8 +780,8 @@ def kabsch_gather_checked(matches: torch.Tensor, idx: torch.Tensor, edge_similar
         raise L.DransacError("kabsch_gather_checked: rejected must be [P] int32")
     models = torch.empty((P, B, 4, 4), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_kabsch_gather_checked_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B),
-           c_int(N), c_int(k), L.c_double(float(edge_similarity)), ptr(models), ptr(valid), ptr(rejected), stream())
+    L.call(f"dr_kabsch_gather_checked_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, k,
+           float(edge_similarity), ptr(models), ptr(valid), ptr(rejected), stream())
     return models, valid
 
 
@@ -822,8 +808,8 @@ def _pair_score(entry: str, matches, models, threshold, valid, want_inliers, thr
     thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(thr2), c_int(P), c_int(M), c_int(N), ptr(scores), ptr(inliers), *(_gate_args(gate) if gated else ()), stream())
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid), ptr(thr2), P,
+           M, N, ptr(scores), ptr(inliers), *(_gate_args(gate) if gated else ()), stream())
     return scores, inliers
 
 
@@ -833,9 +819,9 @@ def _pair_update(entry: str, state: _PairState, matches, models, valid, scores, 
     M = models.shape[1]
     thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
     L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(scores.contiguous()), ptr(thr2), c_int(P), c_int(M), c_int(N), c_int(int(B)), L.c_double(confidence), L.c_double(eps),
-           c_int(state.max_iterations), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
-           ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters), stream())
+           ptr(scores.contiguous()), ptr(thr2), P, M, N, int(B), confidence, eps, state.max_iterations, ptr(state.best_score),
+           ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.iters),
+           ptr(state.max_iters), stream())
 
 
 def _pair_refit(entry: str, side: int, matches, mask, weights):
@@ -848,8 +834,7 @@ def _pair_refit(entry: str, side: int, matches, mask, weights):
     model = torch.empty((P, side, side), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
     L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
-           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(model), ptr(valid),
-           stream())
+           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), P, N, ptr(model), ptr(valid), stream())
     return model, valid
 
 
@@ -903,10 +888,9 @@ def registration_local_optimize(state: RegistrationState, matches, thr2, lo: int
     if lo_refits is not None and (lo_refits.shape != (P,) or lo_refits.dtype != torch.int32):
         raise L.DransacError("registration_local_optimize: lo_refits must be [P] int32")
     mi = state.max_iterations if max_iterations is None else max_iterations
-    L.call(f"dr_registration_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), c_int(P), c_int(N),
-           c_int(int(lo)), c_int(int(lo_iters)), L.c_double(confidence), L.c_double(eps), c_int(int(mi)), ptr(state.best_score),
-           ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.max_iters),
-           ptr(lo_seen), ptr(lo_refits), stream())
+    L.call(f"dr_registration_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(lo), int(lo_iters),
+           confidence, eps, int(mi), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
+           ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits), stream())
 
 
 def registration_irls(state: RegistrationState, matches, thr2, irls_iters: int, irls_fits: torch.Tensor) -> None:
@@ -920,8 +904,8 @@ def registration_irls(state: RegistrationState, matches, thr2, irls_iters: int, 
     P, N, _ = matches.shape
     if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
         raise L.DransacError("registration_irls: irls_fits must be [P] int32")
-    L.call(f"dr_registration_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), c_int(P), c_int(N),
-           c_int(int(irls_iters)), ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
+    L.call(f"dr_registration_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(irls_iters),
+           ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
 
 
 def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
@@ -935,7 +919,7 @@ def _kabsch_fwd(samples: torch.Tensor, weights: Optional[torch.Tensor]):
     Bt, k, _ = samples.shape
     models = torch.empty((Bt, 4, 4), device=samples.device, dtype=samples.dtype)
     valid = torch.empty((Bt,), device=samples.device, dtype=torch.bool)
-    L.call(f"dr_kabsch_{L.suffix(samples.dtype)}", ptr(samples), ptr(weights), c_int(Bt), c_int(k), ptr(models), ptr(valid), stream())
+    L.call(f"dr_kabsch_{L.suffix(samples.dtype)}", ptr(samples), ptr(weights), Bt, k, ptr(models), ptr(valid), stream())
     return models, valid
 
 
@@ -951,7 +935,7 @@ def select_closest(models: torch.Tensor, valid: Optional[torch.Tensor], gt: torc
     which = torch.empty((P, B), device=models.device, dtype=torch.int32)
     keep = torch.empty((P, B), device=models.device, dtype=torch.bool) if want_keep else None
     L.call(f"dr_select_closest_{L.suffix(models.dtype)}", ptr(models.contiguous()), _u8_ptr(valid),
-           ptr(gt.to(models.dtype).contiguous()), c_int(P), c_int(B), c_int(S), ptr(chosen), ptr(which), ptr(keep), stream())
+           ptr(gt.to(models.dtype).contiguous()), P, B, S, ptr(chosen), ptr(which), ptr(keep), stream())
     return (chosen, which, keep) if want_keep else (chosen, which)
 
 
@@ -961,8 +945,8 @@ def refit_essential(matches: torch.Tensor, mask: Optional[torch.Tensor] = None):
     P, N, _ = matches.shape
     models = torch.empty((P, 10, 3, 3), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, 10), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_refit_essential_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask), c_int(P), c_int(N),
-           ptr(models), ptr(valid), stream())
+    L.call(f"dr_refit_essential_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask), P, N, ptr(models), ptr(valid),
+           stream())
     return models, valid
 
 
@@ -973,7 +957,7 @@ def refit_accept(matches: torch.Tensor, cand: torch.Tensor, cand_valid: Optional
     P, N, _ = matches.shape
     S = cand.shape[1]
     L.call(f"dr_refit_accept_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(cand.contiguous()), _u8_ptr(cand_valid),
-           ptr(thr), c_int(P), c_int(S), c_int(N), ptr(best_score), ptr(best_model), stream())
+           ptr(thr), P, S, N, ptr(best_score), ptr(best_model), stream())
 
 
 def refit_fundamental(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
@@ -985,8 +969,7 @@ def refit_fundamental(matches: torch.Tensor, mask: Optional[torch.Tensor] = None
     if weights is not None and weights.shape != (P, N):
         raise L.DransacError("refit weights are [P,N], one per point")
     L.call(f"dr_refit_fundamental_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
-           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), c_int(P), c_int(N), ptr(models), ptr(valid),
-           stream())
+           ptr(None if weights is None else weights.to(matches.dtype).contiguous()), P, N, ptr(models), ptr(valid), stream())
     return models, valid
 
 
@@ -1035,7 +1018,7 @@ class _SolveEssential(torch.autograd.Function):
             s, Bt, n = _flat_samples(samples, 4)
             gs = torch.empty_like(s)
             L.call("dr_solve_nister5_bwd_f64", ptr(s), ptr(models.contiguous()), _u8_ptr(valid),
-                   ptr(g_models.to(torch.float64).contiguous()), c_int(Bt), ptr(gs), stream())
+                   ptr(g_models.to(torch.float64).contiguous()), Bt, ptr(gs), stream())
             return gs.reshape(samples.shape), None, None
         if f64:
             # n > 5 rows per sample in f64 (`-sam 3 -fmat 0 -tr 1 -pr 2`), round 6: f64 samples, weights, models and gradients straight
@@ -1045,8 +1028,8 @@ class _SolveEssential(torch.autograd.Function):
             w = ctx.weights
             gw = None if w is None or not ctx.needs_input_grad[1] else torch.empty((Bt, n), device=s.device, dtype=torch.float64)
             L.call("dr_solve_nister5_nm_bwd_f64", ptr(s), ptr(None if w is None else w.reshape(Bt, n).double().contiguous()),
-                   ptr(models.contiguous()), _u8_ptr(valid), ptr(g_models.to(torch.float64).contiguous()),
-                   c_int(Bt), c_int(n), ptr(gs), ptr(gw), stream())
+                   ptr(models.contiguous()), _u8_ptr(valid), ptr(g_models.to(torch.float64).contiguous()), Bt, n, ptr(gs), ptr(gw),
+                   stream())
             return gs.reshape(samples.shape), (None if gw is None else gw.reshape(w.shape).to(w.dtype)), None
         s, Bt, n = _flat_samples(samples, 4)
         gs = torch.empty_like(s)
@@ -1056,13 +1039,12 @@ class _SolveEssential(torch.autograd.Function):
             w = ctx.weights
             gw = None if w is None or not ctx.needs_input_grad[1] else torch.empty((Bt, n), device=s.device, dtype=torch.float32)
             L.call("dr_solve_nister5_nm_bwd_f32", ptr(s), ptr(None if w is None else w.reshape(Bt, n).float().contiguous()),
-                   ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None),
-                   _u8_ptr(valid), ptr(g_models.contiguous()), c_int(Bt), c_int(n), ptr(gs), ptr(gw),
-                   stream())
+                   ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None), _u8_ptr(valid),
+                   ptr(g_models.contiguous()), Bt, n, ptr(gs), ptr(gw), stream())
             gs = gs.reshape(samples.shape)
             return (gs.double() if f64 else gs), (None if gw is None else gw.reshape(w.shape).to(w.dtype)), None
         L.call("dr_solve_nister5_bwd_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None),
-               _u8_ptr(valid), ptr(g_models.contiguous()), c_int(Bt), ptr(gs), stream())
+               _u8_ptr(valid), ptr(g_models.contiguous()), Bt, ptr(gs), stream())
         gs = gs.reshape(samples.shape)
         return (gs.double() if f64 else gs), None, None
 
@@ -1100,9 +1082,8 @@ class _SolveSelectEssential(torch.autograd.Function):
         samples, models, m64, valid, which = ctx.saved_tensors
         s, Bt, _ = _flat_samples(samples, 4)
         gs = torch.empty_like(s)
-        L.call("dr_solve_nister5_bwd_sel_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous()),
-               _u8_ptr(valid), ptr(g_chosen.contiguous()), ptr(which.contiguous()), c_int(Bt),
-               ptr(gs), stream())
+        L.call("dr_solve_nister5_bwd_sel_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous()), _u8_ptr(valid),
+               ptr(g_chosen.contiguous()), ptr(which.contiguous()), Bt, ptr(gs), stream())
         return gs.reshape(samples.shape), None, None
 
 
@@ -1134,8 +1115,8 @@ class _SolveF8(torch.autograd.Function):
         gs = torch.empty_like(s)
         w = weights.reshape(Bt, n).to(dt).contiguous() if ctx.has_w else None
         gw = torch.empty_like(w) if ctx.has_w else None
-        L.call(f"dr_solve_f8_bwd_{L.suffix(dt)}", ptr(s), ptr(w), ptr(F.to(dt).contiguous()), ptr(gF.to(dt).contiguous()), c_int(Bt),
-               c_int(n), ptr(gs), ptr(gw), stream())
+        L.call(f"dr_solve_f8_bwd_{L.suffix(dt)}", ptr(s), ptr(w), ptr(F.to(dt).contiguous()), ptr(gF.to(dt).contiguous()), Bt, n,
+               ptr(gs), ptr(gw), stream())
         return gs.reshape(samples.shape), (gw.reshape(weights.shape) if ctx.has_w else None)
 
 
@@ -1170,8 +1151,8 @@ class _SolveRigid(torch.autograd.Function):
             g[..., :3, 3] += g_t
         s, Bt, n = _flat_samples(samples, 6)
         gs = torch.empty_like(s)
-        L.call("dr_solve_rigid_bwd_f32", ptr(s), ptr(model.contiguous()), ptr(g.contiguous()), c_int(Bt), c_int(n),
-               c_int(1 if ctx.flag else 0), ptr(gs), stream())
+        L.call("dr_solve_rigid_bwd_f32", ptr(s), ptr(model.contiguous()), ptr(g.contiguous()), Bt, n, bool(ctx.flag), ptr(gs),
+               stream())
         return gs.reshape(samples.shape), None, None
 
 
@@ -1204,8 +1185,8 @@ class _Kabsch(torch.autograd.Function):
         Bt, k, _ = s.shape
         gs = torch.empty_like(s)
         gw = torch.empty((Bt, k), device=s.device, dtype=s.dtype) if (w is not None and ctx.needs_input_grad[1]) else None
-        L.call(f"dr_kabsch_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(w), ptr(_grad_top_rows(g_models, s.dtype)), c_int(Bt), c_int(k),
-               ptr(gs), ptr(gw), stream())
+        L.call(f"dr_kabsch_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(w), ptr(_grad_top_rows(g_models, s.dtype)), Bt, k, ptr(gs), ptr(gw),
+               stream())
         sshape, wshape = ctx.shapes
         return gs.reshape(sshape), None if gw is None else gw.reshape(wshape[0]).to(wshape[1])
 
@@ -1246,8 +1227,8 @@ class _WeightedKabsch(torch.autograd.Function):
         P, N, _ = m.shape
         gm = torch.empty_like(m) if ctx.needs_input_grad[0] else None
         gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if (w is not None and ctx.needs_input_grad[1]) else None
-        L.call(f"dr_refit_rigid_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w), ptr(_grad_top_rows(g_model, m.dtype)),
-               c_int(P), c_int(N), ptr(gm), ptr(gw), stream())
+        L.call(f"dr_refit_rigid_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w), ptr(_grad_top_rows(g_model, m.dtype)), P, N,
+               ptr(gm), ptr(gw), stream())
         return gm, None if gw is None else gw.to(ctx.wdtype), None
 
 
@@ -1279,8 +1260,8 @@ def homography4_gather(matches: torch.Tensor, idx: torch.Tensor):
     B = idx.shape[1]
     models = torch.empty((P, B, 3, 3), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_homography4_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), c_int(P), c_int(B),
-           c_int(N), ptr(models), ptr(valid), stream())
+    L.call(f"dr_homography4_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, ptr(models),
+           ptr(valid), stream())
     return models, valid
 
 
@@ -1330,7 +1311,7 @@ class _Homography4(torch.autograd.Function):
         s, Bt, _ = _flat_samples(samples, 4)
         models = torch.empty((Bt, 3, 3), device=s.device, dtype=s.dtype)
         valid = torch.empty((Bt,), device=s.device, dtype=torch.bool)
-        L.call(f"dr_homography4_{L.suffix(s.dtype)}", ptr(s), c_int(Bt), ptr(models), ptr(valid), stream())
+        L.call(f"dr_homography4_{L.suffix(s.dtype)}", ptr(s), Bt, ptr(models), ptr(valid), stream())
         ctx.save_for_backward(s)
         ctx.sshape = samples.shape
         lead = samples.shape[:-2]
@@ -1344,8 +1325,8 @@ class _Homography4(torch.autograd.Function):
             return None
         (s,) = ctx.saved_tensors
         gs = torch.empty_like(s)
-        L.call(f"dr_homography4_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(g_models.to(s.dtype).reshape(-1, 3, 3).contiguous()),
-               c_int(s.shape[0]), ptr(gs), stream())
+        L.call(f"dr_homography4_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(g_models.to(s.dtype).reshape(-1, 3, 3).contiguous()), s.shape[0],
+               ptr(gs), stream())
         return gs.reshape(ctx.sshape)
 
 
@@ -1379,8 +1360,8 @@ class _MsacScore(torch.autograd.Function):
         P, N, _ = matches.shape
         M = models.shape[1]
         gm = torch.empty_like(models)
-        L.call("dr_msac_score_bwd_f32", ptr(matches.contiguous()), ptr(models.contiguous()), ptr(thr),
-               ptr(g_scores.contiguous()), c_int(P), c_int(M), c_int(N), ptr(gm), stream())
+        L.call("dr_msac_score_bwd_f32", ptr(matches.contiguous()), ptr(models.contiguous()), ptr(thr), ptr(g_scores.contiguous()), P,
+               M, N, ptr(gm), stream())
         return None, gm, None, None
 
 
@@ -1408,8 +1389,8 @@ class _RigidResidual(torch.autograd.Function):
         P, N, _ = pts.shape
         M = models.shape[1]
         gm = torch.empty_like(models)
-        L.call("dr_rigid_residual_bwd_f32", ptr(pts.contiguous()), ptr(models.contiguous()), ptr(g_res.contiguous()),
-               c_int(P), c_int(M), c_int(N), ptr(gm), stream())
+        L.call("dr_rigid_residual_bwd_f32", ptr(pts.contiguous()), ptr(models.contiguous()), ptr(g_res.contiguous()), P, M, N, ptr(gm),
+               stream())
         return None, gm, None
 
 
@@ -1434,8 +1415,7 @@ class _SelectClosest(torch.autograd.Function):
         (which,) = ctx.saved_tensors
         P, B, S = ctx.shape[:3]
         g = torch.empty(ctx.shape, device=g_chosen.device, dtype=g_chosen.dtype)
-        L.call(f"dr_select_closest_bwd_{L.suffix(g_chosen.dtype)}", ptr(g_chosen.contiguous()), ptr(which), c_int(P),
-               c_int(B), c_int(S), ptr(g), stream())
+        L.call(f"dr_select_closest_bwd_{L.suffix(g_chosen.dtype)}", ptr(g_chosen.contiguous()), ptr(which), P, B, S, ptr(g), stream())
         return g, None, None
 
 
@@ -1454,7 +1434,7 @@ def _episym_fwd(matches, mask, models, valid):
     matches, models = matches.contiguous(), models.contiguous()
     mk, v = _u8(mask), _u8(valid)
     sums = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
-    L.call("dr_episym_fwd_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), c_int(P), c_int(M), c_int(N), ptr(sums), stream())
+    L.call("dr_episym_fwd_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), P, M, N, ptr(sums), stream())
     return matches, models, mk, v, sums
 
 
@@ -1476,8 +1456,8 @@ class _EpisymSums(torch.autograd.Function):
         P, N, _ = matches.shape
         M = models.shape[1]
         gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call("dr_episym_bwd_f32", ptr(matches.contiguous()), ptr(mk), ptr(models.contiguous()), ptr(v),
-               ptr(g.contiguous()), c_int(P), c_int(M), c_int(N), ptr(gm), stream())
+        L.call("dr_episym_bwd_f32", ptr(matches.contiguous()), ptr(mk), ptr(models.contiguous()), ptr(v), ptr(g.contiguous()), P, M, N,
+               ptr(gm), stream())
         return None, None, gm, None
 
 
@@ -1499,8 +1479,7 @@ class _MatchLossPair(torch.autograd.Function):
         (P, N, _), M = matches.shape, models.shape[1]
         per_pair = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         coef = torch.empty((P,), device=matches.device, dtype=matches.dtype)
-        L.call("dr_match_loss_pair_f32", ptr(sums), ptr(mk), ptr(v), c_int(P), c_int(M), c_int(N), ptr(per_pair), ptr(coef),
-               stream())
+        L.call("dr_match_loss_pair_f32", ptr(sums), ptr(mk), ptr(v), P, M, N, ptr(per_pair), ptr(coef), stream())
         ctx.save_for_backward(matches, models, coef)
         ctx.aux = (mk, v)
         return per_pair
@@ -1515,8 +1494,7 @@ class _MatchLossPair(torch.autograd.Function):
         M = models.shape[1]
         gp = (g * coef).contiguous()
         gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call("dr_episym_bwd_pair_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), ptr(gp), c_int(P), c_int(M), c_int(N),
-               ptr(gm), stream())
+        L.call("dr_episym_bwd_pair_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), ptr(gp), P, M, N, ptr(gm), stream())
         return None, None, gm, None
 
 
@@ -1531,8 +1509,7 @@ class _MatchLossMean(torch.autograd.Function):
         per_pair = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         coef = torch.empty((P,), device=matches.device, dtype=matches.dtype)
         mean = torch.empty((), device=matches.device, dtype=matches.dtype)
-        L.call("dr_match_loss_mean_f32", ptr(sums), ptr(mk), ptr(v), c_int(P), c_int(M), c_int(N), ptr(per_pair), ptr(coef),
-               ptr(mean), stream())
+        L.call("dr_match_loss_mean_f32", ptr(sums), ptr(mk), ptr(v), P, M, N, ptr(per_pair), ptr(coef), ptr(mean), stream())
         ctx.save_for_backward(matches, models, coef)
         ctx.aux = (mk, v)
         return mean
@@ -1546,8 +1523,8 @@ class _MatchLossMean(torch.autograd.Function):
         P, N, _ = matches.shape
         M = models.shape[1]
         gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call("dr_episym_bwd_mean_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), ptr(coef),
-               ptr(g.to(matches.dtype).contiguous()), c_int(P), c_int(M), c_int(N), ptr(gm), stream())
+        L.call("dr_episym_bwd_mean_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), ptr(coef), ptr(g.to(matches.dtype).contiguous()),
+               P, M, N, ptr(gm), stream())
         return None, None, gm, None
 
 
@@ -1568,8 +1545,8 @@ class _MatchLossFused(torch.autograd.Function):
         per_pair = torch.empty((P,), device=dev, dtype=dt)
         coef = torch.empty((P,), device=dev, dtype=dt)
         mean = torch.empty((), device=dev, dtype=dt)
-        L.call("dr_match_loss_fused_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), c_int(P), c_int(M), c_int(N), ptr(sums),
-               ptr(gun), ptr(per_pair), ptr(coef), ptr(mean), stream())
+        L.call("dr_match_loss_fused_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), P, M, N, ptr(sums), ptr(gun), ptr(per_pair),
+               ptr(coef), ptr(mean), stream())
         ctx.save_for_backward(gun, coef)
         return mean
 
@@ -1580,8 +1557,7 @@ class _MatchLossFused(torch.autograd.Function):
         gun, coef = ctx.saved_tensors
         P, M = gun.shape[0], gun.shape[1]
         gm = torch.empty_like(gun)
-        L.call("dr_match_loss_scale_f32", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), c_int(P), c_int(M), ptr(gm),
-               stream())
+        L.call("dr_match_loss_scale_f32", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), P, M, ptr(gm), stream())
         return None, None, gm, None
 
 
@@ -1652,7 +1628,7 @@ def registration_gt_mask(matches: torch.Tensor, gt_pose: torch.Tensor, threshold
     mask = torch.empty((P, N), device=matches.device, dtype=torch.bool)
     count = torch.empty((P,), device=matches.device, dtype=torch.int32)
     L.call(f"dr_registration_gt_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(gt_pose.contiguous()),
-           ptr(thr2_tensor(threshold, P, matches)), c_int(P), c_int(N), ptr(mask.view(torch.uint8)), ptr(count), stream())
+           ptr(thr2_tensor(threshold, P, matches)), P, N, ptr(mask.view(torch.uint8)), ptr(count), stream())
     return mask, count
 
 
@@ -1673,8 +1649,8 @@ def _registration_loss_fwd(matches, mask, models, threshold, keep):
     dev, dt = matches.device, matches.dtype
     sums = torch.empty((P, M), device=dev, dtype=dt)
     per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-    L.call(f"dr_registration_loss_fwd_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2_tensor(threshold, P, matches)),
-           c_int(P), c_int(M), c_int(N), ptr(sums), ptr(per_pair), ptr(coef), ptr(mean), stream())
+    L.call(f"dr_registration_loss_fwd_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp),
+           ptr(thr2_tensor(threshold, P, matches)), P, M, N, ptr(sums), ptr(per_pair), ptr(coef), ptr(mean), stream())
     return sums, per_pair, coef, mean
 
 
@@ -1689,8 +1665,8 @@ class _RegistrationLossFused(torch.autograd.Function):
         sums = torch.empty((P, M), device=dev, dtype=dt)
         gun = torch.empty((P, M, 4, 4), device=dev, dtype=dt)
         per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-        L.call(f"dr_registration_loss_fused_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2), c_int(P), c_int(M),
-               c_int(N), ptr(sums), ptr(gun), ptr(per_pair), ptr(coef), ptr(mean), stream())
+        L.call(f"dr_registration_loss_fused_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2), P, M, N,
+               ptr(sums), ptr(gun), ptr(per_pair), ptr(coef), ptr(mean), stream())
         ctx.save_for_backward(gun, coef)
         return mean
 
@@ -1702,8 +1678,8 @@ class _RegistrationLossFused(torch.autograd.Function):
         gun, coef = ctx.saved_tensors
         P, M = gun.shape[0], gun.shape[1]
         gm = torch.empty_like(gun)
-        L.call(f"dr_registration_loss_scale_{L.suffix(gun.dtype)}", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), c_int(P),
-               c_int(M), ptr(gm), stream())
+        L.call(f"dr_registration_loss_scale_{L.suffix(gun.dtype)}", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), P, M,
+               ptr(gm), stream())
         return None, None, gm, None, None
 
 
@@ -1742,8 +1718,8 @@ class _PoseError(torch.autograd.Function):
         err_t = torch.empty((P, M), device=dev, dtype=dt)
         which = torch.empty((P, M), device=dev, dtype=torch.int32)
         votes = torch.empty((P, M, 4), device=dev, dtype=torch.int32) if want_votes else None
-        L.call(f"dr_pose_error_fwd_{sfx}", ptr(matches), ptr(models), ptr(gt_R), ptr(gt_t), c_int(P), c_int(M), c_int(N),
-               L.c_double(float(distance_threshold)), ptr(err_R), ptr(err_t), ptr(which), ptr(votes), stream())
+        L.call(f"dr_pose_error_fwd_{sfx}", ptr(matches), ptr(models), ptr(gt_R), ptr(gt_t), P, M, N, float(distance_threshold),
+               ptr(err_R), ptr(err_t), ptr(which), ptr(votes), stream())
         ctx.save_for_backward(models, gt_R, gt_t, which)
         ctx.mark_non_differentiable(which)
         if votes is not None:
@@ -1762,8 +1738,8 @@ class _PoseError(torch.autograd.Function):
             zero = torch.zeros((P, M), device=models.device, dtype=models.dtype)
         g_R = zero if g_R is None else g_R.contiguous()
         g_t = zero if g_t is None else g_t.contiguous()
-        L.call(f"dr_pose_error_bwd_{L.suffix(models.dtype)}", ptr(models), ptr(gt_R), ptr(gt_t), ptr(which), ptr(g_R),
-               ptr(g_t), c_int(P), c_int(M), ptr(gm), stream())
+        L.call(f"dr_pose_error_bwd_{L.suffix(models.dtype)}", ptr(models), ptr(gt_R), ptr(gt_t), ptr(which), ptr(g_R), ptr(g_t), P, M,
+               ptr(gm), stream())
         return None, gm, None, None, None, None
 
 
@@ -1791,8 +1767,8 @@ def pose_error(matches, models, gt_R, gt_t, distance_threshold: float = 50.0, wa
     # once and the caching allocator hands its block to the next temporary
     mt_, md_ = matches.contiguous(), models.detach().contiguous()
     gR_, gt_ = gt_R.reshape(P, 9).to(dt).contiguous(), gt_t.reshape(P, 3).to(dt).contiguous()
-    L.call(f"dr_pose_error_svd_fwd_{L.suffix(dt)}", ptr(mt_), ptr(md_), ptr(gR_), ptr(gt_), c_int(P), c_int(M), c_int(N),
-           L.c_double(float(distance_threshold)), ptr(err_R), ptr(err_t), ptr(which), ptr(votes), stream())
+    L.call(f"dr_pose_error_svd_fwd_{L.suffix(dt)}", ptr(mt_), ptr(md_), ptr(gR_), ptr(gt_), P, M, N, float(distance_threshold),
+           ptr(err_R), ptr(err_t), ptr(which), ptr(votes), stream())
     return err_R, err_t, which, votes
 
 
@@ -1804,6 +1780,6 @@ def recover_pose_mask(matches, models, distance_threshold: float = 50.0):
     M = models.shape[1]
     mask = torch.empty((P, M, N), device=matches.device, dtype=torch.bool)
     which = torch.empty((P, M), device=matches.device, dtype=torch.int32)
-    L.call(f"dr_recover_pose_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models), c_int(P), c_int(M),
-           c_int(N), L.c_double(float(distance_threshold)), ptr(which), ptr(mask), stream())
+    L.call(f"dr_recover_pose_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models), P, M, N,
+           float(distance_threshold), ptr(which), ptr(mask), stream())
     return mask, which

@@ -1,6 +1,6 @@
 """The launches the drivers issue, pinned: every libdransac launch goes through `_lib.call`, so wrapping it records, per
 call, the entry point, the stream it went to (ordinal of first appearance within the case: 0, 1, 2) and its integer scalar
-arguments (the c_int values: P, B, N, k, sub, flags -- no pointers, no seeds).  A fixed list of driver calls on small seeded
+arguments (the `int` parameters of the header: P, B, N, k, sub, flags -- no pointers, no seeds).  A fixed list of driver calls on small seeded
 synthetic input is compared with tests/golden/driver_launch_trace.json.
 
 The golden file pins what the drivers issued BEFORE the host code of ransac.py / ops.py was deduplicated: it was written by
@@ -28,7 +28,8 @@ class _Trace:
 
     def _call(self, name, *a):
         s = self.streams.setdefault(a[-1].value, len(self.streams))     # (every wrapper ends its argument list with stream())
-        self.calls.append([name, s, [int(x.value) for x in a if isinstance(x, self.L.c_int)]])
+        ints = [x for x, t in zip(a, self.L.entries()[name]) if t is self.L.c_int]      # the `int` slots, plain or as c_int
+        self.calls.append([name, s, [int(getattr(x, "value", x)) for x in ints]])
         self.orig(name, *a)
 
     def __exit__(self, *exc):

@@ -139,7 +139,6 @@ def test_entry_is_exported_and_checks_its_arguments_without_touching_the_gpu():
     from differentiable_ransac_amd import _lib as L
     lib = L.lib()
     fn = lib.dr_prosac_sample
-    fn.restype = ctypes.c_int
     u64, i64, i32, vp = ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p
     fake = vp(64)      # never dereferenced: every call below is refused before a launch
 
