@@ -1,6 +1,7 @@
 // Plane-induced homographies (ransac.BatchedHomography): models from minimal samples of four matches by a closed form, its reverse
 // pass for train mode, the MSAC score and inlier count of every model against every point under the symmetric transfer error, the
-// per-pair state step with the adaptive stop, and the normalised DLT refit over the rows a mask selects.
+// per-pair state step with the adaptive stop, the normalised DLT refit over the rows a mask selects, and for scoring = "magsac" the
+// MAGSAC++ score on the same error and the IRLS polish of the pair state under it.
 //   matches [P,N,4] = (x1, y1, x2, y2) in the caller's coordinates (pixels; no K).  A model is the row-major 3x3 H, x2 ~ H x1, stored
 //   with unit Frobenius norm and det H > 0 (det(-H) = -det H: the sign is canonical, and under it a point seen in front of both
 //   cameras has a positive third coordinate in both directions).
@@ -273,8 +274,9 @@ __global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict
   }
 }
 
-// ---- (2), (3) the MSAC score of every model against every point and the state step are pair_state_device.hpp's pair_score_kernel and
-// pair_update_kernel under HomographyGeom and TransferMsacTerm (homography_device.hpp)
+// ---- (2), (3) the score of every model against every point and the state step are pair_state_device.hpp's pair_score_kernel and
+// pair_update_kernel under HomographyGeom and a term of homography_device.hpp: TransferMsacTerm (dr_homography_score) or
+// TransferMagsacTerm (dr_homography_magsac_score: sum_n (1 - l(d2_n / thr2)), the same inlier test and slot rules)
 
 // ---- (4) normalised DLT over the rows a mask selects: one 256-thread block per pair, f64, fixed-order sums -----------------------------
 // Three passes of thread n over rows n, n + 256, ...: the count and the coordinate sums (the centroids), the distance sums (the
@@ -284,45 +286,60 @@ __global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict
 //   Sq = sum w (u^2 + v^2) X X^T:  24 sums instead of 45.  Sums by block_sum_f64: lane, wave butterfly, the four waves in order.
 // Wave 0 then takes the smallest eigenvector with jacobi_eig9_wave, denormalises and canonicalises; valid = 0 (identity) below four
 // rows and for a non-finite or singular result.
+// The passes are dlt_system, shared with the IRLS polish (5) and open to any kernel that refits over a selection: `sel` answers
+// "is row n present, with what weight" -- present(n), row(n), weight(n); the weight is asked for by the third pass only, of present rows.
 constexpr int kHRThreads = kPairThreads;
 
+// the LDS of one fit: s_part = [4][K] of the three sums in turn
+struct DltLds {
+  double s_part[(kHRThreads / 64) * 24], s_tot[24], gram[81], Vl[81], cs[18];
+};
+
+// the rows a mask selects (null: all of them), under per-row weights (null: 1)
 template <typename T>
-__global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
-                                                                      const T *__restrict__ weights, int N, T *__restrict__ model,
-                                                                      uint8_t *__restrict__ valid) {
-  __shared__ double s_part[(kHRThreads / 64) * 24], s_tot[24], gram[81], Vl[81], cs[18];      // s_part: [4][K] of the three sums in turn
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
-  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
-  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+struct MaskedRows4 {
+  const Match4<T> *pt;
+  const uint8_t *mk;
+  const T *wt;
+  __device__ __forceinline__ bool present(int n) const { return !(mk && !mk[n]); }
+  __device__ __forceinline__ Match4<T> row(int n) const { return pt[n]; }
+  __device__ __forceinline__ double weight(int n) const { return wt ? (double)wt[n] : 1.0; }
+};
+
+// -> the number of rows; nz1, nz2 = (cx, cy, s) of the two images, L.gram = the 9x9 Gram matrix of the normalised system (behind a
+// barrier).  Every thread of the block calls it and returns the same values.
+template <typename T, typename Rows>
+__device__ __forceinline__ double dlt_system(const Rows &sel, int N, DltLds &L, double (&nz1)[3], double (&nz2)[3]) {
+  const int tid = threadIdx.x;
   double a[5] = {0, 0, 0, 0, 0};
   for (int n = tid; n < N; n += kHRThreads) {
-    if (mk && !mk[n]) continue;
-    const Match4<T> x = pt[n];
+    if (!sel.present(n)) continue;
+    const Match4<T> x = sel.row(n);
 #pragma unroll
     for (int d = 0; d < 4; ++d) a[d] += (double)x.v[d];
     a[4] += 1.0;
   }
-  block_sum_f64<5>(a, reinterpret_cast<double(*)[5]>(s_part));
+  block_sum_f64<5>(a, reinterpret_cast<double(*)[5]>(L.s_part));
   const double rows = a[4], rn = 1.0 / rows;
   const double mu[4] = {a[0] * rn, a[1] * rn, a[2] * rn, a[3] * rn};
   double dd[2] = {0, 0};
   for (int n = tid; n < N; n += kHRThreads) {
-    if (mk && !mk[n]) continue;
-    const Match4<T> x = pt[n];
+    if (!sel.present(n)) continue;
+    const Match4<T> x = sel.row(n);
     const double q0 = (double)x.v[0] - mu[0], q1 = (double)x.v[1] - mu[1], q2 = (double)x.v[2] - mu[2], q3 = (double)x.v[3] - mu[3];
     dd[0] += sqrt(q0 * q0 + q1 * q1);
     dd[1] += sqrt(q2 * q2 + q3 * q3);
   }
-  block_sum_f64<2>(dd, reinterpret_cast<double(*)[2]>(s_part));
-  const double nz1[3] = {mu[0], mu[1], M_SQRT2 * rows / dd[0]}, nz2[3] = {mu[2], mu[3], M_SQRT2 * rows / dd[1]};
+  block_sum_f64<2>(dd, reinterpret_cast<double(*)[2]>(L.s_part));
+  nz1[0] = mu[0], nz1[1] = mu[1], nz1[2] = M_SQRT2 * rows / dd[0];
+  nz2[0] = mu[2], nz2[1] = mu[3], nz2[2] = M_SQRT2 * rows / dd[1];
   double g[24];
 #pragma unroll
   for (int q = 0; q < 24; ++q) g[q] = 0.0;
   for (int n = tid; n < N; n += kHRThreads) {
-    if (mk && !mk[n]) continue;
-    const Match4<T> m = pt[n];
-    const double w = wt ? (double)wt[n] : 1.0;
+    if (!sel.present(n)) continue;
+    const Match4<T> m = sel.row(n);
+    const double w = sel.weight(n);
     const double x = ((double)m.v[0] - nz1[0]) * nz1[2], y = ((double)m.v[1] - nz1[1]) * nz1[2];
     const double u = ((double)m.v[2] - nz2[0]) * nz2[2], v = ((double)m.v[3] - nz2[1]) * nz2[2];
     const double xx[6] = {w * x * x, w * x * y, w * x, w * y * y, w * y, w};
@@ -335,29 +352,170 @@ __global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *_
       g[18 + e] += q2 * xx[e];
     }
   }
-  block_partials_f64<24>(g, reinterpret_cast<double(*)[24]>(s_part));
-  if (tid < 24) s_tot[tid] = block_total_f64<24>(reinterpret_cast<double(*)[24]>(s_part), tid);      // (the Gram matrix picks its totals by
-  __syncthreads();                                                                                  // a run-time index: they stay in LDS)
+  block_partials_f64<24>(g, reinterpret_cast<double(*)[24]>(L.s_part));
+  if (tid < 24) L.s_tot[tid] = block_total_f64<24>(reinterpret_cast<double(*)[24]>(L.s_part), tid);      // (the Gram matrix picks its totals by
+  __syncthreads();                                                                                      // a run-time index: they stay in LDS)
   if (tid < 81) {
     const int r = tid / 9, c = tid - 9 * r, br = r / 3, bc = c / 3, i = r - 3 * br, j = c - 3 * bc;
     const int lo = min(i, j), hi = max(i, j), e = lo == 0 ? hi : (lo == 1 ? 2 + hi : 5);      // (i, j) -> entry of the symmetric 3x3
     const int bl = min(br, bc), bh = max(br, bc);
     double v = 0.0;
-    if (bl == bh) v = bl == 2 ? s_tot[18 + e] : s_tot[e];
-    else if (bh == 2) v = bl == 0 ? -s_tot[6 + e] : -s_tot[12 + e];
-    gram[tid] = v;
+    if (bl == bh) v = bl == 2 ? L.s_tot[18 + e] : L.s_tot[e];
+    else if (bh == 2) v = bl == 0 ? -L.s_tot[6 + e] : -L.s_tot[12 + e];
+    L.gram[tid] = v;
   }
   __syncthreads();
-  if (tid >= 64) return;
-  jacobi_eig9_wave(gram, Vl, cs, tid);
+  return rows;
+}
+
+// wave 0 behind dlt_system: the smallest eigenvector, denormalised and canonical -> valid (H = identity when not)
+__device__ __forceinline__ bool dlt_solve_wave(DltLds &L, int lane, const double (&nz1)[3], const double (&nz2)[3], double rows,
+                                               double (&H)[9]) {
+  jacobi_eig9_wave(L.gram, L.Vl, L.cs, lane);
   double ev[1][9];
-  smallest_eigvecs9_lds<1>(gram, Vl, ev);
-  double H[9], nrm, sigma;
+  smallest_eigvecs9_lds<1>(L.gram, L.Vl, ev);
+  double nrm, sigma;
   denormalise_h(ev[0], nz1, nz2, H);
-  const bool ok = canonical_h(H, rows >= 4.0, nrm, sigma);
+  return canonical_h(H, rows >= 4.0, nrm, sigma);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                                      const T *__restrict__ weights, int N, T *__restrict__ model,
+                                                                      uint8_t *__restrict__ valid) {
+  __shared__ DltLds L;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MaskedRows4<T> sel{reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N, mask ? mask + (size_t)p * N : nullptr,
+                           weights ? weights + (size_t)p * N : nullptr};
+  double nz1[3], nz2[3];
+  const double rows = dlt_system<T>(sel, N, L, nz1, nz2);
+  if (tid >= 64) return;
+  double H[9];
+  const bool ok = dlt_solve_wave(L, tid, nz1, nz2, rows, H);
   if (tid == 0) {
     store_h(model + (size_t)p * 9, H);
     valid[p] = ok;
+  }
+}
+
+// ---- (5) IRLS polish of the pair state under the MAGSAC++ loss (BatchedHomography(scoring = "magsac")): one 256-thread block per pair ----
+// registration_irls_kernel's sibling.  Up to `iters` times from the pair's (best_model, best_score): the rows of a step
+// are the points inside the cutoff and in front of both cameras under the current model, each with the weight w(s_n) of
+// TransferMagsacTerm; the normalised DLT of (4) over those rows (dlt_system: Hartley's transforms unweighted over the rows, the weight in
+// the Gram sums), wave 0's eigenvector, the candidate rounded to T; its MAGSAC++ score over all points in T (transfer_d2<T> and the
+// scoring kernel's term, so it compares with a best_score that kernel produced); taken only on a STRICTLY higher score.  The loop ends
+// before a fit with fewer than four rows (on the count dlt_system returns, so its other two passes have run by then, over transforms that
+// are inf / NaN without rows -- nothing of them is used or stored), on an invalid or non-finite candidate, on a candidate that does not
+// win, and at the limit.  irls_fits[p] += fits run.  best_mask, best_inliers, iters and max_iters are neither read nor written: the mask
+// stays the RANSAC winner's.
+// The row decision and the weights are evaluated in f64 for either type (the model and the rows widened, thr2 as stored): the refit's
+// sums are f64 already, and f32 weights move a fitted model by more than its output rounding.  They are not stored: the
+// three passes evaluate the same expression on the same values.
+// Mapping: a latency kernel, the steps of a pair are serial, each one four block-stride passes over 16 N bytes that stay in L2.
+// Wave 0 broadcasts the candidate through LDS; every exit is block-uniform; sums go lane, wave butterfly, the four waves in order: no
+// atomics, no read-back, a repeated launch gives the same bits.
+template <typename T>
+struct CutoffRows4 {
+  const Match4<T> *pt;
+  const ScoredH<double> &s;
+  const TransferMagsacTerm<double> &term;
+  __device__ __forceinline__ bool d2(int n, double &out) const {
+    const Match4<T> x = pt[n];
+    const double xd[4] = {(double)x.v[0], (double)x.v[1], (double)x.v[2], (double)x.v[3]};
+    return transfer_d2<double>(s, xd, out);
+  }
+  __device__ __forceinline__ bool present(int n) const {
+    double v;
+    return d2(n, v) && term.inlier(v);
+  }
+  __device__ __forceinline__ Match4<T> row(int n) const { return pt[n]; }
+  __device__ __forceinline__ double weight(int n) const {      // (of a present row: the same expression on the same values)
+    double v;
+    d2(n, v);
+    return term.weight(v);
+  }
+};
+
+// the score of a prepared model over all N points of a pair by the whole block; every thread returns it.  Order: a thread's points in
+// order, the wave butterfly, the four waves in order.  s_part: shared, 4 entries, free again on return.
+template <typename T, typename Term>
+__device__ __forceinline__ T block_score_h(const Match4<T> *__restrict__ pt, int N, const ScoredH<T> &s, const Term &term, T *s_part) {
+  T acc = T(0);
+  for (int n = threadIdx.x; n < N; n += kHRThreads) {
+    const Match4<T> x = pt[n];
+    T d2;
+    const bool live = transfer_d2<T>(s, x.v, d2);
+    acc += term.contrib(d2, live);
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  T sc = s_part[0];
+#pragma unroll
+  for (int w = 1; w < kHRThreads / 64; ++w) sc += s_part[w];
+  __syncthreads();
+  return sc;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kHRThreads) void homography_irls_kernel(const T *__restrict__ matches, const T *__restrict__ thr2, int N,
+                                                                     int iters, T *__restrict__ best_score, T *__restrict__ best_model,
+                                                                     int32_t *__restrict__ irls_fits) {
+  __shared__ DltLds L;
+  __shared__ T s_part[kHRThreads / 64], s_cand[9];
+  __shared__ int s_ok;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
+  T bs = best_score[p];
+  T bm[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) bm[q] = best_model[(size_t)p * 9 + q];
+  __syncthreads();      // (every thread has read the state: thread 0 writes it below)
+  const TransferMagsacTerm<T> term(thr2[p]);
+  const TransferMagsacTerm<double> termd((double)thr2[p]);
+  bool taken = false;
+  int fits = 0;
+  for (int it = 0; it < iters; ++it) {
+    double bd[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) bd[q] = (double)bm[q];
+    ScoredH<double> cur;
+    prepare_h(bd, true, cur);
+    if (cur.kind != kModelScored) break;      // (block-uniform, like every exit below: a NaN or singular state has no rows)
+    const CutoffRows4<T> sel{pt, cur, termd};
+    double nz1[3], nz2[3];
+    const double rows = dlt_system<T>(sel, N, L, nz1, nz2);
+    if (!(rows >= 4.0)) break;
+    if (tid < 64) {
+      double H[9];
+      const bool ok = dlt_solve_wave(L, tid, nz1, nz2, rows, H);
+      if (tid == 0) {
+        store_h(s_cand, H);
+        s_ok = ok;
+      }
+    }
+    __syncthreads();
+    ++fits;
+    T cm[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) cm[q] = s_cand[q];
+    ScoredH<T> cs;
+    prepare_h(cm, true, cs);
+    if (!s_ok || cs.kind != kModelScored) break;      // (s_cand / s_ok are next written behind dlt_system's barriers)
+    const T sc = block_score_h(pt, N, cs, term, s_part);
+    if (!(sc > bs)) break;
+    bs = sc;
+    taken = true;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) bm[q] = cm[q];
+  }
+  if (tid == 0) {
+    if (taken) {
+      best_score[p] = bs;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) best_model[(size_t)p * 9 + q] = bm[q];
+    }
+    irls_fits[p] += fits;
   }
 }
 
@@ -395,6 +553,21 @@ DR_F32_F64(DR_OP)
     DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
     return dr::launch_pair_score<T, dr::HomographyGeom, dr::TransferMsacTerm<T>>(matches, models, valid, thr2, P, M, N, scores,     \
                                                                                  inliers, nullptr, nullptr, stream);                \
+  }                                                                                                                                 \
+  int dr_homography_magsac_score_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, \
+                                       T *scores, int32_t *inliers, void *stream) {                                                 \
+    DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                                                \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    return dr::launch_pair_score<T, dr::HomographyGeom, dr::TransferMagsacTerm<T>>(matches, models, valid, thr2, P, M, N, scores,   \
+                                                                                   inliers, nullptr, nullptr, stream);              \
+  }                                                                                                                                 \
+  int dr_homography_irls_##sfx(const T *matches, const T *thr2, int P, int N, int irls_iters, T *best_score, T *best_model,         \
+                               int32_t *irls_fits, void *stream) {                                                                  \
+    DR_REQUIRE(matches && thr2 && best_score && best_model && irls_fits, "null pointer");                                           \
+    DR_REQUIRE(P > 0 && N > 0, "bad sizes");                                                                                        \
+    DR_REQUIRE(irls_iters >= 1, "irls_iters must be at least 1");                                                                   \
+    return dr::launch("homography_irls_kernel", dr::homography_irls_kernel<T>, dim3(P), dr::kHRThreads, stream, matches, thr2, N,   \
+                      irls_iters, best_score, best_model, irls_fits);                                                               \
   }                                                                                                                                 \
   int dr_homography_update_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P,    \
                                  int M, int N, int B, double confidence, double eps, int max_iterations, T *best_score,             \

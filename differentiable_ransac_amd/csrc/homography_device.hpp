@@ -3,10 +3,12 @@
 //   transfer_d2             the symmetric transfer error of one point -- ONE text for the score kernel, the state step's mask and its
 //                           count, every product an explicit fma, so that -ffp-contract has nothing to decide and the three round alike
 //   TransferMsacTerm        the MSAC term on it
+//   TransferMagsacTerm      the MAGSAC++ term on it: the 4-DoF closed forms of magsac_device.hpp behind the MSAC term's cutoff
 //   HomographyGeom          the family's policy for pair_state_device.hpp's score kernel and state step
 //   canonical_h             unit Frobenius norm, det > 0; false for a non-finite or singular matrix (solver and refit)
 //   denormalise_h           T2^-1 M T1 for the two similarity normalisations (solver and refit)
 #pragma once
+#include "magsac_device.hpp"
 #include "ransac_device.hpp"
 
 namespace dr {
@@ -77,6 +79,23 @@ struct TransferMsacTerm {
     const T sv = fma(-d2, inv, T(1));
     return (live && inlier(d2) && sv > T(0)) ? sv : T(0);
   }
+};
+
+// MAGSAC++ on it: the symmetric transfer error is a 4-vector residual, so the weight and the loss are magsac_device.hpp's
+// 4-degrees-of-freedom closed forms (Magsac4Term::gain, ::weight) as they stand.  thr2 = threshold^2 is read as (k sigma_max)^2,
+// k^2 = chi2.ppf(0.99, 4); s = d2 / thr2.  inlier(d2) is the MSAC term's test, so masks, counts and the adaptive stop are the same
+// under either score.  contrib = 1 - l(s), never below 0 (l(1) = 1: at the cutoff the closed form ends within its rounding of 0, and
+// d2 < thr2 can meet d2 * inv >= 1 by one rounding of inv); weight = w(s) >= 0, 0 outside the cutoff.
+template <typename T>
+struct TransferMagsacTerm {
+  T t2, inv;
+  __device__ __forceinline__ explicit TransferMagsacTerm(T thr2) : t2(thr2), inv(T(1) / thr2) {}
+  __device__ __forceinline__ bool inlier(T d2) const { return d2 < t2; }
+  __device__ __forceinline__ T contrib(T d2, bool live = true) const {
+    const T g = Magsac4Term<T>::gain(d2 * inv);
+    return (live && inlier(d2) && g > T(0)) ? g : T(0);
+  }
+  __device__ __forceinline__ T weight(T d2) const { return inlier(d2) ? Magsac4Term<T>::weight(d2 * inv) : T(0); }
 };
 
 template <typename T>

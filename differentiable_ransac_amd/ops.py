@@ -1277,6 +1277,18 @@ def homography_score(matches: torch.Tensor, models: torch.Tensor, threshold, val
     return _pair_score("homography_score", matches, models, threshold, valid, want_inliers, thr2)
 
 
+def homography_magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
+                            want_inliers: bool = True, thr2: Optional[torch.Tensor] = None):
+    """dr_homography_magsac_score: homography_score's arguments, slot rules and inlier counts with the MAGSAC++ score.  `threshold` is
+    the cutoff DISTANCE, read as k sigma_max (k^2 = 13.276704135987622, the 0.99 quantile of chi^2 with 4 degrees of freedom: the
+    symmetric transfer error is a 4-vector).  With s = d2 / threshold^2: scores [P,M] = sum_n (1 - l(s_n)), l the two-view MAGSAC++ loss
+    (magsac_score states it; 1 for s >= 1); inliers = #{d2_n < threshold^2}.  Bit-repeatable."""
+    _check_matches4("homography_magsac_score", matches)
+    if models.shape != (matches.shape[0], models.shape[1], 3, 3) or models.dtype != matches.dtype:
+        raise L.DransacError("homography_magsac_score: models [P,M,3,3] of the matches' dtype")
+    return _pair_score("homography_magsac_score", matches, models, threshold, valid, want_inliers, thr2)
+
+
 class HomographyState(_PairState):
     """Per-pair state of a BatchedHomography call, on the device: best_score [P] (0), best_model [P,3,3] (identity), best_mask [P,N],
     best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch."""
@@ -1300,6 +1312,23 @@ def refit_homography(matches: torch.Tensor, mask: Optional[torch.Tensor] = None,
     singular result."""
     _check_matches4("refit_homography", matches)
     return _pair_refit("refit_homography", 3, matches, mask, weights)
+
+
+def homography_irls(state: HomographyState, matches, thr2, irls_iters: int, irls_fits: torch.Tensor) -> None:
+    """dr_homography_irls: the IRLS polish under the MAGSAC++ loss, in place on state.best_model / state.best_score: up to irls_iters
+    times the rows inside the cutoff and in front of both cameras under the current model, each with the two-view MAGSAC++ weight
+    w(d2 / thr2) (f64), refit_homography's weighted DLT over them and the candidate's homography_magsac_score score over all points,
+    taken only where it is strictly higher.  thr2 [P] = threshold^2 (thr2_tensor); irls_fits [P] int32 grows by the fits run.  Mask,
+    inlier count and counters of the state are left alone.  One launch, no synchronisation."""
+    tensors = (matches, thr2, irls_fits, state.best_score, state.best_model)
+    if any(t is None or not t.is_cuda for t in tensors):
+        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    _check_matches4("homography_irls", matches)
+    P, N, _ = matches.shape
+    if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
+        raise L.DransacError("homography_irls: irls_fits must be [P] int32")
+    L.call(f"dr_homography_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(irls_iters),
+           ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
 
 
 class _Homography4(torch.autograd.Function):

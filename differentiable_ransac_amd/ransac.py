@@ -1269,6 +1269,14 @@ class BatchedHomography(_PairStateDriver):
     `threshold` is a DISTANCE in the matches' units: a point is an inlier iff d2 < threshold^2, d2 = |x2 - H x1|^2 + |x1 - H^-1 x2|^2
     after the perspective divisions; a point that H or H^-1 sends behind the camera is an outlier.
 
+    scoring = "magsac" (test mode only): every round is scored by dr_homography_magsac_score, the MAGSAC++ loss with `threshold` as
+    the cutoff distance k sigma_max (the transfer error is a 4-vector: k^2 = chi2.ppf(0.99, 4); ops.homography_magsac_score states the
+    formulas) -- the score for a caller who cannot choose a tight pixel threshold in advance.  Mask, inlier count and the adaptive stop
+    keep using d2 < threshold^2.  With `refit` and irls_iters > 0 the final stage is dr_homography_irls in the single refit's place: up
+    to `irls_iters` re-weighted DLT fits over the points inside the cutoff, each kept only where it scores strictly higher; the mask
+    stays the RANSAC winner's.  The result gains irls_fits [P].  Combines with sampling = "prosac".  scoring = "msac" is the path
+    without it: no other launch, allocation or key.
+
     sampling = "prosac" (test mode only): ops.prosac_sample in ops.gumbel_topk's place, round r being PROSAC draws r B + 1 .. (r + 1) B
     of every pair, as in BatchedRegistration.  Refused with train = True and with explicit `gumbels`.
 
@@ -1276,13 +1284,21 @@ class BatchedHomography(_PairStateDriver):
     dict(models [P, rounds * B, 3, 3], keep [P, rounds * B] = the sample's validity) with autograd to the logits, and to `matches`
     where they require it.  `refit` and `confidence` play no part and nothing is read back.
 
-    Not here: local optimisation, MAGSAC++ scoring, device_termination, super-rounds, samples of more than 4 points."""
+    Not here: local optimisation, device_termination, super-rounds, samples of more than 4 points."""
 
     k = 4
 
     def __init__(self, ransac_batch_size=1024, threshold=3.0, confidence=0.999, max_iterations=5000, tau=1.0, seed=0, refit=True,
-                 eps=1e-5, train=False, sampling="gumbel", prosac_draws=200000):
+                 eps=1e-5, train=False, sampling="gumbel", prosac_draws=200000, scoring="msac", irls_iters=10):
         super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws)
+        if scoring not in ("msac", "magsac"):
+            raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
+        if isinstance(irls_iters, bool) or not isinstance(irls_iters, int) or irls_iters < 0:
+            raise ValueError(f"irls_iters must be an int of at least 0, got {irls_iters!r}")
+        if scoring == "magsac" and train:
+            raise ValueError("scoring='magsac' with train=True is refused: train mode scores nothing")
+        self.scoring = scoring
+        self.irls_iters = irls_iters
 
     _columns, _shape_error = 4, "matches must be [P,N,4] = (x1, y1, x2, y2)"
     _State = ops.HomographyState
@@ -1298,4 +1314,15 @@ class BatchedHomography(_PairStateDriver):
         return ops.homography4_gather(c.matches, idx)
 
     def _score(self, c, r, models, valid):
-        return ops.homography_score(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
+        score_fn = ops.homography_magsac_score if self.scoring == "magsac" else ops.homography_score
+        return score_fn(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
+
+    def _finish(self, c):
+        if self.scoring != "magsac":
+            return super()._finish(c)
+        # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
+        irls_fits = torch.zeros(c.P, device=c.matches.device, dtype=torch.int32)
+        if self.refit and self.irls_iters > 0:
+            ops.homography_irls(c.st, c.matches, c.thr2, self.irls_iters, irls_fits)
+        return dict(model=c.st.best_model, mask=c.st.best_mask, score=c.st.best_score, inliers=c.st.best_inliers,
+                    iterations=c.st.iters, irls_fits=irls_fits)

@@ -503,6 +503,17 @@ int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const dou
  *     row's terms in the Gram matrix -> model [P,9], valid [P].  Hartley's transforms come from the selected rows, unweighted; the 9x9
  *     Gram matrix of the two DLT rows per point is summed in f64 in one fixed order; its smallest eigenvector (Jacobi) is denormalised,
  *     scaled to unit norm and given det > 0.  valid = 0, model = identity: fewer than four rows, a non-finite or singular result.
+ *   dr_homography_magsac_score   dr_homography_score's arguments, slot rules and inlier counts with the MAGSAC++ score in the MSAC
+ *     score's place: the transfer error is a 4-vector, so thr2 is read as (k sigma_max)^2 with k^2 = chi2.ppf(0.99, 4), and with
+ *     s = d2 / thr2 a point with d2 < thr2 adds 1 - l(s), l the two-view loss stated at dr_magsac_score.  Bit-repeatable.
+ *   dr_homography_irls      the IRLS polish of the pair state under that loss (BatchedHomography(scoring = "magsac")), one launch, one
+ *     block per pair.  Up to irls_iters (>= 1) times from (best_model [P,9], best_score [P]): the rows = the points with d2 < thr2 in
+ *     front of both cameras under the current model, each with the weight w(s) stated at dr_magsac_irls (row decision and weight in
+ *     f64 for either type); dr_refit_homography's fit over those rows under those weights; the candidate rounded to the type; its
+ *     dr_homography_magsac_score score over all points; taken only on a strictly higher score.  Ends before a fit with fewer than four
+ *     rows, on an invalid or non-finite candidate, on a candidate that does not win, at the limit.  irls_fits [P] int32 += fits run.
+ *     Mask, inlier count, iters and max_iters of the state are neither read nor written.  No atomics: a repeated launch gives the
+ *     same bits.
  * ------------------------------------------------------------------------------------------ */
 int dr_homography4_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, float *models, uint8_t *valid,
                               void *stream);
@@ -528,6 +539,14 @@ int dr_refit_homography_f32(const float *matches, const uint8_t *mask, const flo
                             uint8_t *valid, void *stream);
 int dr_refit_homography_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model,
                             uint8_t *valid, void *stream);
+int dr_homography_magsac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M,
+                                   int N, float *scores, int32_t *inliers, void *stream);
+int dr_homography_magsac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
+                                   int N, double *scores, int32_t *inliers, void *stream);
+int dr_homography_irls_f32(const float *matches, const float *thr2, int P, int N, int irls_iters, float *best_score,
+                           float *best_model, int32_t *irls_fits, void *stream);
+int dr_homography_irls_f64(const double *matches, const double *thr2, int P, int N, int irls_iters, double *best_score,
+                           double *best_model, int32_t *irls_fits, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The training loss of the registration path (loss.RegistrationLoss).  Not a restatement of upstream code: RANSACLayer3D's own loss
