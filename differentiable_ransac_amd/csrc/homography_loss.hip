@@ -1,0 +1,226 @@
+// The training loss of the homography path (loss.HomographyLoss): the truncated symmetric transfer error of EVERY returned model on
+// the ground-truth inlier points, value and gradient in one pass over the (model x point) grid -- what registration_loss.hip is for
+// the 3-D path.  include/dransac.h states the maths:
+//     h = sign(det H) H, a = adj(H), y = h (x1, 1), z = a (x2, 1), e = x2 - y_xy / y_w, f = x1 - z_xy / z_w, d2 = |e|^2 + |f|^2
+//     live = y_w > 0 and z_w > 0 and d2 < thr2,   term = live ? d2 / thr2 : 1,   sums[m] = sum_{n in mask} term[m,n]
+// Mapping (registration_loss_kernel's): one LANE per model (9 + 9 model registers, 1 + 1 + 18 accumulators), one wave per block, grid
+// (ceil(M / 64), P).  The wave compacts the pair's masked points tile by tile into LDS, in ascending order, and every lane walks the
+// tile reading each point as an LDS broadcast: no cross-lane reduction, no atomics, and the order of every sum is the order of the
+// points -- a repeated launch repeats bit for bit.  The grid is arithmetic-bound (~70 vector instructions per model x masked point
+// with the gradient); a tile's staging is ~1 % of its arithmetic, so the tile is sized by the LDS it may take, not by the staging.
+//
+// Gradient.  With t = y_xy / y_w:  d d2 / d y = (2 / y_w) (-e_0, -e_1, e . t), and d d2 / d h = that (x) (x1, 1); the same for z, a and
+// x2.  The two outer products are accumulated separately (gh, ga: nine sums each).  adj is quadratic in H, so the transpose of its
+// Jacobian is linear in H and is applied ONCE per model after the point loop (adjugate3_vjp); the sign of the determinant and
+// 2 / thr2 come last: grad = sign (2 / thr2) (gh + J_adj(h)^T ga).
+//
+// The reciprocal.  transfer_d2 takes v_rcp_f32 as it comes (1 ulp), which is fine for a score: there the reciprocal's error is one
+// more rounding of d2.  Here the gradient is a sum of e / y_w terms in which e = x2 - y_xy / y_w cancels from |x2| ~ 10^2..10^3 pixels
+// down to the threshold's few pixels, so an ulp of the reciprocal is ~|x2| / |e| ulps of the term, as much as the three fma of the
+// linear form together.  One Newton step r <- r + r (1 - w r) (two fma out of ~70 instructions) brings the f32 reciprocal within
+// half an ulp and a bit, and the kernel's error to that of the linear forms alone; f64 divides.  d2 is then not transfer_d2's value
+// to the last bit, only to the reciprocal's ulp: `live` agrees with HomographyGeom::inlier wherever d2 / thr2 is farther from 1, and
+// y_w, z_w farther from 0, than the rounding of either evaluation, which is the guarantee the two paths can give each other (the
+// signs of y_w and z_w, computed by the same fma in the same order, agree always).  The ground-truth mask (homography_gt_mask_kernel)
+// IS HomographyGeom::inlier: bit for bit the mask dr_homography_update writes for the same model.
+#include "homography_device.hpp"
+#include "loss_reduce_device.hpp"
+
+namespace dr {
+
+// points staged per tile: 4 KB of LDS in f32, 8 KB in f64.  One wave per block and ~2.5 blocks per SIMD at a train step's shape: the
+// LDS of a tile never limits the occupancy (160 KB per CU), and 256 keeps the staging (four loads per lane and tile) at ~1 %
+constexpr int kHLTile = 256;
+
+__device__ __forceinline__ float refined_rcp(float w) {
+  const float r = __builtin_amdgcn_rcpf(w);
+  return fma(r, fma(-w, r, 1.0f), r);      // (w = 0 or inf gives NaN here: the caller's `live` is false for those)
+}
+__device__ __forceinline__ double refined_rcp(double w) { return 1.0 / w; }
+
+// out = J^T g for a = adj(h): out[q] = sum_k g[k] d a[k] / d h[q], term by term from adjugate3
+template <typename T>
+__device__ __forceinline__ void adjugate3_vjp(const T (&h)[9], const T (&g)[9], T (&out)[9]) {
+  out[0] = fma(g[4], h[8], fma(-g[5], h[5], fma(-g[7], h[7], g[8] * h[4])));
+  out[1] = fma(-g[1], h[8], fma(g[2], h[5], fma(g[7], h[6], -(g[8] * h[3]))));
+  out[2] = fma(g[1], h[7], fma(-g[2], h[4], fma(-g[4], h[6], g[5] * h[3])));
+  out[3] = fma(-g[3], h[8], fma(g[5], h[2], fma(g[6], h[7], -(g[8] * h[1]))));
+  out[4] = fma(g[0], h[8], fma(-g[2], h[2], fma(-g[6], h[6], g[8] * h[0])));
+  out[5] = fma(-g[0], h[7], fma(g[2], h[1], fma(g[3], h[6], -(g[5] * h[0]))));
+  out[6] = fma(g[3], h[5], fma(-g[4], h[2], fma(-g[6], h[4], g[7] * h[1])));
+  out[7] = fma(-g[0], h[5], fma(g[1], h[2], fma(g[6], h[3], -(g[7] * h[0]))));
+  out[8] = fma(g[0], h[4], fma(-g[1], h[1], fma(-g[3], h[3], g[4] * h[0])));
+}
+
+template <typename T, bool kGrad>
+__global__ __launch_bounds__(64) void homography_loss_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                             const T *__restrict__ models, const uint8_t *__restrict__ keep,
+                                                             const T *__restrict__ thr2, int M, int N, T *__restrict__ sums,
+                                                             T *__restrict__ grad) {
+  __shared__ Match4<T> s_pt[kHLTile];
+  const int p = blockIdx.y, lane = threadIdx.x, m = blockIdx.x * 64 + lane;
+  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T t2 = thr2[p];
+  const bool thr_ok = t2 > T(0);                      // (false for NaN too: every point then takes the truncated branch)
+  // a slot that keep drops is SKIPPED (its model, possibly NaN, is never read); a kept model that prepare_h calls NaN-scoring (a
+  // non-finite entry, det == 0, a non-finite det) is "bad": every masked point counts 1 and nothing flows back
+  const bool kept = m < M && (!keep || keep[(size_t)p * M + m] != 0);
+  T raw[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) raw[q] = kept ? models[((size_t)p * M + m) * 9 + q] : T(0);
+  ScoredH<T> s;
+  prepare_h(raw, kept, s);
+  const bool scored = s.kind == kModelScored;
+  // prepare_h has turned h to det > 0; the gradient is turned back at the end (adj(-H) = adj(H): a needs no sign)
+  const bool neg = fma(raw[0], s.a[0], fma(raw[1], s.a[3], raw[2] * s.a[6])) < T(0);
+  if (!scored) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) s.h[q] = s.a[q] = T(0);      // y_w = z_w = 0: no point is live, nothing non-finite is accumulated
+  }
+
+  T acc = T(0), gh[9], ga[9];
+  int truncated = 0, n_mask = 0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) gh[q] = ga[q] = T(0);
+
+  for (int n0 = 0; n0 < N; n0 += kHLTile) {
+    // the tile's masked points, compacted in ascending order (ballot + prefix count: the wave is the block)
+    int count = 0;
+#pragma unroll
+    for (int j = 0; j < kHLTile / 64; ++j) {
+      const int n = n0 + j * 64 + lane;
+      const bool on = n < N && (!mk || mk[n] != 0);
+      const unsigned long long b = __ballot(on);
+      const int pos = count + __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
+      if (on) s_pt[pos] = pt[n];
+      count += __popcll(b);
+    }
+    __syncthreads();
+    n_mask += count;
+#pragma unroll 2
+    for (int i = 0; i < count; ++i) {
+      const Match4<T> xv = s_pt[i];
+      const T(&x)[4] = xv.v;
+      const T yx = fma(s.h[0], x[0], fma(s.h[1], x[1], s.h[2]));
+      const T yy = fma(s.h[3], x[0], fma(s.h[4], x[1], s.h[5]));
+      const T yw = fma(s.h[6], x[0], fma(s.h[7], x[1], s.h[8]));
+      const T zx = fma(s.a[0], x[2], fma(s.a[1], x[3], s.a[2]));
+      const T zy = fma(s.a[3], x[2], fma(s.a[4], x[3], s.a[5]));
+      const T zw = fma(s.a[6], x[2], fma(s.a[7], x[3], s.a[8]));
+      const T ry = refined_rcp(yw), rz = refined_rcp(zw);
+      const T e0 = fma(-yx, ry, x[2]), e1 = fma(-yy, ry, x[3]);
+      const T f0 = fma(-zx, rz, x[0]), f1 = fma(-zy, rz, x[1]);
+      const T d2 = fma(e0, e0, fma(e1, e1, fma(f0, f0, f1 * f1)));
+      const bool live = yw > T(0) && zw > T(0) && d2 < t2;      // strict; false for a NaN distance
+      acc += live ? d2 : T(0);
+      truncated += live ? 0 : 1;
+      if (kGrad) {
+        // (1 / y_w) (-e_0, -e_1, e . t) with t = y_xy / y_w, and the same for z; the 2 is applied with 1 / thr2 at the end
+        const T u0 = live ? -(e0 * ry) : T(0), u1 = live ? -(e1 * ry) : T(0);
+        const T u2 = live ? fma(e0, yx * ry, e1 * (yy * ry)) * ry : T(0);
+        const T v0 = live ? -(f0 * rz) : T(0), v1 = live ? -(f1 * rz) : T(0);
+        const T v2 = live ? fma(f0, zx * rz, f1 * (zy * rz)) * rz : T(0);
+        gh[0] = fma(u0, x[0], gh[0]), gh[1] = fma(u0, x[1], gh[1]), gh[2] += u0;
+        gh[3] = fma(u1, x[0], gh[3]), gh[4] = fma(u1, x[1], gh[4]), gh[5] += u1;
+        gh[6] = fma(u2, x[0], gh[6]), gh[7] = fma(u2, x[1], gh[7]), gh[8] += u2;
+        ga[0] = fma(v0, x[2], ga[0]), ga[1] = fma(v0, x[3], ga[1]), ga[2] += v0;
+        ga[3] = fma(v1, x[2], ga[3]), ga[4] = fma(v1, x[3], ga[4]), ga[5] += v1;
+        ga[6] = fma(v2, x[2], ga[6]), ga[7] = fma(v2, x[3], ga[7]), ga[8] += v2;
+      }
+    }
+    __syncthreads();
+  }
+
+  if (m >= M) return;
+  const size_t slot = (size_t)p * M + m;
+  const bool good = kept && scored && thr_ok;
+  const T inv = thr_ok ? T(1) / t2 : T(0);
+  sums[slot] = !kept ? T(0) : (good ? fma(acc, inv, (T)truncated) : (T)n_mask);
+  if (kGrad) {
+    T back[9];
+    adjugate3_vjp(s.h, ga, back);
+    const T sc = good ? (neg ? T(-2) : T(2)) * inv : T(0);
+    T *g = grad + slot * 9;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) g[q] = good ? sc * (gh[q] + back[q]) : T(0);
+  }
+}
+
+// mask[p,n] = HomographyGeom::inlier under the pair's ground-truth homography (the score kernels' and the state step's test), count[p]
+template <typename T>
+__global__ __launch_bounds__(256) void homography_gt_mask_kernel(const T *__restrict__ matches, const T *__restrict__ gt_H,
+                                                                const T *__restrict__ thr2, int N, uint8_t *__restrict__ mask,
+                                                                int32_t *__restrict__ count) {
+  __shared__ int s_cnt[4];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  ScoredH<T> s;
+  const bool scored = HomographyGeom::prepare(gt_H + (size_t)p * 9, s) == kModelScored;
+  const T t2 = thr2[p];
+  int c = 0;
+  for (int n = tid; n < N; n += 256) {
+    const Match4<T> x = reinterpret_cast<const Match4<T> *>(matches)[(size_t)p * N + n];
+    const bool on = scored && HomographyGeom::inlier(s, x.v, t2);
+    mask[(size_t)p * N + n] = on ? 1 : 0;
+    c += on ? 1 : 0;
+  }
+  c = wave_sum(c);
+  if ((tid & 63) == 0) s_cnt[tid >> 6] = c;
+  __syncthreads();
+  if (tid == 0) count[p] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
+
+// the loss value (and, kGrad, its unscaled gradient) per model, then the means
+template <typename T, bool kGrad>
+int homography_loss_launch(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2, int P, int M,
+                           int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) {
+  if (int rc = launch("homography_loss_kernel", homography_loss_kernel<T, kGrad>, dim3((M + 63) / 64, P), 64, stream, matches, mask,
+                      models, keep, thr2, M, N, sums, grad_unscaled))
+    return rc;
+  return launch("registration_loss_mean_kernel", registration_loss_mean_kernel<T>, dim3(1), kRLMeanT, stream, sums, mask, keep, P, M, N,
+                per_pair, coef, mean);
+}
+
+}  // namespace dr
+
+extern "C" {
+
+#define DR_HOMOGRAPHY_LOSS_SIZES \
+  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535 && (long)P * M < (1l << 22), "need P, M, N > 0, P <= 65535 and P M < 2^22")
+
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_homography_loss_fused_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,    \
+                                     int P, int M, int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean,                 \
+                                     void *stream) {                                                                                \
+    DR_REQUIRE(matches && models && thr2 && sums && grad_unscaled && per_pair && coef && mean, "null pointer");                     \
+    DR_HOMOGRAPHY_LOSS_SIZES;                                                                                                       \
+    return dr::homography_loss_launch<T, true>(matches, mask, models, keep, thr2, P, M, N, sums, grad_unscaled, per_pair, coef,     \
+                                               mean, stream);                                                                       \
+  }                                                                                                                                 \
+  int dr_homography_loss_fwd_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,      \
+                                   int P, int M, int N, T *sums, T *per_pair, T *coef, T *mean, void *stream) {                     \
+    DR_REQUIRE(matches && models && thr2 && sums && per_pair && coef && mean, "null pointer");                                      \
+    DR_HOMOGRAPHY_LOSS_SIZES;                                                                                                       \
+    return dr::homography_loss_launch<T, false>(matches, mask, models, keep, thr2, P, M, N, sums, (T *)nullptr, per_pair, coef,     \
+                                                mean, stream);                                                                      \
+  }                                                                                                                                 \
+  int dr_homography_loss_scale_##sfx(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,       \
+                                     void *stream) {                                                                                \
+    DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");                                                  \
+    DR_REQUIRE(P > 0 && M > 0 && (long)P * M < (1l << 22), "need P, M > 0 and P M < 2^22");                                         \
+    const size_t total = (size_t)P * M * 9;                                                                                         \
+    return dr::launch("registration_loss_scale_kernel", dr::registration_loss_scale_kernel<T>,                                      \
+                      dim3((unsigned)((total + 255) / 256)), 256, stream, grad_unscaled, coef, grad_mean, T(1) / (T)P,              \
+                      (size_t)M * 9, total, grad_models);                                                                           \
+  }                                                                                                                                 \
+  int dr_homography_gt_mask_##sfx(const T *matches, const T *gt_H, const T *thr2, int P, int N, uint8_t *mask, int32_t *count,      \
+                                  void *stream) {                                                                                   \
+    DR_REQUIRE(matches && gt_H && thr2 && mask && count, "null pointer");                                                           \
+    DR_REQUIRE(P > 0 && N > 0, "need P, N > 0");                                                                                    \
+    return dr::launch("homography_gt_mask_kernel", dr::homography_gt_mask_kernel<T>, dim3(P), 256, stream, matches, gt_H, thr2, N,  \
+                      mask, count);                                                                                                 \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
+}  // extern "C"

@@ -6,12 +6,12 @@
 // masked points tile by tile into LDS, in ascending order, and every lane walks the tile reading each point as an LDS broadcast: no
 // cross-lane reduction, no atomics, and the order of every sum is the order of the points -- a repeated launch repeats bit for bit.
 // The grid is arithmetic-bound (~38 vector instructions per model x masked point); a tile's staging is ~1 % of its arithmetic.
+#include "loss_reduce_device.hpp"
 #include "rigid_device.hpp"
 
 namespace dr {
 
 constexpr int kRLTile = 256;      // points staged per tile: 6 KB of LDS in f32, 12 KB in f64
-constexpr int kRLMeanT = 1024;
 
 template <typename T, bool kGrad>
 __global__ __launch_bounds__(64) void registration_loss_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
@@ -112,53 +112,6 @@ __global__ __launch_bounds__(64) void registration_loss_kernel(const T *__restri
     }
     g[12] = g[13] = g[14] = g[15] = T(0);
   }
-}
-
-// per_pair[p] = sum_m sums[p,m] / max(#kept_p #mask_p, 1), coef[p] = 1 / that denominator, mean = sum_p per_pair[p] / P: ONE block whose
-// sixteen waves take the pairs in turn; lane partials, wave butterfly, waves in order -- a fixed order.  It reads P (5 M + N) bytes
-// on one CU: microseconds at a train step's shape, hence the entries' bound P M < 2^22 (16 MB of sums)
-template <typename T>
-__global__ __launch_bounds__(kRLMeanT) void registration_loss_mean_kernel(const T *__restrict__ sums, const uint8_t *__restrict__ mask,
-                                                                         const uint8_t *__restrict__ keep, int P, int M, int N,
-                                                                         T *__restrict__ per_pair, T *__restrict__ coef,
-                                                                         T *__restrict__ mean) {
-  __shared__ T s_tot[kRLMeanT / 64];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  T wave_total = T(0);
-  for (int p = wv; p < P; p += kRLMeanT / 64) {
-    T acc = T(0);
-    int n_in = 0, n_kept = 0;
-    for (int m = lane; m < M; m += 64) {
-      acc += sums[(size_t)p * M + m];
-      if (keep) n_kept += keep[(size_t)p * M + m] != 0;
-    }
-    if (mask)
-      for (int n = lane; n < N; n += 64) n_in += mask[(size_t)p * N + n] != 0;
-    acc = wave_sum(acc);
-    n_in = mask ? wave_sum(n_in) : N;
-    n_kept = keep ? wave_sum(n_kept) : M;
-    const T den = fmax((T)n_in * (T)n_kept, T(1));
-    if (lane == 0) {
-      per_pair[p] = acc / den;
-      coef[p] = T(1) / den;
-    }
-    wave_total += acc / den;
-  }
-  if (lane == 0) s_tot[wv] = wave_total;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    T t = T(0);
-    for (int w = 0; w < kRLMeanT / 64; ++w) t += s_tot[w];
-    mean[0] = t / (T)P;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void registration_loss_scale_kernel(const T *__restrict__ grad_unscaled, const T *__restrict__ coef,
-                                                                     const T *__restrict__ grad_mean, T inv_pairs, size_t per_pair,
-                                                                     size_t total, T *__restrict__ grad_models) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < total) grad_models[i] = grad_unscaled[i] * (coef[i / per_pair] * grad_mean[0] * inv_pairs);
 }
 
 // mask[p,n] = |R p + t - q|^2 < thr2[p] under the ground-truth pose of the pair (rigid_d2: the score kernels' inlier test), count[p]

@@ -1,5 +1,6 @@
 """The training losses that follow the hot path: MatchLoss and PoseLoss for the two-view drivers,
-RegistrationLoss (at the end) for the 3-D registration driver.
+RegistrationLoss for the 3-D registration driver and HomographyLoss (at the end, with the evaluation metrics registration_errors and
+homography_errors) for the homography driver.
 
 MatchLoss -- the clamped symmetric-epipolar training loss of the reference (loss.py:107-153), on the fused kernel
 `dr_episym_fwd/bwd`.
@@ -151,3 +152,45 @@ def registration_errors(model, gt_pose):
         rre = torch.rad2deg(torch.acos(c.clamp(-1.0, 1.0)))
         rte = (model[..., :3, 3] - gt_pose[..., :3, 3]).norm(dim=-1)
         return rre, rte
+
+
+class HomographyLoss(object):
+    """The training loss of ransac.BatchedHomography(train=True): the truncated symmetric transfer error of every returned model on
+    the ground-truth inlier points, what RegistrationLoss is for rigid poses.  With y = H (x1, 1), z = adj(H) (x2, 1) under the
+    det > 0 sign and d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2 (the residual the score kernels use): per pair the mean over
+    (kept models x masked points) of (d2 / threshold^2 if the point lies in front of both cameras and d2 < threshold^2, else 1); then
+    the mean over the pairs.  The loss lies in [0, 1] and does not depend on the scale or the sign of a model; a hopeless hypothesis
+    contributes the constant 1 and no gradient.  Value and gradient come from one pass of `dr_homography_loss_fused`; nothing
+    synchronises, so a whole train step can be captured by graphs.GraphedStep."""
+
+    def __init__(self, threshold):
+        self.threshold = threshold          # inlier DISTANCE in pixels, float or [P] (BatchedHomography's convention)
+
+    def forward(self, models, matches, gt_H=None, gt_mask=None, keep=None):
+        """models [P,M,3,3] (or [P,3,3]: a test-mode result), matches [P,N,4], gt_mask [P,N] bool or gt_H [P,3,3] (the mask is then
+        the inliers of that homography at the threshold: ops.homography_gt_mask; neither = all points), keep [P,M] bool (models to
+        average over, e.g. the solver's validity; None = all) -> scalar loss, differentiable w.r.t. the models ONLY: `matches` that
+        require grad are refused (pass matches.detach(); the driver's own gradient to `matches` is unaffected)."""
+        if models.dim() == 3:
+            models = models[:, None]
+            keep = keep if keep is None or keep.dim() == 2 else keep[:, None]
+        if gt_mask is None and gt_H is not None:
+            with torch.no_grad():
+                gt_mask = ops.homography_gt_mask(matches, gt_H.to(matches.dtype), self.threshold)[0]
+        return ops.homography_loss_mean(matches, gt_mask, models, self.threshold, keep)
+
+    __call__ = forward
+
+
+def homography_errors(model, gt_H, size):
+    """model [...,3,3], gt_H broadcastable to it, size = (h, w) of the first image -> the mean corner error in pixels: the mean over the
+    corners (0, 0), (w, 0), (w, h), (0, h) of the distance between their images under the two homographies (the scale and the sign
+    of either matrix do not matter).  Plain torch under no_grad, for evaluation; the training signal is HomographyLoss."""
+    with torch.no_grad():
+        h, w = float(size[0]), float(size[1])
+        corners = torch.tensor([[0.0, 0.0, 1.0], [w, 0.0, 1.0], [w, h, 1.0], [0.0, h, 1.0]], dtype=model.dtype, device=model.device)
+
+        def images(H):
+            y = corners @ H.transpose(-1, -2)              # [...,4,3]
+            return y[..., :2] / y[..., 2:]
+        return (images(model) - images(gt_H.to(model.dtype))).norm(dim=-1).mean(-1)

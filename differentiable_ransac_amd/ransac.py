@@ -1282,7 +1282,8 @@ class BatchedHomography(_PairStateDriver):
 
     train = True: every round runs (no adaptive stop), each one ops.SampleGather followed by ops.homography4, and the call returns
     dict(models [P, rounds * B, 3, 3], keep [P, rounds * B] = the sample's validity) with autograd to the logits, and to `matches`
-    where they require it.  `refit` and `confidence` play no part and nothing is read back.
+    where they require it.  `refit` and `confidence` play no part and nothing is read back.  The loss on the returned models is
+    loss.HomographyLoss (pass `keep`).
 
     Not here: local optimisation, device_termination, super-rounds, samples of more than 4 points."""
 

@@ -593,7 +593,55 @@ int dr_registration_gt_mask_f64(const double *matches, const double *gt_pose, co
                                 int32_t *count, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * K5  train-mode best-of-S selection     RANSAC.__call__, ransac.py:87-96
+ * The training loss of the homography path (loss.HomographyLoss): the registration loss above on the symmetric transfer error.
+ * matches [P,N,4], models [P,M,9] (ANY scale and either sign: d2 does not change under a positive scaling of H, and the det > 0
+ * sign is applied here), thr2 [P] as for dr_homography_score; mask [P,N] (the ground-truth inliers; NULL = all points), keep [P,M]
+ * (NULL = all models).  With h = sign(det H) H, a = adj(H), y = h (x1, 1), z = a (x2, 1), e = x2 - y_xy / y_w, f = x1 - z_xy / z_w:
+ *     d2[p,m,n]   = |e|^2 + |f|^2,   live = y_w > 0 and z_w > 0 and d2 < thr2[p]   (strict; false for a NaN),   term = live ? d2 / thr2[p] : 1
+ *     sums[p,m]   = sum_{n in mask} term[p,m,n]
+ *     per_pair[p] = sum_{m kept} sums[p,m] / max(#kept_p #mask_p, 1),   coef[p] = 1 / max(#kept_p #mask_p, 1),   mean = sum_p per_pair / P
+ *     d sums / d h = (2 / thr2) sum (1 / y_w) (-e_0, -e_1, e . y_xy / y_w) (x1, 1)^T,   d sums / d a = the same with f, z, x2, over the live
+ *     points;   d sums / d H = sign(det H) (d sums / d h + J^T d sums / d a),  J = d adj(h) / d h (linear in h: applied once per model)
+ * so <d sums / d H, H> = 0 up to rounding.  A point behind either camera, at or beyond the threshold or with a NaN distance counts 1
+ * and passes no gradient.  A slot keep drops is skipped (sums 0, gradient 0, its model is not read: it may be NaN); a kept model with
+ * a non-finite entry, det == 0 or a non-finite determinant (dr_homography_score's NaN-scoring slots) has sums = #mask_p and a zero
+ * gradient; a pair with an empty mask or no kept model has per_pair 0 and zero gradients; a thr2[p] that is not > 0 (NaN included)
+ * leaves no point below it.  Every output element is written; no floating-point atomics and one fixed order for every sum
+ * (ascending points per model, lanes then waves in the reduction), so a repeated launch gives the same bits, and H and -H give the
+ * same sums and negated gradients bit for bit.  Sums are accumulated in the type of the inputs, sums[p,m] as (sum of the live d2) x
+ * (1 / thr2) + (number of masked points that are not live).  The f32 reciprocals of y_w and z_w are v_rcp_f32 with one Newton step
+ * (the gradient is a sum of e / y_w terms), so d2 is dr_homography_score's up to the reciprocal's ulp and `live` is its inlier test
+ * wherever the two roundings cannot decide otherwise.  P <= 65535 and P M < 2^22 (the per-pair / mean reduction is one block).
+ *
+ *   dr_homography_loss_fused   sums [P,M], grad_unscaled [P,M,9] = d sums[p,m] / d H, per_pair [P], coef [P], mean [1]: value and
+ *     gradient from one pass over the (model x point) grid (two launches: the grid, then the per-pair / mean reduction).
+ *   dr_homography_loss_scale   grad_models = grad_unscaled x coef[p] x grad_mean[0] / P: the whole backward of the mean.
+ *   dr_homography_loss_fwd     the value only (sums, per_pair, coef, mean), the same bits as the fused form's.
+ *   dr_homography_gt_mask      gt_H [P,9] -> mask [P,N] = dr_homography_score's inlier test under the pair's homography (bit for bit the
+ *     mask dr_homography_update writes for that model; all zeros for a NaN-scoring one), count [P] int32.
+ * ------------------------------------------------------------------------------------------ */
+int dr_homography_loss_fused_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep,
+                                 const float *thr2, int P, int M, int N, float *sums, float *grad_unscaled, float *per_pair,
+                                 float *coef, float *mean, void *stream);
+int dr_homography_loss_fused_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                 const double *thr2, int P, int M, int N, double *sums, double *grad_unscaled, double *per_pair,
+                                 double *coef, double *mean, void *stream);
+int dr_homography_loss_scale_f32(const float *grad_unscaled, const float *coef, const float *grad_mean, int P, int M,
+                                 float *grad_models, void *stream);
+int dr_homography_loss_scale_f64(const double *grad_unscaled, const double *coef, const double *grad_mean, int P, int M,
+                                 double *grad_models, void *stream);
+int dr_homography_loss_fwd_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep, const float *thr2,
+                               int P, int M, int N, float *sums, float *per_pair, float *coef, float *mean, void *stream);
+int dr_homography_loss_fwd_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                               const double *thr2, int P, int M, int N, double *sums, double *per_pair, double *coef, double *mean,
+                               void *stream);
+int dr_homography_gt_mask_f32(const float *matches, const float *gt_H, const float *thr2, int P, int N, uint8_t *mask,
+                              int32_t *count, void *stream);
+int dr_homography_gt_mask_f64(const double *matches, const double *gt_H, const double *thr2, int P, int N, uint8_t *mask,
+                              int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * K5  train-mode best-of-S selection    RANSAC.__call__, ransac.py:87-96
  *   chosen[p,b] = models[p,b,argmin_s ||models[p,b,s] - gt[p]||_F]; invalid slots (valid == 0) are
  *   skipped; which [P*B] int32 (-1 when no slot is valid; chosen = eye(3) then).
  * ------------------------------------------------------------------------------------------ */
