@@ -181,30 +181,16 @@ __device__ __forceinline__ void cross_acc(const double *a, const double *b, doub
   out[2] += a[0] * b[1] - a[1] * b[0];
 }
 
-// every output element is written; exact zeros for a sample without a valid model or with a non-finite derivative
-template <typename T>
-__global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict__ samples, const T *__restrict__ grad_models, int Bt,
-                                                             T *__restrict__ grad_samples) {
-  const int smp = blockIdx.x * 64 + threadIdx.x;
-  if (smp >= Bt) return;
-  const T *base = samples + (size_t)smp * 16;
-  H4Image im[2];
-  double M[9], H[9], nrm, sigma;
-  bool ok = homography4_fwd([&](int r) { return base + r * 4; }, true, im, M, H, nrm, sigma);
-  double g0[9], dot = 0.0;
-#pragma unroll
-  for (int q = 0; q < 9; ++q) {
-    g0[q] = (double)grad_models[(size_t)smp * 9 + q];
-    dot += H[q] * g0[q];
-  }
-  const double sc = sigma / nrm;
-#pragma unroll
-  for (int q = 0; q < 9; ++q) g0[q] = sc * (g0[q] - H[q] * dot);
+// H0 = T2^-1 (M T1) backwards: g0 = dL/dH0 -> gM and the direct gradients gnz1, gnz2 of (cx, cy, s) of the two images
+__device__ __forceinline__ void denormalise_h_bwd(const double (&M)[9], const double (&nz1)[3], const double (&nz2)[3],
+                                                  const double (&g0)[9], double (&gM)[9], double (&gnz1)[3], double (&gnz2)[3]) {
   // H0 = T2^-1 G, G = M T1
-  const double s1 = im[0].nz[2], cx1 = im[0].nz[0], cy1 = im[0].nz[1];
-  const double s2 = im[1].nz[2], cx2 = im[1].nz[0], cy2 = im[1].nz[1], r2 = 1.0 / s2;
-  double G[9], gG[9], gnz1[3] = {0.0, 0.0, 0.0}, gnz2[3] = {0.0, 0.0, 0.0}, gM[9];
+  const double s1 = nz1[2], cx1 = nz1[0], cy1 = nz1[1];
+  const double s2 = nz2[2], cx2 = nz2[0], cy2 = nz2[1], r2 = 1.0 / s2;
+  double G[9], gG[9];
   double gr2 = 0.0;
+#pragma unroll
+  for (int q = 0; q < 3; ++q) gnz1[q] = gnz2[q] = 0.0;
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     G[3 * i] = M[3 * i] * s1;
@@ -231,6 +217,29 @@ __global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict
     gnz1[0] -= s1 * g2 * m0;
     gnz1[1] -= s1 * g2 * m1;
   }
+}
+
+// every output element is written; exact zeros for a sample without a valid model or with a non-finite derivative
+template <typename T>
+__global__ __launch_bounds__(64) void homography4_bwd_kernel(const T *__restrict__ samples, const T *__restrict__ grad_models, int Bt,
+                                                             T *__restrict__ grad_samples) {
+  const int smp = blockIdx.x * 64 + threadIdx.x;
+  if (smp >= Bt) return;
+  const T *base = samples + (size_t)smp * 16;
+  H4Image im[2];
+  double M[9], H[9], nrm, sigma;
+  bool ok = homography4_fwd([&](int r) { return base + r * 4; }, true, im, M, H, nrm, sigma);
+  double g0[9], dot = 0.0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    g0[q] = (double)grad_models[(size_t)smp * 9 + q];
+    dot += H[q] * g0[q];
+  }
+  const double sc = sigma / nrm;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) g0[q] = sc * (g0[q] - H[q] * dot);
+  double gnz1[3], gnz2[3], gM[9];
+  denormalise_h_bwd(M, im[0].nz, im[1].nz, g0, gM, gnz1, gnz2);
   // M = A2 B, B = adj(A1)
   double Bm[9], gA2[9], gB[9], gA1[9];
   adjugate3(im[0].A, Bm);
@@ -395,6 +404,179 @@ __global__ __launch_bounds__(kHRThreads) void refit_homography_kernel(const T *_
   if (tid == 0) {
     store_h(model + (size_t)p * 9, H);
     valid[p] = ok;
+  }
+}
+
+// ---- (4b) the reverse pass of (4): gH -> the gradient of the rows and of their weights (dr_refit_homography_bwd) ----------------------
+// Nothing is stored by the forward: the same dlt_system call over the same MaskedRows4 gives the rows, the transforms and the Gram
+// matrix G bit for bit, wave 0's Jacobi all nine eigenpairs (lambda_i, v_i); h = v_0 is the forward's eigenvector.  Backwards:
+//   H = sigma H0 / |H0|         g0 = (sigma / |H0|) (gH - H <H, gH>)       (the rule of (1c): a multiple of H in gH passes nothing on)
+//   H0 = T2^-1 (mat(h) T1)      g_h, and the direct gradients of (cx, cy, s) of each image (denormalise_h_bwd)
+//   h = v_0(G)                  dh = sum_{i != 0} v_i (v_i^T dG h) / (lambda_0 - lambda_i), so with
+//                               z = sum_{i != 0} v_i (v_i . g_h) / (lambda_i - lambda_0):  dL = -z^T dG h,  gG = -(z h^T + h z^T) / 2;
+//                               g_h is taken with respect to the vector as returned, so its arbitrary sign cancels in z h^T
+//   G = sum w (a a^T + b b^T)   f_n = a^T gG a + b^T gG b = -[(a . z)(a . h) + (b . z)(b . h)] = dL/dw_n (the transforms are unweighted:
+//                               the weights enter through G only), and w_n df_n/d(x, y, u, v) is the row's normalised-coordinate gradient
+//   x = (X1 - cx1) s1, ...      per image: g_c = -s sum gx (+ direct), g_s = sum (gx . x) / s (+ direct)
+//   s = sqrt(2) R / D, D = sum |q_n|, q_n = X_n - c, c = mean X_n:  g_D = -g_s s / D;  the centroid enters the centred coordinates and
+//                               D: g_c -= g_D sum q_n / |q_n|;  a row gets  s gx_n + g_D q_n / |q_n| + g_c / R  (q_n / |q_n| := 0 at |q_n| = 0)
+// Mapping: (4)'s -- one 256-thread block per pair, f64, thread n owns rows n, n + 256, ....  Wave 0 hands h, z and the six direct
+// gradients to the block through LDS; pass A reduces the ten sums above with block_sum_f64; pass B writes every row of every requested
+// output: exact zeros for rows the mask drops (never loaded) and for every row of a pair with fewer than four rows, valid = 0,
+// lambda_i - lambda_0 not positive and finite for some i != 0, or a non-finite h-path, sum or centroid / scale gradient -- one
+// block-uniform decision.  No atomics, one reduction order: a repeated launch gives the same bits.
+// f_n and its derivatives for one row; z = the perturbation vector above
+__device__ __forceinline__ void dlt_row_bwd(const double (&h)[9], const double (&z)[9], double x, double y, double u, double v,
+                                            double &f, double (&g)[4]) {
+  const double h2 = h[6] * x + h[7] * y + h[8], z2 = z[6] * x + z[7] * y + z[8];
+  const double ah = v * h2 - (h[3] * x + h[4] * y + h[5]), bh = (h[0] * x + h[1] * y + h[2]) - u * h2;
+  const double az = v * z2 - (z[3] * x + z[4] * y + z[5]), bz = (z[0] * x + z[1] * y + z[2]) - u * z2;
+  f = -(az * ah + bz * bh);
+#pragma unroll
+  for (int d = 0; d < 2; ++d)      // d/dx, d/dy of a . t = v t2 - t1 and b . t = t0 - u t2
+    g[d] = -((v * z[6 + d] - z[3 + d]) * ah + az * (v * h[6 + d] - h[3 + d]) + (z[d] - u * z[6 + d]) * bh + bz * (h[d] - u * h[6 + d]));
+  g[2] = z2 * bh + bz * h2;
+  g[3] = -(z2 * ah + az * h2);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kHRThreads) void refit_homography_bwd_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                                          const T *__restrict__ weights,
+                                                                          const T *__restrict__ grad_model, int N,
+                                                                          T *__restrict__ grad_matches, T *__restrict__ grad_weights) {
+  __shared__ DltLds L;
+  __shared__ double s_hz[18], s_gnz[6];      // h, z; the direct gradients of (cx, cy, s) of the two images
+  __shared__ int s_ok;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const MaskedRows4<T> sel{reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N, mask ? mask + (size_t)p * N : nullptr,
+                           weights ? weights + (size_t)p * N : nullptr};
+  double nz1[3], nz2[3];
+  const double rows = dlt_system<T>(sel, N, L, nz1, nz2);
+  if (tid < 64) {
+    jacobi_eig9_wave(L.gram, L.Vl, L.cs, tid);
+    double ev[1][9], H[9], nrm, sigma;
+    smallest_eigvecs9_lds<1>(L.gram, L.Vl, ev);
+    denormalise_h(ev[0], nz1, nz2, H);
+    bool ok = canonical_h(H, rows >= 4.0, nrm, sigma);
+    int best = 0;      // (the column smallest_eigvecs9_lds took: the first strict minimum)
+    double l0 = INFINITY;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+      const double d = L.gram[i * 10];
+      if (d < l0) {
+        l0 = d;
+        best = i;
+      }
+    }
+    double g0[9], dot = 0.0;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) {
+      g0[q] = (double)grad_model[(size_t)p * 9 + q];
+      dot += H[q] * g0[q];
+    }
+    const double sc = sigma / nrm;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) g0[q] = sc * (g0[q] - H[q] * dot);
+    double gh[9], gnz1[3], gnz2[3], z[9];
+    denormalise_h_bwd(ev[0], nz1, nz2, g0, gh, gnz1, gnz2);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) z[q] = 0.0;
+#pragma unroll 1
+    for (int i = 0; i < 9; ++i) {
+      if (i == best) continue;
+      const double gap = L.gram[i * 10] - l0;
+      ok = ok && gap > 0.0 && is_finite(gap);
+      double c = 0.0;
+#pragma unroll
+      for (int r = 0; r < 9; ++r) c += L.Vl[r * 9 + i] * gh[r];
+      c /= gap;
+#pragma unroll
+      for (int r = 0; r < 9; ++r) z[r] += L.Vl[r * 9 + i] * c;
+    }
+#pragma unroll
+    for (int q = 0; q < 9; ++q) ok = ok && is_finite(z[q]);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) ok = ok && is_finite(gnz1[q]) && is_finite(gnz2[q]);
+    if (tid == 0) {
+#pragma unroll
+      for (int q = 0; q < 9; ++q) {
+        s_hz[q] = ev[0][q];
+        s_hz[9 + q] = z[q];
+      }
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        s_gnz[q] = gnz1[q];
+        s_gnz[3 + q] = gnz2[q];
+      }
+      s_ok = ok;
+    }
+  }
+  __syncthreads();
+  bool ok = s_ok != 0;      // (block-uniform, and so is every term added to it below: the totals are the same in every thread)
+  double h[9], z[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    h[q] = s_hz[q];
+    z[q] = s_hz[9 + q];
+  }
+  // pass A, per image: sum w g, sum w (g . x), sum q / |q| (on the normalised coordinates: the same direction)
+  double a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int n = tid; ok && n < N; n += kHRThreads) {
+    if (!sel.present(n)) continue;
+    const Match4<T> m = sel.row(n);
+    const double w = sel.weight(n);
+    const double x = ((double)m.v[0] - nz1[0]) * nz1[2], y = ((double)m.v[1] - nz1[1]) * nz1[2];
+    const double u = ((double)m.v[2] - nz2[0]) * nz2[2], v = ((double)m.v[3] - nz2[1]) * nz2[2];
+    double f, g[4];
+    dlt_row_bwd(h, z, x, y, u, v, f, g);
+    const double r1 = sqrt(x * x + y * y), r2 = sqrt(u * u + v * v);
+    const double i1 = r1 > 0.0 ? 1.0 / r1 : 0.0, i2 = r2 > 0.0 ? 1.0 / r2 : 0.0;
+    a[0] += w * g[0];
+    a[1] += w * g[1];
+    a[2] += w * (g[0] * x + g[1] * y);
+    a[3] += x * i1;
+    a[4] += y * i1;
+    a[5] += w * g[2];
+    a[6] += w * g[3];
+    a[7] += w * (g[2] * u + g[3] * v);
+    a[8] += u * i2;
+    a[9] += v * i2;
+  }
+  block_sum_f64<10>(a, reinterpret_cast<double(*)[10]>(L.s_part));
+  // per image: the gradient of D = sum |q_n| (s = sqrt(2) R / D) and 1 / R of the centroid's
+  double gD[2], gc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const double s = i ? nz2[2] : nz1[2];
+    const double gs = s_gnz[3 * i + 2] + a[5 * i + 2] / s;
+    gD[i] = -gs * s * s / (M_SQRT2 * rows);
+    gc[i][0] = (s_gnz[3 * i] - s * a[5 * i] - gD[i] * a[5 * i + 3]) / rows;
+    gc[i][1] = (s_gnz[3 * i + 1] - s * a[5 * i + 1] - gD[i] * a[5 * i + 4]) / rows;
+    ok = ok && is_finite(gD[i]) && is_finite(gc[i][0]) && is_finite(gc[i][1]);
+  }
+  // pass B: every row of every requested output
+  Match4<T> *gm = grad_matches ? reinterpret_cast<Match4<T> *>(grad_matches) + (size_t)p * N : nullptr;
+  T *gw = grad_weights ? grad_weights + (size_t)p * N : nullptr;
+  for (int n = tid; n < N; n += kHRThreads) {
+    Match4<T> out{{T(0), T(0), T(0), T(0)}};
+    T fw = T(0);
+    if (ok && sel.present(n)) {
+      const Match4<T> m = sel.row(n);
+      const double w = sel.weight(n);
+      const double x = ((double)m.v[0] - nz1[0]) * nz1[2], y = ((double)m.v[1] - nz1[1]) * nz1[2];
+      const double u = ((double)m.v[2] - nz2[0]) * nz2[2], v = ((double)m.v[3] - nz2[1]) * nz2[2];
+      double f, g[4];
+      dlt_row_bwd(h, z, x, y, u, v, f, g);
+      const double r1 = sqrt(x * x + y * y), r2 = sqrt(u * u + v * v);
+      const double i1 = r1 > 0.0 ? gD[0] / r1 : 0.0, i2 = r2 > 0.0 ? gD[1] / r2 : 0.0;
+      out.v[0] = (T)(nz1[2] * w * g[0] + i1 * x + gc[0][0]);
+      out.v[1] = (T)(nz1[2] * w * g[1] + i1 * y + gc[0][1]);
+      out.v[2] = (T)(nz2[2] * w * g[2] + i2 * u + gc[1][0]);
+      out.v[3] = (T)(nz2[2] * w * g[3] + i2 * v + gc[1][1]);
+      fw = (T)f;
+    }
+    if (gm) gm[n] = out;
+    if (gw) gw[n] = fw;
   }
 }
 
@@ -586,6 +768,14 @@ DR_F32_F64(DR_OP)
     DR_REQUIRE(P > 0 && N > 0, "bad sizes");                                                                                        \
     return dr::launch("refit_homography_kernel", dr::refit_homography_kernel<T>, dim3(P), dr::kHRThreads, stream, matches, mask,    \
                       weights, N, model, valid);                                                                                    \
+  }                                                                                                                                 \
+  int dr_refit_homography_bwd_##sfx(const T *matches, const uint8_t *mask, const T *weights, const T *grad_model, int P, int N,     \
+                                    T *grad_matches, T *grad_weights, void *stream) {                                               \
+    DR_REQUIRE(matches && grad_model, "null pointer");                                                                              \
+    DR_REQUIRE(grad_matches || grad_weights, "nothing to write: grad_matches and grad_weights are both null");                      \
+    DR_REQUIRE(P > 0 && N > 0, "bad sizes");                                                                                        \
+    return dr::launch("refit_homography_bwd_kernel", dr::refit_homography_bwd_kernel<T>, dim3(P), dr::kHRThreads, stream, matches,  \
+                      mask, weights, grad_model, N, grad_matches, grad_weights);                                                    \
   }
 DR_F32_F64(DR_OP)
 #undef DR_OP

@@ -1369,6 +1369,60 @@ def homography4(samples):
     return _Homography4.apply(samples)
 
 
+class _WeightedHomography(torch.autograd.Function):
+    """dr_refit_homography / dr_refit_homography_bwd: the backward recomputes the fit from its inputs, so no model is saved"""
+
+    @staticmethod
+    def forward(ctx, matches, weights, mask):
+        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+        m = matches.contiguous()
+        w = None if weights is None else weights.to(m.dtype).contiguous()
+        model, valid = refit_homography(m, mask, w)
+        ctx.save_for_backward(m, *(() if w is None else (w,)))
+        ctx.mask = None if mask is None else _u8(mask)
+        ctx.wdtype = None if weights is None else weights.dtype
+        ctx.mark_non_differentiable(valid)
+        return model, valid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_model, _gv):
+        want_m, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if g_model is None or not (want_m or want_w):
+            return None, None, None
+        m, *w = ctx.saved_tensors
+        w = w[0] if w else None
+        P, N, _ = m.shape
+        gm = torch.empty_like(m) if want_m else None
+        gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if want_w else None
+        L.call(f"dr_refit_homography_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w),
+               ptr(g_model.to(m.dtype).reshape(P, 9).contiguous()), P, N, ptr(gm), ptr(gw), stream())
+        return gm, None if gw is None else gw.to(ctx.wdtype), None
+
+
+def weighted_homography(matches, weights=None, mask=None):
+    """matches [P,N,4], weights [P,N] | None, mask [P,N] | None -> (model [P,3,3], valid [P] bool): refit_homography (the normalised
+    DLT over the rows the mask selects, a row's weight multiplying its terms in the Gram matrix; the same entry, the same bits) with
+    autograd to `weights` and / or `matches`, whichever require it (dr_refit_homography_bwd), in f32 and f64; once differentiable,
+    `valid` and the mask carry no gradient.  Weights are expected >= 0 and are not checked, as in the forward.
+    Zero rules: rows the mask drops get exact zeros and are never read (a NaN there reaches nothing); every row of a pair gets exact
+    zeros when the pair has fewer than four rows, valid = 0, the smallest eigenvalue of its Gram matrix is not simple (or an
+    eigenvalue gap is not finite), or an intermediate of the derivative is not finite.  A multiple of H in the incoming gradient
+    passes nothing on.  Bit-repeatable."""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != 4:
+        raise L.DransacError("weighted_homography: matches [P,N,4] = (x1, y1, x2, y2)")
+    if matches.dtype not in (torch.float32, torch.float64):
+        raise L.DransacError("weighted_homography: matches must be float32 or float64")
+    P, N, _ = matches.shape
+    if weights is not None and (weights.shape != (P, N) or not weights.is_floating_point()):
+        raise L.DransacError("weighted_homography: weights must be floating point [P,N], one per row of matches")
+    if mask is not None and (mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise L.DransacError("weighted_homography: mask must be bool or uint8 [P,N]")
+    if any(t is not None and not t.is_cuda for t in (matches, weights, mask)):
+        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    return _WeightedHomography.apply(matches, weights, mask)
+
+
 class _MsacScore(torch.autograd.Function):
     @staticmethod
     def forward(ctx, matches, models, thr, want_masks):

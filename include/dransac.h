@@ -503,6 +503,21 @@ int dr_refit_rigid_bwd_f64(const double *matches, const uint8_t *mask, const dou
  *     row's terms in the Gram matrix -> model [P,9], valid [P].  Hartley's transforms come from the selected rows, unweighted; the 9x9
  *     Gram matrix of the two DLT rows per point is summed in f64 in one fixed order; its smallest eigenvector (Jacobi) is denormalised,
  *     scaled to unit norm and given det > 0.  valid = 0, model = identity: fewer than four rows, a non-finite or singular result.
+ *   dr_refit_homography_bwd grad_model [P,9] = dL/dH of the model dr_refit_homography returns for (matches, mask, weights) ->
+ *     grad_matches [P,N,4] and / or grad_weights [P,N] (NULL: not wanted; at least one; grad_weights with weights = NULL is the
+ *     derivative at w = 1).  One 256-thread block per pair, f64 inside; nothing is stored by the forward: the same three passes give
+ *     the rows, nz_i = (cx_i, cy_i, s_i) and the Gram matrix G bit for bit, the Jacobi all eigenpairs (lambda_i, v_i), h = v_0.  Then
+ *       H = sigma H0 / |H0|, H0 = T2^-1 mat(h) T1:  g0 = (sigma / |H0|) (gH - H <H, gH>) (a multiple of H in grad_model passes nothing
+ *         on), g_h = T2^-T g0 T1^T, and the direct gradients of (cx, cy, s) of each image;
+ *       z = sum_{i != 0} v_i (v_i . g_h) / (lambda_i - lambda_0), gG = -(z h^T + h z^T) / 2 (the sign of h cancels);
+ *       per present row, a = (0, -X, v X), b = (X, 0, -u X), X = (x, y, 1):  grad_weights[n] = a^T gG a + b^T gG b =
+ *         -[(a . z)(a . h) + (b . z)(b . h)], and w_n times its derivative by (x, y, u, v) is the normalised-coordinate gradient gx_n;
+ *       per image g_c = -s sum gx_n + direct, g_s = sum (gx_n . x_n) / s + direct, s = sqrt(2) R / D, D = sum |q_n|:  g_D = -g_s s / D,
+ *         g_c -= g_D sum q_n / |q_n|;  grad_matches[n] = s gx_n + g_D q_n / |q_n| + g_c / R (zero subgradient at |q_n| = 0).
+ *     Every element of every requested output is written.  Exact zeros: rows the mask drops (never read: a NaN there reaches nothing),
+ *     and every row of a pair with fewer than four rows, valid = 0, lambda_i - lambda_0 not positive and finite, or a non-finite
+ *     intermediate (one decision per pair).  No atomics, fixed-order sums: a repeated launch gives the same bits.  Weights are
+ *     expected >= 0 and not checked.
  *   dr_homography_magsac_score   dr_homography_score's arguments, slot rules and inlier counts with the MAGSAC++ score in the MSAC
  *     score's place: the transfer error is a 4-vector, so thr2 is read as (k sigma_max)^2 with k^2 = chi2.ppf(0.99, 4), and with
  *     s = d2 / thr2 a point with d2 < thr2 adds 1 - l(s), l the two-view loss stated at dr_magsac_score.  Bit-repeatable.
@@ -539,6 +554,10 @@ int dr_refit_homography_f32(const float *matches, const uint8_t *mask, const flo
                             uint8_t *valid, void *stream);
 int dr_refit_homography_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model,
                             uint8_t *valid, void *stream);
+int dr_refit_homography_bwd_f32(const float *matches, const uint8_t *mask, const float *weights, const float *grad_model, int P, int N,
+                                float *grad_matches, float *grad_weights, void *stream);
+int dr_refit_homography_bwd_f64(const double *matches, const uint8_t *mask, const double *weights, const double *grad_model, int P,
+                                int N, double *grad_matches, double *grad_weights, void *stream);
 int dr_homography_magsac_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M,
                                    int N, float *scores, int32_t *inliers, void *stream);
 int dr_homography_magsac_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M,
