@@ -21,10 +21,10 @@
 // half an ulp and a bit, and the kernel's error to that of the linear forms alone; f64 divides.  d2 is then not transfer_d2's value
 // to the last bit, only to the reciprocal's ulp: `live` agrees with HomographyGeom::inlier wherever d2 / thr2 is farther from 1, and
 // y_w, z_w farther from 0, than the rounding of either evaluation, which is the guarantee the two paths can give each other (the
-// signs of y_w and z_w, computed by the same fma in the same order, agree always).  The ground-truth mask (homography_gt_mask_kernel)
+// signs of y_w and z_w, computed by the same fma in the same order, agree always).  The ground-truth mask (pair_gt_mask_kernel)
 // IS HomographyGeom::inlier: bit for bit the mask dr_homography_update writes for the same model.
 #include "homography_device.hpp"
-#include "loss_reduce_device.hpp"
+#include "pair_loss_device.hpp"
 
 namespace dr {
 
@@ -147,79 +147,11 @@ __global__ __launch_bounds__(64) void homography_loss_kernel(const T *__restrict
   }
 }
 
-// mask[p,n] = HomographyGeom::inlier under the pair's ground-truth homography (the score kernels' and the state step's test), count[p]
-template <typename T>
-__global__ __launch_bounds__(256) void homography_gt_mask_kernel(const T *__restrict__ matches, const T *__restrict__ gt_H,
-                                                                const T *__restrict__ thr2, int N, uint8_t *__restrict__ mask,
-                                                                int32_t *__restrict__ count) {
-  __shared__ int s_cnt[4];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  ScoredH<T> s;
-  const bool scored = HomographyGeom::prepare(gt_H + (size_t)p * 9, s) == kModelScored;
-  const T t2 = thr2[p];
-  int c = 0;
-  for (int n = tid; n < N; n += 256) {
-    const Match4<T> x = reinterpret_cast<const Match4<T> *>(matches)[(size_t)p * N + n];
-    const bool on = scored && HomographyGeom::inlier(s, x.v, t2);
-    mask[(size_t)p * N + n] = on ? 1 : 0;
-    c += on ? 1 : 0;
-  }
-  c = wave_sum(c);
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = c;
-  __syncthreads();
-  if (tid == 0) count[p] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-}
-
-// the loss value (and, kGrad, its unscaled gradient) per model, then the means
-template <typename T, bool kGrad>
-int homography_loss_launch(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2, int P, int M,
-                           int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) {
-  if (int rc = launch("homography_loss_kernel", homography_loss_kernel<T, kGrad>, dim3((M + 63) / 64, P), 64, stream, matches, mask,
-                      models, keep, thr2, M, N, sums, grad_unscaled))
-    return rc;
-  return launch("registration_loss_mean_kernel", registration_loss_mean_kernel<T>, dim3(1), kRLMeanT, stream, sums, mask, keep, P, M, N,
-                per_pair, coef, mean);
-}
-
 }  // namespace dr
 
 extern "C" {
 
-#define DR_HOMOGRAPHY_LOSS_SIZES \
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535 && (long)P * M < (1l << 22), "need P, M, N > 0, P <= 65535 and P M < 2^22")
-
-#define DR_OP(sfx, T)                                                                                                              \
-  int dr_homography_loss_fused_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,    \
-                                     int P, int M, int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean,                 \
-                                     void *stream) {                                                                                \
-    DR_REQUIRE(matches && models && thr2 && sums && grad_unscaled && per_pair && coef && mean, "null pointer");                     \
-    DR_HOMOGRAPHY_LOSS_SIZES;                                                                                                       \
-    return dr::homography_loss_launch<T, true>(matches, mask, models, keep, thr2, P, M, N, sums, grad_unscaled, per_pair, coef,     \
-                                               mean, stream);                                                                       \
-  }                                                                                                                                 \
-  int dr_homography_loss_fwd_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,      \
-                                   int P, int M, int N, T *sums, T *per_pair, T *coef, T *mean, void *stream) {                     \
-    DR_REQUIRE(matches && models && thr2 && sums && per_pair && coef && mean, "null pointer");                                      \
-    DR_HOMOGRAPHY_LOSS_SIZES;                                                                                                       \
-    return dr::homography_loss_launch<T, false>(matches, mask, models, keep, thr2, P, M, N, sums, (T *)nullptr, per_pair, coef,     \
-                                                mean, stream);                                                                      \
-  }                                                                                                                                 \
-  int dr_homography_loss_scale_##sfx(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,       \
-                                     void *stream) {                                                                                \
-    DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");                                                  \
-    DR_REQUIRE(P > 0 && M > 0 && (long)P * M < (1l << 22), "need P, M > 0 and P M < 2^22");                                         \
-    const size_t total = (size_t)P * M * 9;                                                                                         \
-    return dr::launch("registration_loss_scale_kernel", dr::registration_loss_scale_kernel<T>,                                      \
-                      dim3((unsigned)((total + 255) / 256)), 256, stream, grad_unscaled, coef, grad_mean, T(1) / (T)P,              \
-                      (size_t)M * 9, total, grad_models);                                                                           \
-  }                                                                                                                                 \
-  int dr_homography_gt_mask_##sfx(const T *matches, const T *gt_H, const T *thr2, int P, int N, uint8_t *mask, int32_t *count,      \
-                                  void *stream) {                                                                                   \
-    DR_REQUIRE(matches && gt_H && thr2 && mask && count, "null pointer");                                                           \
-    DR_REQUIRE(P > 0 && N > 0, "need P, N > 0");                                                                                    \
-    return dr::launch("homography_gt_mask_kernel", dr::homography_gt_mask_kernel<T>, dim3(P), 256, stream, matches, gt_H, thr2, N,  \
-                      mask, count);                                                                                                 \
-  }
+#define DR_OP(sfx, T) DR_PAIR_LOSS_OP(homography, dr::HomographyGeom, sfx, T)
 DR_F32_F64(DR_OP)
 #undef DR_OP
 

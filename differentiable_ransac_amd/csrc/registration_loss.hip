@@ -6,7 +6,7 @@
 // masked points tile by tile into LDS, in ascending order, and every lane walks the tile reading each point as an LDS broadcast: no
 // cross-lane reduction, no atomics, and the order of every sum is the order of the points -- a repeated launch repeats bit for bit.
 // The grid is arithmetic-bound (~38 vector instructions per model x masked point); a tile's staging is ~1 % of its arithmetic.
-#include "loss_reduce_device.hpp"
+#include "pair_loss_device.hpp"
 #include "rigid_device.hpp"
 
 namespace dr {
@@ -114,82 +114,12 @@ __global__ __launch_bounds__(64) void registration_loss_kernel(const T *__restri
   }
 }
 
-// mask[p,n] = |R p + t - q|^2 < thr2[p] under the ground-truth pose of the pair (rigid_d2: the score kernels' inlier test), count[p]
-template <typename T>
-__global__ __launch_bounds__(256) void registration_gt_mask_kernel(const T *__restrict__ matches, const T *__restrict__ pose,
-                                                                  const T *__restrict__ thr2, int N, uint8_t *__restrict__ mask,
-                                                                  int32_t *__restrict__ count) {
-  __shared__ int s_cnt[4];
-  const int p = blockIdx.x, tid = threadIdx.x;
-  T md[12];
-#pragma unroll
-  for (int q = 0; q < 12; ++q) md[q] = pose[(size_t)p * 16 + q];
-  const T t2 = thr2[p];
-  int c = 0;
-  for (int n = tid; n < N; n += 256) {
-    T x[6];
-#pragma unroll
-    for (int d = 0; d < 6; ++d) x[d] = matches[((size_t)p * N + n) * 6 + d];
-    const bool on = rigid_d2<T>(md, x) < t2;
-    mask[(size_t)p * N + n] = on ? 1 : 0;
-    c += on ? 1 : 0;
-  }
-  c = wave_sum(c);
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = c;
-  __syncthreads();
-  if (tid == 0) count[p] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-}
-
-// the loss value (and, kGrad, its unscaled gradient) per model, then the means
-template <typename T, bool kGrad>
-int registration_loss_launch(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2, int P, int M,
-                             int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean, void *stream) {
-  if (int rc = launch("registration_loss_kernel", registration_loss_kernel<T, kGrad>, dim3((M + 63) / 64, P), 64, stream, matches, mask,
-                      models, keep, thr2, M, N, sums, grad_unscaled))
-    return rc;
-  return launch("registration_loss_mean_kernel", registration_loss_mean_kernel<T>, dim3(1), kRLMeanT, stream, sums, mask, keep, P, M, N,
-                per_pair, coef, mean);
-}
-
 }  // namespace dr
 
 extern "C" {
 
-#define DR_REGISTRATION_LOSS_SIZES \
-  DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535 && (long)P * M < (1l << 22), "need P, M, N > 0, P <= 65535 and P M < 2^22")
-
-#define DR_OP(sfx, T)                                                                                                              \
-  int dr_registration_loss_fused_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,  \
-                                       int P, int M, int N, T *sums, T *grad_unscaled, T *per_pair, T *coef, T *mean,               \
-                                       void *stream) {                                                                              \
-    DR_REQUIRE(matches && models && thr2 && sums && grad_unscaled && per_pair && coef && mean, "null pointer");                     \
-    DR_REGISTRATION_LOSS_SIZES;                                                                                                     \
-    return dr::registration_loss_launch<T, true>(matches, mask, models, keep, thr2, P, M, N, sums, grad_unscaled, per_pair, coef,   \
-                                                 mean, stream);                                                                     \
-  }                                                                                                                                 \
-  int dr_registration_loss_fwd_##sfx(const T *matches, const uint8_t *mask, const T *models, const uint8_t *keep, const T *thr2,    \
-                                     int P, int M, int N, T *sums, T *per_pair, T *coef, T *mean, void *stream) {                   \
-    DR_REQUIRE(matches && models && thr2 && sums && per_pair && coef && mean, "null pointer");                                      \
-    DR_REGISTRATION_LOSS_SIZES;                                                                                                     \
-    return dr::registration_loss_launch<T, false>(matches, mask, models, keep, thr2, P, M, N, sums, (T *)nullptr, per_pair, coef,   \
-                                                  mean, stream);                                                                    \
-  }                                                                                                                                 \
-  int dr_registration_loss_scale_##sfx(const T *grad_unscaled, const T *coef, const T *grad_mean, int P, int M, T *grad_models,     \
-                                       void *stream) {                                                                              \
-    DR_REQUIRE(grad_unscaled && coef && grad_mean && grad_models, "null pointer");                                                  \
-    DR_REQUIRE(P > 0 && M > 0 && (long)P * M < (1l << 22), "need P, M > 0 and P M < 2^22");                                         \
-    const size_t total = (size_t)P * M * 16;                                                                                        \
-    return dr::launch("registration_loss_scale_kernel", dr::registration_loss_scale_kernel<T>,                                      \
-                      dim3((unsigned)((total + 255) / 256)), 256, stream, grad_unscaled, coef, grad_mean, T(1) / (T)P,              \
-                      (size_t)M * 16, total, grad_models);                                                                          \
-  }                                                                                                                                 \
-  int dr_registration_gt_mask_##sfx(const T *matches, const T *gt_pose, const T *thr2, int P, int N, uint8_t *mask,                 \
-                                    int32_t *count, void *stream) {                                                                 \
-    DR_REQUIRE(matches && gt_pose && thr2 && mask && count, "null pointer");                                                        \
-    DR_REQUIRE(P > 0 && N > 0, "need P, N > 0");                                                                                    \
-    return dr::launch("registration_gt_mask_kernel", dr::registration_gt_mask_kernel<T>, dim3(P), 256, stream, matches, gt_pose,    \
-                      thr2, N, mask, count);                                                                                        \
-  }
+// (the ground-truth mask is |R p + t - q|^2 < thr2[p]: RigidGeom::inlier = rigid_d2, the score kernels' inlier test)
+#define DR_OP(sfx, T) DR_PAIR_LOSS_OP(registration, dr::RigidGeom, sfx, T)
 DR_F32_F64(DR_OP)
 #undef DR_OP
 

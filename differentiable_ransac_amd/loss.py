@@ -115,7 +115,26 @@ class ClassificationLoss(object):
     __call__ = forward
 
 
-class RegistrationLoss(object):
+class _PairLoss(object):
+    """What RegistrationLoss and HomographyLoss share: one test-mode model per pair is promoted to [P,1,.,.] (and its keep to [P,1]),
+    and without gt_mask the mask comes from the ground-truth model at the loss's threshold, under no_grad.  A subclass names its two
+    ops functions."""
+    _gt_mask = _loss_mean = None
+
+    def __init__(self, threshold):
+        self.threshold = threshold
+
+    def _forward(self, models, matches, gt_model, gt_mask, keep):
+        if models.dim() == 3:
+            models = models[:, None]
+            keep = keep if keep is None or keep.dim() == 2 else keep[:, None]
+        if gt_mask is None and gt_model is not None:
+            with torch.no_grad():
+                gt_mask = type(self)._gt_mask(matches, gt_model.to(matches.dtype), self.threshold)[0]
+        return type(self)._loss_mean(matches, gt_mask, models, self.threshold, keep)
+
+
+class RegistrationLoss(_PairLoss):
     """The training loss of ransac.BatchedRegistration(train=True): the truncated squared distance of every returned model on the
     ground-truth inlier points, what MatchLoss is for E and F.  Per pair, with d2 = |R p + t - q|^2: the mean over (kept models x
     masked points) of (d2 / threshold^2 if d2 < threshold^2 else 1); then the mean over the pairs.  The loss lies in [0, 1]; a hopeless
@@ -123,21 +142,17 @@ class RegistrationLoss(object):
     over ALL points, which ops.rigid_residual_autograd reproduces).  Value and gradient come from one pass of
     `dr_registration_loss_fused`; nothing synchronises, so a whole train step can be captured by graphs.GraphedStep."""
 
+    _gt_mask, _loss_mean = staticmethod(ops.registration_gt_mask), staticmethod(ops.registration_loss_mean)
+
     def __init__(self, threshold):
-        self.threshold = threshold          # inlier DISTANCE, float or [P] (BatchedRegistration's convention)
+        super().__init__(threshold)         # inlier DISTANCE, float or [P] (BatchedRegistration's convention)
 
     def forward(self, models, matches, gt_pose=None, gt_mask=None, keep=None):
         """models [P,M,4,4] (or [P,4,4]: a test-mode result), matches [P,N,6], gt_mask [P,N] bool or gt_pose [P,4,4] (the mask is then
         the points within the threshold of that pose: ops.registration_gt_mask; neither = all points), keep [P,M] bool (models to
         average over, e.g. the fit's validity; None = all) -> scalar loss, differentiable w.r.t. the models ONLY: `matches` that
         require grad are refused (pass matches.detach(); the driver's own gradient to `matches` is unaffected)."""
-        if models.dim() == 3:
-            models = models[:, None]
-            keep = keep if keep is None or keep.dim() == 2 else keep[:, None]
-        if gt_mask is None and gt_pose is not None:
-            with torch.no_grad():
-                gt_mask = ops.registration_gt_mask(matches, gt_pose.to(matches.dtype), self.threshold)[0]
-        return ops.registration_loss_mean(matches, gt_mask, models, self.threshold, keep)
+        return self._forward(models, matches, gt_pose, gt_mask, keep)
 
     __call__ = forward
 
@@ -154,7 +169,7 @@ def registration_errors(model, gt_pose):
         return rre, rte
 
 
-class HomographyLoss(object):
+class HomographyLoss(_PairLoss):
     """The training loss of ransac.BatchedHomography(train=True): the truncated symmetric transfer error of every returned model on
     the ground-truth inlier points, what RegistrationLoss is for rigid poses.  With y = H (x1, 1), z = adj(H) (x2, 1) under the
     det > 0 sign and d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2 (the residual the score kernels use): per pair the mean over
@@ -163,21 +178,17 @@ class HomographyLoss(object):
     contributes the constant 1 and no gradient.  Value and gradient come from one pass of `dr_homography_loss_fused`; nothing
     synchronises, so a whole train step can be captured by graphs.GraphedStep."""
 
+    _gt_mask, _loss_mean = staticmethod(ops.homography_gt_mask), staticmethod(ops.homography_loss_mean)
+
     def __init__(self, threshold):
-        self.threshold = threshold          # inlier DISTANCE in pixels, float or [P] (BatchedHomography's convention)
+        super().__init__(threshold)         # inlier DISTANCE in pixels, float or [P] (BatchedHomography's convention)
 
     def forward(self, models, matches, gt_H=None, gt_mask=None, keep=None):
         """models [P,M,3,3] (or [P,3,3]: a test-mode result), matches [P,N,4], gt_mask [P,N] bool or gt_H [P,3,3] (the mask is then
         the inliers of that homography at the threshold: ops.homography_gt_mask; neither = all points), keep [P,M] bool (models to
         average over, e.g. the solver's validity; None = all) -> scalar loss, differentiable w.r.t. the models ONLY: `matches` that
         require grad are refused (pass matches.detach(); the driver's own gradient to `matches` is unaffected)."""
-        if models.dim() == 3:
-            models = models[:, None]
-            keep = keep if keep is None or keep.dim() == 2 else keep[:, None]
-        if gt_mask is None and gt_H is not None:
-            with torch.no_grad():
-                gt_mask = ops.homography_gt_mask(matches, gt_H.to(matches.dtype), self.threshold)[0]
-        return ops.homography_loss_mean(matches, gt_mask, models, self.threshold, keep)
+        return self._forward(models, matches, gt_H, gt_mask, keep)
 
     __call__ = forward
 

@@ -4,6 +4,7 @@ torch stream and returns freshly allocated torch tensors; nothing synchronises.
 """
 from __future__ import annotations
 
+import collections
 from typing import Optional, Tuple
 
 import torch
@@ -1699,181 +1700,137 @@ def match_loss_per_pair(matches, mask, models, keep=None):
     return _MatchLossPair.apply(matches, mask, models.reshape(models.shape[0], -1, 3, 3), keep)
 
 
-# ------------------------------------------------------------------------------------------ RegistrationLoss (3-D path)
-# The truncated squared distance of every model on the ground-truth inliers (include/dransac.h, "The training loss of the
-# registration path"): matches [P,N,6], mask [P,N] bool | None, models [P,M,4,4], keep [P,M] bool | None, threshold = DISTANCE.
-def registration_gt_mask(matches: torch.Tensor, gt_pose: torch.Tensor, threshold):
-    """dr_registration_gt_mask: matches [P,N,6], gt_pose [P,4,4], threshold (float or [P]) -> (mask [P,N] bool = the points within the
-    distance threshold of the pair's ground-truth pose, count [P] int32)."""
+# ------------------------------------------------------------------------------------------ the pair families' training losses
+# RegistrationLoss (3-D path): the truncated squared distance of every model on the ground-truth inliers (include/dransac.h, "The
+# training loss of the registration path"): matches [P,N,6], mask [P,N] bool | None, models [P,M,4,4], keep [P,M] bool | None.
+# HomographyLoss (homography path): the truncated symmetric transfer error (include/dransac.h, "The training loss of the homography
+# path"): matches [P,N,4], models [P,M,3,3] of any scale and either sign.  threshold = DISTANCE in both.  One implementation behind a
+# family record: the C entries dr_<entry>_{gt_mask,loss_fwd,loss_fused,loss_scale}, the match width, the model shape, the messages' nouns.
+_PairLossFamily = collections.namedtuple("_PairLossFamily", "entry width shape points gt_noun")
+_REGISTRATION_LOSS = _PairLossFamily("registration", 6, (4, 4), "correspondences", "pose")
+_HOMOGRAPHY_LOSS = _PairLossFamily("homography", 4, (3, 3), "matches", "homography")
+
+
+def _pair_gt_mask(fam, matches, gt_model, threshold):
     P, N, _ = matches.shape
-    if gt_pose.shape != (P, 4, 4) or gt_pose.dtype != matches.dtype:
-        raise L.DransacError("registration_gt_mask: one ground-truth pose [P,4,4] per pair, in the correspondences' dtype")
+    r, c = fam.shape
+    if gt_model.shape != (P, r, c) or gt_model.dtype != matches.dtype:
+        raise L.DransacError(f"{fam.entry}_gt_mask: one ground-truth {fam.gt_noun} [P,{r},{c}] per pair, in the {fam.points}' dtype")
     mask = torch.empty((P, N), device=matches.device, dtype=torch.bool)
     count = torch.empty((P,), device=matches.device, dtype=torch.int32)
-    L.call(f"dr_registration_gt_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(gt_pose.contiguous()),
+    L.call(f"dr_{fam.entry}_gt_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(gt_model.contiguous()),
            ptr(thr2_tensor(threshold, P, matches)), P, N, ptr(mask.view(torch.uint8)), ptr(count), stream())
     return mask, count
 
 
-def _registration_loss_inputs(matches, mask, models, keep):
-    if matches.dim() != 3 or matches.shape[-1] != 6 or models.dim() != 4 or models.shape[-2:] != (4, 4) or \
+def _pair_loss_inputs(fam, matches, mask, models, keep):
+    r, c = fam.shape
+    if matches.dim() != 3 or matches.shape[-1] != fam.width or models.dim() != 4 or models.shape[-2:] != fam.shape or \
             models.shape[0] != matches.shape[0] or models.dtype != matches.dtype:
-        raise L.DransacError("registration loss: correspondences [P,N,6] and models [P,M,4,4] of one dtype")
+        raise L.DransacError(f"{fam.entry} loss: {fam.points} [P,N,{fam.width}] and models [P,M,{r},{c}] of one dtype")
     P, N, _ = matches.shape
     M = models.shape[1]
     if (mask is not None and mask.shape != (P, N)) or (keep is not None and keep.shape != (P, M)):
-        raise L.DransacError("registration loss: mask is [P,N], keep is [P,M]")
+        raise L.DransacError(f"{fam.entry} loss: mask is [P,N], keep is [P,M]")
     return matches.contiguous(), _u8(mask), models.contiguous(), _u8(keep), P, M, N
 
 
-def _registration_loss_fwd(matches, mask, models, threshold, keep):
-    """dr_registration_loss_fwd -> (sums [P,M], per_pair [P], coef [P], mean [])"""
-    matches, mk, models, kp, P, M, N = _registration_loss_inputs(matches, mask, models, keep)
+def _pair_loss_fwd(fam, matches, mask, models, threshold, keep):
+    """dr_<entry>_loss_fwd -> (sums [P,M], per_pair [P], coef [P], mean [])"""
+    matches, mk, models, kp, P, M, N = _pair_loss_inputs(fam, matches, mask, models, keep)
     dev, dt = matches.device, matches.dtype
     sums = torch.empty((P, M), device=dev, dtype=dt)
     per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-    L.call(f"dr_registration_loss_fwd_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp),
+    L.call(f"dr_{fam.entry}_loss_fwd_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp),
            ptr(thr2_tensor(threshold, P, matches)), P, M, N, ptr(sums), ptr(per_pair), ptr(coef), ptr(mean), stream())
     return sums, per_pair, coef, mean
 
 
-class _RegistrationLossFused(torch.autograd.Function):
-    """RegistrationLoss value AND gradient in one pass (dr_registration_loss_fused), as _MatchLossFused: the forward writes the
-    unscaled gradient of every model next to the loss, the backward is one elementwise launch (x coef[p] x upstream / P)."""
+class _PairLossFused(torch.autograd.Function):
+    """A pair family's loss value AND gradient in one pass (dr_<entry>_loss_fused), as _MatchLossFused: the forward writes the
+    unscaled gradient of every model next to the loss, the backward is one elementwise launch (x coef[p] x upstream / P) that reads
+    the upstream scalar from device memory.  `fam` travels in ctx (a Function cannot be parameterised by instance)."""
 
     @staticmethod
-    def forward(ctx, matches, mask, models, keep, thr2):
-        matches, mk, models, kp, P, M, N = _registration_loss_inputs(matches, mask, models, keep)
+    def forward(ctx, fam, matches, mask, models, keep, thr2):
+        matches, mk, models, kp, P, M, N = _pair_loss_inputs(fam, matches, mask, models, keep)
         dev, dt = matches.device, matches.dtype
         sums = torch.empty((P, M), device=dev, dtype=dt)
-        gun = torch.empty((P, M, 4, 4), device=dev, dtype=dt)
+        gun = torch.empty((P, M, *fam.shape), device=dev, dtype=dt)
         per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-        L.call(f"dr_registration_loss_fused_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2), P, M, N,
+        L.call(f"dr_{fam.entry}_loss_fused_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2), P, M, N,
                ptr(sums), ptr(gun), ptr(per_pair), ptr(coef), ptr(mean), stream())
         ctx.save_for_backward(gun, coef)
+        ctx.fam = fam
         return mean
 
     @staticmethod
     @torch.autograd.function.once_differentiable       # (gun is a kernel result: a second derivative through it would be silently wrong)
     def backward(ctx, g):
         if g is None:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         gun, coef = ctx.saved_tensors
         P, M = gun.shape[0], gun.shape[1]
         gm = torch.empty_like(gun)
-        L.call(f"dr_registration_loss_scale_{L.suffix(gun.dtype)}", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), P, M,
+        L.call(f"dr_{ctx.fam.entry}_loss_scale_{L.suffix(gun.dtype)}", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), P, M,
                ptr(gm), stream())
-        return None, None, gm, None, None
+        return None, None, None, gm, None, None
+
+
+def _pair_loss_mean(fam, matches, mask, models, threshold, keep):
+    if torch.is_grad_enabled() and matches.requires_grad:
+        raise L.DransacError(f"{fam.entry}_loss_mean is differentiable w.r.t. the models only: pass matches.detach()")
+    if torch.is_grad_enabled() and models.requires_grad:
+        return _PairLossFused.apply(fam, matches, mask, models, keep, thr2_tensor(threshold, matches.shape[0], matches))
+    return _pair_loss_fwd(fam, matches, mask, models, threshold, keep)[3]
+
+
+def _pair_loss_sums(fam, matches, mask, models, threshold, keep, want_pairs):
+    sums, per_pair, _, _ = _pair_loss_fwd(fam, matches.detach(), mask, models.detach(), threshold, keep)
+    return (sums, per_pair) if want_pairs else sums
+
+
+def registration_gt_mask(matches: torch.Tensor, gt_pose: torch.Tensor, threshold):
+    """dr_registration_gt_mask: matches [P,N,6], gt_pose [P,4,4], threshold (float or [P]) -> (mask [P,N] bool = the points within the
+    distance threshold of the pair's ground-truth pose, count [P] int32)."""
+    return _pair_gt_mask(_REGISTRATION_LOSS, matches, gt_pose, threshold)
 
 
 def registration_loss_mean(matches, mask, models, threshold, keep=None):
     """The registration loss of a batch -> scalar in [0, 1]: per pair the mean over (kept models x masked points) of
     min(d2 / threshold^2, 1), then the mean over the pairs.  Differentiable w.r.t. `models` only; when they require grad, value and
-    gradient come from one pass over the (model x point) grid (_RegistrationLossFused), otherwise the value-only kernel runs.
+    gradient come from one pass over the (model x point) grid (_PairLossFused), otherwise the value-only kernel runs.
     Correspondences that require grad are refused (detach them): no gradient is computed for them, and BatchedRegistration(train=True)
     does pass one to `matches`, so a silent zero here would be half a gradient."""
-    if torch.is_grad_enabled() and matches.requires_grad:
-        raise L.DransacError("registration_loss_mean is differentiable w.r.t. the models only: pass matches.detach()")
-    if torch.is_grad_enabled() and models.requires_grad:
-        return _RegistrationLossFused.apply(matches, mask, models, keep, thr2_tensor(threshold, matches.shape[0], matches))
-    return _registration_loss_fwd(matches, mask, models, threshold, keep)[3]
+    return _pair_loss_mean(_REGISTRATION_LOSS, matches, mask, models, threshold, keep)
 
 
 def registration_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool = False):
     """sums [P,M] = sum over the masked points of min(d2 / threshold^2, 1) for every model (0 for a slot keep drops); no autograd.
     want_pairs: -> (sums, per_pair [P]) with the per-pair means registration_loss_mean averages."""
-    sums, per_pair, _, _ = _registration_loss_fwd(matches.detach(), mask, models.detach(), threshold, keep)
-    return (sums, per_pair) if want_pairs else sums
+    return _pair_loss_sums(_REGISTRATION_LOSS, matches, mask, models, threshold, keep, want_pairs)
 
 
-# ------------------------------------------------------------------------------------------ HomographyLoss (homography path)
-# The truncated symmetric transfer error of every model on the ground-truth inliers (include/dransac.h, "The training loss of the
-# homography path"): matches [P,N,4], mask [P,N] bool | None, models [P,M,3,3] of any scale and either sign, keep [P,M] bool | None,
-# threshold = DISTANCE.  The registration functions above, one for one.
 def homography_gt_mask(matches: torch.Tensor, gt_H: torch.Tensor, threshold):
     """dr_homography_gt_mask: matches [P,N,4], gt_H [P,3,3], threshold (float or [P]) -> (mask [P,N] bool = the points homography_score
     counts as inliers of the pair's ground-truth homography, count [P] int32)."""
     _check_matches4("homography_gt_mask", matches)
-    P, N, _ = matches.shape
-    if gt_H.shape != (P, 3, 3) or gt_H.dtype != matches.dtype:
-        raise L.DransacError("homography_gt_mask: one ground-truth homography [P,3,3] per pair, in the matches' dtype")
-    mask = torch.empty((P, N), device=matches.device, dtype=torch.bool)
-    count = torch.empty((P,), device=matches.device, dtype=torch.int32)
-    L.call(f"dr_homography_gt_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(gt_H.contiguous()),
-           ptr(thr2_tensor(threshold, P, matches)), P, N, ptr(mask.view(torch.uint8)), ptr(count), stream())
-    return mask, count
-
-
-def _homography_loss_inputs(matches, mask, models, keep):
-    if matches.dim() != 3 or matches.shape[-1] != 4 or models.dim() != 4 or models.shape[-2:] != (3, 3) or \
-            models.shape[0] != matches.shape[0] or models.dtype != matches.dtype:
-        raise L.DransacError("homography loss: matches [P,N,4] and models [P,M,3,3] of one dtype")
-    P, N, _ = matches.shape
-    M = models.shape[1]
-    if (mask is not None and mask.shape != (P, N)) or (keep is not None and keep.shape != (P, M)):
-        raise L.DransacError("homography loss: mask is [P,N], keep is [P,M]")
-    return matches.contiguous(), _u8(mask), models.contiguous(), _u8(keep), P, M, N
-
-
-def _homography_loss_fwd(matches, mask, models, threshold, keep):
-    """dr_homography_loss_fwd -> (sums [P,M], per_pair [P], coef [P], mean [])"""
-    matches, mk, models, kp, P, M, N = _homography_loss_inputs(matches, mask, models, keep)
-    dev, dt = matches.device, matches.dtype
-    sums = torch.empty((P, M), device=dev, dtype=dt)
-    per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-    L.call(f"dr_homography_loss_fwd_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp),
-           ptr(thr2_tensor(threshold, P, matches)), P, M, N, ptr(sums), ptr(per_pair), ptr(coef), ptr(mean), stream())
-    return sums, per_pair, coef, mean
-
-
-class _HomographyLossFused(torch.autograd.Function):
-    """HomographyLoss value AND gradient in one pass (dr_homography_loss_fused), as _RegistrationLossFused: the forward writes the
-    unscaled gradient of every model next to the loss, the backward is one elementwise launch (x coef[p] x upstream / P) that reads
-    the upstream scalar from device memory."""
-
-    @staticmethod
-    def forward(ctx, matches, mask, models, keep, thr2):
-        matches, mk, models, kp, P, M, N = _homography_loss_inputs(matches, mask, models, keep)
-        dev, dt = matches.device, matches.dtype
-        sums = torch.empty((P, M), device=dev, dtype=dt)
-        gun = torch.empty((P, M, 3, 3), device=dev, dtype=dt)
-        per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-        L.call(f"dr_homography_loss_fused_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2), P, M, N,
-               ptr(sums), ptr(gun), ptr(per_pair), ptr(coef), ptr(mean), stream())
-        ctx.save_for_backward(gun, coef)
-        return mean
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable       # (gun is a kernel result: a second derivative through it would be silently wrong)
-    def backward(ctx, g):
-        if g is None:
-            return None, None, None, None, None
-        gun, coef = ctx.saved_tensors
-        P, M = gun.shape[0], gun.shape[1]
-        gm = torch.empty_like(gun)
-        L.call(f"dr_homography_loss_scale_{L.suffix(gun.dtype)}", ptr(gun), ptr(coef), ptr(g.to(gun.dtype).contiguous()), P, M,
-               ptr(gm), stream())
-        return None, None, gm, None, None
+    return _pair_gt_mask(_HOMOGRAPHY_LOSS, matches, gt_H, threshold)
 
 
 def homography_loss_mean(matches, mask, models, threshold, keep=None):
     """The homography loss of a batch -> scalar in [0, 1]: per pair the mean over (kept models x masked points) of d2 / threshold^2
     for a point in front of both cameras with d2 < threshold^2 and of 1 for any other, then the mean over the pairs.  Differentiable
     w.r.t. `models` only; when they require grad, value and gradient come from one pass over the (model x point) grid
-    (_HomographyLossFused), otherwise the value-only kernel runs.  Matches that require grad are refused (detach them): no gradient
+    (_PairLossFused), otherwise the value-only kernel runs.  Matches that require grad are refused (detach them): no gradient
     is computed for them, and BatchedHomography(train=True) does pass one to `matches`, so a silent zero here would be half a gradient."""
-    if torch.is_grad_enabled() and matches.requires_grad:
-        raise L.DransacError("homography_loss_mean is differentiable w.r.t. the models only: pass matches.detach()")
-    if torch.is_grad_enabled() and models.requires_grad:
-        return _HomographyLossFused.apply(matches, mask, models, keep, thr2_tensor(threshold, matches.shape[0], matches))
-    return _homography_loss_fwd(matches, mask, models, threshold, keep)[3]
+    return _pair_loss_mean(_HOMOGRAPHY_LOSS, matches, mask, models, threshold, keep)
 
 
 def homography_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool = False):
     """sums [P,M] = sum over the masked points of the truncated d2 / threshold^2 for every model (0 for a slot keep drops); no autograd.
     want_pairs: -> (sums, per_pair [P]) with the per-pair means homography_loss_mean averages."""
-    sums, per_pair, _, _ = _homography_loss_fwd(matches.detach(), mask, models.detach(), threshold, keep)
-    return (sums, per_pair) if want_pairs else sums
+    return _pair_loss_sums(_HOMOGRAPHY_LOSS, matches, mask, models, threshold, keep, want_pairs)
 
 
 # ------------------------------------------------------------------------------------------ PoseLoss pose error (8(f) rank 3)
