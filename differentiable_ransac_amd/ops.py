@@ -63,6 +63,19 @@ def _thr_tensor(threshold, P: int, like: torch.Tensor) -> torch.Tensor:
     return torch.full((P,), float(threshold), device=like.device, dtype=like.dtype)
 
 
+def _gpu_only(tensors, optional: bool = False) -> None:
+    """what the wrappers that check their tensors before the launch refuse first; optional: a None among them is an absent argument"""
+    for t in tensors:      # (a plain loop: this runs in front of launches of every round)
+        if not optional if t is None else not t.is_cuda:
+            raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+
+
+def _check_counter(name: str, what: str, t: Optional[torch.Tensor], P: int) -> None:
+    """a per-pair counter a kernel adds to (irls_fits, lo_refits, rejected): [P] int32, or None where the caller may leave it out"""
+    if t is not None and (t.shape != (P,) or t.dtype != torch.int32):
+        raise L.DransacError(f"{name}: {what} must be [P] int32")
+
+
 # ------------------------------------------------------------------------------------------ K4 / K6
 def msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, want_masks: bool = True,
                valid: Optional[torch.Tensor] = None, path: int = 0, gate=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -123,9 +136,7 @@ def magsac_irls(state: "RansacState", matches, thr, fundamental: bool, irls_iter
     on the weighted Gram matrix) and the candidates' MAGSAC++ scores, the best taken only where it is strictly higher.  thr [P] as
     ransac_init returns it; irls_fits [P] int32 grows by the fits run; weights_ws [P,N] (matches' dtype) is workspace.  Mask, inlier
     count and counters of the state are left alone.  One launch, no synchronisation."""
-    tensors = (matches, thr, irls_fits, weights_ws, state.best_score, state.best_model)
-    if any(t is None or not t.is_cuda for t in tensors):
-        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
+    _gpu_only((matches, thr, irls_fits, weights_ws, state.best_score, state.best_model))
     if matches.dim() != 3 or matches.shape[-1] != 4:
         raise L.DransacError("magsac_irls: correspondences are [P,N,4]")
     P, N, _ = matches.shape
@@ -135,8 +146,7 @@ def magsac_irls(state: "RansacState", matches, thr, fundamental: bool, irls_iter
     if (state.best_score.shape != (P,) or state.best_score.dtype != dt or state.best_model.shape != (P, 3, 3)
             or state.best_model.dtype != dt):
         raise L.DransacError("magsac_irls: the state's best_score [P] / best_model [P,3,3] must have the matches' dtype")
-    if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
-        raise L.DransacError("magsac_irls: irls_fits must be [P] int32")
+    _check_counter("magsac_irls", "irls_fits", irls_fits, P)
     if weights_ws.shape != (P, N) or weights_ws.dtype != matches.dtype or not weights_ws.is_contiguous():
         raise L.DransacError("magsac_irls: weights_ws must be a contiguous [P,N] tensor of the matches' dtype")
     L.call(f"dr_magsac_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), P, N, bool(fundamental), int(irls_iters),
@@ -239,6 +249,17 @@ def ransac_update(state: RansacState, matches, models, valid, scores, thr, B: in
 
 
 # ------------------------------------------------------------------------------------------ K1 / K1u / K2
+def _lo_args(name: str, width: int, state, matches, thr, lo_seen, lo_refits, max_iterations):
+    """what local_optimize and registration_local_optimize check before their launch (lo_seen is [P,width]) -> (P, N, max_iterations)"""
+    _gpu_only((matches, thr, lo_seen, lo_refits, state.best_score, state.best_model, state.best_mask, state.best_inliers,
+               state.max_iters), optional=True)
+    P, N, _ = matches.shape
+    if lo_seen is None or lo_seen.shape != (P, width) or lo_seen.dtype != matches.dtype or not lo_seen.is_contiguous():
+        raise L.DransacError(f"{name}: lo_seen must be a contiguous [P,{width}] tensor of the matches' dtype")
+    _check_counter(name, "lo_refits", lo_refits, P)
+    return P, N, int(state.max_iterations if max_iterations is None else max_iterations)
+
+
 def local_optimize(state: RansacState, matches, thr, fundamental: bool, lo: int, lo_iters: int, k: int,
                    confidence: float = 0.999, eps: float = 1e-5, max_iterations: Optional[int] = None,
                    lo_seen: Optional[torch.Tensor] = None, lo_refits: Optional[torch.Tensor] = None) -> None:
@@ -246,18 +267,9 @@ def local_optimize(state: RansacState, matches, thr, fundamental: bool, lo: int,
     lo_iters), in place on `state`, for the pairs whose best model dr_ransac_update replaced since the last visit.
     lo_seen [P,10] (matches' dtype) is the per-call snapshot, filled with NaN before the first round; lo_refits [P] int32
     (optional) accumulates the refits run per pair.  One launch, no synchronisation."""
-    tensors = (matches, thr, lo_seen, lo_refits, state.best_score, state.best_model, state.best_mask, state.best_inliers,
-               state.max_iters)
-    if any(t is not None and not t.is_cuda for t in tensors):
-        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
-    P, N, _ = matches.shape
-    if lo_seen is None or lo_seen.shape != (P, 10) or lo_seen.dtype != matches.dtype or not lo_seen.is_contiguous():
-        raise L.DransacError("local_optimize: lo_seen must be a contiguous [P,10] tensor of the matches' dtype")
-    if lo_refits is not None and (lo_refits.shape != (P,) or lo_refits.dtype != torch.int32):
-        raise L.DransacError("local_optimize: lo_refits must be [P] int32")
-    mi = state.max_iterations if max_iterations is None else max_iterations
+    P, N, mi = _lo_args("local_optimize", 10, state, matches, thr, lo_seen, lo_refits, max_iterations)
     L.call(f"dr_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), P, N, bool(fundamental), int(lo),
-           int(lo_iters), int(k), confidence, eps, int(mi), ptr(state.best_score), ptr(state.best_model),
+           int(lo_iters), int(k), confidence, eps, mi, ptr(state.best_score), ptr(state.best_model),
            ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits),
            stream())
 
@@ -755,13 +767,7 @@ def kabsch_gather(matches: torch.Tensor, idx: torch.Tensor):
     rigid fit (Kabsch) of every sample; a degenerate sample (coincident / collinear rows) is the identity with valid = 0."""
     if matches.dim() != 3 or matches.shape[-1] != 6 or idx.dim() != 3 or idx.dtype != torch.int32:
         raise L.DransacError("kabsch_gather: correspondences [P,N,6] and int32 index sets [P,B,k]")
-    P, N, _ = matches.shape
-    _, B, k = idx.shape
-    models = torch.empty((P, B, 4, 4), device=matches.device, dtype=matches.dtype)
-    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_kabsch_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, k, ptr(models),
-           ptr(valid), stream())
-    return models, valid
+    return _pair_sample_fit("kabsch_gather", 4, matches, idx, (idx.shape[2],))
 
 
 def kabsch_gather_checked(matches: torch.Tensor, idx: torch.Tensor, edge_similarity: float, rejected: Optional[torch.Tensor] = None):
@@ -775,19 +781,27 @@ def kabsch_gather_checked(matches: torch.Tensor, idx: torch.Tensor, edge_similar
         raise L.DransacError("kabsch_gather_checked: correspondences [P,N,6] and int32 index sets [P,B,k]")
     if not 0.0 <= float(edge_similarity) <= 1.0:      # (false for NaN)
         raise L.DransacError(f"kabsch_gather_checked: edge_similarity must lie in [0, 1], got {edge_similarity!r}")
-    P, N, _ = matches.shape
-    _, B, k = idx.shape
-    if rejected is not None and (rejected.shape != (P,) or rejected.dtype != torch.int32):
-        raise L.DransacError("kabsch_gather_checked: rejected must be [P] int32")
-    models = torch.empty((P, B, 4, 4), device=matches.device, dtype=matches.dtype)
-    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_kabsch_gather_checked_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, k,
-           float(edge_similarity), ptr(models), ptr(valid), ptr(rejected), stream())
-    return models, valid
+    _check_counter("kabsch_gather_checked", "rejected", rejected, matches.shape[0])
+    return _pair_sample_fit("kabsch_gather_checked", 4, matches, idx, (idx.shape[2], float(edge_similarity)), (rejected,))
 
 
 # ---- what the families with their per-pair state on the device share (this one and the homographies below): one state class, and one
-# helper each for "score every model", "update the state" and "refit over mask / weights"; a family names its C entry and model side
+# helper each for "fit every sample", "score every model", "update the state", "refit over mask / weights" and "polish"; a family names
+# its C entry and model side.  What more than one helper needs of a family stands in its record, which the training losses at the end
+# of the file read too: the stem of the entries named after it (dr_<entry>_{update,irls,gt_mask,loss_*}), the columns of its matches,
+# its model shape, the nouns of the loss messages, the stem of its refit (dr_<refit>, dr_<refit>_bwd), whether the backward of the
+# weighted fit is once_differentiable, and the text of the shape check its wrappers open with (None: they run none).
+_PairFamily = collections.namedtuple("_PairFamily", "entry width shape points gt_noun refit once shape_text")
+_REGISTRATION = _PairFamily("registration", 6, (4, 4), "correspondences", "pose", "refit_rigid", False, None)
+_HOMOGRAPHY = _PairFamily("homography", 4, (3, 3), "matches", "homography", "refit_homography", True,
+                          "matches [P,N,4] = (x1, y1, x2, y2)")
+
+
+def _check_matches(fam, name: str, matches: torch.Tensor) -> None:
+    if fam.shape_text is not None and (matches.dim() != 3 or matches.shape[-1] != fam.width):
+        raise L.DransacError(f"{name}: {fam.shape_text}")
+
+
 class _PairState:
     """best_score [P] (0), best_model [P,side,side] (identity), best_mask [P,N], best_inliers [P] int32, iters [P] int32,
     max_iters [P] f64 (= max_iterations).  Allocated and filled with torch (capturable)."""
@@ -800,6 +814,18 @@ class _PairState:
         self.iters = torch.zeros(P, device=device, dtype=torch.int32)
         self.max_iters = torch.full((P,), float(max_iterations), device=device, dtype=torch.float64)
         self.max_iterations = int(max_iterations)
+
+
+def _pair_sample_fit(entry: str, side: int, matches, idx, scalars=(), counters=()):
+    """dr_<entry>_{f32,f64}: the fit of every sample idx [P,B,k] names -> (models [P,B,side,side], valid [P,B] bool); `scalars` follow
+    P, B, N by value, `counters` (tensors or None) the outputs"""
+    P, N, _ = matches.shape
+    B = idx.shape[1]
+    models = torch.empty((P, B, side, side), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, *scalars, ptr(models),
+           ptr(valid), *map(ptr, counters), stream())
+    return models, valid
 
 
 def _pair_score(entry: str, matches, models, threshold, valid, want_inliers, thr2, gated: bool = False, gate=None):
@@ -837,6 +863,16 @@ def _pair_refit(entry: str, side: int, matches, mask, weights):
     L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
            ptr(None if weights is None else weights.to(matches.dtype).contiguous()), P, N, ptr(model), ptr(valid), stream())
     return model, valid
+
+
+def _pair_irls(fam, state: _PairState, matches, thr2, irls_iters: int, irls_fits: torch.Tensor) -> None:
+    """dr_<entry>_irls_{f32,f64}: the family's IRLS polish, in place on state.best_model / state.best_score"""
+    _gpu_only((matches, thr2, irls_fits, state.best_score, state.best_model))
+    _check_matches(fam, f"{fam.entry}_irls", matches)
+    P, N, _ = matches.shape
+    _check_counter(f"{fam.entry}_irls", "irls_fits", irls_fits, P)
+    L.call(f"dr_{fam.entry}_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(irls_iters),
+           ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
 
 
 def rigid_msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
@@ -879,18 +915,9 @@ def registration_local_optimize(state: RegistrationState, matches, thr2, lo: int
     where it scores strictly higher), in place on `state`, for the pairs whose best model dr_registration_update replaced since the
     last visit.  thr2 [P] = threshold^2 (thr2_tensor).  lo_seen [P,17] (matches' dtype) is the per-call snapshot, filled with NaN
     before the first round; lo_refits [P] int32 (optional) accumulates the fits run per pair.  One launch, no synchronisation."""
-    tensors = (matches, thr2, lo_seen, lo_refits, state.best_score, state.best_model, state.best_mask, state.best_inliers,
-               state.max_iters)
-    if any(t is not None and not t.is_cuda for t in tensors):
-        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
-    P, N, _ = matches.shape
-    if lo_seen is None or lo_seen.shape != (P, 17) or lo_seen.dtype != matches.dtype or not lo_seen.is_contiguous():
-        raise L.DransacError("registration_local_optimize: lo_seen must be a contiguous [P,17] tensor of the matches' dtype")
-    if lo_refits is not None and (lo_refits.shape != (P,) or lo_refits.dtype != torch.int32):
-        raise L.DransacError("registration_local_optimize: lo_refits must be [P] int32")
-    mi = state.max_iterations if max_iterations is None else max_iterations
+    P, N, mi = _lo_args("registration_local_optimize", 17, state, matches, thr2, lo_seen, lo_refits, max_iterations)
     L.call(f"dr_registration_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(lo), int(lo_iters),
-           confidence, eps, int(mi), ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
+           confidence, eps, mi, ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
            ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits), stream())
 
 
@@ -899,14 +926,7 @@ def registration_irls(state: RegistrationState, matches, thr2, irls_iters: int, 
     times the weights w(s) = (exp(-u_k s) - c) / (1 - c) under the current model, the weighted Kabsch fit over all points and the
     candidate's MAGSAC++ score, taken only where it is strictly higher.  thr2 [P] = threshold^2 (thr2_tensor); irls_fits [P] int32
     grows by the fits run.  Mask, inlier count and counters of the state are left alone.  One launch, no synchronisation."""
-    tensors = (matches, thr2, irls_fits, state.best_score, state.best_model)
-    if any(t is None or not t.is_cuda for t in tensors):
-        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
-    P, N, _ = matches.shape
-    if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
-        raise L.DransacError("registration_irls: irls_fits must be [P] int32")
-    L.call(f"dr_registration_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(irls_iters),
-           ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
+    _pair_irls(_REGISTRATION, state, matches, thr2, irls_iters, irls_fits)
 
 
 def refit_rigid(matches: torch.Tensor, mask: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None):
@@ -922,10 +942,6 @@ def _kabsch_fwd(samples: torch.Tensor, weights: Optional[torch.Tensor]):
     valid = torch.empty((Bt,), device=samples.device, dtype=torch.bool)
     L.call(f"dr_kabsch_{L.suffix(samples.dtype)}", ptr(samples), ptr(weights), Bt, k, ptr(models), ptr(valid), stream())
     return models, valid
-
-
-def _grad_top_rows(g: torch.Tensor, dtype) -> torch.Tensor:
-    return g.to(dtype).reshape(-1, 4, 4).contiguous()
 
 
 def select_closest(models: torch.Tensor, valid: Optional[torch.Tensor], gt: torch.Tensor, want_keep: bool = False):
@@ -1186,8 +1202,8 @@ class _Kabsch(torch.autograd.Function):
         Bt, k, _ = s.shape
         gs = torch.empty_like(s)
         gw = torch.empty((Bt, k), device=s.device, dtype=s.dtype) if (w is not None and ctx.needs_input_grad[1]) else None
-        L.call(f"dr_kabsch_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(w), ptr(_grad_top_rows(g_models, s.dtype)), Bt, k, ptr(gs), ptr(gw),
-               stream())
+        L.call(f"dr_kabsch_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(w), ptr(g_models.to(s.dtype).reshape(-1, 4, 4).contiguous()), Bt, k,
+               ptr(gs), ptr(gw), stream())
         sshape, wshape = ctx.shapes
         return gs.reshape(sshape), None if gw is None else gw.reshape(wshape[0]).to(wshape[1])
 
@@ -1204,16 +1220,33 @@ def kabsch(samples, weights=None):
     return _Kabsch.apply(samples, weights)
 
 
-class _WeightedKabsch(torch.autograd.Function):
-    """dr_refit_rigid / dr_refit_rigid_bwd"""
+def _weighted_fit_bwd(ctx, g_model, _gv):
+    _, want_m, want_w, _ = ctx.needs_input_grad      # (weights = None never wants a gradient)
+    if g_model is None or not (want_m or want_w):
+        return None, None, None, None
+    m, *w = ctx.saved_tensors
+    w = w[0] if w else None
+    P, N, _ = m.shape
+    gm = torch.empty_like(m) if want_m else None
+    gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if want_w else None
+    L.call(f"dr_{ctx.fam.refit}_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w),
+           ptr(g_model.to(m.dtype).reshape(P, *ctx.fam.shape).contiguous()), P, N, ptr(gm), ptr(gw), stream())
+    return None, gm, None if gw is None else gw.to(ctx.wdtype), None
+
+
+class _WeightedFit(torch.autograd.Function):
+    """dr_<refit> / dr_<refit>_bwd of a pair family (`fam` travels in ctx, as in _PairLossFused): the backward recomputes the fit from
+    its inputs, so no model is saved.  Only a family with `once` set refuses a second derivative (once_differentiable); the rigid fit
+    keeps letting one through unrecorded, as it always has."""
 
     @staticmethod
-    def forward(ctx, matches, weights, mask):
+    def forward(ctx, fam, matches, weights, mask):
         ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
         m = matches.contiguous()
         w = None if weights is None else weights.to(m.dtype).contiguous()
-        model, valid = refit_rigid(m, mask, w)
+        model, valid = _pair_refit(fam.refit, fam.shape[0], m, mask, w)
         ctx.save_for_backward(m, *(() if w is None else (w,)))
+        ctx.fam = fam
         ctx.mask = None if mask is None else _u8(mask)
         ctx.wdtype = None if weights is None else weights.dtype
         ctx.mark_non_differentiable(valid)
@@ -1221,16 +1254,8 @@ class _WeightedKabsch(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_model, _gv):
-        if g_model is None or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
-            return None, None, None
-        m, *w = ctx.saved_tensors
-        w = w[0] if w else None
-        P, N, _ = m.shape
-        gm = torch.empty_like(m) if ctx.needs_input_grad[0] else None
-        gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if (w is not None and ctx.needs_input_grad[1]) else None
-        L.call(f"dr_refit_rigid_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w), ptr(_grad_top_rows(g_model, m.dtype)), P, N,
-               ptr(gm), ptr(gw), stream())
-        return gm, None if gw is None else gw.to(ctx.wdtype), None
+        bwd = torch.autograd.function.once_differentiable(_weighted_fit_bwd) if ctx.fam.once else _weighted_fit_bwd
+        return bwd(ctx, g_model, _gv)
 
 
 def weighted_kabsch(matches, weights=None, mask=None):
@@ -1239,31 +1264,20 @@ def weighted_kabsch(matches, weights=None, mask=None):
     Rows the mask drops, and every row of a pair without a valid fit, get exact zeros; bit-repeatable."""
     if matches.dim() != 3 or matches.shape[-1] != 6:
         raise L.DransacError("weighted_kabsch: correspondences [P,N,6]")
-    return _WeightedKabsch.apply(matches, weights, mask)
+    return _WeightedFit.apply(_REGISTRATION, matches, weights, mask)
 
 
 # ------------------------------------------------------------------------------------------ plane-induced homographies
 # matches [P,N,4] = (x1, y1, x2, y2) in the caller's coordinates (pixels), models [.,3,3] = H with x2 ~ H x1, unit Frobenius norm and
 # det > 0.  d2 = the symmetric transfer error; `threshold` is a DISTANCE: inlier iff d2 < threshold^2 (thr2_tensor).
-def _check_matches4(name: str, matches: torch.Tensor) -> None:
-    if matches.dim() != 3 or matches.shape[-1] != 4:
-        raise L.DransacError(f"{name}: matches [P,N,4] = (x1, y1, x2, y2)")
-
-
 def homography4_gather(matches: torch.Tensor, idx: torch.Tensor):
     """dr_homography4_gather: matches [P,N,4], idx [P,B,4] int32 -> (models [P,B,3,3], valid [P,B] bool): the closed-form homography of
     every four-point sample; a sample with three collinear points, with an orientation that differs between the images, or without a
     finite non-singular model is the identity with valid = 0."""
-    _check_matches4("homography4_gather", matches)
+    _check_matches(_HOMOGRAPHY, "homography4_gather", matches)
     if idx.dim() != 3 or idx.shape[-1] != 4 or idx.dtype != torch.int32 or idx.shape[0] != matches.shape[0]:
         raise L.DransacError("homography4_gather: int32 index sets [P,B,4]")
-    P, N, _ = matches.shape
-    B = idx.shape[1]
-    models = torch.empty((P, B, 3, 3), device=matches.device, dtype=matches.dtype)
-    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_homography4_gather_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, ptr(models),
-           ptr(valid), stream())
-    return models, valid
+    return _pair_sample_fit("homography4_gather", 3, matches, idx)
 
 
 def homography_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
@@ -1272,7 +1286,7 @@ def homography_score(matches: torch.Tensor, models: torch.Tensor, threshold, val
     (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None).  A slot with valid = 0
     scores exactly 0; a non-finite model or one with det == 0 scores NaN; a model of negative determinant scores like its negation.
     Bit-repeatable (fixed reduction order)."""
-    _check_matches4("homography_score", matches)
+    _check_matches(_HOMOGRAPHY, "homography_score", matches)
     if models.shape != (matches.shape[0], models.shape[1], 3, 3) or models.dtype != matches.dtype:
         raise L.DransacError("homography_score: models [P,M,3,3] of the matches' dtype")
     return _pair_score("homography_score", matches, models, threshold, valid, want_inliers, thr2)
@@ -1284,7 +1298,7 @@ def homography_magsac_score(matches: torch.Tensor, models: torch.Tensor, thresho
     the cutoff DISTANCE, read as k sigma_max (k^2 = 13.276704135987622, the 0.99 quantile of chi^2 with 4 degrees of freedom: the
     symmetric transfer error is a 4-vector).  With s = d2 / threshold^2: scores [P,M] = sum_n (1 - l(s_n)), l the two-view MAGSAC++ loss
     (magsac_score states it; 1 for s >= 1); inliers = #{d2_n < threshold^2}.  Bit-repeatable."""
-    _check_matches4("homography_magsac_score", matches)
+    _check_matches(_HOMOGRAPHY, "homography_magsac_score", matches)
     if models.shape != (matches.shape[0], models.shape[1], 3, 3) or models.dtype != matches.dtype:
         raise L.DransacError("homography_magsac_score: models [P,M,3,3] of the matches' dtype")
     return _pair_score("homography_magsac_score", matches, models, threshold, valid, want_inliers, thr2)
@@ -1303,7 +1317,7 @@ def homography_update(state: HomographyState, matches, models, valid, scores, th
     """dr_homography_update, in place on `state`: per pair with iters < max_iters the first arg-max of scores [P,M] over valid, non-NaN
     slots replaces the state if score > best_score (mask and inlier count recomputed with the score kernel's expression,
     max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 4))); iters += B."""
-    _check_matches4("homography_update", matches)
+    _check_matches(_HOMOGRAPHY, "homography_update", matches)
     _pair_update("homography_update", state, matches, models, valid, scores, threshold, B, confidence, eps, thr2)
 
 
@@ -1311,7 +1325,7 @@ def refit_homography(matches: torch.Tensor, mask: Optional[torch.Tensor] = None,
     """dr_refit_homography: the normalised DLT over the rows mask [P,N] selects (None = all), weights [P,N] (optional) multiplying a
     row's terms in the Gram matrix -> (model [P,3,3], valid [P] bool); valid = 0 (identity) below four rows or for a non-finite or
     singular result."""
-    _check_matches4("refit_homography", matches)
+    _check_matches(_HOMOGRAPHY, "refit_homography", matches)
     return _pair_refit("refit_homography", 3, matches, mask, weights)
 
 
@@ -1321,15 +1335,7 @@ def homography_irls(state: HomographyState, matches, thr2, irls_iters: int, irls
     w(d2 / thr2) (f64), refit_homography's weighted DLT over them and the candidate's homography_magsac_score score over all points,
     taken only where it is strictly higher.  thr2 [P] = threshold^2 (thr2_tensor); irls_fits [P] int32 grows by the fits run.  Mask,
     inlier count and counters of the state are left alone.  One launch, no synchronisation."""
-    tensors = (matches, thr2, irls_fits, state.best_score, state.best_model)
-    if any(t is None or not t.is_cuda for t in tensors):
-        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
-    _check_matches4("homography_irls", matches)
-    P, N, _ = matches.shape
-    if irls_fits.shape != (P,) or irls_fits.dtype != torch.int32:
-        raise L.DransacError("homography_irls: irls_fits must be [P] int32")
-    L.call(f"dr_homography_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(irls_iters),
-           ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
+    _pair_irls(_HOMOGRAPHY, state, matches, thr2, irls_iters, irls_fits)
 
 
 class _Homography4(torch.autograd.Function):
@@ -1370,37 +1376,6 @@ def homography4(samples):
     return _Homography4.apply(samples)
 
 
-class _WeightedHomography(torch.autograd.Function):
-    """dr_refit_homography / dr_refit_homography_bwd: the backward recomputes the fit from its inputs, so no model is saved"""
-
-    @staticmethod
-    def forward(ctx, matches, weights, mask):
-        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
-        m = matches.contiguous()
-        w = None if weights is None else weights.to(m.dtype).contiguous()
-        model, valid = refit_homography(m, mask, w)
-        ctx.save_for_backward(m, *(() if w is None else (w,)))
-        ctx.mask = None if mask is None else _u8(mask)
-        ctx.wdtype = None if weights is None else weights.dtype
-        ctx.mark_non_differentiable(valid)
-        return model, valid
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_model, _gv):
-        want_m, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if g_model is None or not (want_m or want_w):
-            return None, None, None
-        m, *w = ctx.saved_tensors
-        w = w[0] if w else None
-        P, N, _ = m.shape
-        gm = torch.empty_like(m) if want_m else None
-        gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if want_w else None
-        L.call(f"dr_refit_homography_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w),
-               ptr(g_model.to(m.dtype).reshape(P, 9).contiguous()), P, N, ptr(gm), ptr(gw), stream())
-        return gm, None if gw is None else gw.to(ctx.wdtype), None
-
-
 def weighted_homography(matches, weights=None, mask=None):
     """matches [P,N,4], weights [P,N] | None, mask [P,N] | None -> (model [P,3,3], valid [P] bool): refit_homography (the normalised
     DLT over the rows the mask selects, a row's weight multiplying its terms in the Gram matrix; the same entry, the same bits) with
@@ -1419,9 +1394,8 @@ def weighted_homography(matches, weights=None, mask=None):
         raise L.DransacError("weighted_homography: weights must be floating point [P,N], one per row of matches")
     if mask is not None and (mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
         raise L.DransacError("weighted_homography: mask must be bool or uint8 [P,N]")
-    if any(t is not None and not t.is_cuda for t in (matches, weights, mask)):
-        raise L.DransacError("libdransac operates on GPU tensors only (got a CPU tensor)")
-    return _WeightedHomography.apply(matches, weights, mask)
+    _gpu_only((matches, weights, mask), optional=True)
+    return _WeightedFit.apply(_HOMOGRAPHY, matches, weights, mask)
 
 
 class _MsacScore(torch.autograd.Function):
@@ -1704,13 +1678,9 @@ def match_loss_per_pair(matches, mask, models, keep=None):
 # RegistrationLoss (3-D path): the truncated squared distance of every model on the ground-truth inliers (include/dransac.h, "The
 # training loss of the registration path"): matches [P,N,6], mask [P,N] bool | None, models [P,M,4,4], keep [P,M] bool | None.
 # HomographyLoss (homography path): the truncated symmetric transfer error (include/dransac.h, "The training loss of the homography
-# path"): matches [P,N,4], models [P,M,3,3] of any scale and either sign.  threshold = DISTANCE in both.  One implementation behind a
-# family record: the C entries dr_<entry>_{gt_mask,loss_fwd,loss_fused,loss_scale}, the match width, the model shape, the messages' nouns.
-_PairLossFamily = collections.namedtuple("_PairLossFamily", "entry width shape points gt_noun")
-_REGISTRATION_LOSS = _PairLossFamily("registration", 6, (4, 4), "correspondences", "pose")
-_HOMOGRAPHY_LOSS = _PairLossFamily("homography", 4, (3, 3), "matches", "homography")
-
-
+# path"): matches [P,N,4], models [P,M,3,3] of any scale and either sign.  threshold = DISTANCE in both.  One implementation behind the
+# family record (_PairFamily): the C entries dr_<entry>_{gt_mask,loss_fwd,loss_fused,loss_scale}, the match width, the model shape, the
+# messages' nouns.
 def _pair_gt_mask(fam, matches, gt_model, threshold):
     P, N, _ = matches.shape
     r, c = fam.shape
@@ -1793,7 +1763,7 @@ def _pair_loss_sums(fam, matches, mask, models, threshold, keep, want_pairs):
 def registration_gt_mask(matches: torch.Tensor, gt_pose: torch.Tensor, threshold):
     """dr_registration_gt_mask: matches [P,N,6], gt_pose [P,4,4], threshold (float or [P]) -> (mask [P,N] bool = the points within the
     distance threshold of the pair's ground-truth pose, count [P] int32)."""
-    return _pair_gt_mask(_REGISTRATION_LOSS, matches, gt_pose, threshold)
+    return _pair_gt_mask(_REGISTRATION, matches, gt_pose, threshold)
 
 
 def registration_loss_mean(matches, mask, models, threshold, keep=None):
@@ -1802,20 +1772,20 @@ def registration_loss_mean(matches, mask, models, threshold, keep=None):
     gradient come from one pass over the (model x point) grid (_PairLossFused), otherwise the value-only kernel runs.
     Correspondences that require grad are refused (detach them): no gradient is computed for them, and BatchedRegistration(train=True)
     does pass one to `matches`, so a silent zero here would be half a gradient."""
-    return _pair_loss_mean(_REGISTRATION_LOSS, matches, mask, models, threshold, keep)
+    return _pair_loss_mean(_REGISTRATION, matches, mask, models, threshold, keep)
 
 
 def registration_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool = False):
     """sums [P,M] = sum over the masked points of min(d2 / threshold^2, 1) for every model (0 for a slot keep drops); no autograd.
     want_pairs: -> (sums, per_pair [P]) with the per-pair means registration_loss_mean averages."""
-    return _pair_loss_sums(_REGISTRATION_LOSS, matches, mask, models, threshold, keep, want_pairs)
+    return _pair_loss_sums(_REGISTRATION, matches, mask, models, threshold, keep, want_pairs)
 
 
 def homography_gt_mask(matches: torch.Tensor, gt_H: torch.Tensor, threshold):
     """dr_homography_gt_mask: matches [P,N,4], gt_H [P,3,3], threshold (float or [P]) -> (mask [P,N] bool = the points homography_score
     counts as inliers of the pair's ground-truth homography, count [P] int32)."""
-    _check_matches4("homography_gt_mask", matches)
-    return _pair_gt_mask(_HOMOGRAPHY_LOSS, matches, gt_H, threshold)
+    _check_matches(_HOMOGRAPHY, "homography_gt_mask", matches)
+    return _pair_gt_mask(_HOMOGRAPHY, matches, gt_H, threshold)
 
 
 def homography_loss_mean(matches, mask, models, threshold, keep=None):
@@ -1824,13 +1794,13 @@ def homography_loss_mean(matches, mask, models, threshold, keep=None):
     w.r.t. `models` only; when they require grad, value and gradient come from one pass over the (model x point) grid
     (_PairLossFused), otherwise the value-only kernel runs.  Matches that require grad are refused (detach them): no gradient
     is computed for them, and BatchedHomography(train=True) does pass one to `matches`, so a silent zero here would be half a gradient."""
-    return _pair_loss_mean(_HOMOGRAPHY_LOSS, matches, mask, models, threshold, keep)
+    return _pair_loss_mean(_HOMOGRAPHY, matches, mask, models, threshold, keep)
 
 
 def homography_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool = False):
     """sums [P,M] = sum over the masked points of the truncated d2 / threshold^2 for every model (0 for a slot keep drops); no autograd.
     want_pairs: -> (sums, per_pair [P]) with the per-pair means homography_loss_mean averages."""
-    return _pair_loss_sums(_HOMOGRAPHY_LOSS, matches, mask, models, threshold, keep, want_pairs)
+    return _pair_loss_sums(_HOMOGRAPHY, matches, mask, models, threshold, keep, want_pairs)
 
 
 # ------------------------------------------------------------------------------------------ PoseLoss pose error (8(f) rank 3)

@@ -57,6 +57,15 @@ def _check_lo(lo, lo_iters):
         raise ValueError(f"lo_iters must be at least 1, got {lo_iters!r}")
 
 
+def _check_scoring(scoring, irls_iters=0):
+    """scoring "msac" / "magsac" and irls_iters an int (no bool) of at least 0; BatchedRegistration reads its irls_iters through int()
+    and checks it itself (_PairStateDriver.__init__)"""
+    if scoring not in ("msac", "magsac"):
+        raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
+    if isinstance(irls_iters, bool) or not isinstance(irls_iters, int) or irls_iters < 0:
+        raise ValueError(f"irls_iters must be an int of at least 0, got {irls_iters!r}")
+
+
 def _is_gumbel(sampler_id):
     # ids 2 and 3 in the reference; id 1 builds a Gumbel sampler there too but then crashes (Q16): treated as 2
     return sampler_id in (1, 2, 3)
@@ -558,10 +567,7 @@ class BatchedRANSAC(_SeededDriver):
         # (ops.magsac_score) in its place -- dr_ransac_update, super-rounds and device_termination as they are -- and, with
         # refit=True and irls_iters > 0, the IRLS polish under that loss (ops.magsac_irls, up to irls_iters weighted refits) in the place
         # of the final refit and its acceptance step; the result gains irls_fits [P].  mask and inliers stay dr_ransac_update's.
-        if scoring not in ("msac", "magsac"):
-            raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
-        if isinstance(irls_iters, bool) or not isinstance(irls_iters, int) or irls_iters < 0:
-            raise ValueError(f"irls_iters must be an int of at least 0, got {irls_iters!r}")
+        _check_scoring(scoring, irls_iters)
         if scoring == "magsac":
             if train:
                 raise ValueError("scoring='magsac' is a test-mode score: train mode scores nothing")
@@ -1009,10 +1015,17 @@ class _PairStateDriver(_SeededDriver):
     """What BatchedRegistration and BatchedHomography share: the constructor's common checks and attributes, the index sets of a round
     (Gumbel top-k or PROSAC, one seed per round), the train loop (ops.SampleGather -> the family's differentiable fit) and the test
     loop on a per-pair state on the device (draw -> fit -> score -> update -> _after_update -> read-back of "does any pair continue?"),
-    and the final refit, taken where it scores strictly higher.  A family sets `k`, `_columns` / `_shape_error`, `_State` and the ops
-    `_fit`, `_fit_train`, `_score`, `_update`, `_refit`; what else it does hangs on _begin, _after_update, _stop_after and _finish."""
+    and the final stage: the refit, taken where it scores strictly higher, or under scoring="magsac" the IRLS polish.  The constructor
+    checks the options of both families once.  A family sets `k`, `_columns` / `_shape_error`, `_State` and the ops `_fit`, `_fit_train`,
+    `_score_msac`, `_score_magsac`, `_update`, `_refit`, `_irls`, and switches on what it supports: local optimisation by taking `lo` /
+    `lo_iters` and naming `_lo_width` and `_local_optimize`, device_termination by exposing `_device_termination_switch` under that
+    name.  What else it does hangs on _begin, _fit and _finish."""
 
-    def __init__(self, ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws):
+    _irls_strict = True      # irls_iters must be an int (no bool); False: whatever int() reads, as BatchedRegistration always took it
+
+    def __init__(self, ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws,
+                 scoring, irls_iters, lo=0, lo_iters=64):
+        _check_lo(lo, lo_iters)
         if sampling not in ("gumbel", "prosac"):
             raise ValueError(f"sampling must be 'gumbel' or 'prosac', got {sampling!r}")
         if sampling == "prosac" and train:
@@ -1032,6 +1045,29 @@ class _PairStateDriver(_SeededDriver):
         self.refit = refit
         self.eps = eps
         self.train = bool(train)
+        if lo and train:
+            raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
+        _check_scoring(scoring, irls_iters if self._irls_strict else 0)
+        if scoring == "magsac" and lo:
+            raise ValueError("scoring='magsac' with lo != 0 is refused: dr_registration_local_opt scores its candidates with MSAC")
+        if scoring == "magsac" and train:
+            raise ValueError("scoring='magsac' with train=True is refused: train mode scores nothing")
+        if int(irls_iters) < 0:
+            raise ValueError(f"irls_iters must be at least 0, got {irls_iters!r}")
+        self.lo = int(lo)
+        self.lo_iters = int(lo_iters)
+        self.scoring = scoring
+        self.irls_iters = int(irls_iters)
+        self._device_termination = False
+
+    def _switch_device_termination(self, on):
+        if on and self.rounds > 16:
+            raise ValueError(f"device_termination issues every round: at most 16 rounds per call, this driver has {self.rounds} "
+                             "(raise ransac_batch_size or lower max_iterations)")
+        self._device_termination = bool(on)
+
+    # device_termination = True: every round is issued, gated on the device, and nothing is read back (a family exposes it by this name)
+    _device_termination_switch = property(lambda self: self._device_termination, _switch_device_termination)
 
     @property
     def rounds(self):
@@ -1072,11 +1108,18 @@ class _PairStateDriver(_SeededDriver):
         pass
 
     def _begin(self, matches, rounds):
-        """the state of a test-mode call: c.matches (contiguous), c.P, c.N, c.st, c.thr2"""
+        """the state of a test-mode call: c.matches (contiguous), c.P, c.N, c.st, c.thr2, and under lo the buffers of the LO launches"""
+        if self._device_termination and rounds > 16:      # (max_iterations / ransac_batch_size assigned after the switch)
+            raise ValueError("device_termination issues every round: at most 16 rounds per call")
         P, N, _ = matches.shape
         matches = matches.contiguous()
         st = self._State(P, N, self.max_iterations, matches.device, matches.dtype)
-        return types.SimpleNamespace(matches=matches, P=P, N=N, st=st, thr2=ops.thr2_tensor(self.threshold, P, matches))
+        c = types.SimpleNamespace(matches=matches, P=P, N=N, st=st, thr2=ops.thr2_tensor(self.threshold, P, matches))
+        c.lo_seen = c.lo_refits = None
+        if self.lo:
+            c.lo_seen = torch.full((P, self._lo_width), float("nan"), device=matches.device, dtype=matches.dtype)
+            c.lo_refits = torch.zeros(P, device=matches.device, dtype=torch.int32)
+        return c
 
     def _draw(self, c, r, logits, g):
         """the index sets of round r; under PROSAC its rows are draws r B + 1 .. (r + 1) B (t0 goes by value: a captured call replays it)"""
@@ -1085,22 +1128,38 @@ class _PairStateDriver(_SeededDriver):
                                      device=c.matches.device)
         return ops.gumbel_topk(logits, self.B, self.k, self.tau, g, self._seeds.next(), soft=False)["idx"]
 
+    def _score(self, c, r, models, valid):
+        """round r's models under the driver's scoring, under device_termination gated on the device from the second round on;
+        r = None: a refit candidate (MSAC)"""
+        score_fn = self._score_magsac if (r is not None and self.scoring == "magsac") else self._score_msac
+        if self._device_termination and r:
+            return score_fn(c.matches, models, None, valid, want_inliers=False, gate=c.st, thr2=c.thr2)[0]
+        return score_fn(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
+
     def _after_update(self, c):
-        pass
+        if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
+            self._local_optimize(c.st, c.matches, c.thr2, self.lo, self.lo_iters, self.confidence, self.eps, self.max_iterations,
+                                 c.lo_seen, c.lo_refits)
 
     def _stop_after(self, c, r, rounds):
-        """the read-back after round r: has every pair terminated"""
-        return r + 1 < rounds and not bool((c.st.iters.double() < c.st.max_iters).any())
+        """the read-back after round r: has every pair terminated (none under device_termination)"""
+        return not self._device_termination and r + 1 < rounds and not bool((c.st.iters.double() < c.st.max_iters).any())
 
     def _finish(self, c):
-        model, score = c.st.best_model, c.st.best_score
-        if self.refit:
+        model, score, extra = c.st.best_model, c.st.best_score, {}
+        if self.scoring == "magsac":      # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
+            extra["irls_fits"] = torch.zeros(c.P, device=c.matches.device, dtype=torch.int32)
+            if self.refit and self.irls_iters > 0:
+                self._irls(c.st, c.matches, c.thr2, self.irls_iters, extra["irls_fits"])
+        elif self.refit:
             cand, cvalid = self._refit(c.matches, c.st.best_mask)
             cscore = self._score(c, None, cand.unsqueeze(1), cvalid.unsqueeze(1))
             take = cscore[:, 0] > score          # (an invalid candidate scores -1 or 0, a NaN never compares higher: neither wins)
             model = torch.where(take[:, None, None], cand, model)
             score = torch.where(take, cscore[:, 0], score)
-        return dict(model=model, mask=c.st.best_mask, score=score, inliers=c.st.best_inliers, iterations=c.st.iters)
+        if self.lo:
+            extra["lo_refits"] = c.lo_refits
+        return dict(model=model, mask=c.st.best_mask, score=score, inliers=c.st.best_inliers, iterations=c.st.iters, **extra)
 
 
 class BatchedRegistration(_PairStateDriver):
@@ -1159,18 +1218,8 @@ class BatchedRegistration(_PairStateDriver):
     def __init__(self, ransac_batch_size=1024, threshold=0.05, confidence=0.999, max_iterations=5000, tau=1.0, seed=0,
                  num_samples=3, refit=True, eps=1e-5, train=False, lo=0, lo_iters=64, scoring="msac", irls_iters=10,
                  edge_similarity=None, sampling="gumbel", prosac_draws=200000):
-        _check_lo(lo, lo_iters)
-        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws)
-        if lo and train:
-            raise ValueError("lo (local optimisation) is a test-mode step: lo != 0 with train=True is refused")
-        if scoring not in ("msac", "magsac"):
-            raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
-        if scoring == "magsac" and lo:
-            raise ValueError("scoring='magsac' with lo != 0 is refused: dr_registration_local_opt scores its candidates with MSAC")
-        if scoring == "magsac" and train:
-            raise ValueError("scoring='magsac' with train=True is refused: train mode scores nothing")
-        if int(irls_iters) < 0:
-            raise ValueError(f"irls_iters must be at least 0, got {irls_iters!r}")
+        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws,
+                         scoring, irls_iters, lo, lo_iters)
         if edge_similarity is not None:
             if not 0.0 < float(edge_similarity) <= 1.0:      # (false for NaN)
                 raise ValueError(f"edge_similarity must be None or lie in (0, 1], got {edge_similarity!r}")
@@ -1180,38 +1229,23 @@ class BatchedRegistration(_PairStateDriver):
         if not 3 <= int(num_samples) <= 8:
             raise ValueError(f"num_samples must be between 3 and 8 points per sample, got {num_samples!r}")
         self.k = int(num_samples)
-        self.lo = int(lo)
-        self.lo_iters = int(lo_iters)
-        self.scoring = scoring
-        self.irls_iters = int(irls_iters)
         self.edge_similarity = None if edge_similarity is None else float(edge_similarity)
-        self._device_termination = False
 
-    @property
-    def device_termination(self):
-        return self._device_termination
-
-    @device_termination.setter
-    def device_termination(self, on):
-        if on and self.rounds > 16:
-            raise ValueError(f"device_termination issues every round: at most 16 rounds per call, this driver has {self.rounds} "
-                             "(raise ransac_batch_size or lower max_iterations)")
-        self._device_termination = bool(on)
-
+    _irls_strict = False
+    device_termination = _PairStateDriver._device_termination_switch
     _columns, _shape_error = 6, "matches must be [P,N,6] = (p, q)"
     _State = ops.RegistrationState
     _fit_train = staticmethod(ops.kabsch)
+    _score_msac = staticmethod(ops.rigid_msac_score)
+    _score_magsac = staticmethod(ops.rigid_magsac_score)
     _update = staticmethod(ops.registration_update)
     _refit = staticmethod(ops.refit_rigid)
+    _irls = staticmethod(ops.registration_irls)
+    _lo_width, _local_optimize = 17, staticmethod(ops.registration_local_optimize)
 
     def _begin(self, matches, rounds):
-        if self._device_termination and rounds > 16:      # (max_iterations / ransac_batch_size assigned after the switch)
-            raise ValueError("device_termination issues every round: at most 16 rounds per call")
         c = super()._begin(matches, rounds)
-        c.lo_seen = c.lo_refits = c.rejected = None
-        if self.lo:
-            c.lo_seen = torch.full((c.P, 17), float("nan"), device=matches.device, dtype=matches.dtype)
-            c.lo_refits = torch.zeros(c.P, device=matches.device, dtype=torch.int32)
+        c.rejected = None
         if self.edge_similarity is not None:
             c.rejected = torch.zeros(c.P, device=matches.device, dtype=torch.int32)
         return c
@@ -1221,33 +1255,8 @@ class BatchedRegistration(_PairStateDriver):
             return ops.kabsch_gather(c.matches, idx)
         return ops.kabsch_gather_checked(c.matches, idx, self.edge_similarity, c.rejected)
 
-    def _score(self, c, r, models, valid):
-        """round r's models under the driver's scoring, gated on the device from the second round on; r = None: a refit candidate (MSAC)"""
-        if r is None:
-            return ops.rigid_msac_score(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
-        score_fn = ops.rigid_magsac_score if self.scoring == "magsac" else ops.rigid_msac_score
-        gate = c.st if (self._device_termination and r > 0) else None
-        return score_fn(c.matches, models, None, valid, want_inliers=False, gate=gate, thr2=c.thr2)[0]
-
-    def _after_update(self, c):
-        if self.lo:     # (gates itself on the device: pairs the round left alone return at once)
-            ops.registration_local_optimize(c.st, c.matches, c.thr2, self.lo, self.lo_iters, self.confidence, self.eps,
-                                            self.max_iterations, c.lo_seen, c.lo_refits)
-
-    def _stop_after(self, c, r, rounds):
-        return not self._device_termination and super()._stop_after(c, r, rounds)
-
     def _finish(self, c):
-        if self.scoring == "magsac":      # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
-            irls_fits = torch.zeros(c.P, device=c.matches.device, dtype=torch.int32)
-            if self.refit and self.irls_iters > 0:
-                ops.registration_irls(c.st, c.matches, c.thr2, self.irls_iters, irls_fits)
-            out = dict(model=c.st.best_model, mask=c.st.best_mask, score=c.st.best_score, inliers=c.st.best_inliers,
-                       iterations=c.st.iters, irls_fits=irls_fits)
-        else:
-            out = super()._finish(c)
-            if self.lo:
-                out["lo_refits"] = c.lo_refits
+        out = super()._finish(c)
         if c.rejected is not None:
             out["rejected"] = c.rejected
         return out
@@ -1291,21 +1300,17 @@ class BatchedHomography(_PairStateDriver):
 
     def __init__(self, ransac_batch_size=1024, threshold=3.0, confidence=0.999, max_iterations=5000, tau=1.0, seed=0, refit=True,
                  eps=1e-5, train=False, sampling="gumbel", prosac_draws=200000, scoring="msac", irls_iters=10):
-        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws)
-        if scoring not in ("msac", "magsac"):
-            raise ValueError(f"scoring must be 'msac' or 'magsac', got {scoring!r}")
-        if isinstance(irls_iters, bool) or not isinstance(irls_iters, int) or irls_iters < 0:
-            raise ValueError(f"irls_iters must be an int of at least 0, got {irls_iters!r}")
-        if scoring == "magsac" and train:
-            raise ValueError("scoring='magsac' with train=True is refused: train mode scores nothing")
-        self.scoring = scoring
-        self.irls_iters = irls_iters
+        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, train, sampling, prosac_draws,
+                         scoring, irls_iters)
 
     _columns, _shape_error = 4, "matches must be [P,N,4] = (x1, y1, x2, y2)"
     _State = ops.HomographyState
     _fit_train = staticmethod(ops.homography4)
+    _score_msac = staticmethod(ops.homography_score)
+    _score_magsac = staticmethod(ops.homography_magsac_score)
     _update = staticmethod(ops.homography_update)
     _refit = staticmethod(ops.refit_homography)
+    _irls = staticmethod(ops.homography_irls)
 
     def _check_train(self, matches, logits):
         if logits.dtype != matches.dtype:      # (the straight-through weights are read in the matches' type)
@@ -1313,17 +1318,3 @@ class BatchedHomography(_PairStateDriver):
 
     def _fit(self, c, idx):
         return ops.homography4_gather(c.matches, idx)
-
-    def _score(self, c, r, models, valid):
-        score_fn = ops.homography_magsac_score if self.scoring == "magsac" else ops.homography_score
-        return score_fn(c.matches, models, None, valid, want_inliers=False, thr2=c.thr2)[0]
-
-    def _finish(self, c):
-        if self.scoring != "magsac":
-            return super()._finish(c)
-        # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
-        irls_fits = torch.zeros(c.P, device=c.matches.device, dtype=torch.int32)
-        if self.refit and self.irls_iters > 0:
-            ops.homography_irls(c.st, c.matches, c.thr2, self.irls_iters, irls_fits)
-        return dict(model=c.st.best_model, mask=c.st.best_mask, score=c.st.best_score, inliers=c.st.best_inliers,
-                    iterations=c.st.iters, irls_fits=irls_fits)
