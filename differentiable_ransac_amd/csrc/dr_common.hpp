@@ -60,6 +60,19 @@ void allow_dynamic_lds(size_t bytes) {
   }
 }
 
+// SIMDs of the current device (4 per CU), cached per device: one process may drive several GPUs
+inline int device_simds() {
+  static int simds[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1024;
+  if (!simds[dev]) {
+    int cus = 256;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    simds[dev] = 4 * (cus > 0 ? cus : 256);
+  }
+  return simds[dev];
+}
+
 // Per-pair gate of the multi-round test-mode drivers (round 5: device-side termination): a pair whose iteration counter has
 // reached its adaptive bound (ransac.py:135-144, kept on the device by dr_ransac_update) has terminated; the kernels of later rounds
 // return at once for its blocks -- nothing about a round is read back by the host, so a whole multi-round call is one HIP graph.

@@ -304,14 +304,8 @@ namespace dr {
 // groups per block: the smallest count for which all waves of the launch are resident at once (`per_simd` = waves per SIMD the
 // callers pass; 4 for both directions: the backward kernel holds three, but six groups per block measured 61 us against 56 us with four), clamped to [1, 16]
 static int episym_groups(int P, int M, int per_simd) {
-  static int simds = 0;
-  if (!simds) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    simds = 4 * (cus > 0 ? cus : 256);
-  }
   const long wave_models = ((long)P * M + kEMW - 1) / kEMW;       // (wave, group) work items
-  const long capacity = (long)simds * per_simd;
+  const long capacity = (long)device_simds() * per_simd;
   long g = (wave_models + capacity - 1) / capacity;
   return (int)(g < 1 ? 1 : (g > 16 ? 16 : g));
 }

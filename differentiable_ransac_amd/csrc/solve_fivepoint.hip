@@ -281,19 +281,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
   }
 }
 
-// SIMDs of the current device (4 per CU), cached per device: one process may drive several GPUs
-static inline int device_simds() {
-  static int simds[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 1024;
-  if (!simds[dev]) {
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    simds[dev] = 4 * (cus > 0 ? cus : 256);
-  }
-  return simds[dev];
-}
-
 // samples per 64-lane block of the two-lanes-per-sample kernels: 32, or fewer (down to 4) while the grid stays within one block
 // per SIMD -- a one-pair call (1024 samples) is 256 blocks of 4 samples instead of 32 blocks of 32 on 1024 SIMDs.  Always even
 // (>= 4).

@@ -322,13 +322,8 @@ int rigid_residual_launch(const T *pts, const T *models, T threshold, int P, int
       // models = 1 525 blocks, one round.
       constexpr int kPts = 8;
       constexpr int kChunkL = kR16Threads * kPts;
-      static int resident = 0;
-      if (!resident) {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-        // resident 2-wave blocks per CU: 76 registers = six waves per SIMD
-        resident = 12 * max(cus, 1);
-      }
+      // resident 2-wave blocks: 76 registers = six waves per SIMD, three blocks
+      const int resident = 3 * device_simds();
       const int chunks = (N + kChunkL - 1) / kChunkL;
       int ny = chunks;                      // one chunk per block whenever the row is longer than a chunk (atomics across them)
       const long per_tile = (long)P * ny;                       // blocks added by one more tile

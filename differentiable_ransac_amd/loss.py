@@ -59,7 +59,7 @@ class MatchLoss(object):
             with torch.no_grad():
                 gt_mask = ops.recover_pose_mask(matches, gt_E)[0][:, 0]
         # per pair: sum of the clamped errors / max(#masked points * #kept models, 1), then the mean over the pairs -- two
-        # launches forward, one backward (ops._MatchLossMean)
+        # launches forward, one backward; one pass and one elementwise launch when the models require grad (ops.match_loss_mean)
         return ops.match_loss_mean(matches, gt_mask, models, keep)
 
     __call__ = forward

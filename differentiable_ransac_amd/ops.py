@@ -1485,7 +1485,7 @@ def select_closest_autograd(models, valid, gt, want_keep: bool = False):
 
 # ------------------------------------------------------------------------------------------ MatchLoss residual (8(f) rank 2)
 def _episym_fwd(matches, mask, models, valid):
-    """dr_episym_fwd_f32, the first launch of the three nodes below -> (matches, models: contiguous; mask, valid: as bytes or None;
+    """dr_episym_fwd_f32, the first launch of every reduction below -> (matches, models: contiguous; mask, valid: as bytes or None;
     sums [P,M]: every slot is written, an invalid one with 0)"""
     P, N, _ = matches.shape
     M = models.shape[1]
@@ -1496,94 +1496,69 @@ def _episym_fwd(matches, mask, models, valid):
     return matches, models, mk, v, sums
 
 
-class _EpisymSums(torch.autograd.Function):
+# What is made of the sums, one record per reduction: the wrapper's name (for its messages), the entry launched after the episym
+# forward (None: the sums are the result), the outputs that entry writes, in its order (the mean where there is one, else the
+# per-pair means, is the result; coef is saved for the backward), the backward entry (one episym_kernel<1> launch each), and what
+# stands in its gradient argument(s): (upstream gradient, [coef] as saved, dtype) -> tensors.
+_Reduction = collections.namedtuple("_Reduction", "name reduce outs bwd grad")
+_SUMS = _Reduction("episym_sums", None, (), "dr_episym_bwd_f32", lambda g, coef, dt: (g.contiguous(),))
+# (the per-pair gradient goes straight into the episym backward: one tiny torch op, no [P,M] gradient tensor)
+_PER_PAIR = _Reduction("match_loss_per_pair", "dr_match_loss_pair_f32", ("per_pair", "coef"), "dr_episym_bwd_pair_f32",
+                       lambda g, coef, dt: ((g * coef[0]).contiguous(),))
+# (per-pair means AND their mean over the pairs in one launch; dr_episym_bwd_mean reads the upstream scalar gradient from device memory)
+_MEAN = _Reduction("match_loss_mean", "dr_match_loss_mean_f32", ("per_pair", "coef", "mean"), "dr_episym_bwd_mean_f32",
+                   lambda g, coef, dt: (coef[0], g.to(dt).contiguous()))
+
+
+class _Episym(torch.autograd.Function):
+    """The episym forward and one reduction of its sums (`red` travels in ctx: a Function cannot be parameterised by instance): one
+    launch, or two with a reduce entry; the backward is one launch."""
+
     @staticmethod
-    def forward(ctx, matches, mask, models, valid):
-        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
-        _, _, mk, v, sums = _episym_fwd(matches, mask, models, valid)
-        ctx.save_for_backward(matches, models)
+    def forward(ctx, red, matches, mask, models, valid):
+        given = (matches, models)
+        matches, models, mk, v, sums = _episym_fwd(matches, mask, models, valid)
+        ctx.red, ctx.aux = red, (mk, v)
+        if red.reduce is None:
+            ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+            ctx.save_for_backward(*given)      # (as given: the backward makes them contiguous once more)
+            return sums
+        (P, N, _), M = matches.shape, models.shape[1]
+        dev, dt = matches.device, matches.dtype
+        per_pair, coef = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt)
+        mean = (torch.empty((), device=dev, dtype=dt),) if "mean" in red.outs else ()
+        L.call(red.reduce, ptr(sums), ptr(mk), ptr(v), P, M, N, ptr(per_pair), ptr(coef), *map(ptr, mean), stream())
+        ctx.save_for_backward(matches, models, coef)
         ctx.aux = (mk, v)
-        return sums
+        return mean[0] if mean else per_pair
 
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return None, None, None, None
-        matches, models = ctx.saved_tensors
+            return None, None, None, None, None
+        red = ctx.red
+        matches, models, *coef = ctx.saved_tensors
+        if red.reduce is None:
+            matches, models = matches.contiguous(), models.contiguous()
         mk, v = ctx.aux
         P, N, _ = matches.shape
         M = models.shape[1]
+        grad = red.grad(g, coef, matches.dtype)
         gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call("dr_episym_bwd_f32", ptr(matches.contiguous()), ptr(mk), ptr(models.contiguous()), ptr(v), ptr(g.contiguous()), P, M, N,
-               ptr(gm), stream())
-        return None, None, gm, None
+        L.call(red.bwd, ptr(matches), ptr(mk), ptr(models), ptr(v), *map(ptr, grad), P, M, N, ptr(gm), stream())
+        return None, None, None, gm, None
+
+
+def _episym(red, matches, mask, models, valid):
+    if matches.dtype != torch.float32:
+        raise L.DransacError(f"{red.name} is implemented for f32")
+    return _Episym.apply(red, matches, mask, models.reshape(models.shape[0], -1, 3, 3), valid)
 
 
 def episym_sums(matches, mask, models, valid=None):
     """sum over masked points of min(symmetric epipolar error, 1) for every model: matches [P,N,4], mask [P,N] bool |
     None, models [P,M,3,3], valid [P,M] bool | None -> [P,M] (differentiable w.r.t. models, f32)."""
-    if matches.dtype != torch.float32:
-        raise L.DransacError("episym_sums is implemented for f32")
-    return _EpisymSums.apply(matches, mask, models.reshape(models.shape[0], -1, 3, 3), valid)
-
-
-class _MatchLossPair(torch.autograd.Function):
-    """episym forward + the per-pair reduction of MatchLoss in two launches; backward in one tiny torch op + one launch
-    (the per-pair gradient goes straight into the episym backward: no [P,M] gradient tensor)."""
-
-    @staticmethod
-    def forward(ctx, matches, mask, models, keep):
-        matches, models, mk, v, sums = _episym_fwd(matches, mask, models, keep)
-        (P, N, _), M = matches.shape, models.shape[1]
-        per_pair = torch.empty((P,), device=matches.device, dtype=matches.dtype)
-        coef = torch.empty((P,), device=matches.device, dtype=matches.dtype)
-        L.call("dr_match_loss_pair_f32", ptr(sums), ptr(mk), ptr(v), P, M, N, ptr(per_pair), ptr(coef), stream())
-        ctx.save_for_backward(matches, models, coef)
-        ctx.aux = (mk, v)
-        return per_pair
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return None, None, None, None
-        matches, models, coef = ctx.saved_tensors
-        mk, v = ctx.aux
-        P, N, _ = matches.shape
-        M = models.shape[1]
-        gp = (g * coef).contiguous()
-        gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call("dr_episym_bwd_pair_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), ptr(gp), P, M, N, ptr(gm), stream())
-        return None, None, gm, None
-
-
-class _MatchLossMean(torch.autograd.Function):
-    """MatchLoss down to the scalar: episym forward + dr_match_loss_mean (per-pair means AND their mean over the pairs) in two
-    launches; backward = ONE launch (dr_episym_bwd_mean reads the upstream scalar gradient from device memory)."""
-
-    @staticmethod
-    def forward(ctx, matches, mask, models, keep):
-        matches, models, mk, v, sums = _episym_fwd(matches, mask, models, keep)
-        (P, N, _), M = matches.shape, models.shape[1]
-        per_pair = torch.empty((P,), device=matches.device, dtype=matches.dtype)
-        coef = torch.empty((P,), device=matches.device, dtype=matches.dtype)
-        mean = torch.empty((), device=matches.device, dtype=matches.dtype)
-        L.call("dr_match_loss_mean_f32", ptr(sums), ptr(mk), ptr(v), P, M, N, ptr(per_pair), ptr(coef), ptr(mean), stream())
-        ctx.save_for_backward(matches, models, coef)
-        ctx.aux = (mk, v)
-        return mean
-
-    @staticmethod
-    def backward(ctx, g):
-        if g is None:
-            return None, None, None, None
-        matches, models, coef = ctx.saved_tensors
-        mk, v = ctx.aux
-        P, N, _ = matches.shape
-        M = models.shape[1]
-        gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call("dr_episym_bwd_mean_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), ptr(coef), ptr(g.to(matches.dtype).contiguous()),
-               P, M, N, ptr(gm), stream())
-        return None, None, gm, None
+    return _episym(_SUMS, matches, mask, models, valid)
 
 
 class _MatchLossFused(torch.autograd.Function):
@@ -1632,7 +1607,7 @@ def match_loss_mean(matches, mask, models, keep=None):
         return _MatchLossFused.apply(matches, mask, models, keep)
     if matches.shape[0] > 64:
         return match_loss_per_pair(matches, mask, models, keep).mean()
-    return _MatchLossMean.apply(matches, mask, models, keep)
+    return _Episym.apply(_MEAN, matches, mask, models, keep)
 
 
 def _match_loss_mean_f64(matches, mask, models, keep, chunk: int = 256):
@@ -1669,9 +1644,7 @@ def match_loss_per_pair(matches, mask, models, keep=None):
     """MatchLoss per pair: mean over the kept models and the masked points of min(symmetric epipolar error, 1).
     matches [P,N,4] f32, mask [P,N] bool | None, models [P,M,3,3], keep [P,M] bool | None -> [P] (differentiable w.r.t.
     models)."""
-    if matches.dtype != torch.float32:
-        raise L.DransacError("match_loss_per_pair is implemented for f32")
-    return _MatchLossPair.apply(matches, mask, models.reshape(models.shape[0], -1, 3, 3), keep)
+    return _episym(_PER_PAIR, matches, mask, models, keep)
 
 
 # ------------------------------------------------------------------------------------------ the pair families' training losses
