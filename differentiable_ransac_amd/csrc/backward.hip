@@ -50,6 +50,61 @@ __device__ __forceinline__ bool solve_spd5(double (&G)[5][5], double (&b)[5]) {
   return true;
 }
 
+// The tangent-space system both five-point backward kernels solve at a returned model E with incoming gradient g: the six tangent
+// directions J_c of the essential manifold (c < 3: [e_c]x E ; c >= 3: E [e_{c-3}]x), Jg[c] = <J_c, g>, AJ[k][c] = aj(k, J_c) -- the
+// k-th defining constraint applied to J_c, the one thing the kernels differ in -- and lam = (AJ AJ^T)^-1 AJ Jg.
+// false: the 5x5 system is singular or lam is not finite (lam is then unspecified); the caller decides what that means.
+template <typename ConstraintOnTangent>
+__device__ __forceinline__ bool essential_tangent_multipliers(const double (&E)[3][3], const double (&g)[3][3], double (&lam)[5],
+                                                              ConstraintOnTangent aj) {
+  double J[6][3][3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    J[0][0][j] = 0;        J[0][1][j] = -E[2][j]; J[0][2][j] = E[1][j];
+    J[1][0][j] = E[2][j];  J[1][1][j] = 0;        J[1][2][j] = -E[0][j];
+    J[2][0][j] = -E[1][j]; J[2][1][j] = E[0][j];  J[2][2][j] = 0;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    J[3][i][0] = 0;        J[3][i][1] = E[i][2];  J[3][i][2] = -E[i][1];
+    J[4][i][0] = -E[i][2]; J[4][i][1] = 0;        J[4][i][2] = E[i][0];
+    J[5][i][0] = E[i][1];  J[5][i][1] = -E[i][0]; J[5][i][2] = 0;
+  }
+  double AJ[5][6], Jg[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    double acc = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc += J[c][i][j] * g[i][j];
+    Jg[c] = acc;
+  }
+#pragma unroll
+  for (int k = 0; k < 5; ++k)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) AJ[k][c] = aj(k, J[c]);
+  double G[5][5];
+#pragma unroll
+  for (int a = 0; a < 5; ++a) {
+    double r = 0;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) r += AJ[a][c] * Jg[c];
+    lam[a] = r;
+#pragma unroll
+    for (int b = 0; b < 5; ++b) {
+      double v = 0;
+#pragma unroll
+      for (int c = 0; c < 6; ++c) v += AJ[a][c] * AJ[b][c];
+      G[a][b] = v;
+    }
+  }
+  bool ok = solve_spd5(G, lam);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) ok = ok && is_finite(lam[k]);
+  return ok;
+}
+
 // T = type of samples / gradients in memory (f32: the training path; f64: `-pr 2 -tr 1`, round 5 -- the arithmetic is f64 either way)
 template <typename MT, typename T = float>
 __global__ __launch_bounds__(64) void fivepoint_bwd_kernel(const T *__restrict__ samples,
@@ -109,59 +164,16 @@ __global__ __launch_bounds__(64) void fivepoint_bwd_kernel(const T *__restrict__
       E[q / 3][q % 3] = models[((size_t)s * 10 + slot) * 9 + q];
       g[q / 3][q % 3] = grad_models[which ? (size_t)s * 9 + q : ((size_t)s * 10 + slot) * 9 + q];
     }
-    // tangent directions J_c (3x3 each): c<3: [e_c]x E ; c>=3: E [e_{c-3}]x
-    double J[6][3][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      J[0][0][j] = 0;        J[0][1][j] = -E[2][j]; J[0][2][j] = E[1][j];
-      J[1][0][j] = E[2][j];  J[1][1][j] = 0;        J[1][2][j] = -E[0][j];
-      J[2][0][j] = -E[1][j]; J[2][1][j] = E[0][j];  J[2][2][j] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      J[3][i][0] = 0;        J[3][i][1] = E[i][2];  J[3][i][2] = -E[i][1];
-      J[4][i][0] = -E[i][2]; J[4][i][1] = 0;        J[4][i][2] = E[i][0];
-      J[5][i][0] = E[i][1];  J[5][i][1] = -E[i][0]; J[5][i][2] = 0;
-    }
-    double AJ[5][6], Jg[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      double acc = 0;
+    double lam[5];
+    const bool ok = essential_tangent_multipliers(E, g, lam, [&](int k, const double (&Jc)[3][3]) {
+      double a = 0;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) acc += J[c][i][j] * g[i][j];
-      Jg[c] = acc;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) {
-        double a = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) a += x2[k][i] * J[c][i][j] * x1[k][j];
-        AJ[k][c] = a;
-      }
-    }
-    double G[5][5], lam[5];
-#pragma unroll
-    for (int a = 0; a < 5; ++a) {
-      double r = 0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) r += AJ[a][c] * Jg[c];
-      lam[a] = r;
-#pragma unroll
-      for (int b = 0; b < 5; ++b) {
-        double v = 0;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) v += AJ[a][c] * AJ[b][c];
-        G[a][b] = v;
-      }
-    }
-    if (!solve_spd5(G, lam)) continue;
-    bool fin = true;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) fin = fin && is_finite(lam[k]);
-    if (!fin) continue;
+        for (int j = 0; j < 3; ++j) a += x2[k][i] * Jc[i][j] * x1[k][j];
+      return a;
+    });
+    if (!ok) continue;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
       // d/dx1 of x2^T E x1 = (E^T x2)[0:2] ; d/dx2 = (E x1)[0:2]
@@ -179,6 +191,10 @@ __global__ __launch_bounds__(64) void fivepoint_bwd_kernel(const T *__restrict__
 #pragma unroll
     for (int d = 0; d < 4; ++d) grad_samples[(size_t)s * 20 + 4 * k + d] = (T)gacc[k][d];
 }
+
+// dynamic LDS of a block of the two kernels that diagonalise a 9x9 Gram matrix per lane (fivepoint_nm_bwd_kernel, f8_bwd_kernel):
+// the matrix (81 doubles) and its eigenvectors (81) for each of 64 lanes
+constexpr size_t kGramEigLdsBytes = sizeof(double) * 162 * 64;
 
 // ---------------------------------------------------------------------------------------------- five-point, n > 5
 // Non-minimal samples (ransac.py:82-83: the 8-point Gumbel sampler feeding the five-point estimator; nister.py:64-65 runs the
@@ -207,16 +223,10 @@ __global__ __launch_bounds__(64) void fivepoint_nm_bwd_kernel(const T *__restric
   const T *pts = samples + (size_t)sc * n * 4;
   const T *wts = weights ? weights + (size_t)sc * n : nullptr;
   LaneWs A{lds + lane}, V{lds + lane + 81 * 64};
-  for (int e = 0; e < 81; ++e) A[e] = 0.0;
-  for (int r = 0; r < n; ++r) {
-    double row[9];
+  gram9_lds(A, n, [&](int r, double (&row)[9]) {
     const double w = wts ? (double)wts[r] : 1.0;
     epipolar_row_5pt((double)pts[4 * r], (double)pts[4 * r + 1], (double)pts[4 * r + 2], (double)pts[4 * r + 3], w, row);
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) A[i * 9 + j] += row[i] * row[j];
-  }
+  });
   jacobi_eig_lds<9>(A, V);
   // the forward's choice of S: four times the smallest remaining eigenvalue (fivepoint_basis_nonminimal)
   unsigned inS = 0;
@@ -260,63 +270,18 @@ __global__ __launch_bounds__(64) void fivepoint_nm_bwd_kernel(const T *__restric
     }
     has = has && gn > 0.0;
     if (!__any(has)) continue;
-    double J[6][3][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      J[0][0][j] = 0;        J[0][1][j] = -E[2][j]; J[0][2][j] = E[1][j];
-      J[1][0][j] = E[2][j];  J[1][1][j] = 0;        J[1][2][j] = -E[0][j];
-      J[2][0][j] = -E[1][j]; J[2][1][j] = E[0][j];  J[2][2][j] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      J[3][i][0] = 0;        J[3][i][1] = E[i][2];  J[3][i][2] = -E[i][1];
-      J[4][i][0] = -E[i][2]; J[4][i][1] = 0;        J[4][i][2] = E[i][0];
-      J[5][i][0] = E[i][1];  J[5][i][1] = -E[i][0]; J[5][i][2] = 0;
-    }
-    double AJ[5][6], Jg[6];
-#pragma unroll
-    for (int c = 0; c < 6; ++c) {
-      double acc = 0;
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc += J[c][i][j] * g[i][j];
-      Jg[c] = acc;
-    }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      double qv[9];
+    double lam[5];
+    const bool fin = essential_tangent_multipliers(E, g, lam, [&](int k, const double (&Jc)[3][3]) {
+      double qv[9], a = 0;
 #pragma unroll
       for (int q = 0; q < 9; ++q) qv[q] = V[q * 9 + cj[k]];
 #pragma unroll
-      for (int c = 0; c < 6; ++c) {
-        double a = 0;
+      for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int j = 0; j < 3; ++j) a += qv[3 * j + i] * J[c][i][j];
-        AJ[k][c] = a;
-      }
-    }
-    double G[5][5], lam[5];
-#pragma unroll
-    for (int a = 0; a < 5; ++a) {
-      double r = 0;
-#pragma unroll
-      for (int c = 0; c < 6; ++c) r += AJ[a][c] * Jg[c];
-      lam[a] = r;
-#pragma unroll
-      for (int b = 0; b < 5; ++b) {
-        double v = 0;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) v += AJ[a][c] * AJ[b][c];
-        G[a][b] = v;
-      }
-    }
-    bool fin = solve_spd5(G, lam);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) fin = fin && is_finite(lam[k]);
-    if (!(has && fin)) {
+        for (int j = 0; j < 3; ++j) a += qv[3 * j + i] * Jc[i][j];
+      return a;
+    });
+    if (!(has && fin)) {   // lam = 0 instead of a `continue`: the wave stays converged for the LDS reads below
 #pragma unroll
       for (int k = 0; k < 5; ++k) lam[k] = 0;
     }
@@ -399,17 +364,11 @@ __global__ __launch_bounds__(64) void f8_bwd_kernel(const T *__restrict__ sample
     d2 += sqrt(c * c + d * d);
   }
   const double r1 = M_SQRT2 * (double)n / d1, r2 = M_SQRT2 * (double)n / d2;
-  for (int e = 0; e < 81; ++e) A[e] = 0.0;
-  for (int r = 0; r < n; ++r) {
-    double row[9];
+  gram9_lds(A, n, [&](int r, double (&row)[9]) {
     const double w = wts ? (double)wts[r] : 1.0;
     epipolar_row_f(((double)pts[4 * r] - mu[0]) * r1, ((double)pts[4 * r + 1] - mu[1]) * r1,
                    ((double)pts[4 * r + 2] - mu[2]) * r2, ((double)pts[4 * r + 3] - mu[3]) * r2, w, row);
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) A[i * 9 + j] += row[i] * row[j];
-  }
+  });
   jacobi_eig_lds<9>(A, V);
   int imin = 0;
   double lmin = INFINITY;
@@ -780,14 +739,16 @@ __global__ __launch_bounds__(kBT) void rigid_residual_bwd_kernel(const float *__
 
 }  // namespace dr
 
-// the f32 five-point backward: from the solver's f64 models where the caller kept them (models_f64), else from the f32 ones
-static int fivepoint_bwd_f32_launch(const float *samples, const float *models, const double *models_f64, const uint8_t *valid,
-                                    const float *grad, const int32_t *which, int Bt, float *grad_samples, void *stream) {
+// The minimal five-point backward with samples and gradients of type IO in memory: from the solver's f64 models where the caller has
+// them (models_f64; the f64 entry has nothing else), else from the IO ones.  which: see the kernel (NULL = dense gradient)
+template <typename IO>
+static int fivepoint_bwd_launch(const IO *samples, const IO *models, const double *models_f64, const uint8_t *valid, const IO *grad,
+                                const int32_t *which, int Bt, IO *grad_samples, void *stream) {
   const dim3 grid((Bt + 63) / 64);
   if (models_f64)
-    return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<double>, grid, 64, stream, samples, models_f64, valid, grad, Bt,
-                      grad_samples, which);
-  return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<float>, grid, 64, stream, samples, models, valid, grad, Bt,
+    return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<double, IO>, grid, 64, stream, samples, models_f64, valid, grad,
+                      Bt, grad_samples, which);
+  return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<IO, IO>, grid, 64, stream, samples, models, valid, grad, Bt,
                     grad_samples, which);
 }
 
@@ -795,35 +756,44 @@ static int fivepoint_bwd_f32_launch(const float *samples, const float *models, c
 template <auto Kernel, typename MT, typename IO>
 static int nm_bwd_launch(const IO *samples, const IO *weights, const MT *models, const uint8_t *valid, const IO *grad_models, int Bt,
                          int n, IO *grad_samples, IO *grad_weights, void *stream) {
-  const size_t smem = sizeof(double) * 162 * 64;
-  dr::allow_dynamic_lds<Kernel>(smem);
-  return dr::launch_lds("fivepoint_nm_bwd_kernel", Kernel, dim3((Bt + 63) / 64), 64, smem, stream, samples, weights, models, valid,
-                        grad_models, Bt, n, grad_samples, grad_weights);
+  dr::allow_dynamic_lds<Kernel>(dr::kGramEigLdsBytes);
+  return dr::launch_lds("fivepoint_nm_bwd_kernel", Kernel, dim3((Bt + 63) / 64), 64, dr::kGramEigLdsBytes, stream, samples, weights,
+                        models, valid, grad_models, Bt, n, grad_samples, grad_weights);
 }
+
+// the argument checks of the five five-point backward entries: which model and gradient pointers the entry needs, and its sizes
+#define DR_FIVEPOINT_BWD_CHECK(models_ok, grads_ok, sizes_ok, sizes_msg)                      \
+  DR_REQUIRE(samples && (models_ok) && valid && (grads_ok) && grad_samples, "null pointer"); \
+  DR_REQUIRE(sizes_ok, sizes_msg)
 
 extern "C" {
 
 int dr_solve_nister5_bwd_f32(const float *samples, const float *models, const double *models_f64,
                              const uint8_t *valid, const float *grad_models, int Bt, float *grad_samples,
                              void *stream) {
-  DR_REQUIRE(samples && (models || models_f64) && valid && grad_models && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0, "need Bt > 0");
-  return fivepoint_bwd_f32_launch(samples, models, models_f64, valid, grad_models, nullptr, Bt, grad_samples, stream);
+  DR_FIVEPOINT_BWD_CHECK(models || models_f64, grad_models, Bt > 0, "need Bt > 0");
+  return fivepoint_bwd_launch<float>(samples, models, models_f64, valid, grad_models, nullptr, Bt, grad_samples, stream);
 }
 
 int dr_solve_nister5_bwd_sel_f32(const float *samples, const float *models, const double *models_f64,
                                  const uint8_t *valid, const float *grad_chosen, const int32_t *which, int Bt,
                                  float *grad_samples, void *stream) {
-  DR_REQUIRE(samples && (models || models_f64) && valid && grad_chosen && which && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0, "need Bt > 0");
-  return fivepoint_bwd_f32_launch(samples, models, models_f64, valid, grad_chosen, which, Bt, grad_samples, stream);
+  DR_FIVEPOINT_BWD_CHECK(models || models_f64, grad_chosen && which, Bt > 0, "need Bt > 0");
+  return fivepoint_bwd_launch<float>(samples, models, models_f64, valid, grad_chosen, which, Bt, grad_samples, stream);
+}
+
+/* minimal five-point backward, everything f64 in memory (dense gradient [Bt,10,9]) */
+int dr_solve_nister5_bwd_f64(const double *samples, const double *models, const uint8_t *valid, const double *grad_models, int Bt,
+                             double *grad_samples, void *stream) {
+  DR_FIVEPOINT_BWD_CHECK(models, grad_models, Bt > 0, "need Bt > 0");
+  return fivepoint_bwd_launch<double>(samples, nullptr, models, valid, grad_models, nullptr, Bt, grad_samples, stream);
 }
 
 int dr_solve_nister5_nm_bwd_f32(const float *samples, const float *weights, const float *models, const double *models_f64,
                                 const uint8_t *valid, const float *grad_models, int Bt, int n, float *grad_samples,
                                 float *grad_weights, void *stream) {
-  DR_REQUIRE(samples && (models || models_f64) && valid && grad_models && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0 && n > 5, "need Bt > 0 and n > 5 points per sample (minimal samples: dr_solve_nister5_bwd_f32)");
+  DR_FIVEPOINT_BWD_CHECK(models || models_f64, grad_models, Bt > 0 && n > 5,
+                         "need Bt > 0 and n > 5 points per sample (minimal samples: dr_solve_nister5_bwd_f32)");
   if (models_f64)
     return nm_bwd_launch<dr::fivepoint_nm_bwd_kernel<double>>(samples, weights, models_f64, valid, grad_models, Bt, n, grad_samples,
                                                               grad_weights, stream);
@@ -834,8 +804,8 @@ int dr_solve_nister5_nm_bwd_f32(const float *samples, const float *weights, cons
 /* the same with everything f64 in memory (`-sam 3 -fmat 0 -tr 1 -pr 2`; round 6: the f32-I/O kernel rounded samples and gradients) */
 int dr_solve_nister5_nm_bwd_f64(const double *samples, const double *weights, const double *models, const uint8_t *valid,
                                 const double *grad_models, int Bt, int n, double *grad_samples, double *grad_weights, void *stream) {
-  DR_REQUIRE(samples && models && valid && grad_models && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0 && n > 5, "need Bt > 0 and n > 5 points per sample (minimal samples: dr_solve_nister5_bwd_f64)");
+  DR_FIVEPOINT_BWD_CHECK(models, grad_models, Bt > 0 && n > 5,
+                         "need Bt > 0 and n > 5 points per sample (minimal samples: dr_solve_nister5_bwd_f64)");
   return nm_bwd_launch<dr::fivepoint_nm_bwd_kernel<double, double>>(samples, weights, models, valid, grad_models, Bt, n, grad_samples,
                                                                     grad_weights, stream);
 }
@@ -846,22 +816,12 @@ int dr_solve_nister5_nm_bwd_f64(const double *samples, const double *weights, co
                             T *grad_samples, T *grad_weights, void *stream) {                                                       \
     DR_REQUIRE(samples && models && grad_models && grad_samples, "null pointer");                                                   \
     DR_REQUIRE(Bt > 0 && n >= 8, "need Bt > 0 and n >= 8");                                                                         \
-    const size_t smem = sizeof(double) * 162 * 64;                                                                                  \
-    dr::allow_dynamic_lds<dr::f8_bwd_kernel<T>>(smem);                                                                              \
-    return dr::launch_lds("f8_bwd_kernel", dr::f8_bwd_kernel<T>, dim3((Bt + 63) / 64), 64, smem, stream, samples, weights, models,  \
-                          grad_models, Bt, n, grad_samples, grad_weights);                                                          \
+    dr::allow_dynamic_lds<dr::f8_bwd_kernel<T>>(dr::kGramEigLdsBytes);                                                              \
+    return dr::launch_lds("f8_bwd_kernel", dr::f8_bwd_kernel<T>, dim3((Bt + 63) / 64), 64, dr::kGramEigLdsBytes, stream, samples,   \
+                          weights, models, grad_models, Bt, n, grad_samples, grad_weights);                                         \
   }
 DR_F32_F64(DR_OP)
 #undef DR_OP
-
-/* minimal five-point backward, everything f64 in memory (dense gradient [Bt,10,9]) */
-int dr_solve_nister5_bwd_f64(const double *samples, const double *models, const uint8_t *valid, const double *grad_models, int Bt,
-                             double *grad_samples, void *stream) {
-  DR_REQUIRE(samples && models && valid && grad_models && grad_samples, "null pointer");
-  DR_REQUIRE(Bt > 0, "need Bt > 0");
-  return dr::launch("fivepoint_bwd_kernel", dr::fivepoint_bwd_kernel<double, double>, dim3((Bt + 63) / 64), 64, stream, samples, models,
-                    valid, grad_models, Bt, grad_samples, nullptr);
-}
 
 int dr_solve_rigid_bwd_f32(const float *samples, const float *models, const float *grad_models, int Bt, int n,
                            int flag, float *grad_samples, void *stream) {

@@ -51,16 +51,10 @@ template <typename T>
 __device__ __forceinline__ void fivepoint_basis_nonminimal(const T *__restrict__ pts, const T *__restrict__ wts, int n,
                                            const LaneWs &ws, double (&nb)[4][9]) {
   LaneWs A{ws.base}, V{ws.base + 81 * 64};
-  for (int e = 0; e < 81; ++e) A[e] = 0.0;
-  for (int r = 0; r < n; ++r) {
-    double row[9];
+  gram9_lds(A, n, [&](int r, double (&row)[9]) {
     const double w = wts ? (double)wts[r] : 1.0;
     epipolar_row_5pt((double)pts[4 * r], (double)pts[4 * r + 1], (double)pts[4 * r + 2], (double)pts[4 * r + 3], w, row);
-#pragma unroll
-    for (int i = 0; i < 9; ++i)
-#pragma unroll
-      for (int j = 0; j < 9; ++j) A[i * 9 + j] += row[i] * row[j];
-  }
+  });
   jacobi_eig_lds<9>(A, V);
   unsigned used = 0;
   for (int t = 3; t >= 0; --t) {  // t = 3 takes the smallest

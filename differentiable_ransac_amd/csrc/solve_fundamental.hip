@@ -78,17 +78,11 @@ __global__ __launch_bounds__(64) void f8_kernel(const T *__restrict__ samples, c
     for (int q = 0; q < 9; ++q) f[q] = nb[0][q];
   } else if constexpr (!kUniform) {
     LaneWs A{lds + lane}, V{lds + lane + 81 * 64};
-    for (int e = 0; e < 81; ++e) A[e] = 0.0;
-    for (int r = 0; r < n; ++r) {
-      double row[9];
+    gram9_lds(A, n, [&](int r, double (&row)[9]) {
       const double w = wts ? (double)wts[r] : 1.0;
       epipolar_row_f(((double)pts[4 * r] - mu[0]) * r1, ((double)pts[4 * r + 1] - mu[1]) * r1,
                      ((double)pts[4 * r + 2] - mu[2]) * r2, ((double)pts[4 * r + 3] - mu[3]) * r2, w, row);
-#pragma unroll
-      for (int i = 0; i < 9; ++i)
-#pragma unroll
-        for (int j = 0; j < 9; ++j) A[i * 9 + j] += row[i] * row[j];
-    }
+    });
     jacobi_eig_lds<9>(A, V);
     int best = 0;
     double bv = INFINITY;

@@ -1023,6 +1023,21 @@ __device__ __forceinline__ void real_roots(const double (&c)[D + 1], double (&ro
   }
 }
 
+// Gram matrix sum_r row_r row_r^T of n equation rows (9 coefficients each) into A (81 doubles of a lane's LDS slice): what the
+// n > minimal paths hand to jacobi_eig_lds<9>.  row_of(r, row) writes row r.
+template <typename RowOf>
+__device__ __forceinline__ void gram9_lds(const LaneWs &A, int n, RowOf row_of) {
+  for (int e = 0; e < 81; ++e) A[e] = 0.0;
+  for (int r = 0; r < n; ++r) {
+    double row[9];
+    row_of(r, row);
+#pragma unroll
+    for (int i = 0; i < 9; ++i)
+#pragma unroll
+      for (int j = 0; j < 9; ++j) A[i * 9 + j] += row[i] * row[j];
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Cyclic Jacobi eigen-decomposition of a symmetric n x n matrix held in LDS (A: n*n, V: n*n).
 // On return A's diagonal holds the eigenvalues and the columns of V the eigenvectors.
@@ -1074,87 +1089,10 @@ __device__ __forceinline__ void jacobi_eig_lds(const LaneWs &A, const LaneWs &V)
   }
 }
 
-// Cyclic Jacobi of a symmetric 9x9 matrix entirely in VGPRs (162 doubles; for kernels that run one wave per SIMD).
-// The (p,q) schedule is static, so nothing needs run-time indexing; used where a single wave would otherwise crawl
-// through LDS latency (K7 refit: one sample per block).  column(V, c) extraction is a 9-way select.
-__device__ __forceinline__ void jacobi_eig9_reg(double (&A)[9][9], double (&V)[9][9]) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i)
-#pragma unroll
-    for (int j = 0; j < 9; ++j) V[i][j] = (i == j) ? 1.0 : 0.0;
-  double prev_off = INFINITY;
-#pragma unroll 1
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0, dg = 0;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-      dg += A[i][i] * A[i][i];
-#pragma unroll
-      for (int j = i + 1; j < 9; ++j) off += A[i][j] * A[i][j];
-    }
-    const bool done = !(off > 1e-30 * dg) || (sweep >= 4 && off > 0.25 * prev_off);
-    prev_off = off;
-    if (__all(done)) break;
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-#pragma unroll
-      for (int q = p + 1; q < 9; ++q) {
-        const double apq = A[p][q];
-        double c = 1.0, s = 0.0;
-        if (fabs(apq) > 1e-300 && !done) {
-          const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-          const double t = dsign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          c = 1.0 / sqrt(t * t + 1.0);
-          s = t * c;
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk;
-          A[q][k] = s * apk + c * aqk;
-        }
-#pragma unroll
-        for (int k = 0; k < 9; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-    }
-  }
-}
-
-// index of the smallest diagonal entry not yet in `used` (bit mask), and that eigenvector
-__device__ __forceinline__ int smallest_eigvec9(const double (&A)[9][9], const double (&V)[9][9], unsigned &used,
-                                                double (&out)[9]) {
-  int best = 0;
-  double bv = INFINITY;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) {
-    const bool free_ = !((used >> i) & 1u);
-    if (free_ && A[i][i] < bv) { bv = A[i][i]; best = i; }
-  }
-  used |= 1u << best;
-#pragma unroll
-  for (int r = 0; r < 9; ++r) {
-    double v = V[r][0];
-#pragma unroll
-    for (int c = 1; c < 9; ++c) v = (c == best) ? V[r][c] : v;
-    out[r] = v;
-  }
-  return best;
-}
-
 // Parallel cyclic Jacobi for ONE symmetric 9x9 matrix held in LDS (A, V: 81 doubles each, row-major), executed by one
 // whole wave: round-robin ordering -- 9 rounds per sweep, 4 disjoint rotations per round (player r sits out in round r)
 // -- lanes 0-3 compute the four (c, s), then 36 lanes apply the column updates of A, 36 those of V, 36 the row updates.
-// ~700 cycles per round instead of ~27 k cycles per sweep of the serial register version above; on return the diagonal
+// ~700 cycles per round instead of ~27 k cycles per sweep of a serial one-lane version in registers; on return the diagonal
 // of A holds the eigenvalues and the columns of V the eigenvectors.  `cs` = 16 doubles of LDS scratch.
 // f64 reciprocal square root / reciprocal from the hardware estimates (v_rsq_f64 / v_rcp_f64, ~26 bits) + two Newton steps: what the
 // rotation angles below need -- finite, well-scaled, positive arguments; none of the scaling / special-case code of sqrt() and "/"

@@ -999,6 +999,33 @@ def soft_weights_row0(logits: torch.Tensor, k: int, tau: float, gumbel: Optional
 
 
 # ------------------------------------------------------------------------------------------ autograd wrappers
+# the five-point backward entry for (minimal sample, f64 in memory, sparse gradient through `which`)
+_FIVEPOINT_BWD = {(True, False, False): "dr_solve_nister5_bwd_f32", (True, False, True): "dr_solve_nister5_bwd_sel_f32",
+                  (True, True, False): "dr_solve_nister5_bwd_f64",
+                  (False, False, False): "dr_solve_nister5_nm_bwd_f32", (False, True, False): "dr_solve_nister5_nm_bwd_f64"}
+
+
+def _fivepoint_bwd(samples, models, m64, valid, grad, which=None, weights=None, want_gw=False):
+    """The host path of every five-point backward: samples [...,n,4] and the gradient of their models ([...,10,3,3]; with `which`,
+    [...,3,3]: that of the one model K5 picked per sample) -> (grad_samples, grad_weights); grad_weights is None unless the rows
+    have weights (n > 5) and the caller wants their gradient.  f64 samples go f64 straight through, gradient included; f32 ones
+    use the solver's f64 models where the forward kept them (m64 not empty): the tangent-space system is conditioned ~1e5."""
+    s, Bt, n = _flat_samples(samples, 4)
+    minimal, f64 = n == 5, s.dtype == torch.float64
+    gs = torch.empty_like(s)
+    w = None if minimal or weights is None else weights.reshape(Bt, n).to(s.dtype).contiguous()
+    gw = torch.empty((Bt, n), device=s.device, dtype=s.dtype) if w is not None and want_gw else None
+    args = [ptr(s)] + ([] if minimal else [ptr(w)]) + [ptr(models.contiguous())]
+    if not f64:
+        args.append(ptr(m64.contiguous() if m64.numel() else None))
+    args += [_u8_ptr(valid), ptr((grad.to(torch.float64) if f64 else grad).contiguous())]
+    if which is not None:
+        args.append(ptr(which.contiguous()))
+    args += [Bt] + ([] if minimal else [n]) + [ptr(gs)] + ([] if minimal else [ptr(gw)])
+    L.call(_FIVEPOINT_BWD[minimal, f64, which is not None], *args, stream())
+    return gs.reshape(samples.shape), (None if gw is None else gw.reshape(weights.shape).to(weights.dtype))
+
+
 class _SolveEssential(torch.autograd.Function):
     """Five-point solve with implicit-function backward (dr_solve_nister5_bwd): at a returned model E the five
     epipolar constraints x2^T E x1 = 0 restricted to the tangent space of the essential manifold determine dE/dpts."""
@@ -1029,41 +1056,8 @@ class _SolveEssential(torch.autograd.Function):
         if g_models is None:
             return None, None, None
         samples, models, m64, valid = ctx.saved_tensors
-        f64 = samples.dtype == torch.float64
-        if f64 and ctx.minimal:
-            # `-pr 2 -tr 1`, round 5: f64 samples, models and gradients straight through (dr_solve_nister5_bwd_f64)
-            s, Bt, n = _flat_samples(samples, 4)
-            gs = torch.empty_like(s)
-            L.call("dr_solve_nister5_bwd_f64", ptr(s), ptr(models.contiguous()), _u8_ptr(valid),
-                   ptr(g_models.to(torch.float64).contiguous()), Bt, ptr(gs), stream())
-            return gs.reshape(samples.shape), None, None
-        if f64:
-            # n > 5 rows per sample in f64 (`-sam 3 -fmat 0 -tr 1 -pr 2`), round 6: f64 samples, weights, models and gradients straight
-            # through (dr_solve_nister5_nm_bwd_f64; rounds 3-5 rounded samples and gradients to f32 on the way in)
-            s, Bt, n = _flat_samples(samples, 4)
-            gs = torch.empty_like(s)
-            w = ctx.weights
-            gw = None if w is None or not ctx.needs_input_grad[1] else torch.empty((Bt, n), device=s.device, dtype=torch.float64)
-            L.call("dr_solve_nister5_nm_bwd_f64", ptr(s), ptr(None if w is None else w.reshape(Bt, n).double().contiguous()),
-                   ptr(models.contiguous()), _u8_ptr(valid), ptr(g_models.to(torch.float64).contiguous()), Bt, n, ptr(gs), ptr(gw),
-                   stream())
-            return gs.reshape(samples.shape), (None if gw is None else gw.reshape(w.shape).to(w.dtype)), None
-        s, Bt, n = _flat_samples(samples, 4)
-        gs = torch.empty_like(s)
-        if not ctx.minimal:
-            # n > 5 rows per sample (the reference's `-sam 3`: 8-point Gumbel sampler feeding the five-point estimator,
-            # ransac.py:82-83): derivative of the invariant subspace the models live in, row weights included
-            w = ctx.weights
-            gw = None if w is None or not ctx.needs_input_grad[1] else torch.empty((Bt, n), device=s.device, dtype=torch.float32)
-            L.call("dr_solve_nister5_nm_bwd_f32", ptr(s), ptr(None if w is None else w.reshape(Bt, n).float().contiguous()),
-                   ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None), _u8_ptr(valid),
-                   ptr(g_models.contiguous()), Bt, n, ptr(gs), ptr(gw), stream())
-            gs = gs.reshape(samples.shape)
-            return (gs.double() if f64 else gs), (None if gw is None else gw.reshape(w.shape).to(w.dtype)), None
-        L.call("dr_solve_nister5_bwd_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous() if m64.numel() else None),
-               _u8_ptr(valid), ptr(g_models.contiguous()), Bt, ptr(gs), stream())
-        gs = gs.reshape(samples.shape)
-        return (gs.double() if f64 else gs), None, None
+        gs, gw = _fivepoint_bwd(samples, models, m64, valid, g_models, weights=ctx.weights, want_gw=ctx.needs_input_grad[1])
+        return gs, gw, None
 
 
 def solve_essential(samples, weights=None, which="nister"):
@@ -1097,11 +1091,7 @@ class _SolveSelectEssential(torch.autograd.Function):
         if g_chosen is None:
             return None, None, None
         samples, models, m64, valid, which = ctx.saved_tensors
-        s, Bt, _ = _flat_samples(samples, 4)
-        gs = torch.empty_like(s)
-        L.call("dr_solve_nister5_bwd_sel_f32", ptr(s), ptr(models.contiguous()), ptr(m64.contiguous()), _u8_ptr(valid),
-               ptr(g_chosen.contiguous()), ptr(which.contiguous()), Bt, ptr(gs), stream())
-        return gs.reshape(samples.shape), None, None
+        return _fivepoint_bwd(samples, models, m64, valid, g_chosen, which=which)[0], None, None
 
 
 def solve_select_essential(samples, gt, weights=None):
