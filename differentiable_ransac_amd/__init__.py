@@ -1,6 +1,6 @@
 """differentiable_ransac_amd: see README.md.  Submodules are imported explicitly (`from differentiable_ransac_amd import ops`);
 the names below are also reachable from the package itself, resolved on first use so that importing the package stays free."""
-__all__ = ["BatchedRegistration", "BatchedHomography"]
+__all__ = ["BatchedRegistration", "BatchedHomography", "BatchedPnP"]
 
 
 def __getattr__(name):

@@ -1,0 +1,455 @@
+// Absolute pose from 2D-3D matches (ransac.BatchedPnP): up to four poses from every minimal sample of three matches by a closed-form
+// P3P, the MSAC score and inlier count of every pose against every point under the reprojection error, the per-pair state step with
+// the adaptive stop, and the Levenberg-Marquardt refit over the rows a mask selects.  Conventions, residual and slot rules:
+// pnp_device.hpp.  The threshold is a DISTANCE in normalised units and enters as thr2 = threshold^2 per pair: inlier <=> d2 < thr2;
+// MSAC score = sum_n max(0, 1 - d2_n / thr2).
+#include "pair_state_device.hpp"
+#include "pnp_device.hpp"
+#include "rigid_device.hpp"
+#include "solver_common.hpp"
+
+namespace dr {
+
+// ---- (1) three matches -> up to four poses: Grunert's P3P in the Fischler-Bolles ratio form -----------------------------------------
+// Bearings f_i = normalize(u_i, v_i, 1), unknown depths s_i along them (the camera points are Y_i = s_i f_i), world distances
+// a = |X_1 - X_2|, b = |X_0 - X_2|, c = |X_0 - X_1| and cosines ca = f_1 . f_2, cb = f_0 . f_2, cg = f_0 . f_1.  The law of cosines in the
+// three triangles camera-centre / two points:
+//   s_1^2 + s_2^2 - 2 s_1 s_2 ca = a^2      s_0^2 + s_2^2 - 2 s_0 s_2 cb = b^2      s_0^2 + s_1^2 - 2 s_0 s_1 cg = c^2.
+// With s_1 = x s_0 and s_2 = v s_0 the middle one gives s_0^2 = b^2 / (1 + v^2 - 2 v cb); dividing the other two by it,
+//   x^2 + v^2 - 2 x v ca = (a^2 / b^2) g(v)      1 + x^2 - 2 x cg = (c^2 / b^2) g(v)      g(v) = 1 + v^2 - 2 v cb,
+// and their difference is linear in x:  x = p(v) / q(v),  p = (K - 1) v^2 - 2 K cb v + (K + 1),  q = 2 (cg - v ca),  K = (a^2 - c^2) / b^2.
+// Put into the second one and multiplied by q^2:  p^2 - 2 cg p q + q^2 (1 - (c^2 / b^2) g(v)) = 0, a quartic in v whose coefficients are
+// formed by multiplying the polynomials out.  Its real roots come from solver_common.hpp's real_roots<4>; each one with v > 0 gives
+// (s_0, x s_0, v s_0), polished by kP3PNewton Newton steps on the three law-of-cosines equations in (s_0, s_1, s_2) (a fixed number:
+// the 64 samples of a wave never wait for one; a step that is not finite is not taken).  A root is kept when the three depths are
+// positive and finite.  The pose follows without a decomposition: the orthonormal frames (e_0, e_1, e_0 x e_1) of the world triangle
+// and of the camera triangle by Gram-Schmidt on their two edges from point 0, R = sum_k e'_k e_k^T (rotation_from_frames: proper and
+// orthonormal by construction, whatever is left of the triangles' incongruence), t = mean Y - R mean X; the slot is valid when every
+// entry is finite and R X_i + t has z > 0 for the three points.
+// Slots 4 b + j of sample b: the valid ones first, in ascending order of their root v; every other slot is the identity with
+// valid = 0.  A sample has four invalid slots when an index is out of range, two world points coincide (a repeated index), the
+// world points are collinear or two bearings coincide (sin^2 of the angle below kP3PSin2: 1e-6 rad), or no root survives.
+// Mapping: one lane per sample, 64-thread blocks, all f64 in registers for either type, as homography4_gather_kernel.  No atomics, no
+// LDS; a repeated launch gives the same bits.
+constexpr int kP3PNewton = 2;
+constexpr double kP3PSin2 = 1e-12;
+
+__device__ __forceinline__ double dot3(const double (&a)[3], const double (&b)[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+
+__device__ __forceinline__ double cross_norm2(const double (&a)[3], const double (&b)[3]) {
+  const double c0 = a[1] * b[2] - a[2] * b[1], c1 = a[2] * b[0] - a[0] * b[2], c2 = a[0] * b[1] - a[1] * b[0];
+  return c0 * c0 + c1 * c1 + c2 * c2;
+}
+
+// e0 = d1 / |d1|, e1 = the part of d2 orthogonal to it, normalised.  The projection is taken out twice: after one pass a thin
+// triangle leaves e0 . e1 at eps / sin(angle), after the second it is at eps whatever the angle, so R is orthonormal to rounding.
+__device__ __forceinline__ void frame2(const double (&d1)[3], const double (&d2)[3], double (&e0)[3], double (&e1)[3]) {
+  const double r1 = 1.0 / sqrt(dot3(d1, d1));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    e0[i] = d1[i] * r1;
+    e1[i] = d2[i];
+  }
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const double h = dot3(e1, e0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) e1[i] -= h * e0[i];
+  }
+  const double r2 = 1.0 / sqrt(dot3(e1, e1));
+#pragma unroll
+  for (int i = 0; i < 3; ++i) e1[i] *= r2;
+}
+
+struct P3PSample {
+  double X[3][3], f[3][3];      // world points, unit bearings
+  double a2, b2, c2, ca, cb, cg;
+  double e0[3], e1[3], xm[3];   // the world triangle's frame and centroid
+};
+
+// one root v of the quartic -> the pose (R, t); false: the slot is dropped
+__device__ __forceinline__ bool p3p_pose(const P3PSample &S, double v, double (&R)[3][3], double (&t)[3]) {
+  const double K = (S.a2 - S.c2) / S.b2;
+  const double x = ((K - 1.0) * v * v - 2.0 * K * S.cb * v + (K + 1.0)) / (2.0 * (S.cg - v * S.ca));
+  double s[3];
+  s[0] = sqrt(S.b2 / (1.0 + v * v - 2.0 * v * S.cb));
+  s[1] = x * s[0];
+  s[2] = v * s[0];
+#pragma unroll
+  for (int it = 0; it < kP3PNewton; ++it) {
+    const double F0 = s[1] * s[1] + s[2] * s[2] - 2.0 * s[1] * s[2] * S.ca - S.a2;
+    const double F1 = s[0] * s[0] + s[2] * s[2] - 2.0 * s[0] * s[2] * S.cb - S.b2;
+    const double F2 = s[0] * s[0] + s[1] * s[1] - 2.0 * s[0] * s[1] * S.cg - S.c2;
+    // J = [[0, j01, j02], [j10, 0, j12], [j20, j21, 0]]; det J = j01 j12 j20 + j02 j10 j21, the step by Cramer's rule
+    const double j01 = 2.0 * (s[1] - s[2] * S.ca), j02 = 2.0 * (s[2] - s[1] * S.ca);
+    const double j10 = 2.0 * (s[0] - s[2] * S.cb), j12 = 2.0 * (s[2] - s[0] * S.cb);
+    const double j20 = 2.0 * (s[0] - s[1] * S.cg), j21 = 2.0 * (s[1] - s[0] * S.cg);
+    const double rd = 1.0 / (j01 * j12 * j20 + j02 * j10 * j21);
+    const double d0 = (-j12 * j21 * F0 + j02 * j21 * F1 + j01 * j12 * F2) * rd;
+    const double d1 = (j12 * j20 * F0 - j02 * j20 * F1 + j02 * j10 * F2) * rd;
+    const double d2 = (j10 * j21 * F0 + j01 * j20 * F1 - j01 * j10 * F2) * rd;
+    const bool take = is_finite(d0) && is_finite(d1) && is_finite(d2);
+    s[0] = take ? s[0] - d0 : s[0];
+    s[1] = take ? s[1] - d1 : s[1];
+    s[2] = take ? s[2] - d2 : s[2];
+  }
+  bool ok = v > 0.0;
+  double Y[3][3], ym[3], g1[3], g2[3], c0[3], c1[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    ok = ok && s[i] > 0.0 && is_finite(s[i]);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) Y[i][d] = s[i] * S.f[i][d];
+  }
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    ym[d] = (Y[0][d] + Y[1][d] + Y[2][d]) * (1.0 / 3.0);
+    g1[d] = Y[1][d] - Y[0][d];
+    g2[d] = Y[2][d] - Y[0][d];
+  }
+  frame2(g1, g2, c0, c1);
+  ok = rotation_from_frames(c0, c1, S.e0, S.e1, R) && ok;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    t[i] = ym[i] - (R[i][0] * S.xm[0] + R[i][1] * S.xm[1] + R[i][2] * S.xm[2]);
+    ok = ok && is_finite(t[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) ok = ok && (R[2][0] * S.X[i][0] + R[2][1] * S.X[i][1] + R[2][2] * S.X[i][2] + t[2]) > 0.0;
+  return ok;
+}
+
+__device__ __forceinline__ void sort_step(double &a, double &b) {
+  const double lo = fmin(a, b), hi = fmax(a, b);
+  a = lo;
+  b = hi;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void p3p_gather_kernel(const T *__restrict__ matches, const int32_t *__restrict__ idx, int Bt, int B,
+                                                        int N, T *__restrict__ models, uint8_t *__restrict__ valid) {
+  const int smp = blockIdx.x * 64 + threadIdx.x;
+  if (smp >= Bt) return;
+  const T *base = matches + (size_t)(smp / B) * N * 5;
+  const int32_t *gi = idx + (size_t)smp * 3;
+  bool usable = true;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) usable = usable && gi[r] >= 0 && gi[r] < N;      // (a bad index reads row 0, every slot invalid)
+  P3PSample S;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const T *row = base + (size_t)(usable ? gi[r] : 0) * 5;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) S.X[r][d] = (double)row[d];
+    const double u = (double)row[3], w = (double)row[4], rn = 1.0 / sqrt(u * u + w * w + 1.0);
+    S.f[r][0] = u * rn;
+    S.f[r][1] = w * rn;
+    S.f[r][2] = rn;
+  }
+  double d01[3], d02[3], d12[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    d01[d] = S.X[1][d] - S.X[0][d];
+    d02[d] = S.X[2][d] - S.X[0][d];
+    d12[d] = S.X[2][d] - S.X[1][d];
+    S.xm[d] = (S.X[0][d] + S.X[1][d] + S.X[2][d]) * (1.0 / 3.0);
+  }
+  S.a2 = dot3(d12, d12);
+  S.b2 = dot3(d02, d02);
+  S.c2 = dot3(d01, d01);
+  S.ca = dot3(S.f[1], S.f[2]);
+  S.cb = dot3(S.f[0], S.f[2]);
+  S.cg = dot3(S.f[0], S.f[1]);
+  // (every test false for NaN)
+  usable = usable && S.a2 > 0.0 && S.b2 > 0.0 && S.c2 > 0.0 && cross_norm2(d01, d02) > kP3PSin2 * S.b2 * S.c2;
+  usable = usable && cross_norm2(S.f[1], S.f[2]) > kP3PSin2 && cross_norm2(S.f[0], S.f[2]) > kP3PSin2 &&
+           cross_norm2(S.f[0], S.f[1]) > kP3PSin2;
+  frame2(d01, d02, S.e0, S.e1);
+  // the quartic, ascending
+  const double K = (S.a2 - S.c2) / S.b2, Cb = S.c2 / S.b2;
+  const double p0 = K + 1.0, p1 = -2.0 * K * S.cb, p2 = K - 1.0, q0 = 2.0 * S.cg, q1 = -2.0 * S.ca;
+  const double w0 = 1.0 - Cb, w1 = 2.0 * Cb * S.cb, w2 = -Cb;
+  const double qq0 = q0 * q0, qq1 = 2.0 * q0 * q1, qq2 = q1 * q1, m2 = -2.0 * S.cg;
+  double c[5];
+  c[0] = p0 * p0 + m2 * (p0 * q0) + qq0 * w0;
+  c[1] = 2.0 * p0 * p1 + m2 * (p0 * q1 + p1 * q0) + qq0 * w1 + qq1 * w0;
+  c[2] = 2.0 * p0 * p2 + p1 * p1 + m2 * (p1 * q1 + p2 * q0) + qq0 * w2 + qq1 * w1 + qq2 * w0;
+  c[3] = 2.0 * p1 * p2 + m2 * (p2 * q1) + qq1 * w2 + qq2 * w1;
+  c[4] = p2 * p2 + qq2 * w2;
+  double roots[4];
+  int count = 0;
+  real_roots<4>(c, roots, count);
+  if (!usable) count = 0;
+  double r0 = count > 0 ? roots[0] : INFINITY, r1 = count > 1 ? roots[1] : INFINITY, r2 = count > 2 ? roots[2] : INFINITY,
+         r3 = count > 3 ? roots[3] : INFINITY;
+  sort_step(r0, r1);      // ascending, the unused entries (+inf) last
+  sort_step(r2, r3);
+  sort_step(r0, r2);
+  sort_step(r1, r3);
+  sort_step(r1, r2);
+  T *out = models + (size_t)smp * 64;
+  uint8_t *vout = valid + (size_t)smp * 4;
+  int nv = 0;
+#pragma unroll 1
+  for (int k = 0; k < 4; ++k) {
+    const double v = k == 0 ? r0 : (k == 1 ? r1 : (k == 2 ? r2 : r3));
+    double R[3][3], t[3];
+    if (k < count && p3p_pose(S, v, R, t)) {
+      store_rigid_model(out + nv * 16, R, t);
+      vout[nv] = 1;
+      ++nv;
+    }
+  }
+  double R[3][3], t[3];
+  set_identity(R, t);
+  for (int j = nv; j < 4; ++j) {
+    store_rigid_model(out + j * 16, R, t);
+    vout[j] = 0;
+  }
+}
+
+// ---- (2), (3) the score of every pose against every point and the state step are pair_state_device.hpp's pair_score_kernel and
+// pair_update_kernel under PnPGeom and TransferMsacTerm (dr_pnp_score, dr_pnp_update); M = 4 B slots per round, iters += B
+
+// ---- (4) Levenberg-Marquardt on the reprojection error over the rows a mask selects (dr_refit_pnp) ----------------------------------
+// From init_model, `iters` passes at most.  A pass at the iterate (R, t): the row set is the mask's rows with z_c > 0 and a finite
+// residual under (R, t); over it the 21 + 6 + 1 sums upper(J^T J), J^T r, cost = sum |r|^2 (only when the iterate has moved since they
+// were last taken), with r = (x_c / z_c - u, y_c / z_c - v) and J its derivative with respect to a LEFT-multiplied step
+// (w, d): x_c' = exp([w]x) x_c + d, so per row, with i = 1 / z_c, x = x_c i, y = y_c i,
+//   d r_u = (-x y, 1 + x^2, -y, i, 0, -x i),   d r_v = (-1 - y^2, x y, x, 0, i, -y i).
+// Every thread solves (J^T J + lambda diag(J^T J)) step = -J^T r by Cholesky on the block's sums (they are the same bits in every
+// thread: nothing is broadcast), forms the candidate R' = exp([w]x) R, t' = exp([w]x) t + d (Rodrigues; the series below 1e-4 rad),
+// and the block sums the candidate's cost over the SAME row set.  The step is taken on a strictly lower cost with every row of the
+// set still in front of the camera and finite: lambda /= 10 (not below 1e-12); otherwise, and when the damped matrix is not positive
+// definite, lambda *= 10 and the iterate stays.  lambda starts at 1e-3.
+// valid = 0 (identity) for a non-finite start, fewer than three rows in front of the camera under the start, or a non-finite result.
+// Mapping: a latency kernel like registration_local_opt_kernel -- one 256-thread block per pair, f64, thread n owns rows n, n + 256,
+// ...; the passes of a pair are serial, each one two block-stride sweeps over the pair's 5 N values and N mask bytes.  The rows are
+// not staged in LDS: a sweep reads each row once, so LDS would only add a copy, and between sweeps the 20 N (40 N) bytes of a pair stay in
+// L2 (a few hundred KB at most for the row counts the drivers use); 64 KB of LDS would hold 1600 f64 rows, fewer than a pair may have.
+// Sums go lane, wave butterfly, the four waves in order (block_sum_f64); every branch that holds a barrier is block-uniform, no
+// atomics: a repeated launch gives the same bits.
+constexpr int kPRThreads = kPairThreads;
+
+// x_c = R X + t of a row -> is it in front of the camera with a finite residual; r = the residual
+__device__ __forceinline__ bool pnp_row(const double (&R)[3][3], const double (&t)[3], const double (&m)[5], double (&xc)[3],
+                                        double (&r)[2]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) xc[i] = R[i][0] * m[0] + R[i][1] * m[1] + R[i][2] * m[2] + t[i];
+  const double iz = 1.0 / xc[2];
+  r[0] = xc[0] * iz - m[3];
+  r[1] = xc[1] * iz - m[4];
+  return xc[2] > 0.0 && is_finite(r[0]) && is_finite(r[1]);
+}
+
+// (A + lambda diag A) s = -g for the upper triangle a[0..20] (row-major, i <= j) and g = a[21..26] -> is the matrix positive definite
+__device__ __forceinline__ bool lm_solve6(const double (&a)[28], double lambda, double (&s)[6]) {
+  double L[6][6];
+  {
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) L[j][i] = a[q++] * (i == j ? 1.0 + lambda : 1.0);
+  }
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = L[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d -= L[j][k] * L[j][k];
+    ok = ok && d > 0.0 && is_finite(d);
+    const double ld = sqrt(d), rl = 1.0 / ld;
+    L[j][j] = ld;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double v = L[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+      L[i][j] = v * rl;
+    }
+  }
+  double y[6];
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double v = -a[21 + i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+    y[i] = v / L[i][i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double v = y[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) v -= L[k][i] * s[k];
+    s[i] = v / L[i][i];
+    ok = ok && is_finite(s[i]);
+  }
+  return ok;
+}
+
+// (R', t') = (exp([w]x) R, exp([w]x) t + d), step = (w, d)
+__device__ __forceinline__ void lm_step(const double (&R)[3][3], const double (&t)[3], const double (&s)[6], double (&Rn)[3][3],
+                                        double (&tn)[3]) {
+  const double th2 = s[0] * s[0] + s[1] * s[1] + s[2] * s[2], th = sqrt(th2);
+  const bool small = th < 1e-4;
+  const double A = small ? 1.0 - th2 * (1.0 / 6.0) : sin(th) / th;
+  const double Bc = small ? 0.5 - th2 * (1.0 / 24.0) : (1.0 - cos(th)) / th2;
+  double E[3][3];
+  const double w[3] = {s[0], s[1], s[2]};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) E[i][j] = Bc * w[i] * w[j] + (i == j ? 1.0 - Bc * th2 : 0.0);      // I + B [w]x^2 = (1 - B th^2) I + B w w^T
+  E[0][1] -= A * w[2];
+  E[0][2] += A * w[1];
+  E[1][0] += A * w[2];
+  E[1][2] -= A * w[0];
+  E[2][0] -= A * w[1];
+  E[2][1] += A * w[0];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) Rn[i][j] = E[i][0] * R[0][j] + E[i][1] * R[1][j] + E[i][2] * R[2][j];
+    tn[i] = E[i][0] * t[0] + E[i][1] * t[1] + E[i][2] * t[2] + s[3 + i];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPRThreads) void refit_pnp_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                               const T *__restrict__ init_model, int N, int iters,
+                                                               T *__restrict__ model, uint8_t *__restrict__ valid) {
+  __shared__ double s_red[(kPRThreads / 64) * 28];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const T *pt = matches + (size_t)p * N * 5;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  double R[3][3], t[3];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      R[i][j] = (double)init_model[(size_t)p * 16 + 4 * i + j];
+      ok = ok && is_finite(R[i][j]);
+    }
+    t[i] = (double)init_model[(size_t)p * 16 + 4 * i + 3];
+    ok = ok && is_finite(t[i]);
+  }
+  auto load = [&](int n, double (&m)[5]) {
+#pragma unroll
+    for (int d = 0; d < 5; ++d) m[d] = (double)pt[(size_t)n * 5 + d];
+  };
+  double rows[1] = {0.0};
+  for (int n = tid; ok && n < N; n += kPRThreads) {
+    if (mk && !mk[n]) continue;
+    double m[5], xc[3], r[2];
+    load(n, m);
+    rows[0] += pnp_row(R, t, m, xc, r) ? 1.0 : 0.0;
+  }
+  block_sum_f64<1>(rows, reinterpret_cast<double(*)[1]>(s_red));
+  ok = ok && rows[0] >= 3.0;      // (block-uniform: the start is the same in every thread, the count a block sum)
+  double a[28], lambda = 1e-3;
+  bool fresh = false;
+  for (int it = 0; ok && it < iters; ++it) {
+    if (!fresh) {
+#pragma unroll
+      for (int q = 0; q < 28; ++q) a[q] = 0.0;
+      for (int n = tid; n < N; n += kPRThreads) {
+        if (mk && !mk[n]) continue;
+        double m[5], xc[3], r[2];
+        load(n, m);
+        if (!pnp_row(R, t, m, xc, r)) continue;
+        const double iz = 1.0 / xc[2], x = xc[0] * iz, y = xc[1] * iz;
+        const double ju[6] = {-x * y, 1.0 + x * x, -y, iz, 0.0, -x * iz}, jv[6] = {-1.0 - y * y, x * y, x, 0.0, iz, -y * iz};
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+#pragma unroll
+          for (int j = i; j < 6; ++j) a[q++] += ju[i] * ju[j] + jv[i] * jv[j];
+          a[21 + i] += ju[i] * r[0] + jv[i] * r[1];
+        }
+        a[27] += r[0] * r[0] + r[1] * r[1];
+      }
+      block_sum_f64<28>(a, reinterpret_cast<double(*)[28]>(s_red));
+      fresh = true;
+    }
+    double step[6], Rc[3][3], tc[3];
+    const bool spd = lm_solve6(a, lambda, step);      // (the same in every thread)
+    lm_step(R, t, step, Rc, tc);
+    double c[2] = {0.0, 0.0};      // the candidate's cost over the iterate's row set; rows it loses
+    for (int n = tid; spd && n < N; n += kPRThreads) {
+      if (mk && !mk[n]) continue;
+      double m[5], xc[3], r[2];
+      load(n, m);
+      if (!pnp_row(R, t, m, xc, r)) continue;
+      if (pnp_row(Rc, tc, m, xc, r)) c[0] += r[0] * r[0] + r[1] * r[1];
+      else c[1] += 1.0;
+    }
+    block_sum_f64<2>(c, reinterpret_cast<double(*)[2]>(s_red));
+    if (spd && c[1] == 0.0 && c[0] < a[27]) {
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[i][j] = Rc[i][j];
+        t[i] = tc[i];
+      }
+      lambda = fmax(lambda * 0.1, 1e-12);
+      fresh = false;
+    } else {
+      lambda *= 10.0;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) ok = ok && is_finite(R[i][j]);
+    ok = ok && is_finite(t[i]);
+  }
+  if (tid == 0) {
+    if (!ok) set_identity(R, t);
+    store_rigid_model(model + (size_t)p * 16, R, t);
+    valid[p] = ok;
+  }
+}
+
+}  // namespace dr
+
+extern "C" {
+
+#define DR_OP(sfx, T)                                                                                                              \
+  int dr_p3p_gather_##sfx(const T *matches, const int32_t *idx, int P, int B, int N, T *models, uint8_t *valid, void *stream) {     \
+    DR_REQUIRE(matches && idx && models && valid, "null pointer");                                                                  \
+    DR_REQUIRE(P > 0 && B > 0 && N > 0 && (long)P * B < (1l << 29), "need P, B, N > 0 and P * B < 2^29");                           \
+    return dr::launch("p3p_gather_kernel", dr::p3p_gather_kernel<T>, dim3((P * B + 63) / 64), 64, stream, matches, idx, P * B, B,   \
+                      N, models, valid);                                                                                            \
+  }                                                                                                                                 \
+  int dr_pnp_score_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,    \
+                         int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {                 \
+    DR_REQUIRE(matches && models && thr2 && scores, "null pointer");                                                                \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && P <= 65535, "bad sizes");                                                                 \
+    DR_REQUIRE((gate_iters == nullptr) == (gate_max_iters == nullptr), "gate: both pointers or neither");                           \
+    return dr::launch_pair_score<T, dr::PnPGeom, dr::TransferMsacTerm<T>>(matches, models, valid, thr2, P, M, N, scores, inliers,   \
+                                                                          gate_iters, gate_max_iters, stream);                      \
+  }                                                                                                                                 \
+  int dr_pnp_update_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *scores, const T *thr2, int P, int M,    \
+                          int N, int B, double confidence, double eps, int max_iterations, T *best_score, T *best_model,            \
+                          uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters, void *stream) {             \
+    DR_REQUIRE(matches && models && scores && thr2 && best_score && best_model && best_mask && best_inliers && iters && max_iters,  \
+               "null pointer");                                                                                                     \
+    DR_REQUIRE(P > 0 && M > 0 && N > 0 && B > 0 && max_iterations > 0, "bad sizes");                                                \
+    return dr::launch("pair_update_kernel", dr::pair_update_kernel<T, dr::PnPGeom>, dim3(P), dr::kPairThreads, stream, matches,     \
+                      models, valid, scores, thr2, M, N, B, confidence, eps, max_iterations, best_score, best_model, best_mask,     \
+                      best_inliers, iters, max_iters);                                                                              \
+  }                                                                                                                                 \
+  int dr_refit_pnp_##sfx(const T *matches, const uint8_t *mask, const T *init_model, int P, int N, int iters, T *model,             \
+                         uint8_t *valid, void *stream) {                                                                            \
+    DR_REQUIRE(matches && init_model && model && valid, "null pointer");                                                            \
+    DR_REQUIRE(P > 0 && N > 0 && (long)N * 5 < (1l << 31), "bad sizes");                                                            \
+    DR_REQUIRE(iters >= 0, "iters must be at least 0");                                                                             \
+    return dr::launch("refit_pnp_kernel", dr::refit_pnp_kernel<T>, dim3(P), dr::kPRThreads, stream, matches, mask, init_model, N,   \
+                      iters, model, valid);                                                                                         \
+  }
+DR_F32_F64(DR_OP)
+#undef DR_OP
+
+}  // extern "C"

@@ -795,6 +795,7 @@ _PairFamily = collections.namedtuple("_PairFamily", "entry width shape points gt
 _REGISTRATION = _PairFamily("registration", 6, (4, 4), "correspondences", "pose", "refit_rigid", False, None)
 _HOMOGRAPHY = _PairFamily("homography", 4, (3, 3), "matches", "homography", "refit_homography", True,
                           "matches [P,N,4] = (x1, y1, x2, y2)")
+_PNP = _PairFamily("pnp", 5, (4, 4), "matches", "pose", "refit_pnp", True, "matches [P,N,5] = (X, Y, Z, u, v)")
 
 
 def _check_matches(fam, name: str, matches: torch.Tensor) -> None:
@@ -816,13 +817,13 @@ class _PairState:
         self.max_iterations = int(max_iterations)
 
 
-def _pair_sample_fit(entry: str, side: int, matches, idx, scalars=(), counters=()):
-    """dr_<entry>_{f32,f64}: the fit of every sample idx [P,B,k] names -> (models [P,B,side,side], valid [P,B] bool); `scalars` follow
-    P, B, N by value, `counters` (tensors or None) the outputs"""
+def _pair_sample_fit(entry: str, side: int, matches, idx, scalars=(), counters=(), slots: int = 1):
+    """dr_<entry>_{f32,f64}: the fit of every sample idx [P,B,k] names -> (models [P,slots B,side,side], valid [P,slots B] bool), `slots`
+    model slots per sample; `scalars` follow P, B, N by value, `counters` (tensors or None) the outputs"""
     P, N, _ = matches.shape
     B = idx.shape[1]
-    models = torch.empty((P, B, side, side), device=matches.device, dtype=matches.dtype)
-    valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
+    models = torch.empty((P, slots * B, side, side), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P, slots * B), device=matches.device, dtype=torch.bool)
     L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, *scalars, ptr(models),
            ptr(valid), *map(ptr, counters), stream())
     return models, valid
@@ -1326,6 +1327,88 @@ def homography_irls(state: HomographyState, matches, thr2, irls_iters: int, irls
     taken only where it is strictly higher.  thr2 [P] = threshold^2 (thr2_tensor); irls_fits [P] int32 grows by the fits run.  Mask,
     inlier count and counters of the state are left alone.  One launch, no synchronisation."""
     _pair_irls(_HOMOGRAPHY, state, matches, thr2, irls_iters, irls_fits)
+
+
+# ------------------------------------------------------------------------------------------ absolute pose from 2D-3D matches
+# matches [P,N,5] = (X, Y, Z, u, v): a world point and its observation in NORMALISED image coordinates (K^-1 applied by the caller),
+# models [.,4,4] = [[R, t], [0, 0, 0, 1]] with x_c = R X + t (the registration layout: loss.registration_errors reads it).
+# d2 = (x_c / z_c - u)^2 + (y_c / z_c - v)^2; a point with z_c <= 0 never counts; `threshold` is a DISTANCE in normalised units.
+def _check_pnp_models(name: str, matches: torch.Tensor, models: torch.Tensor) -> None:
+    if models.dim() != 4 or models.shape != (matches.shape[0], models.shape[1], 4, 4) or models.dtype != matches.dtype:
+        raise L.DransacError(f"{name}: models [P,M,4,4] of the matches' dtype")
+
+
+def p3p_gather(matches: torch.Tensor, idx: torch.Tensor):
+    """dr_p3p_gather: matches [P,N,5], idx [P,B,3] int32 -> (models [P,4B,4,4], valid [P,4B] bool): the closed-form P3P poses of every
+    three-point sample.  Slots 4 b + j belong to sample b: the valid ones first, in ascending order of the quartic's root, each with R
+    orthonormal, det R = +1 and the three sample points in front of the camera; every other slot is the identity with valid = 0.  A
+    sample with coincident or collinear world points, coincident bearings or no finite solution has four invalid slots."""
+    _gpu_only((matches, idx))
+    _check_matches(_PNP, "p3p_gather", matches)
+    if idx.dim() != 3 or idx.shape[-1] != 3 or idx.dtype != torch.int32 or idx.shape[0] != matches.shape[0]:
+        raise L.DransacError("p3p_gather: int32 index sets [P,B,3]")
+    return _pair_sample_fit("p3p_gather", 4, matches, idx, slots=4)
+
+
+def pnp_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: Optional[torch.Tensor] = None,
+              want_inliers: bool = True, gate=None, thr2: Optional[torch.Tensor] = None):
+    """dr_pnp_score: matches [P,N,5], models [P,M,4,4], threshold = inlier DISTANCE in normalised units (float or [P]) ->
+    (scores [P,M] = sum_n max(0, 1 - d2_n / threshold^2), inliers [P,M] int32 = #{d2_n < threshold^2} | None) over the points in front
+    of the camera.  A slot with valid = 0 scores exactly 0; a non-finite model scores NaN.  Bit-repeatable (fixed reduction order).
+    gate = PnPState: the blocks of terminated pairs return at once and their rows keep their contents."""
+    _gpu_only((matches, models))
+    _gpu_only((valid, thr2), optional=True)
+    _check_matches(_PNP, "pnp_score", matches)
+    _check_pnp_models("pnp_score", matches, models)
+    if valid is not None and valid.shape != models.shape[:2]:
+        raise L.DransacError("pnp_score: valid [P,M], one flag per model slot")
+    return _pair_score("pnp_score", matches, models, threshold, valid, want_inliers, thr2, True, gate)
+
+
+class PnPState(_PairState):
+    """Per-pair state of a BatchedPnP call, on the device: best_score [P] (0), best_model [P,4,4] (identity), best_mask [P,N],
+    best_inliers [P] int32, iters [P] int32, max_iters [P] f64 (= max_iterations).  Allocated and filled with torch (capturable)."""
+
+    def __init__(self, P: int, N: int, max_iterations: int, device, dtype):
+        super().__init__(4, P, N, max_iterations, device, dtype)
+
+
+def pnp_update(state: PnPState, matches, models, valid, scores, threshold, B: int, confidence: float = 0.999, eps: float = 1e-5,
+               thr2: Optional[torch.Tensor] = None) -> None:
+    """dr_pnp_update, in place on `state`: per pair with iters < max_iters the first arg-max of scores [P,M] over valid, non-NaN slots
+    replaces the state if score > best_score (mask and inlier count recomputed with the score kernel's expression,
+    max_iters = min(max_iterations, adaptive_iteration_number(inliers, N, 3))); iters += B -- the SAMPLES of the round, M = 4 B slots."""
+    _gpu_only((matches, models, scores, state.best_score))
+    _gpu_only((valid, thr2), optional=True)
+    _check_matches(_PNP, "pnp_update", matches)
+    _check_pnp_models("pnp_update", matches, models)
+    if scores.shape != models.shape[:2] or scores.dtype != matches.dtype:
+        raise L.DransacError("pnp_update: scores [P,M] of the matches' dtype")
+    if state.best_model.shape != (matches.shape[0], 4, 4) or state.best_mask.shape != matches.shape[:2]:
+        raise L.DransacError("pnp_update: the state is a PnPState of this call's P and N")
+    _pair_update("pnp_update", state, matches, models, valid, scores, threshold, B, confidence, eps, thr2)
+
+
+def refit_pnp(matches: torch.Tensor, mask: Optional[torch.Tensor], init_model: torch.Tensor, iters: int = 10):
+    """dr_refit_pnp: Levenberg-Marquardt on the reprojection error from init_model [P,4,4], over the rows mask [P,N] selects (None = all)
+    that lie in front of the camera under the current iterate -> (model [P,4,4], valid [P] bool).  `iters` passes at most; a step (a
+    left-multiplied rotation vector and a translation) is taken only on a strictly lower cost over the same rows, otherwise the damping
+    grows.  valid = 0 (identity) for a non-finite start or result and below three rows."""
+    _gpu_only((matches, init_model))
+    _gpu_only((mask,), optional=True)
+    _check_matches(_PNP, "refit_pnp", matches)
+    P, N, _ = matches.shape
+    if init_model.shape != (P, 4, 4) or init_model.dtype != matches.dtype:
+        raise L.DransacError("refit_pnp: init_model [P,4,4] of the matches' dtype")
+    if mask is not None and mask.shape != (P, N):
+        raise L.DransacError("the refit mask is [P,N], one flag per point")
+    if int(iters) < 0:
+        raise L.DransacError(f"refit_pnp: iters must be at least 0, got {iters!r}")
+    model = torch.empty((P, 4, 4), device=matches.device, dtype=matches.dtype)
+    valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
+    L.call(f"dr_refit_pnp_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask), ptr(init_model.contiguous()), P, N,
+           int(iters), ptr(model), ptr(valid), stream())
+    return model, valid
 
 
 class _Homography4(torch.autograd.Function):

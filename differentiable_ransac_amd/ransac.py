@@ -1012,12 +1012,12 @@ class BatchedRANSAC3D(_SeededDriver):
 
 
 class _PairStateDriver(_SeededDriver):
-    """What BatchedRegistration and BatchedHomography share: the constructor's common checks and attributes, the index sets of a round
+    """What BatchedRegistration, BatchedHomography and BatchedPnP share: the constructor's common checks and attributes, the index sets of a round
     (Gumbel top-k or PROSAC, one seed per round), the train loop (ops.SampleGather -> the family's differentiable fit) and the test
     loop on a per-pair state on the device (draw -> fit -> score -> update -> _after_update -> read-back of "does any pair continue?"),
     and the final stage: the refit, taken where it scores strictly higher, or under scoring="magsac" the IRLS polish.  The constructor
     checks the options of both families once.  A family sets `k`, `_columns` / `_shape_error`, `_State` and the ops `_fit`, `_fit_train`,
-    `_score_msac`, `_score_magsac`, `_update`, `_refit`, `_irls`, and switches on what it supports: local optimisation by taking `lo` /
+    `_score_msac`, `_score_magsac`, `_update`, `_refit` (or `_refit_candidate`, where the refit needs more than the mask), `_irls`, and switches on what it supports: local optimisation by taking `lo` /
     `lo_iters` and naming `_lo_width` and `_local_optimize`, device_termination by exposing `_device_termination_switch` under that
     name.  What else it does hangs on _begin, _fit and _finish."""
 
@@ -1145,6 +1145,10 @@ class _PairStateDriver(_SeededDriver):
         """the read-back after round r: has every pair terminated (none under device_termination)"""
         return not self._device_termination and r + 1 < rounds and not bool((c.st.iters.double() < c.st.max_iters).any())
 
+    def _refit_candidate(self, c):
+        """the refit candidate of this call -> (model [P,.,.], valid [P]); a family whose refit needs more than the mask overrides it"""
+        return self._refit(c.matches, c.st.best_mask)
+
     def _finish(self, c):
         model, score, extra = c.st.best_model, c.st.best_score, {}
         if self.scoring == "magsac":      # the IRLS polish in the single refit's place, in place on the state; the mask stays the RANSAC winner's
@@ -1152,7 +1156,7 @@ class _PairStateDriver(_SeededDriver):
             if self.refit and self.irls_iters > 0:
                 self._irls(c.st, c.matches, c.thr2, self.irls_iters, extra["irls_fits"])
         elif self.refit:
-            cand, cvalid = self._refit(c.matches, c.st.best_mask)
+            cand, cvalid = self._refit_candidate(c)
             cscore = self._score(c, None, cand.unsqueeze(1), cvalid.unsqueeze(1))
             take = cscore[:, 0] > score          # (an invalid candidate scores -1 or 0, a NaN never compares higher: neither wins)
             model = torch.where(take[:, None, None], cand, model)
@@ -1318,3 +1322,55 @@ class BatchedHomography(_PairStateDriver):
 
     def _fit(self, c, idx):
         return ops.homography4_gather(c.matches, idx)
+
+
+class BatchedPnP(_PairStateDriver):
+    """Robust absolute camera pose from 2D-3D matches: matches [P,N,5] = (X, Y, Z, u, v) -- a world point and its observation in
+    NORMALISED image coordinates (the caller has applied K^-1; there is no K) --, logits [P,N] -> dict(model [P,4,4] =
+    [[R, t], [0, 0, 0, 1]] with x_cam = R X + t, mask [P,N], score [P], inliers [P], iterations [P]).  The model layout is
+    BatchedRegistration's, so loss.registration_errors gives RRE / RTE on it.
+
+    One round = K1 Gumbel top-k (index sets of 3 points) -> dr_p3p_gather (the closed-form P3P poses of every sample: 4 slots per
+    sample, the valid ones first; a degenerate sample has none) -> dr_pnp_score (MSAC score of all 4 B slots against every point under
+    the reprojection error) -> dr_pnp_update (first arg-max, strictly-better test, mask, adaptive stop with sample size 3, all
+    per-pair state on the device).  `iterations` advances by the B SAMPLES of a round, not by its 4 B slots.  The host reads back "does
+    any pair continue?" after each round.  With `refit`, dr_refit_pnp -- at most `refit_iters` Levenberg-Marquardt passes on the
+    reprojection error, from the state's best model over its best mask -- replaces the model where it scores strictly higher; the mask
+    stays the RANSAC winner's.
+
+    `threshold` is a DISTANCE in normalised units (pixels divided by the focal length): a point is an inlier iff
+    d2 = (x_c / z_c - u)^2 + (y_c / z_c - v)^2 < threshold^2; a point with z_c <= 0 never counts.
+
+    device_termination = True issues every round, gated on the device, with no read-back; it is refused above 16 rounds.
+    sampling = "prosac": ops.prosac_sample in ops.gumbel_topk's place, as in BatchedRegistration; refused with explicit `gumbels`.
+
+    Not here, each refused with NotImplementedError: train = True (a differentiable P3P needs a backward),
+    scoring = "magsac", lo != 0."""
+
+    k = 3
+
+    def __init__(self, ransac_batch_size=1024, threshold=0.005, confidence=0.999, max_iterations=5000, tau=1.0, seed=0, refit=True,
+                 refit_iters=10, eps=1e-5, sampling="gumbel", prosac_draws=200000, train=False, scoring="msac", lo=0):
+        if train:
+            raise NotImplementedError("BatchedPnP(train=True): a differentiable P3P needs a backward, which is not built (DESIGN.md §8)")
+        if scoring != "msac":
+            raise NotImplementedError(f"BatchedPnP(scoring={scoring!r}): only MSAC scoring is built for this family (DESIGN.md §8)")
+        if lo:
+            raise NotImplementedError(f"BatchedPnP(lo={lo!r}): local optimisation is not built for this family (DESIGN.md §8)")
+        super().__init__(ransac_batch_size, threshold, confidence, max_iterations, tau, seed, refit, eps, False, sampling, prosac_draws,
+                         "msac", 0)
+        if isinstance(refit_iters, bool) or int(refit_iters) != refit_iters or int(refit_iters) < 0:
+            raise ValueError(f"refit_iters must be an integer of at least 0, got {refit_iters!r}")
+        self.refit_iters = int(refit_iters)
+
+    device_termination = _PairStateDriver._device_termination_switch
+    _columns, _shape_error = 5, "matches must be [P,N,5] = (X, Y, Z, u, v)"
+    _State = ops.PnPState
+    _score_msac = staticmethod(ops.pnp_score)
+    _update = staticmethod(ops.pnp_update)
+
+    def _fit(self, c, idx):
+        return ops.p3p_gather(c.matches, idx)
+
+    def _refit_candidate(self, c):
+        return ops.refit_pnp(c.matches, c.st.best_mask, c.st.best_model, self.refit_iters)

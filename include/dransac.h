@@ -568,6 +568,52 @@ int dr_homography_irls_f64(const double *matches, const double *thr2, int P, int
                            double *best_model, int32_t *irls_fits, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Absolute pose from 2D-3D matches (ransac.BatchedPnP).  Not a restatement of upstream code.  matches [P,N,5] = (X, Y, Z, u, v): a
+ * world point and its observation in NORMALISED image coordinates (the caller has applied K^-1; there is no K).  A model [.,16] is the
+ * row-major 4x4 [[R, t], [0, 0, 0, 1]] with x_c = R X + t, the layout of the registration entries.  Residual:
+ * d2 = (x_c / z_c - u)^2 + (y_c / z_c - v)^2; a point with z_c <= 0 or a non-finite d2 is an outlier and contributes nothing.  The
+ * threshold is a DISTANCE in normalised units (pixels / focal length) and enters as thr2 [P] = threshold^2: inlier iff d2 < thr2, MSAC
+ * score = sum_n max(0, 1 - d2_n / thr2).
+ *
+ *   dr_p3p_gather   idx [P,B,3] int32 -> models [P,4B,16], valid [P,4B]: the closed-form P3P of every sample, f64 inside, one lane per
+ *     sample.  Bearings f_i = normalize(u_i, v_i, 1); with the depths s_1 = x s_0, s_2 = v s_0 the law of cosines in the three triangles
+ *     (camera centre, two points) gives x = p(v) / q(v) and the quartic p^2 - 2 cos(f_0, f_1) p q + q^2 (1 - (c^2 / b^2) g(v)) = 0
+ *     (Grunert's P3P in the Fischler-Bolles ratio form; pnp.hip states p, q, g).  Each real root with positive depths, polished by two
+ *     Newton steps on the three distance equations, gives one pose through the orthonormal frames of the world and the camera triangle.
+ *     Slots 4 b + j of sample b: the valid ones first, in ascending order of v; a valid slot has R orthonormal with det = +1 and the
+ *     three sample points at z_c > 0; every other slot is the identity with valid = 0.  All four are invalid for an index outside
+ *     [0, N), coincident or collinear world points, coincident bearings, or no surviving root.  No atomics: bit-repeatable.
+ *   dr_pnp_score    models [P,M,16], valid [P,M] or NULL -> scores [P,M], inliers [P,M] int32 (or NULL).  A slot with valid = 0
+ *     scores exactly 0 (0 inliers) and is never evaluated; a model with a non-finite entry scores NaN (0 inliers).  f32 computes in
+ *     f32 (one v_rcp_f32 per model and point), f64 in f64.  gate_iters / gate_max_iters (both or neither): the blocks of pairs with
+ *     iters >= max_iters return at once and the pair's outputs keep their contents.  No [P,M,N] tensor, no atomics, one fixed
+ *     reduction order: a repeated launch gives the same bits.  P <= 65535.
+ *   dr_pnp_update   dr_homography_update's state step with sample size 3 in the adaptive stop and best_model [P,16]: strict
+ *     "better?" test in every round, iters += B (B = samples of the round; M = 4 B slots).
+ *   dr_refit_pnp    Levenberg-Marquardt on the reprojection error from init_model [P,16] over the rows mask [P,N] selects (NULL = all)
+ *     that lie in front of the camera under the current iterate -> model [P,16], valid [P].  `iters` passes at most; a pass solves
+ *     (J^T J + lambda diag(J^T J)) step = -J^T r (f64 sums in one fixed order, Cholesky), the step is a left-multiplied rotation vector
+ *     and a translation, taken only on a strictly lower cost over the same row set (lambda / 10, else lambda x 10; from 1e-3).
+ *     valid = 0, model = identity: a non-finite start or result, fewer than three such rows under the start.  Bit-repeatable.
+ * ------------------------------------------------------------------------------------------ */
+int dr_p3p_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, float *models, uint8_t *valid, void *stream);
+int dr_p3p_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, double *models, uint8_t *valid, void *stream);
+int dr_pnp_score_f32(const float *matches, const float *models, const uint8_t *valid, const float *thr2, int P, int M, int N,
+                     float *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream);
+int dr_pnp_score_f64(const double *matches, const double *models, const uint8_t *valid, const double *thr2, int P, int M, int N,
+                     double *scores, int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream);
+int dr_pnp_update_f32(const float *matches, const float *models, const uint8_t *valid, const float *scores, const float *thr2, int P,
+                      int M, int N, int B, double confidence, double eps, int max_iterations, float *best_score, float *best_model,
+                      uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters, void *stream);
+int dr_pnp_update_f64(const double *matches, const double *models, const uint8_t *valid, const double *scores, const double *thr2,
+                      int P, int M, int N, int B, double confidence, double eps, int max_iterations, double *best_score,
+                      double *best_model, uint8_t *best_mask, int32_t *best_inliers, int32_t *iters, double *max_iters, void *stream);
+int dr_refit_pnp_f32(const float *matches, const uint8_t *mask, const float *init_model, int P, int N, int iters, float *model,
+                     uint8_t *valid, void *stream);
+int dr_refit_pnp_f64(const double *matches, const uint8_t *mask, const double *init_model, int P, int N, int iters, double *model,
+                     uint8_t *valid, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * The training loss of the registration path (loss.RegistrationLoss).  Not a restatement of upstream code: RANSACLayer3D's own loss
  * (model_cl.py:586-589) is the mean squared residual over ALL points, which dr_rigid_residual already reproduces.  matches, models,
  * thr2 as above; mask [P,N] (the ground-truth inliers; NULL = all points), keep [P,M] (NULL = all models).  With r = R p + t - q:
