@@ -125,23 +125,19 @@ __device__ __forceinline__ void sort_step(double &a, double &b) {
   b = hi;
 }
 
-template <typename T>
-__global__ __launch_bounds__(64) void p3p_gather_kernel(const T *__restrict__ matches, const int32_t *__restrict__ idx, int Bt, int B,
-                                                        int N, T *__restrict__ models, uint8_t *__restrict__ valid) {
-  const int smp = blockIdx.x * 64 + threadIdx.x;
-  if (smp >= Bt) return;
-  const T *base = matches + (size_t)(smp / B) * N * 5;
-  const int32_t *gi = idx + (size_t)smp * 3;
-  bool usable = true;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) usable = usable && gi[r] >= 0 && gi[r] < N;      // (a bad index reads row 0, every slot invalid)
+// The whole closed form of one sample, shared by the gather kernel, the kernel on explicit samples and the reverse pass: the three rows
+// come through row(r) (a pointer to the five values of row r), and slot(j, R, t, S) is called once for every valid pose, in slot
+// order j = 0, 1, ... (ascending root).  Returns the number of valid slots.  One text, so the three kernels compute the same poses in
+// the same order; the slot loop stays rolled (#pragma unroll 1: four copies of p3p_pose would not fit the register file).
+template <typename T, typename RowFn, typename SlotFn>
+__device__ __forceinline__ int p3p_fwd(RowFn row, bool usable, SlotFn slot) {
   P3PSample S;
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    const T *row = base + (size_t)(usable ? gi[r] : 0) * 5;
+    const T *p = row(r);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) S.X[r][d] = (double)row[d];
-    const double u = (double)row[3], w = (double)row[4], rn = 1.0 / sqrt(u * u + w * w + 1.0);
+    for (int d = 0; d < 3; ++d) S.X[r][d] = (double)p[d];
+    const double u = (double)p[3], w = (double)p[4], rn = 1.0 / sqrt(u * u + w * w + 1.0);
     S.f[r][0] = u * rn;
     S.f[r][1] = w * rn;
     S.f[r][2] = rn;
@@ -187,25 +183,248 @@ __global__ __launch_bounds__(64) void p3p_gather_kernel(const T *__restrict__ ma
   sort_step(r0, r2);
   sort_step(r1, r3);
   sort_step(r1, r2);
-  T *out = models + (size_t)smp * 64;
-  uint8_t *vout = valid + (size_t)smp * 4;
   int nv = 0;
 #pragma unroll 1
   for (int k = 0; k < 4; ++k) {
     const double v = k == 0 ? r0 : (k == 1 ? r1 : (k == 2 ? r2 : r3));
     double R[3][3], t[3];
     if (k < count && p3p_pose(S, v, R, t)) {
-      store_rigid_model(out + nv * 16, R, t);
-      vout[nv] = 1;
+      slot(nv, R, t, S);
       ++nv;
     }
   }
+  return nv;
+}
+
+// the valid poses into slots 0 .. nv - 1 of the sample, the identity with valid = 0 into the rest
+template <typename T, typename RowFn>
+__device__ __forceinline__ void p3p_store(RowFn row, bool usable, T *__restrict__ out, uint8_t *__restrict__ vout) {
+  const int nv = p3p_fwd<T>(row, usable, [&](int j, const double (&R)[3][3], const double (&t)[3], const P3PSample &) {
+    store_rigid_model(out + j * 16, R, t);
+    vout[j] = 1;
+  });
   double R[3][3], t[3];
   set_identity(R, t);
   for (int j = nv; j < 4; ++j) {
     store_rigid_model(out + j * 16, R, t);
     vout[j] = 0;
   }
+}
+
+// rows read through the index sets: one lane = one sample (a bad index reads row 0, every slot invalid)
+template <typename T>
+__global__ __launch_bounds__(64) void p3p_gather_kernel(const T *__restrict__ matches, const int32_t *__restrict__ idx, int Bt, int B,
+                                                        int N, T *__restrict__ models, uint8_t *__restrict__ valid) {
+  const int smp = blockIdx.x * 64 + threadIdx.x;
+  if (smp >= Bt) return;
+  const T *base = matches + (size_t)(smp / B) * N * 5;
+  const int32_t *gi = idx + (size_t)smp * 3;
+  bool usable = true;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) usable = usable && gi[r] >= 0 && gi[r] < N;
+  p3p_store<T>([&](int r) { return base + (size_t)(usable ? gi[r] : 0) * 5; }, usable, models + (size_t)smp * 64,
+               valid + (size_t)smp * 4);
+}
+
+// explicit sample tensors [Bt,3,5]: what train mode fits.  On samples = matches[idx] the bits of the gather kernel.
+template <typename T>
+__global__ __launch_bounds__(64) void p3p_kernel(const T *__restrict__ samples, int Bt, T *__restrict__ models,
+                                                 uint8_t *__restrict__ valid) {
+  const int smp = blockIdx.x * 64 + threadIdx.x;
+  if (smp >= Bt) return;
+  const T *base = samples + (size_t)smp * 15;
+  p3p_store<T>([&](int r) { return base + r * 5; }, true, models + (size_t)smp * 64, valid + (size_t)smp * 4);
+}
+
+// ---- (1b) the reverse pass of (1): grad_models [4 Bt,4,4] -> grad_samples [Bt,3,5] ---------------------------------------------------
+// A valid pose (R, t) of a sample is a root of the six equations r(theta; sample) = 0, r_i = (x_c / z_c - u_i, y_c / z_c - v_i) at
+// x_c = R X_i + t for the three rows: its derivative follows from the implicit function theorem, whatever route the forward took to the
+// root (quartic, Newton polish, frames).  theta is dr_refit_pnp's LEFT-multiplied step (w, d): R' = exp([w]x) R, t' = exp([w]x) t + d.
+//   1. the incoming G = grad_models of the slot (rows 0-2 read, row 3 ignored) as a tangent gradient:
+//        g_theta = (sum_j R[:,j] x G_R[:,j] + t x G_t,  G_t).
+//      Only the tangential part of G_R enters: a component normal to the rotation manifold (symmetric G_R R^T) passes nothing on.
+//   2. J (6x6) = d r / d theta: per row i the two rows d r_u, d r_v of dr_refit_pnp's header, i.e. A_i [-[x_c]x | I] with
+//      A_i = (1 / z_c) [[1, 0, -x], [0, 1, -y]].
+//   3. J^T lambda = g_theta by LU with partial pivoting in registers (lu_solve6).
+//   4. d r_i / d X_i = A_i R and d r_i / d (u, v)_i = -I, so  grad X_i += -(A_i R)^T lambda_i,  grad (u, v)_i += lambda_i.
+// The theorem holds AT the root, and the forward's pose is a few ulp times the sample's conditioning away from it (two Newton steps on
+// the depths, then the frames); an ill-conditioned sample turns that distance into a gradient error hundreds of times as large.  So
+// before step 1 the slot's pose takes ONE Gauss-Newton step on r = 0 in the same parametrisation, J delta = -r by the same LU,
+// (R, t) <- (exp([w]x) R, exp([w]x) t + d) (lm_step): the six equations have six unknowns, the step converges quadratically and one of
+// them leaves the pose at the rounding of r, which is evaluated as a two-term sum (dd_row, dd_residual) so that it is the rounding of
+// the pose's own entries and not eps times the conditioning.  The step is not taken when a pivot fails the guard below or delta is not finite.  The
+// models the forward returned are not touched: the polish moves only the point at which the derivative is evaluated.
+// The lane recomputes the sample's poses with p3p_fwd -- the slot order is the forward's by construction, no model is saved -- and adds
+// the contributions of the valid slots in slot order.  A slot contributes exact zeros when it is invalid (its gradient is never read:
+// NaN there reaches nothing), when a pivot of the elimination is not larger than kP3PPivot times the largest |entry| of J (a pose at
+// a double root of the quartic: J is singular there and the derivative does not exist; false for NaN too), or when any of its fifteen
+// results is not finite.  Every output element is written; a sample with no contributing slot gets fifteen exact zeros.
+// Mapping: the forward's -- one lane per sample, 64-thread blocks, f64 in registers for either type; no atomics, no LDS: a repeated
+// launch repeats bit for bit.
+constexpr double kP3PPivot = 1e-12;
+
+// A x = b in place (b becomes x) by LU with partial pivoting, fully unrolled: the row exchange is a compare-and-select sweep that
+// leaves the column's largest entry in row k, so nothing is indexed at run time and the matrix stays in registers.
+// false: a pivot with |pivot| <= tiny (or NaN).
+__device__ __forceinline__ bool lu_solve6(double (&A)[6][6], double (&b)[6], double tiny) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int r = k + 1; r < 6; ++r) {
+      const bool sw = fabs(A[r][k]) > fabs(A[k][k]);
+#pragma unroll
+      for (int c = k; c < 6; ++c) {
+        const double hi = A[k][c], lo = A[r][c];
+        A[k][c] = sw ? lo : hi;
+        A[r][c] = sw ? hi : lo;
+      }
+      const double hi = b[k], lo = b[r];
+      b[k] = sw ? lo : hi;
+      b[r] = sw ? hi : lo;
+    }
+    ok = ok && fabs(A[k][k]) > tiny;
+    const double rp = 1.0 / A[k][k];
+#pragma unroll
+    for (int r = k + 1; r < 6; ++r) {
+      const double f = A[r][k] * rp;
+#pragma unroll
+      for (int c = k + 1; c < 6; ++c) A[r][c] -= f * A[k][c];
+      b[r] -= f * b[k];
+    }
+  }
+#pragma unroll
+  for (int k = 5; k >= 0; --k) {
+    double v = b[k];
+#pragma unroll
+    for (int c = k + 1; c < 6; ++c) v -= A[k][c] * b[c];
+    b[k] = v / A[k][k];
+  }
+  return ok;
+}
+
+// the two rows of J = d r / d (w, d) of one sample row at x_c = R X + t (dr_refit_pnp's header), and 1 / z_c, x, y
+__device__ __forceinline__ void p3p_jac_rows(const double (&R)[3][3], const double (&t)[3], const double (&X)[3], double (&ju)[6],
+                                             double (&jv)[6], double &iz, double &x, double &y) {
+  double xc[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) xc[r] = R[r][0] * X[0] + R[r][1] * X[1] + R[r][2] * X[2] + t[r];
+  iz = 1.0 / xc[2];
+  x = xc[0] * iz;
+  y = xc[1] * iz;
+  ju[0] = -x * y, ju[1] = 1.0 + x * x, ju[2] = -y, ju[3] = iz, ju[4] = 0.0, ju[5] = -x * iz;
+  jv[0] = -1.0 - y * y, jv[1] = x * y, jv[2] = x, jv[3] = 0.0, jv[4] = iz, jv[5] = -y * iz;
+}
+
+__device__ __forceinline__ void lm_step(const double (&R)[3][3], const double (&t)[3], const double (&s)[6], double (&Rn)[3][3],
+                                        double (&tn)[3]);      // (section 4)
+
+// r . X + t as an unevaluated sum hi + lo (exact products by fma, Knuth's two-sum): the residual of the polish cancels from |x_c| to
+// 1e-15 and an f64 evaluation would leave the step at eps times the sample's conditioning.  No contraction here: the error terms
+// are differences of the very products and sums a contraction would fuse.
+__device__ __forceinline__ void dd_row(const double (&r)[3], double t, const double (&X)[3], double &hi, double &lo) {
+#pragma clang fp contract(off)
+  hi = t;
+  lo = 0.0;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const double p = r[j] * X[j], pe = fma(r[j], X[j], -p);
+    const double s = hi + p, bb = s - hi;
+    lo += ((hi - (s - bb)) + (p - bb)) + pe;
+    hi = s;
+  }
+}
+
+// (x_c - u z_c) / z_c of one coordinate from the two-term forms of x_c and z_c: the subtraction is exact where it cancels
+__device__ __forceinline__ double dd_residual(double xh, double xl, double zh, double zl, double u) {
+#pragma clang fp contract(off)
+  const double q = u * zh, qe = fma(u, zh, -q);
+  return ((xh - q) + ((xl - qe) - u * zl)) / zh;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void p3p_bwd_kernel(const T *__restrict__ samples, const T *__restrict__ grad_models, int Bt,
+                                                     T *__restrict__ grad_samples) {
+  const int smp = blockIdx.x * 64 + threadIdx.x;
+  if (smp >= Bt) return;
+  const T *base = samples + (size_t)smp * 15;
+  double acc[15];
+#pragma unroll
+  for (int q = 0; q < 15; ++q) acc[q] = 0.0;
+  p3p_fwd<T>([&](int r) { return base + r * 5; }, true, [&](int j, const double (&R0)[3][3], const double (&t0)[3], const P3PSample &S) {
+    // one Gauss-Newton step onto the root of the sample's six reprojection equations
+    double R[3][3], t[3];
+    {
+      double J[6][6], d[6], big = 0.0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        double iz, x, y;
+        p3p_jac_rows(R0, t0, S.X[i], J[2 * i], J[2 * i + 1], iz, x, y);
+        double xh, xl, yh, yl, zh, zl;
+        dd_row(R0[0], t0[0], S.X[i], xh, xl);
+        dd_row(R0[1], t0[1], S.X[i], yh, yl);
+        dd_row(R0[2], t0[2], S.X[i], zh, zl);
+        d[2 * i] = -dd_residual(xh, xl, zh, zl, (double)base[5 * i + 3]);
+        d[2 * i + 1] = -dd_residual(yh, yl, zh, zl, (double)base[5 * i + 4]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) big = fmax(big, fmax(fabs(J[2 * i][a]), fabs(J[2 * i + 1][a])));
+      }
+      bool step = lu_solve6(J, d, kP3PPivot * big);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) step = step && is_finite(d[a]);
+      if (!step) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) d[a] = 0.0;      // (the identity step: the forward's pose)
+      }
+      lm_step(R0, t0, d, R, t);
+    }
+    const T *G = grad_models + ((size_t)smp * 4 + j) * 16;
+    double gR[3][3], g[6];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) gR[i][c] = (double)G[4 * i + c];
+      g[3 + i] = (double)G[4 * i + 3];
+    }
+    // sum_j R[:,j] x G_R[:,j] + t x G_t
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int a = (i + 1) % 3, b = (i + 2) % 3;
+      double v = t[a] * g[3 + b] - t[b] * g[3 + a];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) v += R[a][c] * gR[b][c] - R[b][c] * gR[a][c];
+      g[i] = v;
+    }
+    // J^T, column 2 i and 2 i + 1 from row i; the largest |entry|
+    double Jt[6][6], iz[3], x[3], y[3], big = 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double ju[6], jv[6];
+      p3p_jac_rows(R, t, S.X[i], ju, jv, iz[i], x[i], y[i]);
+#pragma unroll
+      for (int a = 0; a < 6; ++a) {
+        Jt[a][2 * i] = ju[a];
+        Jt[a][2 * i + 1] = jv[a];
+        big = fmax(big, fmax(fabs(ju[a]), fabs(jv[a])));
+      }
+    }
+    bool ok = lu_solve6(Jt, g, kP3PPivot * big);      // g is lambda from here
+    double out[15];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c)      // -(A_i R)^T lambda_i, A_i R = (1 / z_c) (R_0 - x R_2, R_1 - y R_2)
+        out[5 * i + c] = -iz[i] * ((R[0][c] - x[i] * R[2][c]) * g[2 * i] + (R[1][c] - y[i] * R[2][c]) * g[2 * i + 1]);
+      out[5 * i + 3] = g[2 * i];
+      out[5 * i + 4] = g[2 * i + 1];
+    }
+#pragma unroll
+    for (int q = 0; q < 15; ++q) ok = ok && is_finite(out[q]);
+#pragma unroll
+    for (int q = 0; q < 15; ++q) acc[q] += ok ? out[q] : 0.0;
+  });
+#pragma unroll
+  for (int q = 0; q < 15; ++q) grad_samples[(size_t)smp * 15 + q] = (T)acc[q];
 }
 
 // ---- (2), (3) the score of every pose against every point and the state step are pair_state_device.hpp's pair_score_kernel and
@@ -422,6 +641,17 @@ extern "C" {
     DR_REQUIRE(P > 0 && B > 0 && N > 0 && (long)P * B < (1l << 29), "need P, B, N > 0 and P * B < 2^29");                           \
     return dr::launch("p3p_gather_kernel", dr::p3p_gather_kernel<T>, dim3((P * B + 63) / 64), 64, stream, matches, idx, P * B, B,   \
                       N, models, valid);                                                                                            \
+  }                                                                                                                                 \
+  int dr_p3p_##sfx(const T *samples, int Bt, T *models, uint8_t *valid, void *stream) {                                             \
+    DR_REQUIRE(samples && models && valid, "null pointer");                                                                         \
+    DR_REQUIRE(Bt > 0 && Bt < (1 << 29), "need 0 < Bt < 2^29");                                                                     \
+    return dr::launch("p3p_kernel", dr::p3p_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, Bt, models, valid);               \
+  }                                                                                                                                 \
+  int dr_p3p_bwd_##sfx(const T *samples, const T *grad_models, int Bt, T *grad_samples, void *stream) {                             \
+    DR_REQUIRE(samples && grad_models && grad_samples, "null pointer");                                                             \
+    DR_REQUIRE(Bt > 0 && Bt < (1 << 29), "need 0 < Bt < 2^29");                                                                     \
+    return dr::launch("p3p_bwd_kernel", dr::p3p_bwd_kernel<T>, dim3((Bt + 63) / 64), 64, stream, samples, grad_models, Bt,          \
+                      grad_samples);                                                                                                \
   }                                                                                                                                 \
   int dr_pnp_score_##sfx(const T *matches, const T *models, const uint8_t *valid, const T *thr2, int P, int M, int N, T *scores,    \
                          int32_t *inliers, const int32_t *gate_iters, const double *gate_max_iters, void *stream) {                 \

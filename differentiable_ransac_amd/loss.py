@@ -1,6 +1,6 @@
 """The training losses that follow the hot path: MatchLoss and PoseLoss for the two-view drivers,
-RegistrationLoss for the 3-D registration driver and HomographyLoss (at the end, with the evaluation metrics registration_errors and
-homography_errors) for the homography driver.
+RegistrationLoss for the 3-D registration driver, HomographyLoss for the homography driver (with the evaluation metrics
+registration_errors and homography_errors) and, at the end, PnPLoss for the absolute-pose driver.
 
 MatchLoss -- the clamped symmetric-epipolar training loss of the reference (loss.py:107-153), on the fused kernel
 `dr_episym_fwd/bwd`.
@@ -116,7 +116,7 @@ class ClassificationLoss(object):
 
 
 class _PairLoss(object):
-    """What RegistrationLoss and HomographyLoss share: one test-mode model per pair is promoted to [P,1,.,.] (and its keep to [P,1]),
+    """What RegistrationLoss, HomographyLoss and PnPLoss share: one test-mode model per pair is promoted to [P,1,.,.] (and its keep to [P,1]),
     and without gt_mask the mask comes from the ground-truth model at the loss's threshold, under no_grad.  A subclass names its two
     ops functions."""
     _gt_mask = _loss_mean = None
@@ -205,3 +205,27 @@ def homography_errors(model, gt_H, size):
             y = corners @ H.transpose(-1, -2)              # [...,4,3]
             return y[..., :2] / y[..., 2:]
         return (images(model) - images(gt_H.to(model.dtype))).norm(dim=-1).mean(-1)
+
+
+class PnPLoss(_PairLoss):
+    """The training loss of ransac.BatchedPnP.hypotheses: the truncated squared reprojection error of every returned pose on the
+    ground-truth inlier points, what RegistrationLoss is for rigid registration.  With x_c = R X + t and
+    d2 = (x_c / z_c - u)^2 + (y_c / z_c - v)^2 (the residual the score kernels use): per pair the mean over (kept models x masked
+    points) of (d2 / threshold^2 if the point lies in front of the camera and d2 < threshold^2, else 1); then the mean over the pairs.
+    The loss lies in [0, 1]; a hopeless hypothesis contributes the constant 1 and no gradient.  Value and gradient come from one pass
+    of `dr_pnp_loss_fused`; nothing synchronises.  The evaluation metric on a pose is registration_errors (the model layout is the
+    registration family's)."""
+
+    _gt_mask, _loss_mean = staticmethod(ops.pnp_gt_mask), staticmethod(ops.pnp_loss_mean)
+
+    def __init__(self, threshold):
+        super().__init__(threshold)         # inlier DISTANCE in normalised units, float or [P] (BatchedPnP's convention)
+
+    def forward(self, models, matches, gt_pose=None, gt_mask=None, keep=None):
+        """models [P,M,4,4] (or [P,4,4]: a test-mode result), matches [P,N,5], gt_mask [P,N] bool or gt_pose [P,4,4] (the mask is then
+        the inliers of that pose at the threshold: ops.pnp_gt_mask; neither = all points), keep [P,M] bool (models to average over,
+        e.g. the solver's validity; None = all) -> scalar loss, differentiable w.r.t. the models ONLY: `matches` that require grad are
+        refused (pass matches.detach(); the driver's own gradient to `matches` is unaffected)."""
+        return self._forward(models, matches, gt_pose, gt_mask, keep)
+
+    __call__ = forward

@@ -1411,6 +1411,51 @@ def refit_pnp(matches: torch.Tensor, mask: Optional[torch.Tensor], init_model: t
     return model, valid
 
 
+class _P3P(torch.autograd.Function):
+    """dr_p3p / dr_p3p_bwd: the backward recomputes the poses from the samples (the forward's device function, so the forward's slot
+    order), so no model is saved"""
+
+    @staticmethod
+    def forward(ctx, samples):
+        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+        s, Bt, _ = _flat_samples(samples, 5)
+        models = torch.empty((Bt, 4, 4, 4), device=s.device, dtype=s.dtype)
+        valid = torch.empty((Bt, 4), device=s.device, dtype=torch.bool)
+        L.call(f"dr_p3p_{L.suffix(s.dtype)}", ptr(s), Bt, ptr(models), ptr(valid), stream())
+        ctx.save_for_backward(s)
+        ctx.sshape = samples.shape
+        lead = samples.shape[:-2]
+        valid = valid.reshape(*lead, 4)
+        ctx.mark_non_differentiable(valid)
+        return models.reshape(*lead, 4, 4, 4), valid
+
+    @staticmethod
+    def backward(ctx, g_models, _gv):
+        if g_models is None:
+            return None
+        (s,) = ctx.saved_tensors
+        gs = torch.empty_like(s)
+        L.call(f"dr_p3p_bwd_{L.suffix(s.dtype)}", ptr(s), ptr(g_models.to(s.dtype).reshape(-1, 4, 4).contiguous()), s.shape[0], ptr(gs),
+               stream())
+        return gs.reshape(ctx.sshape)
+
+
+def p3p(samples):
+    """samples [..., 3, 5] = three (X, Y, Z, u, v) rows -> (models [..., 4, 4, 4], keep [..., 4] bool): the closed-form P3P poses of
+    every sample with autograd to `samples` in f32 and f64 (dr_p3p, dr_p3p_bwd).  Slot j of a sample: the valid ones first, in
+    ascending order of the quartic's root, the identity with keep = 0 elsewhere; on samples = matches[idx] the models and flags of
+    p3p_gather bit for bit.  The backward is one launch: per valid slot the implicit function theorem on the six reprojection
+    equations of the sample, at the slot's pose after one Gauss-Newton step onto their root (include/dransac.h states it); only rows 0-2 of a model's gradient are read, and the part of the
+    rotation's gradient normal to the rotation manifold passes nothing on.  A slot that is invalid (a NaN in its gradient reaches
+    nothing), whose Jacobian is singular to 1e-12 of its largest entry, or whose derivative is not finite passes exact zeros back."""
+    if not isinstance(samples, torch.Tensor) or samples.dim() < 3 or samples.shape[-2:] != (3, 5):
+        raise L.DransacError("p3p: samples [..., 3, 5], three matches (X, Y, Z, u, v) per sample")
+    if samples.dtype not in (torch.float32, torch.float64):
+        raise L.DransacError("p3p: samples must be float32 or float64")
+    _gpu_only((samples,))
+    return _P3P.apply(samples)
+
+
 class _Homography4(torch.autograd.Function):
     """dr_homography4 / dr_homography4_bwd: the backward recomputes the closed form from the samples, so no model is saved"""
 
@@ -1847,6 +1892,31 @@ def homography_loss_sums(matches, mask, models, threshold, keep=None, want_pairs
     """sums [P,M] = sum over the masked points of the truncated d2 / threshold^2 for every model (0 for a slot keep drops); no autograd.
     want_pairs: -> (sums, per_pair [P]) with the per-pair means homography_loss_mean averages."""
     return _pair_loss_sums(_HOMOGRAPHY, matches, mask, models, threshold, keep, want_pairs)
+
+
+def pnp_gt_mask(matches: torch.Tensor, gt_pose: torch.Tensor, threshold):
+    """dr_pnp_gt_mask: matches [P,N,5], gt_pose [P,4,4], threshold (float or [P]) -> (mask [P,N] bool = the points pnp_score counts
+    as inliers of the pair's ground-truth pose, count [P] int32)."""
+    _check_matches(_PNP, "pnp_gt_mask", matches)
+    return _pair_gt_mask(_PNP, matches, gt_pose, threshold)
+
+
+def pnp_loss_mean(matches, mask, models, threshold, keep=None):
+    """The absolute-pose loss of a batch -> scalar in [0, 1]: per pair the mean over (kept models x masked points) of d2 / threshold^2
+    for a point in front of the camera with d2 < threshold^2 and of 1 for any other (d2 = the squared reprojection error in normalised
+    units), then the mean over the pairs.  Differentiable w.r.t. `models` only; when they require grad, value and gradient come from
+    one pass over the (model x point) grid (_PairLossFused), otherwise the value-only kernel runs.  Matches that require grad are
+    refused (detach them): no gradient is computed for them, and BatchedPnP.hypotheses does pass one to `matches`, so a silent zero
+    here would be half a gradient."""
+    _check_matches(_PNP, "pnp_loss_mean", matches)
+    return _pair_loss_mean(_PNP, matches, mask, models, threshold, keep)
+
+
+def pnp_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool = False):
+    """sums [P,M] = sum over the masked points of the truncated d2 / threshold^2 for every model (0 for a slot keep drops); no autograd.
+    want_pairs: -> (sums, per_pair [P]) with the per-pair means pnp_loss_mean averages."""
+    _check_matches(_PNP, "pnp_loss_sums", matches)
+    return _pair_loss_sums(_PNP, matches, mask, models, threshold, keep, want_pairs)
 
 
 # ------------------------------------------------------------------------------------------ PoseLoss pose error (8(f) rank 3)

@@ -1013,7 +1013,7 @@ class BatchedRANSAC3D(_SeededDriver):
 
 class _PairStateDriver(_SeededDriver):
     """What BatchedRegistration, BatchedHomography and BatchedPnP share: the constructor's common checks and attributes, the index sets of a round
-    (Gumbel top-k or PROSAC, one seed per round), the train loop (ops.SampleGather -> the family's differentiable fit) and the test
+    (Gumbel top-k or PROSAC, one seed per round), the train loop (_train_rounds: ops.SampleGather -> the family's differentiable fit) and the test
     loop on a per-pair state on the device (draw -> fit -> score -> update -> _after_update -> read-back of "does any pair continue?"),
     and the final stage: the refit, taken where it scores strictly higher, or under scoring="magsac" the IRLS polish.  The constructor
     checks the options of both families once.  A family sets `k`, `_columns` / `_shape_error`, `_State` and the ops `_fit`, `_fit_train`,
@@ -1082,13 +1082,7 @@ class _PairStateDriver(_SeededDriver):
             raise ValueError("sampling='prosac' draws index sets from the ranking of the logits: explicit noise is refused")
         rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
         if self.train:
-            self._check_train(matches, logits)
-            out = []
-            for r in range(rounds):
-                g = None if gumbels is None else gumbels[r]
-                samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
-                out.append(self._fit_train(samples))
-            return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
+            return self._train_rounds(matches, logits, gumbels, rounds)
         with torch.no_grad():
             c = self._begin(matches, rounds)
             c.order = c.growth = None
@@ -1103,6 +1097,16 @@ class _PairStateDriver(_SeededDriver):
                 if self._stop_after(c, r, rounds):
                     break
             return self._finish(c)
+
+    def _train_rounds(self, matches, logits, gumbels, rounds):
+        """the train loop: every round ops.SampleGather -> the family's differentiable fit, one seed per round; no state, no read-back"""
+        self._check_train(matches, logits)
+        out = []
+        for r in range(rounds):
+            g = None if gumbels is None else gumbels[r]
+            samples, _, _ = ops.SampleGather.apply(matches, logits, self.B, self.k, self.tau, g, self._seeds.next())
+            out.append(self._fit_train(samples))
+        return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1))
 
     def _check_train(self, matches, logits):
         pass
@@ -1344,7 +1348,14 @@ class BatchedPnP(_PairStateDriver):
     device_termination = True issues every round, gated on the device, with no read-back; it is refused above 16 rounds.
     sampling = "prosac": ops.prosac_sample in ops.gumbel_topk's place, as in BatchedRegistration; refused with explicit `gumbels`.
 
-    Not here, each refused with NotImplementedError: train = True (a differentiable P3P needs a backward),
+    hypotheses(matches, logits, gumbels=None) is the train-mode call: every round runs (no adaptive stop), each one ops.SampleGather
+    (k = 3) followed by ops.p3p, and it returns dict(models [P, rounds * 4 B, 4, 4], keep [P, rounds * 4 B] = the slots' validity; slots
+    4 b + j of a round belong to its sample b) with autograd to the logits, and to `matches` where they require it.  `refit`,
+    `confidence` and `threshold` play no part, nothing is read back and no state is kept.  The loss on the returned models is
+    loss.PnPLoss (pass `keep`).  It is a method, not the constructor's train = True, which stays refused.  Refused with
+    ValueError: sampling = "prosac", device_termination switched on, logits of another dtype than the matches.
+
+    Not here, each refused with NotImplementedError: train = True in the constructor (the train path is `hypotheses`),
     scoring = "magsac", lo != 0."""
 
     k = 3
@@ -1352,7 +1363,8 @@ class BatchedPnP(_PairStateDriver):
     def __init__(self, ransac_batch_size=1024, threshold=0.005, confidence=0.999, max_iterations=5000, tau=1.0, seed=0, refit=True,
                  refit_iters=10, eps=1e-5, sampling="gumbel", prosac_draws=200000, train=False, scoring="msac", lo=0):
         if train:
-            raise NotImplementedError("BatchedPnP(train=True): a differentiable P3P needs a backward, which is not built (DESIGN.md §8)")
+            raise NotImplementedError("BatchedPnP(train=True): the train path of this family is the method BatchedPnP.hypotheses, "
+                                      "not the constructor flag (DESIGN.md §8)")
         if scoring != "msac":
             raise NotImplementedError(f"BatchedPnP(scoring={scoring!r}): only MSAC scoring is built for this family (DESIGN.md §8)")
         if lo:
@@ -1368,6 +1380,27 @@ class BatchedPnP(_PairStateDriver):
     _State = ops.PnPState
     _score_msac = staticmethod(ops.pnp_score)
     _update = staticmethod(ops.pnp_update)
+
+    @staticmethod
+    def _fit_train(samples):
+        """samples [P,B,3,5] -> (models [P,4B,4,4], keep [P,4B]): the four slots of a sample side by side, as p3p_gather lays them out"""
+        models, keep = ops.p3p(samples)
+        return models.reshape(samples.shape[0], -1, 4, 4), keep.reshape(samples.shape[0], -1)
+
+    def _check_train(self, matches, logits):
+        if self.sampling == "prosac":
+            raise ValueError("sampling='prosac' yields index sets only: hypotheses needs the Gumbel sampler")
+        if self._device_termination:
+            raise ValueError("hypotheses runs every round and keeps no state: a driver with device_termination switched on is refused")
+        if logits.dtype != matches.dtype:      # (the straight-through weights are read in the matches' type)
+            raise ValueError(f"hypotheses needs logits of the matches' dtype, got {logits.dtype} and {matches.dtype}")
+
+    def hypotheses(self, matches, logits, gumbels=None):
+        """the train-mode call (class docstring): dict(models [P, rounds * 4 B, 4, 4], keep [P, rounds * 4 B])"""
+        if matches.dim() != 3 or matches.shape[-1] != self._columns:
+            raise ValueError(self._shape_error)
+        rounds = self.rounds if gumbels is None else min(self.rounds, len(gumbels))
+        return self._train_rounds(matches, logits, gumbels, rounds)
 
     def _fit(self, c, idx):
         return ops.p3p_gather(c.matches, idx)

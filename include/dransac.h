@@ -595,6 +595,21 @@ int dr_homography_irls_f64(const double *matches, const double *thr2, int P, int
  *     (J^T J + lambda diag(J^T J)) step = -J^T r (f64 sums in one fixed order, Cholesky), the step is a left-multiplied rotation vector
  *     and a translation, taken only on a strictly lower cost over the same row set (lambda / 10, else lambda x 10; from 1e-3).
  *     valid = 0, model = identity: a non-finite start or result, fewer than three such rows under the start.  Bit-repeatable.
+ *   dr_p3p          dr_p3p_gather on explicit samples [Bt,3,5] -> models [4 Bt,16], valid [4 Bt] (slots 4 b + j, the same rules); on
+ *     samples = matches[idx] the same bits: one device function serves both.  What train mode fits.  Bt < 2^29.
+ *   dr_p3p_bwd      grad_models [4 Bt,16] -> grad_samples [Bt,3,5]: the reverse pass of the closed form by the implicit function
+ *     theorem.  A valid pose is a root of the six reprojection equations of its three rows; with dr_refit_pnp's left-multiplied step
+ *     theta = (w, d) and J = d r / d theta (6x6, the two rows per sample row stated there, at x_c = R X_i + t):
+ *         g_theta = (sum_j R[:,j] x G_R[:,j] + t x G_t, G_t),   J^T lambda = g_theta,
+ *         grad X_i += -(A_i R)^T lambda_i,   grad (u, v)_i += lambda_i,   A_i = (1 / z_c) [[1, 0, -x], [0, 1, -y]]
+ *     per valid slot, at the slot's pose after ONE Gauss-Newton step onto the root of those six equations (J delta = -r, the residual
+ *     in two-term arithmetic: the theorem holds at the root, and an ill-conditioned sample turns the forward's few ulp of distance
+ *     from it into a gradient error hundreds of times as large; the forward's models are not touched), G = the slot's grad_models (rows 0-2; row 3 is ignored; the part of G_R normal to the rotation manifold passes
+ *     nothing on).  One lane per sample recomputes the poses with the forward's device function (no model is saved, the slot order is
+ *     the forward's) and adds the valid slots' contributions in slot order, f64 inside.  A slot contributes exact zeros when it is
+ *     invalid (its grad_models are never read: NaN there reaches nothing), when a pivot of the LU (partial pivoting) is not larger
+ *     than 1e-12 x the largest |entry| of J, or when any of its fifteen results is not finite.  Every output element is written.  No
+ *     atomics: bit-repeatable.
  * ------------------------------------------------------------------------------------------ */
 int dr_p3p_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, float *models, uint8_t *valid, void *stream);
 int dr_p3p_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, double *models, uint8_t *valid, void *stream);
@@ -612,6 +627,10 @@ int dr_refit_pnp_f32(const float *matches, const uint8_t *mask, const float *ini
                      uint8_t *valid, void *stream);
 int dr_refit_pnp_f64(const double *matches, const uint8_t *mask, const double *init_model, int P, int N, int iters, double *model,
                      uint8_t *valid, void *stream);
+int dr_p3p_f32(const float *samples, int Bt, float *models, uint8_t *valid, void *stream);
+int dr_p3p_f64(const double *samples, int Bt, double *models, uint8_t *valid, void *stream);
+int dr_p3p_bwd_f32(const float *samples, const float *grad_models, int Bt, float *grad_samples, void *stream);
+int dr_p3p_bwd_f64(const double *samples, const double *grad_models, int Bt, double *grad_samples, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The training loss of the registration path (loss.RegistrationLoss).  Not a restatement of upstream code: RANSACLayer3D's own loss
@@ -704,6 +723,48 @@ int dr_homography_gt_mask_f32(const float *matches, const float *gt_H, const flo
                               int32_t *count, void *stream);
 int dr_homography_gt_mask_f64(const double *matches, const double *gt_H, const double *thr2, int P, int N, uint8_t *mask,
                               int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The training loss of the absolute-pose path (loss.PnPLoss): the registration loss above on the reprojection error.  matches
+ * [P,N,5], models [P,M,16], thr2 [P] as for dr_pnp_score; mask [P,N] (the ground-truth inliers; NULL = all points), keep [P,M]
+ * (NULL = all models).  With x_c = R X + t, i = 1 / z_c, (x, y) = (x_c, y_c) i, e = (x - u, y - v):
+ *     d2[p,m,n]   = |e|^2,   live = z_c > 0 and d2 < thr2[p]   (strict; false for a NaN),   term = live ? d2 / thr2[p] : 1
+ *     sums[p,m]   = sum_{n in mask} term[p,m,n]
+ *     per_pair[p] = sum_{m kept} sums[p,m] / max(#kept_p #mask_p, 1),   coef[p] = 1 / max(#kept_p #mask_p, 1),   mean = sum_p per_pair / P
+ *     h = (2 / thr2) (e_0 i, e_1 i, -(e_0 x + e_1 y) i),   d sums / d t = sum h,   d sums / d R = sum h X^T   over the live points; row 3 = 0
+ * A point behind the camera, at or beyond the threshold or with a NaN distance counts 1 and passes no gradient.  A slot keep drops is
+ * skipped (sums 0, gradient 0, its model is not read: it may be NaN); a kept model with a non-finite entry among its twelve has
+ * sums = #mask_p and a zero gradient; a pair with an empty mask or no kept model has per_pair 0 and zero gradients; a thr2[p] that is
+ * not > 0 (NaN included) leaves no point below it.  Every output element is written; no floating-point atomics and one fixed order
+ * for every sum, so a repeated launch gives the same bits.  Sums are accumulated in the type of the inputs.  1 / z_c is a division
+ * (correctly rounded), not dr_pnp_score's v_rcp_f32: d2 is the score's up to that ulp, and `live` is its inlier test wherever the two
+ * roundings cannot decide otherwise.  P <= 65535 and P M < 2^22.  No gradient is computed for the matches.
+ *
+ *   dr_pnp_loss_fused   sums [P,M], grad_unscaled [P,M,16] = d sums[p,m] / d model, per_pair [P], coef [P], mean [1]: value and
+ *     gradient from one pass over the (model x point) grid (two launches: the grid, then the per-pair / mean reduction).
+ *   dr_pnp_loss_scale   grad_models = grad_unscaled x coef[p] x grad_mean[0] / P: the whole backward of the mean.
+ *   dr_pnp_loss_fwd     the value only (sums, per_pair, coef, mean), the same bits as the fused form's.
+ *   dr_pnp_gt_mask      gt_pose [P,16] -> mask [P,N] = dr_pnp_score's inlier test under the pair's pose (bit for bit the mask
+ *     dr_pnp_update writes for that model; all zeros for a non-finite one), count [P] int32.
+ * ------------------------------------------------------------------------------------------ */
+int dr_pnp_loss_fused_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep, const float *thr2,
+                          int P, int M, int N, float *sums, float *grad_unscaled, float *per_pair, float *coef, float *mean,
+                          void *stream);
+int dr_pnp_loss_fused_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep, const double *thr2,
+                          int P, int M, int N, double *sums, double *grad_unscaled, double *per_pair, double *coef, double *mean,
+                          void *stream);
+int dr_pnp_loss_scale_f32(const float *grad_unscaled, const float *coef, const float *grad_mean, int P, int M, float *grad_models,
+                          void *stream);
+int dr_pnp_loss_scale_f64(const double *grad_unscaled, const double *coef, const double *grad_mean, int P, int M, double *grad_models,
+                          void *stream);
+int dr_pnp_loss_fwd_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep, const float *thr2, int P,
+                        int M, int N, float *sums, float *per_pair, float *coef, float *mean, void *stream);
+int dr_pnp_loss_fwd_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep, const double *thr2,
+                        int P, int M, int N, double *sums, double *per_pair, double *coef, double *mean, void *stream);
+int dr_pnp_gt_mask_f32(const float *matches, const float *gt_pose, const float *thr2, int P, int N, uint8_t *mask, int32_t *count,
+                       void *stream);
+int dr_pnp_gt_mask_f64(const double *matches, const double *gt_pose, const double *thr2, int P, int N, uint8_t *mask, int32_t *count,
+                       void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * K5  train-mode best-of-S selection    RANSAC.__call__, ransac.py:87-96

@@ -11,6 +11,12 @@ segments of back-to-back launches after a warm-up, the variants alternating, the
   refit       ops.refit_pnp          (10 passes from the generating pose moved by 3 degrees, over the inlier rows)
   round       the four launches of a round back to back
   call        BatchedPnP(...)(matches, logits) with device_termination (every round issued, no read-back): max_iterations = 4 B
+--train times the train step in their place (one round: max_iterations = B, so P x 4 B models):
+  p3p         ops.p3p on explicit samples [P,B,3,5]   (dr_p3p)
+  p3p_bwd     its backward                            (dr_p3p_bwd, one launch)
+  loss        ops.pnp_loss_mean on models that require grad (dr_pnp_loss_fused: the grid and the mean reduction)
+  loss_bwd    its backward                            (dr_pnp_loss_scale)
+  step        BatchedPnP.hypotheses -> loss.PnPLoss(keep) -> backward to the logits, the gradient cleared in between
 One JSON line.  The process ends itself after --timeout s."""
 import argparse
 import faulthandler
@@ -57,6 +63,7 @@ def main():
     ap.add_argument("--segments", type=int, default=7)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--timeout", type=int, default=300)
+    ap.add_argument("--train", action="store_true")
     a = ap.parse_args()
     faulthandler.dump_traceback_later(a.timeout, exit=True)
     if not torch.cuda.is_available():
@@ -72,6 +79,8 @@ def main():
     rng = np.random.default_rng(1)
     init = torch.from_numpy(np.stack([R.perturbed(s["pose"], rng) for s in sc])).to(dev, dt)
     logits = torch.zeros(P, N, device=dev, dtype=dt)
+    if a.train:
+        return train(a, ops, BatchedPnP, R, sc, m, mask, logits)
     thr2 = ops.thr2_tensor(R.THRESHOLD, P, m)
     idx = ops.gumbel_topk(logits, B, 3, 1.0, None, 1, soft=False)["idx"]
     models, valid = ops.p3p_gather(m, idx)
@@ -100,6 +109,38 @@ def main():
                                    f"call = {drv.rounds} rounds + refit, device_termination",
                           segments=a.segments, launches_per_segment=a.launches, inliers_found_over_true_min=round(min(found), 3), **res)),
           flush=True)
+    faulthandler.cancel_dump_traceback_later()
+
+
+def train(a, ops, BatchedPnP, R, sc, m, mask, logits):
+    from differentiable_ransac_amd.loss import PnPLoss
+    P, B, N = a.pairs, a.samples, a.points
+    crit = PnPLoss(R.THRESHOLD)
+    drv = BatchedPnP(ransac_batch_size=B, threshold=R.THRESHOLD, max_iterations=B)
+    lg = logits.clone().requires_grad_(True)
+
+    def step():
+        lg.grad = None
+        out = drv.hypotheses(m, lg)
+        crit(out["models"], m, gt_mask=mask, keep=out["keep"]).backward()
+
+    step()
+    assert bool(torch.isfinite(lg.grad).all()) and float(lg.grad.abs().sum()) > 0.0
+    samples = ops.SampleGather.apply(m, logits, B, 3, 1.0, None, 1)[0].detach().requires_grad_(True)
+    models, keep = ops.p3p(samples)
+    flat, kflat = models.detach().reshape(P, 4 * B, 4, 4).requires_grad_(True), keep.reshape(P, 4 * B)
+    g_models = torch.randn_like(models)
+    loss = ops.pnp_loss_mean(m, mask, flat, R.THRESHOLD, kflat)
+    one = torch.ones_like(loss)
+    variants = {"p3p": (lambda: ops.p3p(samples), a.launches),
+                "p3p_bwd": (lambda: torch.autograd.grad(models, samples, g_models, retain_graph=True), a.launches),
+                "loss": (lambda: ops.pnp_loss_mean(m, mask, flat, R.THRESHOLD, kflat), a.launches),
+                "loss_bwd": (lambda: torch.autograd.grad(loss, flat, one, retain_graph=True), a.launches),
+                "step": (step, 5)}
+    res = summary(timed(variants, a.segments))
+    print(json.dumps(dict(workload=f"train step P={P} B={B} (4B={4 * B} models) N={N} f32, {a.share:.2f} inliers masked, "
+                                   f"{float(keep.float().mean()):.3f} of the slots valid, loss {float(loss.detach()):.4f}",
+                          segments=a.segments, launches_per_segment=a.launches, **res)), flush=True)
     faulthandler.cancel_dump_traceback_later()
 
 
