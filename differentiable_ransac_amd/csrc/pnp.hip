@@ -534,14 +534,35 @@ __device__ __forceinline__ void lm_step(const double (&R)[3][3], const double (&
   }
 }
 
-template <typename T>
+// kWeighted (dr_refit_pnp_weighted with a weights pointer): a row's weight w multiplies its terms in J^T J, J^T r and both costs -- the
+// minimiser of sum w |r|^2.  The unweighted instantiation's text is the one dr_refit_pnp has always run: nothing of the weight reaches
+// it, and -ffp-contract decides how its sums round.  The weighted one must give those bits at w = 1, so it does not leave that to the
+// compiler: every sum is written out with fma in the shape the unweighted ones compile to (read from the kernel's assembly and
+// pinned by tests/test_gpu_weighted_pnp.py) -- a[q] += fma(one product, the other product rounded), the rounded one being the jv
+// product except where ju[2] = -y is a factor (the negation moves the multiplication there); (3,3) and (4,4), whose other product is
+// 0 x 0, are one fma into the sum.  This pins the weighted text to what ONE compiler does with the unweighted one: a compiler that
+// contracts those sums differently breaks the w = 1 equality without any change here (weights = NULL stays bit-equal: it IS the
+// unweighted instantiation), test_weights_of_exactly_one_give_the_bits_of_the_plain_refit is the tripwire, and the repair is to read
+// the unweighted kernel's assembly again and restate the shape below.  The weight sits on one factor of each product (w ju, w jv,
+// w r).  The row set does not look
+// at the weights: a row with w = 0 counts towards the three-row rule and adds exact zeros to every sum (the mask is the selection).
+__device__ __forceinline__ double two_products(double ua, double ub, double va, double vb, bool round_u) {
+  return round_u ? fma(va, vb, ua * ub) : fma(ua, ub, va * vb);
+}
+
+template <typename T, bool kWeighted>
 __global__ __launch_bounds__(kPRThreads) void refit_pnp_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
-                                                               const T *__restrict__ init_model, int N, int iters,
-                                                               T *__restrict__ model, uint8_t *__restrict__ valid) {
+                                                               const T *__restrict__ weights, const T *__restrict__ init_model, int N,
+                                                               int iters, T *__restrict__ model, uint8_t *__restrict__ valid) {
   __shared__ double s_red[(kPRThreads / 64) * 28];
   const int p = blockIdx.x, tid = threadIdx.x;
   const T *pt = matches + (size_t)p * N * 5;
   const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T *wt = kWeighted ? weights + (size_t)p * N : nullptr;
+  auto scaled = [&](int n, double x) {      // w_n x
+    if constexpr (kWeighted) return (double)wt[n] * x;
+    else return x;
+  };
   double R[3][3], t[3];
   bool ok = true;
 #pragma unroll
@@ -580,14 +601,27 @@ __global__ __launch_bounds__(kPRThreads) void refit_pnp_kernel(const T *__restri
         if (!pnp_row(R, t, m, xc, r)) continue;
         const double iz = 1.0 / xc[2], x = xc[0] * iz, y = xc[1] * iz;
         const double ju[6] = {-x * y, 1.0 + x * x, -y, iz, 0.0, -x * iz}, jv[6] = {-1.0 - y * y, x * y, x, 0.0, iz, -y * iz};
+        const double wr[2] = {scaled(n, r[0]), scaled(n, r[1])};
         int q = 0;
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
+          const double wju = scaled(n, ju[i]), wjv = scaled(n, jv[i]);
+          if constexpr (kWeighted) {
 #pragma unroll
-          for (int j = i; j < 6; ++j) a[q++] += ju[i] * ju[j] + jv[i] * jv[j];
-          a[21 + i] += ju[i] * r[0] + jv[i] * r[1];
+            for (int j = i; j < 6; ++j, ++q) {
+              if (i == j && i == 3) a[q] = fma(wju, ju[j], a[q]);
+              else if (i == j && i == 4) a[q] = fma(wjv, jv[j], a[q]);
+              else a[q] += two_products(wju, ju[j], wjv, jv[j], (i == 2) != (j == 2));
+            }
+            a[21 + i] += two_products(ju[i], wr[0], jv[i], wr[1], i == 2);
+          } else {
+#pragma unroll
+            for (int j = i; j < 6; ++j) a[q++] += wju * ju[j] + wjv * jv[j];
+            a[21 + i] += ju[i] * wr[0] + jv[i] * wr[1];
+          }
         }
-        a[27] += r[0] * r[0] + r[1] * r[1];
+        if constexpr (kWeighted) a[27] += fma(wr[0], r[0], wr[1] * r[1]);
+        else a[27] += wr[0] * r[0] + wr[1] * r[1];
       }
       block_sum_f64<28>(a, reinterpret_cast<double(*)[28]>(s_red));
       fresh = true;
@@ -601,7 +635,10 @@ __global__ __launch_bounds__(kPRThreads) void refit_pnp_kernel(const T *__restri
       double m[5], xc[3], r[2];
       load(n, m);
       if (!pnp_row(R, t, m, xc, r)) continue;
-      if (pnp_row(Rc, tc, m, xc, r)) c[0] += r[0] * r[0] + r[1] * r[1];
+      if (pnp_row(Rc, tc, m, xc, r)) {
+        if constexpr (kWeighted) c[0] += fma(scaled(n, r[0]), r[0], scaled(n, r[1]) * r[1]);
+        else c[0] += scaled(n, r[0]) * r[0] + scaled(n, r[1]) * r[1];
+      }
       else c[1] += 1.0;
     }
     block_sum_f64<2>(c, reinterpret_cast<double(*)[2]>(s_red));
@@ -622,6 +659,397 @@ __global__ __launch_bounds__(kPRThreads) void refit_pnp_kernel(const T *__restri
   for (int i = 0; i < 3; ++i) {
 #pragma unroll
     for (int j = 0; j < 3; ++j) ok = ok && is_finite(R[i][j]);
+    ok = ok && is_finite(t[i]);
+  }
+  if (tid == 0) {
+    if (!ok) set_identity(R, t);
+    store_rigid_model(model + (size_t)p * 16, R, t);
+    valid[p] = ok;
+  }
+}
+
+// ---- (4b) the reverse pass of the weighted fit (dr_refit_pnp_bwd): grad_model [P,16] -> grad_matches [P,N,5], grad_weights [P,N] -----
+// The fit's result is a stationary point of c(theta) = 1/2 sum_i w_i |r_i|^2 over its row set in the chart theta = (w, d) of lm_step:
+// g = sum w_i J_i^T r_i = 0, whatever start and damping the forward went through, so its derivative is the implicit function
+// theorem's.  Per row at x_c = R X + t, with i = 1 / z_c, (x, y) = (x_c, y_c) i, r = (r_u, r_v), s = r_u x + r_v y:
+//   V  = [-[x_c]x | I] (3x6), the derivative of x_c' = exp([w]x) x_c + d at theta = 0;   J = D pi V, D pi = i [[1, 0, -x], [0, 1, -y]];
+//   p  = D pi^T r = i (r_u, r_v, -s), the gradient of 1/2 |r|^2 with respect to x_c;
+//   B  = D pi^T D pi + r . D^2 pi = i^2 ([[1, 0, -x], [0, 1, -y], [-x, -y, x^2 + y^2]] + [[0, 0, -r_u], [0, 0, -r_v], [-r_u, -r_v, 2 s]]),
+//        its Hessian with respect to x_c;
+//   H += w (V^T B V + [[sym(p x_c^T), 0], [0, 0]]),   g += w V^T p.
+// The last term of H is the second-order part of the chart, p . 1/2 (e_a x (e_b x x_c) + e_b x (e_a x x_c)) = 1/2 (p_a x_b + p_b x_a)
+// (p . x_c = 0).  This is the FULL Hessian: with noisy rows the two residual terms are of the size of the gradient they correct.
+//   g_theta = (sum_j R[:,j] x G_R[:,j] + t x G_t, G_t) as in dr_p3p_bwd (rows 0-2 of G are read),   H lambda = g_theta by Cholesky,
+//   v = lambda_w x x_c + lambda_d,   phi = p . v:   grad w_i = -phi,   grad (u, v)_i = w_i D pi v,
+//   grad X_i = -w_i R^T (B v + p x lambda_w)      (the gradient of phi with respect to x_c, r moving with it).
+// The forward's model is `iters` passes in the type's rounding away from the root, and the theorem holds AT the root: first
+// kBwdNewton Newton steps theta = -H^-1 g with the full H, f64 (each taken only if H is positive definite and the step finite), as
+// dr_p3p_bwd polishes its pose.  The model the forward returned is not touched.  The row set is the mask's rows in front of the
+// camera with a finite residual under the model the forward returned, and is a constant of the derivative: the polish does not move it.
+// Sweeps over the pair's rows: kBwdNewton + 1 reductions of the 21 + 6 sums (plus the row count), one that computes every row's
+// gradient to see that all are finite, one that writes each of them once.
+// Zeros: a row the mask drops is never read; a row outside the row set; every row of a pair with fewer than three rows in the set, a
+// non-finite model, an H that is not positive definite at the polished pose, any non-finite result, or a row of the set that any of
+// the polished poses puts behind the camera (or at a non-finite residual): the steps are assumed small, and a pair for which they
+// are not has no derivative to give.
+// Mapping: refit_pnp_kernel's.  No atomics, fixed summation order: a repeated launch gives the same bits.
+constexpr int kBwdNewton = 2;
+
+struct PnPRowTerms {
+  double iz, x, y, p[3], B[6];      // B: upper triangle (00, 01, 02, 11, 12, 22)
+};
+
+__device__ __forceinline__ void pnp_row_terms(const double (&xc)[3], const double (&r)[2], PnPRowTerms &q) {
+  q.iz = 1.0 / xc[2];
+  q.x = xc[0] * q.iz;
+  q.y = xc[1] * q.iz;
+  const double s = r[0] * q.x + r[1] * q.y, i2 = q.iz * q.iz;
+  q.p[0] = q.iz * r[0];
+  q.p[1] = q.iz * r[1];
+  q.p[2] = -q.iz * s;
+  q.B[0] = i2;
+  q.B[1] = 0.0;
+  q.B[2] = -i2 * (q.x + r[0]);
+  q.B[3] = i2;
+  q.B[4] = -i2 * (q.y + r[1]);
+  q.B[5] = i2 * (q.x * q.x + q.y * q.y + 2.0 * s);
+}
+
+__device__ __forceinline__ void sym3_mul(const double (&B)[6], const double (&v)[3], double (&o)[3]) {
+  o[0] = B[0] * v[0] + B[1] * v[1] + B[2] * v[2];
+  o[1] = B[1] * v[0] + B[3] * v[1] + B[4] * v[2];
+  o[2] = B[2] * v[0] + B[4] * v[1] + B[5] * v[2];
+}
+
+template <typename T>
+__global__ __launch_bounds__(kPRThreads) void refit_pnp_bwd_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                                   const T *__restrict__ weights, const T *__restrict__ model,
+                                                                   const T *__restrict__ grad_model, int N,
+                                                                   T *__restrict__ grad_matches, T *__restrict__ grad_weights) {
+  __shared__ double s_red[(kPRThreads / 64) * 28];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const T *pt = matches + (size_t)p * N * 5;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+  double R0[3][3], t0[3], R[3][3], t[3], G[3][4];
+  bool ok = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      R[i][j] = R0[i][j] = (double)model[(size_t)p * 16 + 4 * i + j];
+      ok = ok && is_finite(R0[i][j]);
+    }
+    t[i] = t0[i] = (double)model[(size_t)p * 16 + 4 * i + 3];
+    ok = ok && is_finite(t0[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) G[i][j] = (double)grad_model[(size_t)p * 16 + 4 * i + j];
+  }
+  double lost = 0.0;
+  // row n of the set -> m, x_c and r at the current pose (R, t); false: not in the set
+  auto row = [&](int n, double (&m)[5], double (&xc)[3], double (&r)[2]) {
+    if (mk && !mk[n]) return false;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) m[d] = (double)pt[(size_t)n * 5 + d];
+    if (!pnp_row(R0, t0, m, xc, r)) return false;
+    if (!pnp_row(R, t, m, xc, r)) lost += 1.0;      // (the polish took it out of the front: the pair passes nothing on, below)
+    return true;
+  };
+  double a[28], lam[6];
+  bool spd = false;
+#pragma unroll 1
+  for (int pass = 0; pass <= kBwdNewton; ++pass) {
+#pragma unroll
+    for (int q = 0; q < 28; ++q) a[q] = 0.0;
+    for (int n = tid; ok && n < N; n += kPRThreads) {
+      double m[5], xc[3], r[2];
+      if (!row(n, m, xc, r)) continue;
+      const double w = wt ? (double)wt[n] : 1.0;
+      PnPRowTerms q;
+      pnp_row_terms(xc, r, q);
+      const double V[3][6] = {{0.0, xc[2], -xc[1], 1.0, 0.0, 0.0}, {-xc[2], 0.0, xc[0], 0.0, 1.0, 0.0}, {xc[1], -xc[0], 0.0, 0.0, 0.0, 1.0}};
+      double BV[3][6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) {
+        const double col[3] = {V[0][c], V[1][c], V[2][c]};
+        double o[3];
+        sym3_mul(q.B, col, o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) BV[k][c] = w * o[k];
+      }
+      int e = 0;
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+          double h = V[0][i] * BV[0][j] + V[1][i] * BV[1][j] + V[2][i] * BV[2][j];
+          if (j < 3) h += w * 0.5 * (q.p[i] * xc[j] + q.p[j] * xc[i]);
+          a[e++] += h;
+        }
+        a[21 + i] += w * (V[0][i] * q.p[0] + V[1][i] * q.p[1] + V[2][i] * q.p[2]);
+      }
+      a[27] += 1.0;
+    }
+    block_sum_f64<28>(a, reinterpret_cast<double(*)[28]>(s_red));
+    if (pass < kBwdNewton) {
+      double step[6], Rn[3][3], tn[3];
+      bool take = lm_solve6(a, 0.0, step);      // step = -H^-1 g
+      lm_step(R, t, step, Rn, tn);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) take = take && is_finite(Rn[i][j]);
+        take = take && is_finite(tn[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) R[i][j] = take ? Rn[i][j] : R[i][j];
+        t[i] = take ? tn[i] : t[i];
+      }
+    } else {
+      // -g_theta in g's place: lm_solve6 returns H^-1 g_theta
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int b = (i + 1) % 3, c = (i + 2) % 3;
+        double v = t[b] * G[c][3] - t[c] * G[b][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) v += R[b][j] * G[c][j] - R[c][j] * G[b][j];
+        a[21 + i] = -v;
+        a[24 + i] = -G[i][3];
+      }
+      spd = lm_solve6(a, 0.0, lam);
+    }
+  }
+  ok = ok && a[27] >= 3.0 && spd;      // (block-uniform: block sums and the model)
+  // one row's results: grad X (3), grad (u, v) (2), grad w
+  auto grads = [&](int n, double (&o)[6]) {
+    double m[5], xc[3], r[2];
+#pragma unroll
+    for (int d = 0; d < 6; ++d) o[d] = 0.0;
+    if (!row(n, m, xc, r)) return;
+    const double w = wt ? (double)wt[n] : 1.0;
+    PnPRowTerms q;
+    pnp_row_terms(xc, r, q);
+    const double v[3] = {lam[1] * xc[2] - lam[2] * xc[1] + lam[3], lam[2] * xc[0] - lam[0] * xc[2] + lam[4],
+                         lam[0] * xc[1] - lam[1] * xc[0] + lam[5]};
+    double gx[3];
+    sym3_mul(q.B, v, gx);
+    gx[0] += q.p[1] * lam[2] - q.p[2] * lam[1];
+    gx[1] += q.p[2] * lam[0] - q.p[0] * lam[2];
+    gx[2] += q.p[0] * lam[1] - q.p[1] * lam[0];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = -w * (R[0][c] * gx[0] + R[1][c] * gx[1] + R[2][c] * gx[2]);
+    o[3] = w * q.iz * (v[0] - q.x * v[2]);
+    o[4] = w * q.iz * (v[1] - q.y * v[2]);
+    o[5] = -(q.p[0] * v[0] + q.p[1] * v[1] + q.p[2] * v[2]);
+  };
+  double bad[1] = {0.0};
+  for (int n = tid; ok && n < N; n += kPRThreads) {
+    double o[6];
+    grads(n, o);
+    bool fin = true;
+#pragma unroll
+    for (int d = 0; d < 6; ++d) fin = fin && is_finite(o[d]);
+    bad[0] += fin ? 0.0 : 1.0;
+  }
+  bad[0] += lost;
+  block_sum_f64<1>(bad, reinterpret_cast<double(*)[1]>(s_red));
+  ok = ok && bad[0] == 0.0;
+  for (int n = tid; n < N; n += kPRThreads) {
+    double o[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (ok) grads(n, o);
+    if (grad_matches) {
+#pragma unroll
+      for (int d = 0; d < 5; ++d) grad_matches[((size_t)p * N + n) * 5 + d] = (T)o[d];
+    }
+    if (grad_weights) grad_weights[(size_t)p * N + n] = (T)o[5];
+  }
+}
+
+// ---- (5) the weighted normalised DLT: a pose from six or more rows without a start (dr_pnp_dlt) --------------------------------------
+// Hartley normalisation of the WORLD points (the observations are normalised image coordinates already): c = the weighted centroid,
+// s = sqrt(3) / the weighted mean distance from it, Xn = (s (X - c), 1).  A row gives the two equations [Xn^T, 0, -u Xn^T] and
+// [0, Xn^T, -v Xn^T] on the twelve entries of [M | m] (row-major, x ~ M X + m), and the Gram matrix of all of them under the weights is
+//   [[Q1, 0, -Qu], [0, Q1, -Qv], [-Qu, -Qv, Qq]],   Q1 = sum w Xn Xn^T, Qu = sum w u Xn Xn^T, Qv = sum w v Xn Xn^T,
+//   Qq = sum w (u^2 + v^2) Xn Xn^T:
+// its 78 upper-triangle entries are 40 distinct block sums (four symmetric 4x4), taken through block_sum_f64.  Wave 0 takes all
+// eigenpairs with jacobi_eig12_wave; the eigenvector of the smallest eigenvalue, the normalisation undone, is [M | m] up to scale and
+// sign.  The sign makes the weighted majority of the rows lie in front of the camera (sum w sign(z) >= 0 of z = the third row on Xn:
+// one more block sum), R = the rotation nearest to M (nearest_rotation3) and t = m / M's mean singular value.
+// valid = 0 (identity): fewer than six rows under the mask (as in the refit, a row of weight 0 counts: the mask selects), a non-finite
+// sum, no positive weight or spread, a non-finite or non-positive scale, a non-finite result, or a smallest eigenvalue that is not
+// simple: lambda_1 - lambda_0 <= kDltGap lambda_max.  A coplanar world set has a four-dimensional null space (lambda_0 .. lambda_3 at
+// rounding level, 1e-16 lambda_max in f64 sums; world points that f32 rounded off a plane leave 1e-14), a usable set has
+// lambda_1 / lambda_max at the square of its relief over its extent.  kDltGap = 1e-10 lies between: it refuses what is flat to 1e-5
+// of its extent, where the pose the eigenvector gives is noise anyway, and passes everything a start can be taken from.
+// Mapping: refit_pnp_kernel's; 3.8 KB of LDS (the sums' partials, the Gram matrix, its eigenvectors).  No atomics: bit-repeatable.
+constexpr double kDltGap = 1e-10;
+
+template <typename T>
+__global__ __launch_bounds__(kPRThreads) void pnp_dlt_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
+                                                             const T *__restrict__ weights, int N, T *__restrict__ model,
+                                                             uint8_t *__restrict__ valid) {
+  __shared__ double s_red[(kPRThreads / 64) * 40], s_gram[144], s_vec[144], s_cs[24];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const T *pt = matches + (size_t)p * N * 5;
+  const uint8_t *mk = mask ? mask + (size_t)p * N : nullptr;
+  const T *wt = weights ? weights + (size_t)p * N : nullptr;
+  auto row = [&](int n, double (&m)[5], double &w) {
+    if (mk && !mk[n]) return false;
+#pragma unroll
+    for (int d = 0; d < 5; ++d) m[d] = (double)pt[(size_t)n * 5 + d];
+    w = wt ? (double)wt[n] : 1.0;
+    return true;
+  };
+  double a5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};      // rows, sum w, sum w X
+  for (int n = tid; n < N; n += kPRThreads) {
+    double m[5], w;
+    if (!row(n, m, w)) continue;
+    a5[0] += 1.0;
+    a5[1] += w;
+#pragma unroll
+    for (int d = 0; d < 3; ++d) a5[2 + d] += w * m[d];
+  }
+  block_sum_f64<5>(a5, reinterpret_cast<double(*)[5]>(s_red));
+  bool ok = a5[0] >= 6.0 && a5[1] > 0.0;
+  const double rw = 1.0 / a5[1], c[3] = {a5[2] * rw, a5[3] * rw, a5[4] * rw};
+  double dist[1] = {0.0};
+  for (int n = tid; n < N; n += kPRThreads) {
+    double m[5], w;
+    if (!row(n, m, w)) continue;
+    const double dx = m[0] - c[0], dy = m[1] - c[1], dz = m[2] - c[2];
+    dist[0] += w * sqrt(dx * dx + dy * dy + dz * dz);
+  }
+  block_sum_f64<1>(dist, reinterpret_cast<double(*)[1]>(s_red));
+  ok = ok && dist[0] > 0.0;
+  const double sc = sqrt(3.0) * a5[1] / dist[0];
+  double a[40];
+#pragma unroll
+  for (int q = 0; q < 40; ++q) a[q] = 0.0;
+  for (int n = tid; n < N; n += kPRThreads) {
+    double m[5], w;
+    if (!row(n, m, w)) continue;
+    const double xn[4] = {sc * (m[0] - c[0]), sc * (m[1] - c[1]), sc * (m[2] - c[2]), 1.0};
+    const double k[4] = {w, w * m[3], w * m[4], w * (m[3] * m[3] + m[4] * m[4])};
+    int e = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = i; j < 4; ++j) {
+        const double xx = xn[i] * xn[j];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) a[10 * b + e] += k[b] * xx;
+        ++e;
+      }
+  }
+  block_sum_f64<40>(a, reinterpret_cast<double(*)[40]>(s_red));
+#pragma unroll
+  for (int q = 0; q < 40; ++q) ok = ok && is_finite(a[q]);
+  if (tid == 0) {
+#pragma unroll
+    for (int q = 0; q < 40; ++q) s_red[q] = a[q];
+  }
+  __syncthreads();
+  if (tid < 144) {
+    const int i = tid / 12, j = tid % 12, bi = i / 4, bj = j / 4, qi = min(i % 4, j % 4), qj = max(i % 4, j % 4);
+    const int e = qi * 4 - qi * (qi - 1) / 2 + (qj - qi);      // (qi, qj) of the 4x4 upper triangle, row-major
+    const int lo = min(bi, bj), hi = max(bi, bj);
+    double g = 0.0;
+    if (lo == hi) g = s_red[(lo == 2 ? 30 : 0) + e];
+    else if (hi == 2) g = -s_red[(lo == 0 ? 10 : 20) + e];
+    s_gram[tid] = ok ? g : (i == j ? 1.0 : 0.0);
+  }
+  __syncthreads();
+  if (tid < 64) jacobi_eig12_wave(s_gram, s_vec, s_cs, tid);
+  __syncthreads();
+  // the two smallest eigenvalues and the largest (every thread: the same LDS values)
+  int best = 0;
+  double l0 = INFINITY, l1 = INFINITY, lmax = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < 12; ++i) {
+    const double d = s_gram[13 * i];
+    lmax = fmax(lmax, d);
+    if (d < l0) {
+      l1 = l0;
+      l0 = d;
+      best = i;
+    } else if (d < l1) {
+      l1 = d;
+    }
+  }
+  ok = ok && (l1 - l0) > kDltGap * lmax;      // (false for NaN)
+  double h[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) h[q] = s_vec[q * 12 + best];
+  // One refinement step on the equations themselves.  The Gram matrix is known to eps lambda_max, which leaves h at
+  // eps lambda_max / (lambda_1 - lambda_0): the square of what the equations allow.  g = A^T (A h), summed over the rows, is known to
+  // eps sigma_max |A h| instead, and with the eigenpairs at hand  h <- h - sum_{k != 0} v_k (v_k . g) / (lambda_k - h . g)  is the
+  // first-order correction of the eigenvector (v_k . h = 0).  A term with a non-finite coefficient is not taken.
+  double g[12];
+#pragma unroll
+  for (int q = 0; q < 12; ++q) g[q] = 0.0;
+  for (int n = tid; n < N; n += kPRThreads) {
+    double m[5], w;
+    if (!row(n, m, w)) continue;
+    const double xn[4] = {sc * (m[0] - c[0]), sc * (m[1] - c[1]), sc * (m[2] - c[2]), 1.0};
+    double d[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) d[b] = h[4 * b] * xn[0] + h[4 * b + 1] * xn[1] + h[4 * b + 2] * xn[2] + h[4 * b + 3];
+    const double e1 = w * (d[0] - m[3] * d[2]), e2 = w * (d[1] - m[4] * d[2]), e3 = -(m[3] * e1 + m[4] * e2);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      g[q] += e1 * xn[q];
+      g[4 + q] += e2 * xn[q];
+      g[8 + q] += e3 * xn[q];
+    }
+  }
+  block_sum_f64<12>(g, reinterpret_cast<double(*)[12]>(s_red));
+  {
+    double l0r = 0.0, hn[12], nrm = 0.0;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) {
+      l0r += h[q] * g[q];
+      hn[q] = h[q];
+    }
+#pragma unroll 1
+    for (int k = 0; k < 12; ++k) {
+      if (k == best) continue;
+      double vg = 0.0;
+#pragma unroll
+      for (int q = 0; q < 12; ++q) vg += s_vec[q * 12 + k] * g[q];
+      const double coef = vg / (s_gram[13 * k] - l0r);
+      if (!is_finite(coef)) continue;
+#pragma unroll
+      for (int q = 0; q < 12; ++q) hn[q] -= coef * s_vec[q * 12 + k];
+    }
+#pragma unroll
+    for (int q = 0; q < 12; ++q) nrm += hn[q] * hn[q];
+    const double rn = 1.0 / sqrt(nrm);
+#pragma unroll
+    for (int q = 0; q < 12; ++q) h[q] = is_finite(rn) ? hn[q] * rn : h[q];
+  }
+  double front[1] = {0.0};
+  for (int n = tid; n < N; n += kPRThreads) {
+    double m[5], w;
+    if (!row(n, m, w)) continue;
+    const double z = h[8] * (sc * (m[0] - c[0])) + h[9] * (sc * (m[1] - c[1])) + h[10] * (sc * (m[2] - c[2])) + h[11];
+    front[0] += z > 0.0 ? w : -w;
+  }
+  block_sum_f64<1>(front, reinterpret_cast<double(*)[1]>(s_red));
+  const double sg = front[0] < 0.0 ? -1.0 : 1.0;
+  double M[3][3], mt[3], R[3][3], t[3], msv;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) M[i][j] = sg * sc * h[4 * i + j];
+    mt[i] = sg * h[4 * i + 3] - (M[i][0] * c[0] + M[i][1] * c[1] + M[i][2] * c[2]);
+  }
+  ok = nearest_rotation3(M, R, msv) && ok;
+  ok = ok && msv > 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    t[i] = mt[i] / msv;
     ok = ok && is_finite(t[i]);
   }
   if (tid == 0) {
@@ -676,8 +1104,31 @@ extern "C" {
     DR_REQUIRE(matches && init_model && model && valid, "null pointer");                                                            \
     DR_REQUIRE(P > 0 && N > 0 && (long)N * 5 < (1l << 31), "bad sizes");                                                            \
     DR_REQUIRE(iters >= 0, "iters must be at least 0");                                                                             \
-    return dr::launch("refit_pnp_kernel", dr::refit_pnp_kernel<T>, dim3(P), dr::kPRThreads, stream, matches, mask, init_model, N,   \
-                      iters, model, valid);                                                                                         \
+    return dr::launch("refit_pnp_kernel", dr::refit_pnp_kernel<T, false>, dim3(P), dr::kPRThreads, stream, matches, mask,           \
+                      (const T *)nullptr, init_model, N, iters, model, valid);                                                      \
+  }                                                                                                                                 \
+  int dr_refit_pnp_weighted_##sfx(const T *matches, const uint8_t *mask, const T *weights, const T *init_model, int P, int N,       \
+                                  int iters, T *model, uint8_t *valid, void *stream) {                                              \
+    DR_REQUIRE(matches && init_model && model && valid, "null pointer");                                                            \
+    DR_REQUIRE(P > 0 && N > 0 && (long)N * 5 < (1l << 31), "bad sizes");                                                            \
+    DR_REQUIRE(iters >= 0, "iters must be at least 0");                                                                             \
+    return dr::launch("refit_pnp_kernel", weights ? dr::refit_pnp_kernel<T, true> : dr::refit_pnp_kernel<T, false>, dim3(P),        \
+                      dr::kPRThreads, stream, matches, mask, weights, init_model, N, iters, model, valid);                          \
+  }                                                                                                                                 \
+  int dr_refit_pnp_bwd_##sfx(const T *matches, const uint8_t *mask, const T *weights, const T *model, const T *grad_model, int P,   \
+                             int N, T *grad_matches, T *grad_weights, void *stream) {                                               \
+    DR_REQUIRE(matches && model && grad_model, "null pointer");                                                                     \
+    DR_REQUIRE(grad_matches || grad_weights, "no gradient asked for");                                                              \
+    DR_REQUIRE(P > 0 && N > 0 && (long)N * 5 < (1l << 31), "bad sizes");                                                            \
+    return dr::launch("refit_pnp_bwd_kernel", dr::refit_pnp_bwd_kernel<T>, dim3(P), dr::kPRThreads, stream, matches, mask, weights, \
+                      model, grad_model, N, grad_matches, grad_weights);                                                            \
+  }                                                                                                                                 \
+  int dr_pnp_dlt_##sfx(const T *matches, const uint8_t *mask, const T *weights, int P, int N, T *model, uint8_t *valid,             \
+                       void *stream) {                                                                                              \
+    DR_REQUIRE(matches && model && valid, "null pointer");                                                                          \
+    DR_REQUIRE(P > 0 && N > 0 && (long)N * 5 < (1l << 31), "bad sizes");                                                            \
+    return dr::launch("pnp_dlt_kernel", dr::pnp_dlt_kernel<T>, dim3(P), dr::kPRThreads, stream, matches, mask, weights, N, model,   \
+                      valid);                                                                                                       \
   }
 DR_F32_F64(DR_OP)
 #undef DR_OP

@@ -1411,6 +1411,106 @@ def refit_pnp(matches: torch.Tensor, mask: Optional[torch.Tensor], init_model: t
     return model, valid
 
 
+def _check_weighted_pnp(name: str, matches, weights, mask, init_model=None) -> None:
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != 5:
+        raise L.DransacError(f"{name}: {_PNP.shape_text}")
+    if matches.dtype not in (torch.float32, torch.float64):
+        raise L.DransacError(f"{name}: matches must be float32 or float64")
+    P, N, _ = matches.shape
+    if weights is not None and (not isinstance(weights, torch.Tensor) or weights.shape != (P, N) or not weights.is_floating_point()):
+        raise L.DransacError(f"{name}: weights must be floating point [P,N], one per row of matches")
+    if mask is not None and (not isinstance(mask, torch.Tensor) or mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise L.DransacError(f"{name}: mask must be bool or uint8 [P,N]")
+    if init_model is not None and (not isinstance(init_model, torch.Tensor) or init_model.shape != (P, 4, 4)
+                                   or init_model.dtype != matches.dtype):
+        raise L.DransacError(f"{name}: init_model [P,4,4] of the matches' dtype")
+    _gpu_only((matches, weights, mask, init_model), optional=True)
+
+
+def _pnp_dlt(m, w, mask):
+    P, N, _ = m.shape
+    model = torch.empty((P, 4, 4), device=m.device, dtype=m.dtype)
+    valid = torch.empty((P,), device=m.device, dtype=torch.bool)
+    L.call(f"dr_pnp_dlt_{L.suffix(m.dtype)}", ptr(m), _u8_ptr(mask), ptr(w), P, N, ptr(model), ptr(valid), stream())
+    return model, valid
+
+
+def pnp_dlt(matches, weights=None, mask=None):
+    """dr_pnp_dlt: matches [P,N,5], weights [P,N] | None, mask [P,N] | None -> (model [P,4,4], valid [P] bool): a pose from six or more
+    rows without a start model, by the weighted normalised DLT (Hartley-normalised world points, the smallest eigenvector of the 12x12
+    Gram matrix, the rotation nearest to its 3x3 part, the sign that puts the weighted majority of the rows in front of the camera).
+    Forward only, f32 and f64; weights are expected >= 0 and are not checked.  valid = 0 (identity) below six rows under the mask, for a
+    non-finite sum or result, and when the smallest eigenvalue is not simple (within 1e-10 of the largest): a coplanar world set has no
+    DLT pose -- pass such a pair's start to weighted_pnp yourself.  Bit-repeatable."""
+    _check_weighted_pnp("pnp_dlt", matches, weights, mask)
+    m = matches.detach().contiguous()
+    return _pnp_dlt(m, None if weights is None else weights.detach().to(m.dtype).contiguous(), mask)
+
+
+class _WeightedPnP(torch.autograd.Function):
+    """dr_refit_pnp_weighted / dr_refit_pnp_bwd.  Unlike _WeightedFit's closed forms the fit is iterative, so the backward does not
+    recompute it: the forward's model is saved and the reverse pass differentiates the stationary point it stands (nearly) on."""
+
+    @staticmethod
+    def forward(ctx, matches, weights, init_model, mask, iters):
+        ctx.set_materialize_grads(False)   # unused / non-differentiable outputs arrive as None, not as zero-filled tensors
+        m = matches.contiguous()
+        w = None if weights is None else weights.to(m.dtype).contiguous()
+        P, N, _ = m.shape
+        model = torch.empty((P, 4, 4), device=m.device, dtype=m.dtype)
+        valid = torch.empty((P,), device=m.device, dtype=torch.bool)
+        L.call(f"dr_refit_pnp_weighted_{L.suffix(m.dtype)}", ptr(m), _u8_ptr(mask), ptr(w), ptr(init_model.contiguous()), P, N,
+               int(iters), ptr(model), ptr(valid), stream())
+        # the entry of the backward has no `valid`: a pair without a fit travels as a NaN model, which it answers with exact zeros
+        saved = torch.where(valid[:, None, None], model, torch.full_like(model, float("nan")))
+        ctx.save_for_backward(m, saved, *(() if w is None else (w,)))
+        ctx.mask = None if mask is None else _u8(mask)
+        ctx.wdtype = None if weights is None else weights.dtype
+        ctx.mark_non_differentiable(valid)
+        return model, valid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_model, _gv):
+        want_m, want_w = ctx.needs_input_grad[:2]      # (weights = None never wants a gradient)
+        if g_model is None or not (want_m or want_w):
+            return None, None, None, None, None
+        m, model, *w = ctx.saved_tensors
+        w = w[0] if w else None
+        P, N, _ = m.shape
+        gm = torch.empty_like(m) if want_m else None
+        gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if want_w else None
+        L.call(f"dr_refit_pnp_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w), ptr(model),
+               ptr(g_model.to(m.dtype).reshape(P, 4, 4).contiguous()), P, N, ptr(gm), ptr(gw), stream())
+        return gm, None if gw is None else gw.to(ctx.wdtype), None, None, None
+
+
+def weighted_pnp(matches, weights=None, init_model=None, mask=None, iters: int = 20):
+    """matches [P,N,5], weights [P,N] | None, init_model [P,4,4] | None, mask [P,N] | None -> (model [P,4,4], valid [P] bool): the pose
+    that minimises sum_i w_i |r_i|^2 of the reprojection residual over the rows the mask selects that lie in front of the camera --
+    refit_pnp's Levenberg-Marquardt loop (the same kernel; without weights the same bits) from `init_model`, `iters` passes at most,
+    or from pnp_dlt(matches, weights, mask) when no start is given -- with autograd to `weights` and / or `matches`, whichever require
+    it (dr_refit_pnp_bwd), in f32 and f64.  Once differentiable; `valid`, the mask (a selection) and `init_model` carry no gradient: the
+    minimiser does not depend on where the loop started.  Weights are expected >= 0 and are not checked; a row of weight 0 still
+    counts as a row.  The backward is the implicit function theorem at the stationary point with the full 6x6 Hessian (not J^T J),
+    after two Newton steps onto the root in f64; it assumes the forward converged -- give it the passes it needs.
+    Zero rules: rows the mask drops get exact zeros and are never read (a NaN there reaches nothing), and so do rows behind the camera
+    under the returned model; every row of a pair gets exact zeros when the pair has fewer than three rows in front of the camera,
+    valid = 0, its Hessian is not positive definite (not a strict minimum), or any result of the pair is not finite.  A pair whose
+    DLT start fails (a coplanar world set, fewer than six rows) returns valid = 0 with the identity: pass a start.  Bit-repeatable."""
+    _check_weighted_pnp("weighted_pnp", matches, weights, mask, init_model)
+    if int(iters) < 0:
+        raise L.DransacError(f"weighted_pnp: iters must be at least 0, got {iters!r}")
+    if init_model is None:
+        m = matches.detach().contiguous()
+        start, usable = _pnp_dlt(m, None if weights is None else weights.detach().to(m.dtype).contiguous(), mask)
+        # a failed start is the identity, under which the loop might still find rows: such a pair stays invalid (NaN start -> valid = 0)
+        start = torch.where(usable[:, None, None], start, torch.full_like(start, float("nan")))
+    else:
+        start = init_model.detach()
+    return _WeightedPnP.apply(matches, weights, start, mask, int(iters))
+
+
 class _P3P(torch.autograd.Function):
     """dr_p3p / dr_p3p_bwd: the backward recomputes the poses from the samples (the forward's device function, so the forward's slot
     order), so no model is saved"""

@@ -610,6 +610,38 @@ int dr_homography_irls_f64(const double *matches, const double *thr2, int P, int
  *     invalid (its grad_models are never read: NaN there reaches nothing), when a pivot of the LU (partial pivoting) is not larger
  *     than 1e-12 x the largest |entry| of J, or when any of its fifteen results is not finite.  Every output element is written.  No
  *     atomics: bit-repeatable.
+ *   dr_refit_pnp_weighted   dr_refit_pnp with weights [P,N] (>= 0, not checked; NULL = 1): the same kernel text and Levenberg-Marquardt
+ *     loop, a row's weight multiplying its terms in J^T J, J^T r and both costs, so the result minimises sum_i w_i |r_i|^2 over the
+ *     row set.  With weights = NULL it launches dr_refit_pnp's instantiation (the same bits); weights of exactly 1 give those bits
+ *     too: the weighted sums are written with fma in the shape the unweighted ones compile to.  The MASK is the selection, the
+ *     weights are not: a row with w_i = 0 still counts towards the three-row rule (and adds exact zeros to every sum), so a pair
+ *     whose positive weights sit on fewer than three rows returns its start with valid = 1, the damped matrix never becoming
+ *     positive definite.
+ *   dr_refit_pnp_bwd   model [P,16] (what the forward returned), grad_model [P,16] -> grad_matches [P,N,5] and / or grad_weights
+ *     [P,N] (either may be NULL, not both): the reverse pass of the weighted fit by the implicit function theorem at the stationary
+ *     point g = sum w_i J_i^T r_i = 0, in the chart theta = (w, d) of the left-multiplied step.  With x_c = R X_i + t,
+ *     V = [-[x_c]x | I], p = D pi^T r and B = D pi^T D pi + r . D^2 pi (the gradient and Hessian of |r|^2 / 2 in x_c):
+ *         H = sum w_i (V^T B V + [[sym(p x_c^T), 0], [0, 0]])    (the full 6x6 Hessian, not J^T J),
+ *         g_theta = (sum_j R[:,j] x G_R[:,j] + t x G_t, G_t)     (rows 0-2 of grad_model; row 3 is not read),
+ *         H lambda = g_theta by Cholesky,   v = lambda_w x x_c + lambda_d,   phi_i = p . v,
+ *         grad w_i = -phi_i,   grad (u, v)_i = w_i D pi v,   grad X_i = -w_i R^T (B v + p x lambda_w).
+ *     Before that the pose takes two Newton steps theta = -H^-1 g with this H in f64 (each only if H is positive definite and the
+ *     step finite): the forward stops `iters` passes in its type's rounding away from the root the theorem needs.  `model` is not
+ *     written.  The row set -- the mask's rows with z_c > 0 and a finite residual under `model` -- is a constant of the derivative.
+ *     Exact zeros: rows the mask drops (never read: a NaN there reaches nothing), rows outside the row set, and every row of a pair
+ *     with fewer than three rows in the set, a non-finite model, an H that is not positive definite, any non-finite result, or a
+ *     row of the set that a Newton step puts behind the camera.
+ *     Every output element is written once.  One 256-thread block per pair, four reduction sweeps and one write sweep over its rows;
+ *     no atomics: bit-repeatable.
+ *   dr_pnp_dlt      the weighted normalised DLT: a pose from six or more rows without a start model.  World points under Hartley's
+ *     normalisation (weighted centroid, mean distance sqrt 3), two equations per row, the 12x12 Gram matrix from 40 distinct f64
+ *     block sums (four symmetric 4x4 blocks), its smallest eigenvector by cyclic Jacobi in f64, refined by one first-order step with
+ *     A^T (A h) summed over the rows (the Gram matrix alone leaves it at the square of the equations' conditioning) -> [M | m]; the sign puts the weighted
+ *     majority of the rows in front of the camera, R = the rotation nearest to M, t = m / M's mean singular value.  valid = 0,
+ *     model = identity: fewer than six rows under the mask (a row of weight 0 counts), a non-finite sum or result, no positive total
+ *     weight, or a smallest eigenvalue that is not simple, lambda_1 - lambda_0 <= 1e-10 lambda_max -- a coplanar world set (its null
+ *     space has four dimensions; rounding leaves 1e-16 .. 1e-14 there) and anything flat to 1e-5 of its extent: such a pair needs a
+ *     start model from the caller.  Forward only.  Bit-repeatable.
  * ------------------------------------------------------------------------------------------ */
 int dr_p3p_gather_f32(const float *matches, const int32_t *idx, int P, int B, int N, float *models, uint8_t *valid, void *stream);
 int dr_p3p_gather_f64(const double *matches, const int32_t *idx, int P, int B, int N, double *models, uint8_t *valid, void *stream);
@@ -631,6 +663,18 @@ int dr_p3p_f32(const float *samples, int Bt, float *models, uint8_t *valid, void
 int dr_p3p_f64(const double *samples, int Bt, double *models, uint8_t *valid, void *stream);
 int dr_p3p_bwd_f32(const float *samples, const float *grad_models, int Bt, float *grad_samples, void *stream);
 int dr_p3p_bwd_f64(const double *samples, const double *grad_models, int Bt, double *grad_samples, void *stream);
+int dr_refit_pnp_weighted_f32(const float *matches, const uint8_t *mask, const float *weights, const float *init_model, int P, int N,
+                              int iters, float *model, uint8_t *valid, void *stream);
+int dr_refit_pnp_weighted_f64(const double *matches, const uint8_t *mask, const double *weights, const double *init_model, int P, int N,
+                              int iters, double *model, uint8_t *valid, void *stream);
+int dr_refit_pnp_bwd_f32(const float *matches, const uint8_t *mask, const float *weights, const float *model, const float *grad_model,
+                         int P, int N, float *grad_matches, float *grad_weights, void *stream);
+int dr_refit_pnp_bwd_f64(const double *matches, const uint8_t *mask, const double *weights, const double *model,
+                         const double *grad_model, int P, int N, double *grad_matches, double *grad_weights, void *stream);
+int dr_pnp_dlt_f32(const float *matches, const uint8_t *mask, const float *weights, int P, int N, float *model, uint8_t *valid,
+                   void *stream);
+int dr_pnp_dlt_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *model, uint8_t *valid,
+                   void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * The training loss of the registration path (loss.RegistrationLoss).  Not a restatement of upstream code: RANSACLayer3D's own loss
