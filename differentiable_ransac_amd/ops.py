@@ -796,6 +796,9 @@ _REGISTRATION = _PairFamily("registration", 6, (4, 4), "correspondences", "pose"
 _HOMOGRAPHY = _PairFamily("homography", 4, (3, 3), "matches", "homography", "refit_homography", True,
                           "matches [P,N,4] = (x1, y1, x2, y2)")
 _PNP = _PairFamily("pnp", 5, (4, 4), "matches", "pose", "refit_pnp", True, "matches [P,N,5] = (X, Y, Z, u, v)")
+# the two-view fit is here for _WeightedFit alone (refit, shape, width, once, shape_text): its state, scoring and losses have entries of
+# their own (dr_ransac_*, MatchLoss), so the entry stem, the nouns and the loss fields of this record are unused
+_FUNDAMENTAL = _PairFamily(None, 4, (3, 3), None, None, "refit_fundamental", True, "matches [P,N,4] = (x1, y1, x2, y2)")
 
 
 def _check_matches(fam, name: str, matches: torch.Tensor) -> None:
@@ -1614,6 +1617,30 @@ def weighted_homography(matches, weights=None, mask=None):
         raise L.DransacError("weighted_homography: mask must be bool or uint8 [P,N]")
     _gpu_only((matches, weights, mask), optional=True)
     return _WeightedFit.apply(_HOMOGRAPHY, matches, weights, mask)
+
+
+def weighted_fundamental(matches, weights=None, mask=None):
+    """matches [P,N,4] (N >= 8), weights [P,N] | None, mask [P,N] | None -> (F [P,3,3], valid [P] bool): refit_fundamental (the
+    Hartley-normalised weighted eight-point fit over the rows the mask selects; the same entry, the same bits) with autograd to
+    `weights` and / or `matches`, whichever require it (dr_refit_fundamental_bwd), in f32 and f64; once differentiable, `valid` and the
+    mask carry no gradient.  The weights scale the epipolar ROWS, so they enter the Gram matrix SQUARED (hand over sqrt(w) for a fit
+    that minimises sum w r^2); they are not checked, as in the forward.  F is the denormalised smallest eigenvector as it comes: not
+    normalised (its scale follows the Hartley transforms) and not rank 2.  On calibrated matches (K^-1 applied) it is the linear
+    estimate of E, which MatchLoss / PoseLoss accept.
+    Zero rules: rows the mask drops get exact zeros and are never read (a NaN there reaches nothing); every row of a pair gets exact
+    zeros when the pair has fewer than eight rows, valid = 0, the smallest eigenvalue of its Gram matrix is not simple (or an
+    eigenvalue gap is not finite), or an intermediate of the derivative is not finite.  Bit-repeatable."""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != _FUNDAMENTAL.width:
+        raise L.DransacError(f"weighted_fundamental: {_FUNDAMENTAL.shape_text}")
+    if matches.dtype not in (torch.float32, torch.float64):
+        raise L.DransacError("weighted_fundamental: matches must be float32 or float64")
+    P, N, _ = matches.shape
+    if weights is not None and (weights.shape != (P, N) or not weights.is_floating_point()):
+        raise L.DransacError("weighted_fundamental: weights must be floating point [P,N], one per row of matches")
+    if mask is not None and (mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
+        raise L.DransacError("weighted_fundamental: mask must be bool or uint8 [P,N]")
+    _gpu_only((matches, weights, mask), optional=True)
+    return _WeightedFit.apply(_FUNDAMENTAL, matches, weights, mask)
 
 
 class _MsacScore(torch.autograd.Function):

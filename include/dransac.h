@@ -894,6 +894,22 @@ int dr_ransac_update_f64(const double *matches, const double *models, const uint
  *                         `weighted=1`, ransac.py:151-153 -- `estimate_model(inlier_points, soft_weights[0, inlier_indices[0]])`,
  *                         the weights multiply the epipolar rows (fundamental_matrix_estimator.py:243-244); the Hartley
  *                         normalisation of the selected points stays unweighted (:177-228).
+ *   dr_refit_fundamental_bwd  grad_model [P,9] = dL/dF of the model dr_refit_fundamental returns for (matches, mask, weights) ->
+ *     grad_matches [P,N,4] and / or grad_weights [P,N] (NULL: not wanted; at least one; grad_weights with weights = NULL is the
+ *     derivative at w = 1).  One 256-thread block per pair, f64 inside; nothing is stored by the forward: the same three passes give
+ *     the nsel selected rows' centroids mu, r_i = sqrt(2) nsel / D_i and the Gram matrix G = sum w_n^2 rho_n rho_n^T (the weights
+ *     scale the ROWS, so they enter squared) bit for bit, the same Jacobi all eigenpairs (lambda_i, v_i) and fh = v_0 with the
+ *     forward's sign.  F = T2^T mat(fh) T1 is differentiated as returned: no rank-2 projection, no unit norm.  Then
+ *       g_fh = T2 gF T1^T, and the direct gradients of (mu, r) of each image through T1, T2;
+ *       z = sum_{i != 0} v_i (v_i . g_fh) / (lambda_i - lambda_0), gG = -(z fh^T + fh z^T) / 2;
+ *       per present row, rho_n unscaled, s_n = -(rho_n . z)(rho_n . fh):  grad_weights[n] = 2 w_n s_n, and w_n^2 times the derivative
+ *         of s_n by (x1, y1, x2, y2) is the normalised-coordinate gradient gx_n;
+ *       per image g_mu = -r sum gx_n + direct, g_r = sum (gx_n . x_n) / r + direct, D = sum |q_n|:  g_D = -g_r r / D,
+ *         g_mu -= g_D sum q_n / |q_n|;  grad_matches[n] = r gx_n + g_D q_n / |q_n| + g_mu / nsel (zero subgradient at |q_n| = 0).
+ *     Every element of every requested output is written.  Exact zeros: rows the mask drops (never read: a NaN there reaches nothing),
+ *     and every row of a pair with nsel < 8, valid = 0, lambda_i - lambda_0 not positive and finite for some i != 0, or a non-finite
+ *     z, direct gradient, g_D or g_mu (one decision per pair).  N may be below 8 (all zeros).  -grad_model negates every output bit
+ *     for bit.  No atomics, fixed-order sums: a repeated launch gives the same bytes.  Weights are not checked, as in the forward.
  * ------------------------------------------------------------------------------------------ */
 int dr_refit_essential_f32(const float *matches, const uint8_t *mask, int P, int N, float *models, uint8_t *valid,
                            void *stream);
@@ -903,6 +919,10 @@ int dr_refit_fundamental_f32(const float *matches, const uint8_t *mask, const fl
                              uint8_t *valid, void *stream);
 int dr_refit_fundamental_f64(const double *matches, const uint8_t *mask, const double *weights, int P, int N, double *models,
                              uint8_t *valid, void *stream);
+int dr_refit_fundamental_bwd_f32(const float *matches, const uint8_t *mask, const float *weights, const float *grad_model, int P, int N,
+                                 float *grad_matches, float *grad_weights, void *stream);
+int dr_refit_fundamental_bwd_f64(const double *matches, const uint8_t *mask, const double *weights, const double *grad_model, int P,
+                                 int N, double *grad_matches, double *grad_weights, void *stream);
 
 /* K7 acceptance (ransac.py:173-185): MSAC scores of the S refit candidates of every pair (cand [P,S,9], cand_valid [P,S]
  * or NULL; non-finite and all-zero candidates do not compete, as their NaN score of dr_msac_score would not); where the
