@@ -1,6 +1,6 @@
 """The training losses that follow the hot path: MatchLoss and PoseLoss for the two-view drivers,
 RegistrationLoss for the 3-D registration driver, HomographyLoss for the homography driver (with the evaluation metrics
-registration_errors and homography_errors) and, at the end, PnPLoss for the absolute-pose driver.
+registration_errors and homography_errors) and, at the end, PnPLoss and PnPExpectedLoss (DSAC) for the absolute-pose driver.
 
 MatchLoss -- the clamped symmetric-epipolar training loss of the reference (loss.py:107-153), on the fused kernel
 `dr_episym_fwd/bwd`.
@@ -227,5 +227,76 @@ class PnPLoss(_PairLoss):
         e.g. the solver's validity; None = all) -> scalar loss, differentiable w.r.t. the models ONLY: `matches` that require grad are
         refused (pass matches.detach(); the driver's own gradient to `matches` is unaffected)."""
         return self._forward(models, matches, gt_pose, gt_mask, keep)
+
+    __call__ = forward
+
+
+def pnp_pose_errors(models, gt_pose, trans_weight, max_loss):
+    """models [P,M,4,4], gt_pose [P,4,4] -> l [P,M] = min(max(RRE in degrees, trans_weight RTE), max_loss), differentiable w.r.t. the
+    models: plain torch on [P,M], as homography_errors is.  RRE = acos(c), c = (tr(Rg^T R) - 1) / 2 clamped to [-_ACOS_MAX, _ACOS_MAX],
+    so a pose equal to the ground truth (derivative of acos at 1: infinite) has a rotation term of 0.081 degrees with a zero gradient.
+    It is evaluated as 2 asin(sqrt(q / 2)) with q = 1 - c = |R - Rg|_F^2 / 4 (for two rotations: tr(Rg^T R) = 3 - |R - Rg|_F^2 / 2) and
+    the clamp carried over to q: the same function, but c itself holds an angle of 0.2 degrees in the last two of f32's seven digits
+    (1 - c = 6e-6 against an eps of 6e-8: one per cent of the angle), while q holds it in all of them."""
+    D = models[..., :3, :3] - gt_pose[:, None, :3, :3]
+    q = ((D * D).sum((-1, -2)) / 4.0).clamp(1.0 - _ACOS_MAX, 1.0 + _ACOS_MAX)
+    rre = torch.rad2deg(2.0 * torch.asin(torch.sqrt(q / 2.0)))
+    d = models[..., :3, 3] - gt_pose[:, None, :3, 3]
+    rte = torch.sqrt((d * d).sum(-1) + _RTE_EPS2)         # (smooth at a zero difference)
+    return torch.maximum(rre, trans_weight * rte).clamp(max=max_loss)
+
+
+_ACOS_MAX = 1.0 - 1e-6
+_RTE_EPS2 = 1e-24
+
+
+class PnPExpectedLoss(object):
+    """The DSAC / DSAC* training loss on ransac.BatchedPnP.hypotheses: the expected pose error of the hypotheses under a soft-max of
+    their soft inlier scores.  It needs no ground-truth inlier mask, weights a hypothesis by how many points agree with it, and gives
+    a gradient to `matches` -- whose 3-D column is a network output in scene-coordinate regression -- through the minimal solver (the
+    models) and through the scores.
+
+        score[p,m] = ops.pnp_soft_score: sum over the scored points of sigmoid(beta (1 - d2 / threshold^2))
+        probs[p,:] = softmax(alpha score[p,:] / N_p) over the usable slots, N_p = the number of scored points; 0 elsewhere
+        l[p,m]     = min(max(RRE in degrees, trans_weight RTE), max_loss) against gt_pose            (pnp_pose_errors)
+        loss       = mean over the pairs of sum_m probs l
+
+    A slot is usable if keep holds it and its model is finite.  A pair without a usable slot contributes 0 and passes no gradient.
+    Defaults: DSAC*'s published hyper-parameters (Brachmann and Rother, TPAMI 2021) restated for this package's units.  DSAC* scores
+    with sigmoid(beta_px (tau - r)) on the reprojection error r in pixels, tau = 10 px and beta_px = 0.5 / px, so beta_px tau = 5
+    = `beta` here, the weight's slope in units of the threshold, whatever the threshold's unit; the threshold itself is the driver's,
+    in normalised units (10 px / f), and the error enters SQUARED (the package's convention).  alpha = 100 is DSAC*'s
+    inlier alpha on the score divided by the number of points.  DSAC* compares degrees with centimetres: trans_weight = 100 for a
+    scene in metres, and clamps the pose loss at 100; both are kept.  They are hyper-parameters, not tuned here."""
+
+    def __init__(self, threshold, beta=5.0, alpha=100.0, trans_weight=100.0, max_loss=100.0):
+        self.threshold, self.beta, self.alpha = threshold, float(beta), float(alpha)
+        self.trans_weight, self.max_loss = float(trans_weight), float(max_loss)
+        self.per_pair = self.probs = self.scores = None       # of the last call (detached)
+
+    def forward(self, models, matches, gt_pose, keep=None, mask=None):
+        """models [P,M,4,4], matches [P,N,5] (they MAY require grad), gt_pose [P,4,4], keep [P,M] bool (e.g. hypotheses' keep; None =
+        all), mask [P,N] bool (the points that are scored; None = all) -> scalar loss.  The per-pair values, the probabilities and the
+        scores of the call stay on the object as .per_pair [P], .probs [P,M], .scores [P,M], detached."""
+        scores = ops.pnp_soft_score(matches, models, self.threshold, self.beta, mask, keep)
+        P, M = scores.shape
+        usable = torch.isfinite(models[:, :, :3]).all(-1).all(-1)
+        if keep is not None:
+            usable = usable & keep
+        n_p = matches.shape[1] if mask is None else mask.sum(1, keepdim=True).clamp(min=1).to(scores.dtype)
+        # the soft-max over the usable slots, written out (exp of the logits less their largest, 0 at an unusable slot, over the sum): a
+        # pair without a usable slot gets zeros, and nothing depends on how a library soft-max treats -inf or a long row
+        logits = self.alpha * scores / n_p
+        top = logits.detach().masked_fill(~usable, float("-inf")).max(1, keepdim=True).values
+        top = torch.where(usable.any(1, keepdim=True), top, torch.zeros_like(top))
+        e = torch.where(usable, torch.exp(logits - top), torch.zeros_like(logits))
+        probs = e / e.sum(1, keepdim=True).clamp(min=torch.finfo(e.dtype).tiny)
+        # an unusable slot's model (possibly NaN) is replaced BEFORE the errors: a NaN behind a where() would still poison its gradient
+        eye = torch.eye(4, device=models.device, dtype=models.dtype)
+        errors = pnp_pose_errors(torch.where(usable[:, :, None, None], models, eye), gt_pose.to(models.dtype), self.trans_weight,
+                                 self.max_loss)
+        per_pair = (probs * errors).sum(1)
+        self.per_pair, self.probs, self.scores = per_pair.detach(), probs.detach(), scores.detach()
+        return per_pair.mean()
 
     __call__ = forward

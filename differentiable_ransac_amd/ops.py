@@ -2046,6 +2046,58 @@ def pnp_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool 
     return _pair_loss_sums(_PNP, matches, mask, models, threshold, keep, want_pairs)
 
 
+class _PnPSoftScore(torch.autograd.Function):
+    """dr_pnp_soft_score / dr_pnp_soft_score_bwd on checked, contiguous inputs (pnp_soft_score): the backward recomputes the residuals
+    from the saved inputs, writes grad_models and, when the matches need a gradient, grad_matches by the transposed launch."""
+
+    @staticmethod
+    def forward(ctx, matches, models, thr2, beta, mask, keep):
+        (P, N, _), M, dt = matches.shape, models.shape[1], matches.dtype
+        scores = torch.empty((P, M), device=matches.device, dtype=dt)
+        L.call(f"dr_pnp_soft_score_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2), L.scalar(dt, beta),
+               P, M, N, ptr(scores), stream())
+        ctx.save_for_backward(matches, models, thr2, mask, keep)
+        ctx.beta = beta
+        return scores
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable       # (the gradients are kernel results: a second derivative would be silently wrong)
+    def backward(ctx, g):
+        matches, models, thr2, mask, keep = ctx.saved_tensors
+        (P, N, _), M, dt = matches.shape, models.shape[1], matches.dtype
+        gm = torch.empty_like(models)
+        gx = torch.empty_like(matches) if ctx.needs_input_grad[0] else None
+        L.call(f"dr_pnp_soft_score_bwd_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2),
+               L.scalar(dt, ctx.beta), ptr(g.to(dt).contiguous()), P, M, N, ptr(gm), ptr(gx), stream())
+        return gx, gm, None, None, None, None
+
+
+def pnp_soft_score(matches, models, threshold, beta: float = 5.0, mask=None, keep=None):
+    """The differentiable soft-inlier score (DSAC) of every pose on every point: matches [P,N,5], models [P,M,4,4], threshold = the
+    inlier DISTANCE (float or [P]), beta > 0, mask [P,N] bool | None (the points that are scored), keep [P,M] bool | None ->
+    scores [P,M] = sum over the scored points of sigmoid(beta (1 - d2 / threshold^2)), d2 the squared reprojection error; a point
+    behind the camera or with beta (1 - d2 / threshold^2) < -40 adds nothing (include/dransac.h states the rules).  A slot keep drops
+    and a kept model with a non-finite entry score 0.  Differentiable (once) w.r.t. `models`, and w.r.t. `matches` when they require
+    grad: the second pass over the grid runs only then.  No gradient for threshold, beta, mask or keep.  f32 and f64; nothing
+    synchronises or reads back, so the op can be captured in a HIP graph."""
+    r, c = _PNP.shape
+    _check_matches(_PNP, "pnp_soft_score", matches)
+    if models.dim() != 4 or models.shape[-2:] != _PNP.shape or models.shape[0] != matches.shape[0]:
+        raise L.DransacError(f"pnp_soft_score: models [P,M,{r},{c}], one row of poses per row of matches")
+    if models.dtype != matches.dtype or matches.dtype not in (torch.float32, torch.float64):
+        raise L.DransacError("pnp_soft_score: matches and models of one dtype, float32 or float64")
+    (P, N, _), M = matches.shape, models.shape[1]
+    if (mask is not None and (mask.shape != (P, N) or mask.dtype != torch.bool)) or \
+            (keep is not None and (keep.shape != (P, M) or keep.dtype != torch.bool)):
+        raise L.DransacError("pnp_soft_score: mask is [P,N] bool, keep is [P,M] bool")
+    if isinstance(beta, torch.Tensor) or not 0.0 < float(beta) < float("inf"):      # (false for NaN)
+        raise L.DransacError(f"pnp_soft_score: beta is a positive, finite Python number, got {beta!r}")
+    _gpu_only((matches, models))
+    _gpu_only((mask, keep), optional=True)
+    return _PnPSoftScore.apply(matches.contiguous(), models.contiguous(), thr2_tensor(threshold, P, matches).detach(), float(beta),
+                               _u8(mask), _u8(keep))
+
+
 # ------------------------------------------------------------------------------------------ PoseLoss pose error (8(f) rank 3)
 class _PoseError(torch.autograd.Function):
     @staticmethod
