@@ -1414,9 +1414,12 @@ def refit_pnp(matches: torch.Tensor, mask: Optional[torch.Tensor], init_model: t
     return model, valid
 
 
-def _check_weighted_pnp(name: str, matches, weights, mask, init_model=None) -> None:
-    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != 5:
-        raise L.DransacError(f"{name}: {_PNP.shape_text}")
+def _check_weighted(name: str, fam, matches, weights, mask, init_model=None) -> None:
+    """what the weighted fits refuse before the launch, in this order: matches [P,N,fam.width] f32 / f64, weights a floating
+    [P,N] | None, mask a bool / uint8 [P,N] | None, a start model [P,*fam.shape] | None of the matches' dtype (the iterative fit's
+    alone), and any of them on the CPU"""
+    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != fam.width:
+        raise L.DransacError(f"{name}: {fam.shape_text}")
     if matches.dtype not in (torch.float32, torch.float64):
         raise L.DransacError(f"{name}: matches must be float32 or float64")
     P, N, _ = matches.shape
@@ -1424,9 +1427,9 @@ def _check_weighted_pnp(name: str, matches, weights, mask, init_model=None) -> N
         raise L.DransacError(f"{name}: weights must be floating point [P,N], one per row of matches")
     if mask is not None and (not isinstance(mask, torch.Tensor) or mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
         raise L.DransacError(f"{name}: mask must be bool or uint8 [P,N]")
-    if init_model is not None and (not isinstance(init_model, torch.Tensor) or init_model.shape != (P, 4, 4)
+    if init_model is not None and (not isinstance(init_model, torch.Tensor) or init_model.shape != (P, *fam.shape)
                                    or init_model.dtype != matches.dtype):
-        raise L.DransacError(f"{name}: init_model [P,4,4] of the matches' dtype")
+        raise L.DransacError(f"{name}: init_model [P,{fam.shape[0]},{fam.shape[1]}] of the matches' dtype")
     _gpu_only((matches, weights, mask, init_model), optional=True)
 
 
@@ -1445,7 +1448,7 @@ def pnp_dlt(matches, weights=None, mask=None):
     Forward only, f32 and f64; weights are expected >= 0 and are not checked.  valid = 0 (identity) below six rows under the mask, for a
     non-finite sum or result, and when the smallest eigenvalue is not simple (within 1e-10 of the largest): a coplanar world set has no
     DLT pose -- pass such a pair's start to weighted_pnp yourself.  Bit-repeatable."""
-    _check_weighted_pnp("pnp_dlt", matches, weights, mask)
+    _check_weighted("pnp_dlt", _PNP, matches, weights, mask)
     m = matches.detach().contiguous()
     return _pnp_dlt(m, None if weights is None else weights.detach().to(m.dtype).contiguous(), mask)
 
@@ -1501,7 +1504,7 @@ def weighted_pnp(matches, weights=None, init_model=None, mask=None, iters: int =
     under the returned model; every row of a pair gets exact zeros when the pair has fewer than three rows in front of the camera,
     valid = 0, its Hessian is not positive definite (not a strict minimum), or any result of the pair is not finite.  A pair whose
     DLT start fails (a coplanar world set, fewer than six rows) returns valid = 0 with the identity: pass a start.  Bit-repeatable."""
-    _check_weighted_pnp("weighted_pnp", matches, weights, mask, init_model)
+    _check_weighted("weighted_pnp", _PNP, matches, weights, mask, init_model)
     if int(iters) < 0:
         raise L.DransacError(f"weighted_pnp: iters must be at least 0, got {iters!r}")
     if init_model is None:
@@ -1606,16 +1609,7 @@ def weighted_homography(matches, weights=None, mask=None):
     zeros when the pair has fewer than four rows, valid = 0, the smallest eigenvalue of its Gram matrix is not simple (or an
     eigenvalue gap is not finite), or an intermediate of the derivative is not finite.  A multiple of H in the incoming gradient
     passes nothing on.  Bit-repeatable."""
-    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != 4:
-        raise L.DransacError("weighted_homography: matches [P,N,4] = (x1, y1, x2, y2)")
-    if matches.dtype not in (torch.float32, torch.float64):
-        raise L.DransacError("weighted_homography: matches must be float32 or float64")
-    P, N, _ = matches.shape
-    if weights is not None and (weights.shape != (P, N) or not weights.is_floating_point()):
-        raise L.DransacError("weighted_homography: weights must be floating point [P,N], one per row of matches")
-    if mask is not None and (mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
-        raise L.DransacError("weighted_homography: mask must be bool or uint8 [P,N]")
-    _gpu_only((matches, weights, mask), optional=True)
+    _check_weighted("weighted_homography", _HOMOGRAPHY, matches, weights, mask)
     return _WeightedFit.apply(_HOMOGRAPHY, matches, weights, mask)
 
 
@@ -1630,16 +1624,7 @@ def weighted_fundamental(matches, weights=None, mask=None):
     Zero rules: rows the mask drops get exact zeros and are never read (a NaN there reaches nothing); every row of a pair gets exact
     zeros when the pair has fewer than eight rows, valid = 0, the smallest eigenvalue of its Gram matrix is not simple (or an
     eigenvalue gap is not finite), or an intermediate of the derivative is not finite.  Bit-repeatable."""
-    if not isinstance(matches, torch.Tensor) or matches.dim() != 3 or matches.shape[-1] != _FUNDAMENTAL.width:
-        raise L.DransacError(f"weighted_fundamental: {_FUNDAMENTAL.shape_text}")
-    if matches.dtype not in (torch.float32, torch.float64):
-        raise L.DransacError("weighted_fundamental: matches must be float32 or float64")
-    P, N, _ = matches.shape
-    if weights is not None and (weights.shape != (P, N) or not weights.is_floating_point()):
-        raise L.DransacError("weighted_fundamental: weights must be floating point [P,N], one per row of matches")
-    if mask is not None and (mask.shape != (P, N) or mask.dtype not in (torch.bool, torch.uint8)):
-        raise L.DransacError("weighted_fundamental: mask must be bool or uint8 [P,N]")
-    _gpu_only((matches, weights, mask), optional=True)
+    _check_weighted("weighted_fundamental", _FUNDAMENTAL, matches, weights, mask)
     return _WeightedFit.apply(_FUNDAMENTAL, matches, weights, mask)
 
 
