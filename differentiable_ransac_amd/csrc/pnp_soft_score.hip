@@ -17,6 +17,7 @@
 //     by a wave-uniform branch, so a NaN there reaches nothing), and at the end the waves' partial sums are added in wave order through
 //     LDS.  The order of every sum depends on (M, N) and these constants alone: a repeated launch repeats its bytes.
 // Every barrier sits under a block-uniform branch (the tile loops' trip counts depend on M, N alone).
+#include "compensated_device.hpp"
 #include "pair_loss_device.hpp"
 #include "pnp_device.hpp"
 
@@ -35,29 +36,7 @@ constexpr float kSSCutoff = -40.0f;           // below it a point has no weight 
 // type's precision and rounded once: in f32 through f64 (an f64 fma costs what an unpacked f32 fma does), in f64 through the
 // compensated dot product of Ogita, Rump and Oishi (Dot2: TwoProduct by fma, TwoSum) -- e = n / z_c is then good to a few eps of ITSELF.
 // The error-free transformations must not be contracted (p = a b; s = c + p is not fma(a, b, c) here): contraction is off inside them.
-template <typename T>
-__device__ __forceinline__ void two_sum(T a, T b, T &s, T &e) {
-#pragma clang fp contract(off)
-  s = a + b;
-  const T bb = s - a;
-  e = (a - (s - bb)) + (b - bb);
-}
-
-// hi + lo = m[0] x[0] + m[1] x[1] + m[2] x[2] + m[3] to about twice the type's precision
-template <typename T>
-__device__ __forceinline__ void dot2(const T *m, const T (&x)[5], T &hi, T &lo) {
-#pragma clang fp contract(off)
-  T s = m[3], c = T(0);
-#pragma unroll
-  for (int k = 2; k >= 0; --k) {
-    const T p = m[k] * x[k];
-    const T ep = fma(m[k], x[k], -p);
-    T es;
-    two_sum(s, p, s, es);
-    c += ep + es;
-  }
-  hi = s, lo = c;
-}
+// two_sum and dot2 stand in compensated_device.hpp, which registration_soft_score.hip shares.
 
 // (a_hi + a_lo) - u (z_hi + z_lo), rounded once
 template <typename T>

@@ -1,6 +1,7 @@
 """The training losses that follow the hot path: MatchLoss and PoseLoss for the two-view drivers,
 RegistrationLoss for the 3-D registration driver, HomographyLoss for the homography driver (with the evaluation metrics
-registration_errors and homography_errors) and, at the end, PnPLoss and PnPExpectedLoss (DSAC) for the absolute-pose driver.
+registration_errors and homography_errors) and, at the end, PnPLoss and PnPExpectedLoss (DSAC) for the absolute-pose driver and
+RegistrationExpectedLoss, the same expected loss on the registration driver's hypotheses.
 
 MatchLoss -- the clamped symmetric-epipolar training loss of the reference (loss.py:107-153), on the fused kernel
 `dr_episym_fwd/bwd`.
@@ -250,7 +251,55 @@ _ACOS_MAX = 1.0 - 1e-6
 _RTE_EPS2 = 1e-24
 
 
-class PnPExpectedLoss(object):
+class _ExpectedLoss(object):
+    """What PnPExpectedLoss and RegistrationExpectedLoss share: the expected pose error of the hypotheses under a soft-max of their
+    soft inlier scores, on the [P,M,4,4] pose layout of both families.  A subclass names its score op and its defaults.
+
+        score[p,m] = the family's soft score: sum over the scored points of sigmoid(beta (1 - d2 / threshold^2))
+        probs[p,:] = softmax(alpha score[p,:] / N_p) over the usable slots, N_p = the number of scored points; 0 elsewhere
+        l[p,m]     = min(max(RRE in degrees, trans_weight RTE), max_loss) against gt_pose            (pnp_pose_errors)
+        loss       = mean over the pairs of sum_m probs l
+
+    A slot is usable if keep holds it and its model is finite.  A pair without a usable slot contributes 0 and passes no gradient."""
+    _score_op = None                                          # the name of the family's score in ops (looked up at the call)
+    _tail_f64 = False                                         # everything behind the scores in f64 whatever their type (below)
+
+    def __init__(self, threshold, beta, alpha, trans_weight, max_loss):
+        self.threshold, self.beta, self.alpha = threshold, float(beta), float(alpha)
+        self.trans_weight, self.max_loss = float(trans_weight), float(max_loss)
+        self.per_pair = self.probs = self.scores = None       # of the last call (detached)
+
+    def _forward(self, models, matches, gt_pose, keep, mask):
+        scores = getattr(ops, self._score_op)(matches, models, self.threshold, self.beta, mask, keep)
+        P, M = scores.shape
+        usable = torch.isfinite(models[:, :, :3]).all(-1).all(-1)
+        if keep is not None:
+            usable = usable & keep
+        # f32 logits of alpha score / N ~ 60 carry 2e-6 each, and a slot's probability and its whole gradient row carry that RELATIVE
+        # error, as much again as the f32 score tensor itself brings; l - sum probs l cancels likewise.  A family that sets _tail_f64 runs
+        # everything behind the scores -- [P,M]-sized torch ops -- and its backward in f64; the results and the two gradients are
+        # rounded to the inputs' type once.  PnPExpectedLoss keeps the type's own arithmetic, bit for bit.
+        dt = scores.dtype
+        wide = torch.float64 if self._tail_f64 else dt
+        n_p = matches.shape[1] if mask is None else mask.sum(1, keepdim=True).clamp(min=1).to(wide)
+        # the soft-max over the usable slots, written out (exp of the logits less their largest, 0 at an unusable slot, over the sum): a
+        # pair without a usable slot gets zeros, and nothing depends on how a library soft-max treats -inf or a long row
+        logits = self.alpha * scores.to(wide) / n_p
+        top = logits.detach().masked_fill(~usable, float("-inf")).max(1, keepdim=True).values
+        top = torch.where(usable.any(1, keepdim=True), top, torch.zeros_like(top))
+        e = torch.where(usable, torch.exp(logits - top), torch.zeros_like(logits))
+        probs = e / e.sum(1, keepdim=True).clamp(min=torch.finfo(e.dtype).tiny)
+        # an unusable slot's model (possibly NaN) is replaced BEFORE the errors: a NaN behind a where() would still poison its gradient
+        eye = torch.eye(4, device=models.device, dtype=models.dtype)
+        errors = pnp_pose_errors(torch.where(usable[:, :, None, None], models, eye).to(wide), gt_pose.to(wide), self.trans_weight,
+                                 self.max_loss)
+        per_pair = (probs * errors).sum(1).to(dt)
+        probs = probs.to(dt)
+        self.per_pair, self.probs, self.scores = per_pair.detach(), probs.detach(), scores.detach()
+        return per_pair.mean()
+
+
+class PnPExpectedLoss(_ExpectedLoss):
     """The DSAC / DSAC* training loss on ransac.BatchedPnP.hypotheses: the expected pose error of the hypotheses under a soft-max of
     their soft inlier scores.  It needs no ground-truth inlier mask, weights a hypothesis by how many points agree with it, and gives
     a gradient to `matches` -- whose 3-D column is a network output in scene-coordinate regression -- through the minimal solver (the
@@ -269,34 +318,48 @@ class PnPExpectedLoss(object):
     inlier alpha on the score divided by the number of points.  DSAC* compares degrees with centimetres: trans_weight = 100 for a
     scene in metres, and clamps the pose loss at 100; both are kept.  They are hyper-parameters, not tuned here."""
 
+    _score_op = "pnp_soft_score"
+
     def __init__(self, threshold, beta=5.0, alpha=100.0, trans_weight=100.0, max_loss=100.0):
-        self.threshold, self.beta, self.alpha = threshold, float(beta), float(alpha)
-        self.trans_weight, self.max_loss = float(trans_weight), float(max_loss)
-        self.per_pair = self.probs = self.scores = None       # of the last call (detached)
+        super().__init__(threshold, beta, alpha, trans_weight, max_loss)
 
     def forward(self, models, matches, gt_pose, keep=None, mask=None):
         """models [P,M,4,4], matches [P,N,5] (they MAY require grad), gt_pose [P,4,4], keep [P,M] bool (e.g. hypotheses' keep; None =
         all), mask [P,N] bool (the points that are scored; None = all) -> scalar loss.  The per-pair values, the probabilities and the
         scores of the call stay on the object as .per_pair [P], .probs [P,M], .scores [P,M], detached."""
-        scores = ops.pnp_soft_score(matches, models, self.threshold, self.beta, mask, keep)
-        P, M = scores.shape
-        usable = torch.isfinite(models[:, :, :3]).all(-1).all(-1)
-        if keep is not None:
-            usable = usable & keep
-        n_p = matches.shape[1] if mask is None else mask.sum(1, keepdim=True).clamp(min=1).to(scores.dtype)
-        # the soft-max over the usable slots, written out (exp of the logits less their largest, 0 at an unusable slot, over the sum): a
-        # pair without a usable slot gets zeros, and nothing depends on how a library soft-max treats -inf or a long row
-        logits = self.alpha * scores / n_p
-        top = logits.detach().masked_fill(~usable, float("-inf")).max(1, keepdim=True).values
-        top = torch.where(usable.any(1, keepdim=True), top, torch.zeros_like(top))
-        e = torch.where(usable, torch.exp(logits - top), torch.zeros_like(logits))
-        probs = e / e.sum(1, keepdim=True).clamp(min=torch.finfo(e.dtype).tiny)
-        # an unusable slot's model (possibly NaN) is replaced BEFORE the errors: a NaN behind a where() would still poison its gradient
-        eye = torch.eye(4, device=models.device, dtype=models.dtype)
-        errors = pnp_pose_errors(torch.where(usable[:, :, None, None], models, eye), gt_pose.to(models.dtype), self.trans_weight,
-                                 self.max_loss)
-        per_pair = (probs * errors).sum(1)
-        self.per_pair, self.probs, self.scores = per_pair.detach(), probs.detach(), scores.detach()
-        return per_pair.mean()
+        return self._forward(models, matches, gt_pose, keep, mask)
+
+    __call__ = forward
+
+
+class RegistrationExpectedLoss(_ExpectedLoss):
+    """The DSAC training loss on ransac.BatchedRegistration(train=True): PnPExpectedLoss's definition on the registration family's
+    soft score (ops.registration_soft_score, d2 = |R p + t - q|^2).  Unlike RegistrationLoss it needs no ground-truth inlier mask,
+    weights a hypothesis by how many correspondences agree with it instead of averaging the kept ones equally, and gives a gradient
+    to `matches` through the minimal solver (the models) and through the scores.
+
+        score[p,m] = ops.registration_soft_score: sum over the scored points of sigmoid(beta (1 - d2 / threshold^2))
+        probs[p,:] = softmax(alpha score[p,:] / N_p) over the usable slots, N_p = the number of scored points; 0 elsewhere
+        l[p,m]     = min(max(RRE in degrees, trans_weight RTE), max_loss) against gt_pose            (pnp_pose_errors)
+        loss       = mean over the pairs of sum_m probs l
+
+    A slot is usable if keep holds it and its model is finite.  A pair without a usable slot contributes 0 and passes no gradient.
+    Defaults: beta = 5, alpha = 100 and max_loss = 100 are PnPExpectedLoss's (DSAC*'s, restated in units of the threshold); the
+    threshold is the driver's inlier distance.  trans_weight = 50 sets one degree against 2 cm, the ratio of the usual 3DMatch recall
+    criterion (15 degrees and 0.3 m).  All of them are hyper-parameters, not tuned here.  What follows the scores (the soft-max, the
+    pose errors, the sums: [P,M]-sized) and its backward run in f64 whatever the type of the inputs (_ExpectedLoss._forward says why);
+    the results and the gradients are rounded to that type once."""
+
+    _score_op = "registration_soft_score"
+    _tail_f64 = True
+
+    def __init__(self, threshold, beta=5.0, alpha=100.0, trans_weight=50.0, max_loss=100.0):
+        super().__init__(threshold, beta, alpha, trans_weight, max_loss)
+
+    def forward(self, models, matches, gt_pose, keep=None, mask=None):
+        """models [P,M,4,4], matches [P,N,6] (they MAY require grad), gt_pose [P,4,4], keep [P,M] bool (e.g. the driver's keep; None =
+        all), mask [P,N] bool (the points that are scored; None = all) -> scalar loss.  The per-pair values, the probabilities and the
+        scores of the call stay on the object as .per_pair [P], .probs [P,M], .scores [P,M], detached."""
+        return self._forward(models, matches, gt_pose, keep, mask)
 
     __call__ = forward

@@ -2031,18 +2031,18 @@ def pnp_loss_sums(matches, mask, models, threshold, keep=None, want_pairs: bool 
     return _pair_loss_sums(_PNP, matches, mask, models, threshold, keep, want_pairs)
 
 
-class _PnPSoftScore(torch.autograd.Function):
-    """dr_pnp_soft_score / dr_pnp_soft_score_bwd on checked, contiguous inputs (pnp_soft_score): the backward recomputes the residuals
-    from the saved inputs, writes grad_models and, when the matches need a gradient, grad_matches by the transposed launch."""
+class _SoftScore(torch.autograd.Function):
+    """dr_<entry>_soft_score / dr_<entry>_soft_score_bwd on checked, contiguous inputs (_soft_score): the backward recomputes the
+    residuals from the saved inputs, writes grad_models and, when the matches need a gradient, grad_matches by the transposed launch."""
 
     @staticmethod
-    def forward(ctx, matches, models, thr2, beta, mask, keep):
+    def forward(ctx, matches, models, thr2, beta, mask, keep, entry):
         (P, N, _), M, dt = matches.shape, models.shape[1], matches.dtype
         scores = torch.empty((P, M), device=matches.device, dtype=dt)
-        L.call(f"dr_pnp_soft_score_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2), L.scalar(dt, beta),
+        L.call(f"dr_{entry}_soft_score_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2), L.scalar(dt, beta),
                P, M, N, ptr(scores), stream())
         ctx.save_for_backward(matches, models, thr2, mask, keep)
-        ctx.beta = beta
+        ctx.beta, ctx.entry = beta, entry
         return scores
 
     @staticmethod
@@ -2052,9 +2052,31 @@ class _PnPSoftScore(torch.autograd.Function):
         (P, N, _), M, dt = matches.shape, models.shape[1], matches.dtype
         gm = torch.empty_like(models)
         gx = torch.empty_like(matches) if ctx.needs_input_grad[0] else None
-        L.call(f"dr_pnp_soft_score_bwd_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2),
+        L.call(f"dr_{ctx.entry}_soft_score_bwd_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2),
                L.scalar(dt, ctx.beta), ptr(g.to(dt).contiguous()), P, M, N, ptr(gm), ptr(gx), stream())
-        return gx, gm, None, None, None, None
+        return gx, gm, None, None, None, None, None
+
+
+def _soft_score(fam, name, matches, models, threshold, beta, mask, keep):
+    """the argument checks of the soft-inlier scores (before any launch), then _SoftScore on the family's entries"""
+    r, c = fam.shape
+    _check_matches(fam, name, matches)
+    if matches.dim() != 3 or matches.shape[-1] != fam.width:      # (a family whose record carries no shape text)
+        raise L.DransacError(f"{name}: {fam.points} [P,N,{fam.width}]")
+    if models.dim() != 4 or models.shape[-2:] != fam.shape or models.shape[0] != matches.shape[0]:
+        raise L.DransacError(f"{name}: models [P,M,{r},{c}], one row of {fam.gt_noun}s per row of matches")
+    if models.dtype != matches.dtype or matches.dtype not in (torch.float32, torch.float64):
+        raise L.DransacError(f"{name}: matches and models of one dtype, float32 or float64")
+    (P, N, _), M = matches.shape, models.shape[1]
+    if (mask is not None and (mask.shape != (P, N) or mask.dtype != torch.bool)) or \
+            (keep is not None and (keep.shape != (P, M) or keep.dtype != torch.bool)):
+        raise L.DransacError(f"{name}: mask is [P,N] bool, keep is [P,M] bool")
+    if isinstance(beta, torch.Tensor) or not 0.0 < float(beta) < float("inf"):      # (false for NaN)
+        raise L.DransacError(f"{name}: beta is a positive, finite Python number, got {beta!r}")
+    _gpu_only((matches, models))
+    _gpu_only((mask, keep), optional=True)
+    return _SoftScore.apply(matches.contiguous(), models.contiguous(), thr2_tensor(threshold, P, matches).detach(), float(beta),
+                            _u8(mask), _u8(keep), fam.entry)
 
 
 def pnp_soft_score(matches, models, threshold, beta: float = 5.0, mask=None, keep=None):
@@ -2065,22 +2087,18 @@ def pnp_soft_score(matches, models, threshold, beta: float = 5.0, mask=None, kee
     and a kept model with a non-finite entry score 0.  Differentiable (once) w.r.t. `models`, and w.r.t. `matches` when they require
     grad: the second pass over the grid runs only then.  No gradient for threshold, beta, mask or keep.  f32 and f64; nothing
     synchronises or reads back, so the op can be captured in a HIP graph."""
-    r, c = _PNP.shape
-    _check_matches(_PNP, "pnp_soft_score", matches)
-    if models.dim() != 4 or models.shape[-2:] != _PNP.shape or models.shape[0] != matches.shape[0]:
-        raise L.DransacError(f"pnp_soft_score: models [P,M,{r},{c}], one row of poses per row of matches")
-    if models.dtype != matches.dtype or matches.dtype not in (torch.float32, torch.float64):
-        raise L.DransacError("pnp_soft_score: matches and models of one dtype, float32 or float64")
-    (P, N, _), M = matches.shape, models.shape[1]
-    if (mask is not None and (mask.shape != (P, N) or mask.dtype != torch.bool)) or \
-            (keep is not None and (keep.shape != (P, M) or keep.dtype != torch.bool)):
-        raise L.DransacError("pnp_soft_score: mask is [P,N] bool, keep is [P,M] bool")
-    if isinstance(beta, torch.Tensor) or not 0.0 < float(beta) < float("inf"):      # (false for NaN)
-        raise L.DransacError(f"pnp_soft_score: beta is a positive, finite Python number, got {beta!r}")
-    _gpu_only((matches, models))
-    _gpu_only((mask, keep), optional=True)
-    return _PnPSoftScore.apply(matches.contiguous(), models.contiguous(), thr2_tensor(threshold, P, matches).detach(), float(beta),
-                               _u8(mask), _u8(keep))
+    return _soft_score(_PNP, "pnp_soft_score", matches, models, threshold, beta, mask, keep)
+
+
+def registration_soft_score(matches, models, threshold, beta: float = 5.0, mask=None, keep=None):
+    """The differentiable soft-inlier score (DSAC) of every rigid model on every correspondence: matches [P,N,6] = (p, q), models
+    [P,M,4,4], threshold = the inlier DISTANCE (float or [P]), beta > 0, mask [P,N] bool | None (the points that are scored),
+    keep [P,M] bool | None -> scores [P,M] = sum over the scored points of sigmoid(beta (1 - d2 / threshold^2)), d2 = |R p + t - q|^2;
+    a point with beta (1 - d2 / threshold^2) < -40 adds nothing (include/dransac.h states the rules).  A slot keep drops, a kept model
+    with a non-finite entry and a pair whose threshold is not > 0 score 0.  Differentiable (once) w.r.t. `models`, and w.r.t. `matches`
+    when they require grad: the second pass over the grid runs only then.  No gradient for threshold, beta, mask or keep.  f32 and
+    f64; nothing synchronises or reads back, so the op can be captured in a HIP graph."""
+    return _soft_score(_REGISTRATION, "registration_soft_score", matches, models, threshold, beta, mask, keep)
 
 
 # ------------------------------------------------------------------------------------------ PoseLoss pose error (8(f) rank 3)

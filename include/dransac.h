@@ -847,6 +847,42 @@ int dr_pnp_soft_score_bwd_f64(const double *matches, const uint8_t *mask, const 
                               double *grad_matches, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The differentiable soft-inlier score of the registration path (ops.registration_soft_score, loss.RegistrationExpectedLoss): the
+ * DSAC score of every rigid model on every correspondence, with a reverse pass to the models and to the points.  matches [P,N,6] =
+ * (p, q), models [P,M,16] = [[R, t], [0,0,0,1]], thr2 [P], mask [P,N] (the points that are scored; NULL = all), keep [P,M] (NULL =
+ * all models) as for dr_registration_loss_*; beta > 0 by value.
+ *     d = R p + t - q,   d2[p,m,n] = |d|^2,   a = beta (1 - d2 / thr2[p]),   live = d2 finite and a >= -40
+ *     w = live ? 1 / (1 + exp(-a)) : 0,       scores[p,m] = sum_{n in mask} w[p,m,n]
+ * (weight 1/2 at the threshold, 1 / (1 + exp(-beta)) at zero distance; the SQUARED distance, the package's convention).  The cutoff
+ * a < -40 (w < 4.3e-18) is part of the definition, as for dr_pnp_soft_score.  With g = 2 grad_scores[p,m] (-beta / thr2[p]) w (1 - w)
+ * per live term:
+ *     grad_models[p,m]:   d / d t = sum_n g d,   d / d R = sum_n g d p^T   over the masked points, row 3 = 0
+ *     grad_matches[p,n]:  d / d p = sum_m R^T (g d),   d / d q = sum_m -g d   over the kept models
+ * A slot keep drops is never read (score 0, gradient exactly 0, its model and its grad_scores may be NaN); a kept model with a
+ * non-finite entry among its twelve scores 0 and passes exact zeros to itself and to the points; a thr2[p] that is not > 0 (NaN
+ * included) gives the pair score 0 and zero gradients; a point outside the mask gets exact zeros.  Every output element is written.
+ * No floating-point atomics, no workspace, and one order for every sum that depends on (P, M, N) alone: a repeated launch gives the
+ * same bits.  d is formed beyond the type's precision (f32: in f64; f64: a compensated dot product and TwoSum) and rounded once: its
+ * cancellation costs no digits.  The gradients are accumulated in the type of the inputs, the score with a compensated (TwoSum) sum
+ * in it.  P <= 65535 and P M < 2^22.  No gradient for thr2 or beta.
+ *
+ *   dr_registration_soft_score       scores [P,M]: one lane per model, the points in ascending order.
+ *   dr_registration_soft_score_bwd   grad_scores [P,M] -> grad_models [P,M,16] (the forward's mapping) and, unless grad_matches is
+ *     NULL, grad_matches [P,N,6] by a second launch with the transposed mapping (one lane per point; the models in tiles of 512,
+ *     every eighth of a tile summed by its own wave, the eight partial sums added in order).  Both recompute the residuals.
+ * ------------------------------------------------------------------------------------------ */
+int dr_registration_soft_score_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep,
+                                   const float *thr2, float beta, int P, int M, int N, float *scores, void *stream);
+int dr_registration_soft_score_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                   const double *thr2, double beta, int P, int M, int N, double *scores, void *stream);
+int dr_registration_soft_score_bwd_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep,
+                                       const float *thr2, float beta, const float *grad_scores, int P, int M, int N,
+                                       float *grad_models, float *grad_matches, void *stream);
+int dr_registration_soft_score_bwd_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                       const double *thr2, double beta, const double *grad_scores, int P, int M, int N,
+                                       double *grad_models, double *grad_matches, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K5  train-mode best-of-S selection    RANSAC.__call__, ransac.py:87-96
  *   chosen[p,b] = models[p,b,argmin_s ||models[p,b,s] - gt[p]||_F]; invalid slots (valid == 0) are
  *   skipped; which [P*B] int32 (-1 when no slot is valid; chosen = eye(3) then).
