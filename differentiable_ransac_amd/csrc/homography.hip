@@ -580,22 +580,16 @@ __global__ __launch_bounds__(kHRThreads) void refit_homography_bwd_kernel(const 
   }
 }
 
-// ---- (5) IRLS polish of the pair state under the MAGSAC++ loss (BatchedHomography(scoring = "magsac")): one 256-thread block per pair ----
-// registration_irls_kernel's sibling.  Up to `iters` times from the pair's (best_model, best_score): the rows of a step
-// are the points inside the cutoff and in front of both cameras under the current model, each with the weight w(s_n) of
-// TransferMagsacTerm; the normalised DLT of (4) over those rows (dlt_system: Hartley's transforms unweighted over the rows, the weight in
-// the Gram sums), wave 0's eigenvector, the candidate rounded to T; its MAGSAC++ score over all points in T (transfer_d2<T> and the
-// scoring kernel's term, so it compares with a best_score that kernel produced); taken only on a STRICTLY higher score.  The loop ends
-// before a fit with fewer than four rows (on the count dlt_system returns, so its other two passes have run by then, over transforms that
-// are inf / NaN without rows -- nothing of them is used or stored), on an invalid or non-finite candidate, on a candidate that does not
-// win, and at the limit.  irls_fits[p] += fits run.  best_mask, best_inliers, iters and max_iters are neither read nor written: the mask
-// stays the RANSAC winner's.
+// ---- (5) IRLS polish of the pair state under the MAGSAC++ loss (BatchedHomography(scoring = "magsac")): pair_polish under this fit ----
+//   The rows of a step are the points inside the cutoff and in front of both cameras under the current model, each with
+// the weight w(s_n) of TransferMagsacTerm; the fit is the normalised DLT of (4) over those rows (dlt_system: Hartley's transforms
+// unweighted over the rows, the weight in the Gram sums) and wave 0's eigenvector, which reaches the block through LDS.  Nothing is
+// fitted from a NaN or singular state, which has no rows, or with fewer than four rows (on the count dlt_system returns, so its other
+// two passes have run by then, over transforms that are inf / NaN without rows -- nothing of them is used or stored).  The mask stays
+// the RANSAC winner's.
 // The row decision and the weights are evaluated in f64 for either type (the model and the rows widened, thr2 as stored): the refit's
 // sums are f64 already, and f32 weights move a fitted model by more than its output rounding.  They are not stored: the
-// three passes evaluate the same expression on the same values.
-// Mapping: a latency kernel, the steps of a pair are serial, each one four block-stride passes over 16 N bytes that stay in L2.
-// Wave 0 broadcasts the candidate through LDS; every exit is block-uniform; sums go lane, wave butterfly, the four waves in order: no
-// atomics, no read-back, a repeated launch gives the same bits.
+// three passes evaluate the same expression on the same values.  A step is four block-stride passes over 16 N bytes.
 template <typename T>
 struct CutoffRows4 {
   const Match4<T> *pt;
@@ -618,26 +612,38 @@ struct CutoffRows4 {
   }
 };
 
-// the score of a prepared model over all N points of a pair by the whole block; every thread returns it.  Order: a thread's points in
-// order, the wave butterfly, the four waves in order.  s_part: shared, 4 entries, free again on return.
-template <typename T, typename Term>
-__device__ __forceinline__ T block_score_h(const Match4<T> *__restrict__ pt, int N, const ScoredH<T> &s, const Term &term, T *s_part) {
-  T acc = T(0);
-  for (int n = threadIdx.x; n < N; n += kHRThreads) {
-    const Match4<T> x = pt[n];
-    T d2;
-    const bool live = transfer_d2<T>(s, x.v, d2);
-    acc += term.contrib(d2, live);
-  }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  T sc = s_part[0];
+template <typename T>
+struct HomographyIrlsFit {
+  const Match4<T> *pt;
+  int N;
+  const TransferMagsacTerm<double> &term;
+  DltLds &L;
+  T *s_cand;      // shared: the candidate's 9 values and, in s_ok, the fit's validity; both are next written behind dlt_system's
+  int *s_ok;      // barriers, after every thread has read them (pair_block_score's two barriers lie in between)
+  __device__ __forceinline__ int operator()(const T (&cur)[9], T (&cand)[9]) const {
+    double bd[9];
 #pragma unroll
-  for (int w = 1; w < kHRThreads / 64; ++w) sc += s_part[w];
-  __syncthreads();
-  return sc;
-}
+    for (int q = 0; q < 9; ++q) bd[q] = (double)cur[q];
+    ScoredH<double> s;
+    prepare_h(bd, true, s);
+    if (s.kind != kModelScored) return kFitStop;
+    double nz1[3], nz2[3];
+    const double rows = dlt_system<T>(CutoffRows4<T>{pt, s, term}, N, L, nz1, nz2);
+    if (!(rows >= 4.0)) return kFitStop;
+    if (threadIdx.x < 64) {
+      double H[9];
+      const bool ok = dlt_solve_wave(L, threadIdx.x, nz1, nz2, rows, H);
+      if (threadIdx.x == 0) {
+        store_h(s_cand, H);
+        *s_ok = ok;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 9; ++q) cand[q] = s_cand[q];
+    return *s_ok ? kFitValid : kFitInvalid;
+  }
+};
 
 template <typename T>
 __global__ __launch_bounds__(kHRThreads) void homography_irls_kernel(const T *__restrict__ matches, const T *__restrict__ thr2, int N,
@@ -646,59 +652,12 @@ __global__ __launch_bounds__(kHRThreads) void homography_irls_kernel(const T *__
   __shared__ DltLds L;
   __shared__ T s_part[kHRThreads / 64], s_cand[9];
   __shared__ int s_ok;
-  const int p = blockIdx.x, tid = threadIdx.x;
-  const Match4<T> *pt = reinterpret_cast<const Match4<T> *>(matches) + (size_t)p * N;
-  T bs = best_score[p];
-  T bm[9];
-#pragma unroll
-  for (int q = 0; q < 9; ++q) bm[q] = best_model[(size_t)p * 9 + q];
-  __syncthreads();      // (every thread has read the state: thread 0 writes it below)
+  const int p = blockIdx.x;
+  const T *pt = matches + (size_t)p * N * 4;
   const TransferMagsacTerm<T> term(thr2[p]);
   const TransferMagsacTerm<double> termd((double)thr2[p]);
-  bool taken = false;
-  int fits = 0;
-  for (int it = 0; it < iters; ++it) {
-    double bd[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) bd[q] = (double)bm[q];
-    ScoredH<double> cur;
-    prepare_h(bd, true, cur);
-    if (cur.kind != kModelScored) break;      // (block-uniform, like every exit below: a NaN or singular state has no rows)
-    const CutoffRows4<T> sel{pt, cur, termd};
-    double nz1[3], nz2[3];
-    const double rows = dlt_system<T>(sel, N, L, nz1, nz2);
-    if (!(rows >= 4.0)) break;
-    if (tid < 64) {
-      double H[9];
-      const bool ok = dlt_solve_wave(L, tid, nz1, nz2, rows, H);
-      if (tid == 0) {
-        store_h(s_cand, H);
-        s_ok = ok;
-      }
-    }
-    __syncthreads();
-    ++fits;
-    T cm[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) cm[q] = s_cand[q];
-    ScoredH<T> cs;
-    prepare_h(cm, true, cs);
-    if (!s_ok || cs.kind != kModelScored) break;      // (s_cand / s_ok are next written behind dlt_system's barriers)
-    const T sc = block_score_h(pt, N, cs, term, s_part);
-    if (!(sc > bs)) break;
-    bs = sc;
-    taken = true;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) bm[q] = cm[q];
-  }
-  if (tid == 0) {
-    if (taken) {
-      best_score[p] = bs;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) best_model[(size_t)p * 9 + q] = bm[q];
-    }
-    irls_fits[p] += fits;
-  }
+  const HomographyIrlsFit<T> fit{reinterpret_cast<const Match4<T> *>(pt), N, termd, L, s_cand, &s_ok};
+  pair_polish<T, HomographyGeom>(pt, N, iters, term, fit, s_part, best_score + p, best_model + (size_t)p * 9, irls_fits + p);
 }
 
 }  // namespace dr

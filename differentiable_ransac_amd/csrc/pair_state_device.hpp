@@ -1,7 +1,7 @@
 // What the per-pair test-mode families with their state on the device share (registration.hip: rigid models, homography.hip:
-// plane-induced homographies): the kernel that scores every model against every point, the state step, and the block-wide f64 sum
-// of their refits.  A family enters as a policy struct Geom (RigidGeom in rigid_device.hpp, HomographyGeom in
-// homography_device.hpp):
+// plane-induced homographies): the kernel that scores every model against every point, the state step, the block-wide f64 sum
+// of their refits, and the polish of the state behind the step (pair_block_score, pair_polish).  A family enters as a policy struct
+// Geom (RigidGeom in rigid_device.hpp, HomographyGeom in homography_device.hpp):
 //   kModel, kWidth, kSample        values per model (16 / 9) and per match (6 / 4), sample size of the adaptive stop (3 / 4)
 //   kFirstRoundTakes               does the state step take the first round's best even when it is not strictly higher
 //   Slot<T>, prepare(m, slot)      a model ready to be evaluated -> its kind (ransac_device.hpp's ModelKind); wave-uniform
@@ -175,6 +175,97 @@ __device__ __forceinline__ void block_sum_f64(double *v, double (*s)[K]) {
 #pragma unroll
   for (int i = 0; i < K; ++i) v[i] = block_total_f64<K>(s, i);
   __syncthreads();   // (the buffer may be reused)
+}
+
+// ---- the score of ONE prepared slot over the N rows of a pair (pt = the pair's first row), by the whole block, under the scoring
+// kernel's term -> the score in every thread, and through `count` (with its slots s_cnt) the number of inliers; a caller that passes
+// neither pays nothing for the count: the function is forced inline, so `count` is a constant there, and term.inlier has no side
+// effect, so the row loop's count is dead code.  Thread n owns rows n, n + 256, ...; sums: lane, wave butterfly, the four waves in order.
+// Two barriers; s_part / s_cnt (kPairThreads / 64 entries each) are free again on return.
+template <typename T, typename Geom, typename Term>
+__device__ __forceinline__ T pair_block_score(const T *pt, int N, const typename Geom::template Slot<T> &s, const Term &term, T *s_part,
+                                              int *s_cnt = nullptr, int *count = nullptr) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  T acc = T(0);
+  int cnt = 0;
+  for (int n = tid; n < N; n += kPairThreads) {
+    const auto x = Geom::template Point<T>::load(pt, n);
+    T d2;
+    const bool live = Geom::d2(s, x.v, d2);
+    acc += term.contrib(d2, live);
+    cnt += (live && term.inlier(d2)) ? 1 : 0;
+  }
+  acc = wave_sum(acc);
+  if (count) cnt = wave_sum(cnt);
+  if (lane == 0) {
+    s_part[wv] = acc;
+    if (count) s_cnt[wv] = cnt;
+  }
+  __syncthreads();
+  T sc = s_part[0];
+#pragma unroll
+  for (int w = 1; w < kPairThreads / 64; ++w) sc += s_part[w];
+  if (count) {
+    cnt = s_cnt[0];
+#pragma unroll
+    for (int w = 1; w < kPairThreads / 64; ++w) cnt += s_cnt[w];
+    *count = cnt;
+  }
+  __syncthreads();
+  return sc;
+}
+
+// ---- the polish of a pair's (best_score, best_model) behind the state step: one accept loop under a family's fit ---------------------
+// One block per pair.  Every thread reads the state; behind a barrier (thread 0 writes it at the end) up to `iters` times:
+//   fit(current model, candidate) -> kFitStop: nothing was fitted, the loop ends and the step is not counted; otherwise a fit has run
+//   and counts, and the candidate holds its model rounded to T as the family's refit stores it.  The loop ends there on kFitInvalid
+//   and on a candidate that Geom::prepare does not call scored or that holds a non-finite value (RigidGeom::prepare classifies
+//   nothing, so the values are tested here; for HomographyGeom the test repeats what prepare_h has folded into the kind);
+//   the candidate's score over all N rows with the scoring kernel's term (pair_block_score), so that it compares with a best_score
+//   that kernel produced; it is taken only if it scores STRICTLY higher (the state step and the drivers' final refits use > too), and
+//   a candidate that does not win ends the loop.
+// Thread 0 then stores score and model if a candidate was taken, and adds the fits run to the pair's counter.  Nothing else of the
+// state is read or written.  A latency kernel: the steps of a pair are serial, each one a few block-stride passes over rows that stay
+// in L2 -- they are not staged in LDS, so there is one path for every N.  `fit` is called by every thread of the block and returns
+// the same value and the same candidate in each, so every exit is block-uniform; all sums go lane, wave butterfly, the four waves in
+// order: no atomics, no read-back, a repeated launch gives the same bits.
+enum { kFitStop, kFitValid, kFitInvalid };
+
+template <typename T, typename Geom, typename Term, typename Fit>
+__device__ __forceinline__ void pair_polish(const T *pt, int N, int iters, const Term &term, const Fit &fit, T *s_part,
+                                            T *__restrict__ best_score, T *__restrict__ best_model, int32_t *__restrict__ fit_count) {
+  T bs = *best_score;
+  T bm[Geom::kModel];
+#pragma unroll
+  for (int q = 0; q < Geom::kModel; ++q) bm[q] = best_model[q];
+  __syncthreads();      // (every thread has read the state: thread 0 writes it below)
+  bool taken = false;
+  int fits = 0;
+  for (int it = 0; it < iters; ++it) {
+    T cm[Geom::kModel];
+    const int fitted = fit(bm, cm);
+    if (fitted == kFitStop) break;
+    ++fits;
+    typename Geom::template Slot<T> cs;
+    bool ok = Geom::prepare(cm, cs) == kModelScored && fitted == kFitValid;
+#pragma unroll
+    for (int q = 0; q < Geom::kModel; ++q) ok = ok && is_finite(cm[q]);
+    if (!ok) break;
+    const T sc = pair_block_score<T, Geom>(pt, N, cs, term, s_part);
+    if (!(sc > bs)) break;
+    bs = sc;
+    taken = true;
+#pragma unroll
+    for (int q = 0; q < Geom::kModel; ++q) bm[q] = cm[q];
+  }
+  if (threadIdx.x == 0) {
+    if (taken) {
+      *best_score = bs;
+#pragma unroll
+      for (int q = 0; q < Geom::kModel; ++q) best_model[q] = bm[q];
+    }
+    *fit_count += fits;
+  }
 }
 
 }  // namespace dr

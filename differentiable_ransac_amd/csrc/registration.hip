@@ -371,7 +371,7 @@ __global__ __launch_bounds__(64) void kabsch_bwd_kernel(const T *__restrict__ sa
 }
 
 // ---- (2) score and inlier count of every model against every point: pair_state_device.hpp's pair_score_kernel under RigidGeom and one
-// of the two terms below.  block_score walks existing rows with the same terms and relies on their default live = true.
+// of the two terms below; the polish kernels (5), (6) score their candidates with the same terms through its pair_block_score.
 // MSAC: max(0, 1 - d2 / thr2).  The contribution and the count keep their own predicates (sv > 0 and d2 < thr2 can differ by a rounding)
 template <typename T>
 struct MsacTerm {
@@ -588,58 +588,18 @@ __global__ __launch_bounds__(kRFThreads) void refit_rigid_bwd_kernel(const T *__
   }
 }
 
-// ---- the score of ONE model over all N points of a pair, by the whole block, with the per-point term of (2): -> the score in every
-// thread, and through `count` (with its slots s_cnt) the number of inliers; a caller that passes neither pays nothing for the count.
-// Sums: lane, wave butterfly, the four waves in order.  Two barriers; s_part / s_cnt are free again on return.
-template <typename T, typename Term>
-__device__ __forceinline__ T block_score(const T *pt, int N, const T (&m)[12], const Term &term, T *s_part, int *s_cnt = nullptr,
-                                         int *count = nullptr) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  T acc = T(0);
-  int cnt = 0;
-  for (int n = tid; n < N; n += kRFThreads) {
-    T x[6];
-    load_row(pt, n, x);
-    const T d2 = rigid_d2<T>(m, x);
-    acc += term.contrib(d2);
-    cnt += term.inlier(d2) ? 1 : 0;
-  }
-  acc = wave_sum(acc);
-  if (count) cnt = wave_sum(cnt);
-  if (lane == 0) {
-    s_part[wv] = acc;
-    if (count) s_cnt[wv] = cnt;
-  }
-  __syncthreads();
-  T sc = s_part[0];
-#pragma unroll
-  for (int w = 1; w < kRFThreads / 64; ++w) sc += s_part[w];
-  if (count) {
-    cnt = s_cnt[0];
-#pragma unroll
-    for (int w = 1; w < kRFThreads / 64; ++w) cnt += s_cnt[w];
-    *count = cnt;
-  }
-  __syncthreads();
-  return sc;
-}
-
 // ---- (5) local optimisation of the pair state (BatchedRegistration(lo = 1 / 2)): one block per pair, right behind (3) ----------
 // A pair whose (best_score, best_model) still equals its snapshot lo_seen[p] bit for bit -- only (3) replaces them, and the snapshot
-// starts as NaN -- returns at once, whether or not it has terminated.  Otherwise, up to `iters` times: the fit of (4) over the best
-// mask (block_moments + kabsch3, f64), the candidate rounded to T as (4) stores it, its MSAC score and inlier count over all N points
-// (block_score with the term of (2), the test of (3)); the candidate is taken only if it scores STRICTLY higher ((3) and the driver's final refit
-// use > too), and then a further pass rewrites the mask and compares it with the old one.  The loop ends on an invalid or non-finite
-// fit, on a candidate that loses, and on an accepted mask that equals the previous one (the next fit would see the same rows).  Then
-// max_iters from the inlier count, the snapshot, and lo_refits[p] += fits run.  Below three inliers only the snapshot is stored.
-// Mapping (a latency kernel: a pair's fits are serial, each one four block-stride passes over 24 N bytes that stay in L2):
-//  - the points are NOT staged in LDS: one path for every N (a staged copy needs a size limit and a second path behind it), and a
-//    pass has 6 ceil(N / 256) independent loads per thread in flight, so it costs about one L2 round trip;
-//  - the candidate's mask is not held anywhere before acceptance: the accepting pass evaluates term.inlier(rigid_d2) again, the same
-//    expression on the same values as the counting pass, so the count is the written mask's count, for every N;
-//  - every thread runs kabsch3 on the block's sums (same inputs, same instructions, same bits): no broadcast and no barrier
-//    between the fit and the score pass.  Thread n owns points n, n + 256, ... in every pass, mask bytes included.
-// Sums: lane, wave butterfly, the four waves in order -- no floating-point atomics, a repeated launch gives the same bits.
+// starts as NaN -- returns at once, whether or not it has terminated.  Otherwise pair_state_device.hpp's accept loop (pair_polish: the
+// mapping and the sum order are stated there) with four things of its own, which is why it is written out here: a fit counts whether
+// or not it is valid; the score pass counts the inliers too; an accepted candidate is followed by a pass that rewrites the mask and
+// compares it with the old one, and the loop also ends on an accepted mask that equals the previous one (the next fit would see the
+// same rows); and the write-back adds the inlier count, max_iters from it, the snapshot, and lo_refits[p] += fits run.  The fit is
+// (4)'s over the best mask (block_moments + kabsch3, f64; every thread runs kabsch3 on the block's sums).  Below three inliers only
+// the snapshot is stored.
+// The candidate's mask is not held anywhere before acceptance: the accepting pass evaluates term.inlier(rigid_d2) again, the same
+// expression on the same values as the counting pass, so the count is the written mask's count, for every N.  Thread n owns points
+// n, n + 256, ... in every pass, mask bytes included; a pass has 6 ceil(N / 256) independent loads per thread in flight.
 template <typename T>
 __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
     const T *__restrict__ pts, const T *__restrict__ thr2, int N, int iters, double confidence, double eps, int max_iterations,
@@ -683,8 +643,10 @@ __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
 #pragma unroll
     for (int q = 0; q < 12; ++q) ok = ok && is_finite(m[q]);
     if (!ok) break;     // (block-uniform, like every exit below: all threads hold the same sums)
+    RigidGeom::Slot<T> cs;
+    RigidGeom::prepare(m, cs);
     int cnt;
-    const T sc = block_score(pt, N, m, term, s_part, s_cnt, &cnt);
+    const T sc = pair_block_score<T, RigidGeom>(pt, N, cs, term, s_part, s_cnt, &cnt);
     if (!(sc > bs)) break;
     int chg = 0;
     for (int n = tid; n < N; n += kRFThreads) {
@@ -722,20 +684,15 @@ __global__ __launch_bounds__(kRFThreads) void registration_local_opt_kernel(
   }
 }
 
-// ---- (6) IRLS polish of the pair state under the MAGSAC++ loss (BatchedRegistration(scoring = "magsac")): one block per pair ----------
-// The sigma-consensus++ step, up to `iters` times from the pair's (best_model, best_score): the weights w(s_n) of (2b) under the current
-// model; the weighted fit over ALL points (block_moments with these weights, kabsch3; f64), the candidate rounded to T;
-// its MAGSAC++ score over all points (block_score with the term of (2b)); taken only if it scores STRICTLY higher.  The loop ends before
-// a fit when fewer than three points have d2 < thr2 (the points with a non-zero weight), on an invalid or non-finite fit, and on a
-// candidate that does not win.  (That first exit is taken on the row count block_moments returns, so its second pass has run by then:
-// one more pass over the points, over means that are inf / NaN when the weight sum is 0 -- nothing of it is used or stored.)
-// irls_fits[p] += fits run.  best_mask, best_inliers, iters and max_iters are neither read nor written:
-// the mask stays the RANSAC winner's, as with the single final refit of the MSAC path.
-// Mapping: registration_local_opt_kernel's (a latency kernel: the steps of a pair are serial, each one three block-stride passes over
-// 24 N bytes that stay in L2 -- weighted means, weighted H, score).  The weights are not stored: passes 1 and 2 evaluate the same
-// expression on the same values.  Every thread runs kabsch3 on the block's sums; sums go lane, wave butterfly, the four waves in
-// order -- no atomics, no read-back, a repeated launch gives the same bits.
-// the rows of a step: those inside the cutoff under the current model (read through the reference at every pass), with the weight of (2b)
+// ---- (6) IRLS polish of the pair state under the MAGSAC++ loss (BatchedRegistration(scoring = "magsac")): pair_polish under this fit ----
+// The sigma-consensus++ step: the weights w(s_n) of (2b) under the current model, the weighted fit over ALL points (block_moments with
+// these weights, kabsch3; f64).  Nothing is fitted when fewer than three points have d2 < thr2 (the points with a non-zero weight);
+// that exit is taken on the row count block_moments returns, so its second pass has run by then: one more pass over the points, over
+// means that are inf / NaN when the weight sum is 0 -- nothing of it is used or stored.  Every thread runs kabsch3 on the block's sums
+// (same inputs, same instructions, same bits): no broadcast and no barrier between the fit and the score pass.  The weights are not
+// stored: passes 1 and 2 evaluate the same expression on the same values.  The mask stays the RANSAC winner's, as with the single
+// final refit of the MSAC path.
+// the rows of a step: those inside the cutoff under the current model, with the weight of (2b)
 template <typename T>
 struct CutoffRows {
   const T *pt;
@@ -752,6 +709,24 @@ struct CutoffRows {
 };
 
 template <typename T>
+struct RigidIrlsFit {
+  const T *pt;
+  int N;
+  const MagsacTerm<T> &term;
+  double (*s_red)[9];
+  __device__ __forceinline__ int operator()(const T (&cur)[16], T (&cand)[16]) const {
+    RigidGeom::Slot<T> s;
+    RigidGeom::prepare(cur, s);
+    double c[6], H[3][3], rows, R[3][3], t[3];
+    const double W = block_moments<T>(N, CutoffRows<T>{pt, s.m, term}, s_red, c, H, rows);
+    if (!(rows >= 3.0)) return kFitStop;
+    const bool ok = kabsch3(H, c, W > 0.0, R, t);
+    store_rigid_model(cand, R, t);
+    return ok ? kFitValid : kFitInvalid;
+  }
+};
+
+template <typename T>
 __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *__restrict__ pts, const T *__restrict__ thr2, int N,
                                                                        int iters, T *__restrict__ best_score,
                                                                        T *__restrict__ best_model, int32_t *__restrict__ irls_fits) {
@@ -759,48 +734,9 @@ __global__ __launch_bounds__(kRFThreads) void registration_irls_kernel(const T *
   __shared__ T s_part[kRFThreads / 64];
   const int p = blockIdx.x;
   const T *pt = pts + (size_t)p * N * 6;
-  T bs = best_score[p];
-  T m[12];
-#pragma unroll
-  for (int q = 0; q < 12; ++q) m[q] = best_model[(size_t)p * 16 + q];
-  __syncthreads();      // (every thread has read the state: thread 0 writes it below)
   const MagsacTerm<T> term(thr2[p]);
-  const CutoffRows<T> weighted{pt, m, term};
-  bool taken = false;
-  int fits = 0;
-  for (int it = 0; it < iters; ++it) {
-    double c[6], H[3][3], rows, R[3][3], t[3];
-    const double W = block_moments<T>(N, weighted, s_red, c, H, rows);
-    if (!(rows >= 3.0)) break;      // (block-uniform, like every exit below: all threads hold the same sums)
-    bool ok = kabsch3(H, c, W > 0.0, R, t);
-    ++fits;
-    T cm[12];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) cm[4 * i + j] = (T)R[i][j];
-      cm[4 * i + 3] = (T)t[i];
-    }
-#pragma unroll
-    for (int q = 0; q < 12; ++q) ok = ok && is_finite(cm[q]);
-    if (!ok) break;
-    const T sc = block_score(pt, N, cm, term, s_part);
-    if (!(sc > bs)) break;
-    bs = sc;
-    taken = true;
-#pragma unroll
-    for (int q = 0; q < 12; ++q) m[q] = cm[q];
-  }
-  if (threadIdx.x == 0) {
-    if (taken) {
-      best_score[p] = bs;
-#pragma unroll
-      for (int q = 0; q < 12; ++q) best_model[(size_t)p * 16 + q] = m[q];
-      best_model[(size_t)p * 16 + 12] = best_model[(size_t)p * 16 + 13] = best_model[(size_t)p * 16 + 14] = T(0);
-      best_model[(size_t)p * 16 + 15] = T(1);
-    }
-    irls_fits[p] += fits;
-  }
+  pair_polish<T, RigidGeom>(pt, N, iters, term, RigidIrlsFit<T>{pt, N, term, s_red}, s_part, best_score + p,
+                            best_model + (size_t)p * 16, irls_fits + p);
 }
 
 }  // namespace dr
