@@ -1,4 +1,6 @@
-// What the homography kernels (homography.hip) share.
+// What the homography kernels (homography.hip, homography_loss.hip, homography_soft_score.hip) share.
+//   refined_rcp             the reciprocal of the two differentiable kernels: v_rcp_f32 and one Newton step in f32, a division in f64
+//   adjugate3_vjp           the transpose of adj's Jacobian (linear in H), applied once per model by the two reverse passes
 //   ScoredH / prepare_h     a model slot as the score and update kernels evaluate it: the det > 0 sign applied, adj(H), its kind
 //   transfer_d2             the symmetric transfer error of one point -- ONE text for the score kernel, the state step's mask and its
 //                           count, every product an explicit fma, so that -ffp-contract has nothing to decide and the three round alike
@@ -25,6 +27,26 @@ __device__ __forceinline__ void adjugate3(const T (&h)[9], T (&a)[9]) {
   a[6] = fma(h[3], h[7], -(h[4] * h[6]));
   a[7] = fma(h[1], h[6], -(h[0] * h[7]));
   a[8] = fma(h[0], h[4], -(h[1] * h[3]));
+}
+
+__device__ __forceinline__ float refined_rcp(float w) {
+  const float r = __builtin_amdgcn_rcpf(w);
+  return fma(r, fma(-w, r, 1.0f), r);      // (w = 0 or inf gives NaN here: the caller's `live` is false for those)
+}
+__device__ __forceinline__ double refined_rcp(double w) { return 1.0 / w; }
+
+// out = J^T g for a = adj(h): out[q] = sum_k g[k] d a[k] / d h[q], term by term from adjugate3
+template <typename T>
+__device__ __forceinline__ void adjugate3_vjp(const T (&h)[9], const T (&g)[9], T (&out)[9]) {
+  out[0] = fma(g[4], h[8], fma(-g[5], h[5], fma(-g[7], h[7], g[8] * h[4])));
+  out[1] = fma(-g[1], h[8], fma(g[2], h[5], fma(g[7], h[6], -(g[8] * h[3]))));
+  out[2] = fma(g[1], h[7], fma(-g[2], h[4], fma(-g[4], h[6], g[5] * h[3])));
+  out[3] = fma(-g[3], h[8], fma(g[5], h[2], fma(g[6], h[7], -(g[8] * h[1]))));
+  out[4] = fma(g[0], h[8], fma(-g[2], h[2], fma(-g[6], h[6], g[8] * h[0])));
+  out[5] = fma(-g[0], h[7], fma(g[2], h[1], fma(g[3], h[6], -(g[5] * h[0]))));
+  out[6] = fma(g[3], h[5], fma(-g[4], h[2], fma(-g[6], h[4], g[7] * h[1])));
+  out[7] = fma(-g[0], h[5], fma(g[1], h[2], fma(g[6], h[3], -(g[7] * h[0]))));
+  out[8] = fma(g[0], h[4], fma(-g[1], h[1], fma(-g[3], h[3], g[4] * h[0])));
 }
 
 // One model slot, ready to be evaluated: h = H under the det > 0 sign, a = adj(H), kind as model_kind() has it -- skipped (the slot

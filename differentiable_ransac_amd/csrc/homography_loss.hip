@@ -32,26 +32,6 @@ namespace dr {
 // LDS of a tile never limits the occupancy (160 KB per CU), and 256 keeps the staging (four loads per lane and tile) at ~1 %
 constexpr int kHLTile = 256;
 
-__device__ __forceinline__ float refined_rcp(float w) {
-  const float r = __builtin_amdgcn_rcpf(w);
-  return fma(r, fma(-w, r, 1.0f), r);      // (w = 0 or inf gives NaN here: the caller's `live` is false for those)
-}
-__device__ __forceinline__ double refined_rcp(double w) { return 1.0 / w; }
-
-// out = J^T g for a = adj(h): out[q] = sum_k g[k] d a[k] / d h[q], term by term from adjugate3
-template <typename T>
-__device__ __forceinline__ void adjugate3_vjp(const T (&h)[9], const T (&g)[9], T (&out)[9]) {
-  out[0] = fma(g[4], h[8], fma(-g[5], h[5], fma(-g[7], h[7], g[8] * h[4])));
-  out[1] = fma(-g[1], h[8], fma(g[2], h[5], fma(g[7], h[6], -(g[8] * h[3]))));
-  out[2] = fma(g[1], h[7], fma(-g[2], h[4], fma(-g[4], h[6], g[5] * h[3])));
-  out[3] = fma(-g[3], h[8], fma(g[5], h[2], fma(g[6], h[7], -(g[8] * h[1]))));
-  out[4] = fma(g[0], h[8], fma(-g[2], h[2], fma(-g[6], h[6], g[8] * h[0])));
-  out[5] = fma(-g[0], h[7], fma(g[2], h[1], fma(g[3], h[6], -(g[5] * h[0]))));
-  out[6] = fma(g[3], h[5], fma(-g[4], h[2], fma(-g[6], h[4], g[7] * h[1])));
-  out[7] = fma(-g[0], h[5], fma(g[1], h[2], fma(g[6], h[3], -(g[7] * h[0]))));
-  out[8] = fma(g[0], h[4], fma(-g[1], h[1], fma(-g[3], h[3], g[4] * h[0])));
-}
-
 template <typename T, bool kGrad>
 __global__ __launch_bounds__(64) void homography_loss_kernel(const T *__restrict__ matches, const uint8_t *__restrict__ mask,
                                                              const T *__restrict__ models, const uint8_t *__restrict__ keep,

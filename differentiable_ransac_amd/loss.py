@@ -1,7 +1,8 @@
 """The training losses that follow the hot path: MatchLoss and PoseLoss for the two-view drivers,
 RegistrationLoss for the 3-D registration driver, HomographyLoss for the homography driver (with the evaluation metrics
 registration_errors and homography_errors) and, at the end, PnPLoss and PnPExpectedLoss (DSAC) for the absolute-pose driver and
-RegistrationExpectedLoss, the same expected loss on the registration driver's hypotheses.
+RegistrationExpectedLoss and HomographyExpectedLoss, the same expected loss on the registration and the homography drivers'
+hypotheses.
 
 MatchLoss -- the clamped symmetric-epipolar training loss of the reference (loss.py:107-153), on the fused kernel
 `dr_episym_fwd/bwd`.
@@ -252,27 +253,36 @@ _RTE_EPS2 = 1e-24
 
 
 class _ExpectedLoss(object):
-    """What PnPExpectedLoss and RegistrationExpectedLoss share: the expected pose error of the hypotheses under a soft-max of their
-    soft inlier scores, on the [P,M,4,4] pose layout of both families.  A subclass names its score op and its defaults.
+    """What PnPExpectedLoss, RegistrationExpectedLoss and HomographyExpectedLoss share: the expected error of the hypotheses under a
+    soft-max of their soft inlier scores.  A subclass names its score op and its defaults, and says which models are usable
+    (`_usable`) and what their errors against the ground truth are (`_errors`).
 
         score[p,m] = the family's soft score: sum over the scored points of sigmoid(beta (1 - d2 / threshold^2))
         probs[p,:] = softmax(alpha score[p,:] / N_p) over the usable slots, N_p = the number of scored points; 0 elsewhere
-        l[p,m]     = min(max(RRE in degrees, trans_weight RTE), max_loss) against gt_pose            (pnp_pose_errors)
+        l[p,m]     = the family's error of model m against the pair's ground truth, at most max_loss
         loss       = mean over the pairs of sum_m probs l
 
-    A slot is usable if keep holds it and its model is finite.  A pair without a usable slot contributes 0 and passes no gradient."""
+    A slot is usable if keep holds it and the family calls its model usable.  A pair without a usable slot contributes 0 and passes
+    no gradient."""
     _score_op = None                                          # the name of the family's score in ops (looked up at the call)
     _tail_f64 = False                                         # everything behind the scores in f64 whatever their type (below)
 
-    def __init__(self, threshold, beta, alpha, trans_weight, max_loss):
-        self.threshold, self.beta, self.alpha = threshold, float(beta), float(alpha)
-        self.trans_weight, self.max_loss = float(trans_weight), float(max_loss)
+    def __init__(self, threshold, beta, alpha, max_loss):
+        self.threshold, self.beta, self.alpha, self.max_loss = threshold, float(beta), float(alpha), float(max_loss)
         self.per_pair = self.probs = self.scores = None       # of the last call (detached)
 
-    def _forward(self, models, matches, gt_pose, keep, mask):
+    def _usable(self, models):
+        """models [P,M,r,c] -> [P,M] bool: the slots whose model the family's score kernel evaluates"""
+        raise NotImplementedError
+
+    def _errors(self, models, gt):
+        """models [P,M,r,c] (every slot usable), gt [P,r,c], both in the tail's type -> l [P,M], differentiable w.r.t. the models"""
+        raise NotImplementedError
+
+    def _forward(self, models, matches, gt_model, keep, mask):
         scores = getattr(ops, self._score_op)(matches, models, self.threshold, self.beta, mask, keep)
         P, M = scores.shape
-        usable = torch.isfinite(models[:, :, :3]).all(-1).all(-1)
+        usable = self._usable(models)
         if keep is not None:
             usable = usable & keep
         # f32 logits of alpha score / N ~ 60 carry 2e-6 each, and a slot's probability and its whole gradient row carry that RELATIVE
@@ -290,16 +300,30 @@ class _ExpectedLoss(object):
         e = torch.where(usable, torch.exp(logits - top), torch.zeros_like(logits))
         probs = e / e.sum(1, keepdim=True).clamp(min=torch.finfo(e.dtype).tiny)
         # an unusable slot's model (possibly NaN) is replaced BEFORE the errors: a NaN behind a where() would still poison its gradient
-        eye = torch.eye(4, device=models.device, dtype=models.dtype)
-        errors = pnp_pose_errors(torch.where(usable[:, :, None, None], models, eye).to(wide), gt_pose.to(wide), self.trans_weight,
-                                 self.max_loss)
+        eye = torch.eye(models.shape[-1], device=models.device, dtype=models.dtype)
+        errors = self._errors(torch.where(usable[:, :, None, None], models, eye).to(wide), gt_model.to(wide))
         per_pair = (probs * errors).sum(1).to(dt)
         probs = probs.to(dt)
         self.per_pair, self.probs, self.scores = per_pair.detach(), probs.detach(), scores.detach()
         return per_pair.mean()
 
 
-class PnPExpectedLoss(_ExpectedLoss):
+class _PoseExpectedLoss(_ExpectedLoss):
+    """The two families on the [P,M,4,4] pose layout: a model is usable if its twelve entries are finite, and its error is
+    l = min(max(RRE in degrees, trans_weight RTE), max_loss) against gt_pose (pnp_pose_errors)."""
+
+    def __init__(self, threshold, beta, alpha, trans_weight, max_loss):
+        super().__init__(threshold, beta, alpha, max_loss)
+        self.trans_weight = float(trans_weight)
+
+    def _usable(self, models):
+        return torch.isfinite(models[:, :, :3]).all(-1).all(-1)
+
+    def _errors(self, models, gt):
+        return pnp_pose_errors(models, gt, self.trans_weight, self.max_loss)
+
+
+class PnPExpectedLoss(_PoseExpectedLoss):
     """The DSAC / DSAC* training loss on ransac.BatchedPnP.hypotheses: the expected pose error of the hypotheses under a soft-max of
     their soft inlier scores.  It needs no ground-truth inlier mask, weights a hypothesis by how many points agree with it, and gives
     a gradient to `matches` -- whose 3-D column is a network output in scene-coordinate regression -- through the minimal solver (the
@@ -332,7 +356,7 @@ class PnPExpectedLoss(_ExpectedLoss):
     __call__ = forward
 
 
-class RegistrationExpectedLoss(_ExpectedLoss):
+class RegistrationExpectedLoss(_PoseExpectedLoss):
     """The DSAC training loss on ransac.BatchedRegistration(train=True): PnPExpectedLoss's definition on the registration family's
     soft score (ops.registration_soft_score, d2 = |R p + t - q|^2).  Unlike RegistrationLoss it needs no ground-truth inlier mask,
     weights a hypothesis by how many correspondences agree with it instead of averaging the kept ones equally, and gives a gradient
@@ -361,5 +385,128 @@ class RegistrationExpectedLoss(_ExpectedLoss):
         all), mask [P,N] bool (the points that are scored; None = all) -> scalar loss.  The per-pair values, the probabilities and the
         scores of the call stay on the object as .per_pair [P], .probs [P,M], .scores [P,M], detached."""
         return self._forward(models, matches, gt_pose, keep, mask)
+
+    __call__ = forward
+
+
+_CORNER_EPS2 = 1e-12
+
+
+def _det3(m):
+    return (m[..., 0, 0] * (m[..., 1, 1] * m[..., 2, 2] - m[..., 1, 2] * m[..., 2, 1])
+            - m[..., 0, 1] * (m[..., 1, 0] * m[..., 2, 2] - m[..., 1, 2] * m[..., 2, 0])
+            + m[..., 0, 2] * (m[..., 1, 0] * m[..., 2, 1] - m[..., 1, 1] * m[..., 2, 0]))
+
+
+def _two_sum(a, b):
+    s = a + b
+    bb = s - a
+    return s, (a - (s - bb)) + (b - bb)
+
+
+def _two_prod(a, b):
+    """a b = p + e exactly (Dekker's product on Veltkamp's split: torch has no fused multiply-add to ask the remainder of)"""
+    def split(x):
+        c = 134217729.0 * x
+        hi = c - (c - x)
+        return hi, x - hi
+    p = a * b
+    (ah, al), (bh, bl) = split(a), split(b)
+    return p, ((ah * bh - p) + ah * bl + al * bh) + al * bl
+
+
+def _corner_images(H, corners):
+    """H [...,3,3], corners [4,3] = (x, y, 1), f64 -> (t, t_lo, w): the images H (x, y, 1)_xy / w of the corners as hi + lo
+    [...,4,2] and w [...,4] (replaced by 1 where it is not positive, BEFORE the division).  Every linear form is summed error-free
+    and the quotient is corrected by its remainder: an image of hundreds of pixels is good to an eps of an eps of itself."""
+    def form(r):                                           # H[r,0] x + H[r,1] y + H[r,2]
+        p0, e0 = _two_prod(H[..., None, r, 0], corners[:, 0])
+        p1, e1 = _two_prod(H[..., None, r, 1], corners[:, 1])
+        s, es0 = _two_sum(p0, p1)
+        hi, es1 = _two_sum(s, H[..., None, r, 2].expand_as(s))
+        return hi, (e0 + e1) + (es0 + es1)
+    (x, xl), (y, yl), (w, wl) = form(0), form(1), form(2)
+    back = ~(w > 0)
+    w, wl = torch.where(back, torch.ones_like(w), w), torch.where(back, torch.zeros_like(wl), wl)
+
+    def quotient(n, nl):
+        q = n / w
+        p, e = _two_prod(q, w)
+        return q, (((n - p) - e) + (nl - q * wl)) / w
+    (tx, txl), (ty, tyl) = quotient(x, xl), quotient(y, yl)
+    return torch.stack((tx, ty), -1), torch.stack((txl, tyl), -1), torch.where(back, torch.zeros_like(w), w)
+
+
+def homography_corner_errors(models, gt_H, size, max_loss):
+    """models [P,M,3,3] (finite, det != 0), gt_H [P,3,3], size = (h, w) of the first image (homography_errors' convention) -> l [P,M] =
+    min(mean corner error in pixels, max_loss), differentiable w.r.t. the models: plain torch on [P,M], what pnp_pose_errors is for
+    poses.  The corner error is homography_errors' -- the mean over the corners (0, 0), (w, 0), (w, h), (0, h) of the distance between
+    their images under the two homographies -- with each distance as sqrt(|d|^2 + 1e-12) (smooth at a zero difference: within a
+    millionth of a pixel of it the direction d / |d| of the plain norm's gradient is made of roundings).  A model that sends any of
+    the four corners to w <= 0 under the det > 0 sign (the sign the score kernels evaluate it under) maps the image through infinity:
+    it takes l = max_loss and no gradient; the division is guarded by a where() BEFORE it, so no NaN reaches a gradient.
+    d is the difference of two images of hundreds of pixels and, for a good hypothesis, a fraction of a pixel itself; its direction
+    d / |d| is the whole gradient, and in plain f64 it would carry 1e-13 / |d|, more than an ulp of the inputs moves it.  So the VALUE of d
+    is formed in f64 beyond its precision whatever the type of the models (_corner_images: hi + lo images, differenced exactly),
+    while its derivative, which cancels nothing, is autograd's of the plain expression."""
+    h, w = float(size[0]), float(size[1])
+    corners = torch.tensor([[0.0, 0.0, 1.0], [w, 0.0, 1.0], [w, h, 1.0], [0.0, h, 1.0]], dtype=models.dtype, device=models.device)
+    det = _det3(models.detach())
+    sign = torch.where(det < 0, -torch.ones_like(det), torch.ones_like(det))
+    y = torch.einsum("pmij,cj->pmci", models * sign[..., None, None], corners)         # [P,M,4,3]
+    front = y[..., 2] > 0
+    yw = torch.where(front, y[..., 2], torch.ones_like(y[..., 2]))
+    g = torch.einsum("pij,cj->pci", gt_H.to(models.dtype), corners)                    # [P,4,3]
+    d = y[..., :2] / yw[..., None] - (g[..., :2] / g[..., 2:])[:, None]
+    with torch.no_grad():
+        c64 = corners.double()
+        t, tl, tw = _corner_images((models * sign[..., None, None]).double(), c64)
+        u, ul, _ = _corner_images(gt_H.double()[:, None], c64)
+        s, e = _two_sum(t, -u.expand_as(t))
+        exact = (s + (e + (tl - ul))).to(models.dtype)
+        front = front & (tw > 0)
+    d = d + (torch.where(front[..., None], exact, d) - d).detach()
+    err = torch.sqrt((d * d).sum(-1) + _CORNER_EPS2).mean(-1).clamp(max=max_loss)
+    return torch.where(front.all(-1), err, torch.full_like(err, max_loss))
+
+
+class HomographyExpectedLoss(_ExpectedLoss):
+    """The DSAC training loss on ransac.BatchedHomography(train=True): the expected corner error of the hypotheses under a soft-max of
+    their soft inlier scores (ops.homography_soft_score, d2 = the squared symmetric transfer error).  Unlike HomographyLoss it needs
+    no ground-truth inlier mask, weights a hypothesis by how many matches agree with it instead of averaging the kept ones equally,
+    and gives a gradient to `matches` through the minimal solver (the models) and through the scores.
+
+        score[p,m] = ops.homography_soft_score: sum over the scored points of sigmoid(beta (1 - d2 / threshold^2))
+        probs[p,:] = softmax(alpha score[p,:] / N_p) over the usable slots, N_p = the number of scored points; 0 elsewhere
+        l[p,m]     = min(mean corner error in pixels of H_m against gt_H, max_loss)                  (homography_corner_errors)
+        loss       = mean over the pairs of sum_m probs l
+
+    A slot is usable if keep holds it, its model is finite and det != 0 (the score kernel's usable set).  A usable model that sends a
+    corner of the image to w <= 0 takes l = max_loss and no gradient through l.  A pair without a usable slot contributes 0 and passes
+    no gradient.  `size` = (h, w) of the first image, homography_errors' convention; the threshold is the driver's inlier distance in
+    pixels.  Defaults: beta = 5 and alpha = 100 are PnPExpectedLoss's (DSAC*'s, restated in units of the threshold), max_loss = 100
+    pixels is DSAC*'s clamp of 100 carried to this family's unit; they are stated, not tuned here.  What follows the scores (the
+    soft-max, the corner errors, the sums: [P,M]-sized) and its backward run in f64 whatever the type of the inputs
+    (_ExpectedLoss._forward says why); the results and the gradients are rounded to that type once."""
+
+    _score_op = "homography_soft_score"
+    _tail_f64 = True
+
+    def __init__(self, threshold, size, beta=5.0, alpha=100.0, max_loss=100.0):
+        super().__init__(threshold, beta, alpha, max_loss)
+        self.size = (float(size[0]), float(size[1]))
+
+    def _usable(self, models):
+        det = _det3(models)
+        return torch.isfinite(models).all(-1).all(-1) & torch.isfinite(det) & (det != 0)
+
+    def _errors(self, models, gt):
+        return homography_corner_errors(models, gt, self.size, self.max_loss)
+
+    def forward(self, models, matches, gt_H, keep=None, mask=None):
+        """models [P,M,3,3], matches [P,N,4] (they MAY require grad), gt_H [P,3,3], keep [P,M] bool (e.g. the driver's keep; None =
+        all), mask [P,N] bool (the points that are scored; None = all) -> scalar loss.  The per-pair values, the probabilities and the
+        scores of the call stay on the object as .per_pair [P], .probs [P,M], .scores [P,M], detached."""
+        return self._forward(models, matches, gt_H, keep, mask)
 
     __call__ = forward

@@ -2101,6 +2101,20 @@ def registration_soft_score(matches, models, threshold, beta: float = 5.0, mask=
     return _soft_score(_REGISTRATION, "registration_soft_score", matches, models, threshold, beta, mask, keep)
 
 
+def homography_soft_score(matches, models, threshold, beta: float = 5.0, mask=None, keep=None):
+    """The differentiable soft-inlier score (DSAC) of every homography on every match: matches [P,N,4] = (x1, y1, x2, y2), models
+    [P,M,3,3], threshold = the inlier DISTANCE in pixels (float or [P]), beta > 0, mask [P,N] bool | None (the points that are scored),
+    keep [P,M] bool | None -> scores [P,M] = sum over the scored points of sigmoid(beta (1 - d2 / threshold^2)), d2 the squared
+    symmetric transfer error of the score kernels and of HomographyLoss (y = H (x1, 1), z = adj(H) (x2, 1) under the det > 0 sign,
+    d2 = |x2 - y_xy / y_w|^2 + |x1 - z_xy / z_w|^2); a point behind either camera (y_w <= 0 or z_w <= 0) or with
+    beta (1 - d2 / threshold^2) < -40 adds nothing (include/dransac.h states the rules).  The score does not depend on the scale or
+    the sign of a model.  A slot keep drops, a kept model with a non-finite entry or a zero or non-finite determinant and a pair whose
+    threshold is not > 0 score 0.  Differentiable (once) w.r.t. `models`, and w.r.t. `matches` when they require grad: the second pass
+    over the grid runs only then.  No gradient for threshold, beta, mask or keep.  f32 and f64; nothing synchronises or reads back,
+    so the op can be captured in a HIP graph."""
+    return _soft_score(_HOMOGRAPHY, "homography_soft_score", matches, models, threshold, beta, mask, keep)
+
+
 # ------------------------------------------------------------------------------------------ PoseLoss pose error (8(f) rank 3)
 class _PoseError(torch.autograd.Function):
     @staticmethod

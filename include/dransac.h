@@ -883,6 +883,46 @@ int dr_registration_soft_score_bwd_f64(const double *matches, const uint8_t *mas
                                        double *grad_models, double *grad_matches, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The differentiable soft-inlier score of the homography path (ops.homography_soft_score, loss.HomographyExpectedLoss): the DSAC
+ * score of every homography on every match, with a reverse pass to the models and to the matches.  matches [P,N,4] = (x1, y1, x2,
+ * y2), models [P,M,9], thr2 [P], mask [P,N] (the points that are scored; NULL = all), keep [P,M] (NULL = all models) as for
+ * dr_homography_loss_*; beta > 0 by value.  With the loss's residual,
+ *     h = sign(det H) H,  A = adj(H),  y = h (x1, 1),  z = A (x2, 1),  e = x2 - y_xy / y_w,  f = x1 - z_xy / z_w:
+ *     d2[p,m,n] = |e|^2 + |f|^2,   a = beta (1 - d2 / thr2[p]),   live = y_w > 0 and z_w > 0 and d2 finite and a >= -40
+ *     w = live ? 1 / (1 + exp(-a)) : 0,                            scores[p,m] = sum_{n in mask} w[p,m,n]
+ * (weight 1/2 at the threshold, 1 / (1 + exp(-beta)) at zero error; the SQUARED error, the package's convention; the score does not
+ * depend on the scale or the sign of a model).  The cutoff a < -40 (w < 4.3e-18) is part of the definition, as for
+ * dr_pnp_soft_score.  With g = grad_scores[p,m] (-beta / thr2[p]) w (1 - w) per live term, t = y_xy / y_w,
+ * d d2 / d y = (2 / y_w) (-e_0, -e_1, e . t), and the same for z, f and A:
+ *     grad_models[p,m]  = sign(det H) sum_n g (d d2 / d y (x1, 1)^T + J_adj(h)^T [d d2 / d z (x2, 1)^T])   over the masked points
+ *     grad_matches[p,n] = sum_m g (2 f + h[:, :2]^T d d2 / d y,  2 e + A[:, :2]^T d d2 / d z)               over the kept models
+ * A slot keep drops is never read (score 0, gradient exactly 0, its model and its grad_scores may be NaN); a kept model with a
+ * non-finite entry, with det == 0 or with a non-finite det scores 0 and passes exact zeros to itself and to the points; a thr2[p]
+ * that is not > 0 (NaN included) gives the pair score 0 and zero gradients; a point outside the mask gets exact zeros.  Every output
+ * element is written.  No floating-point atomics, no workspace, and one order for every sum that depends on (P, M, N) alone: a
+ * repeated launch gives the same bits.  e and f are formed beyond the type's precision and rounded once (f32: adj(H), y, z, the
+ * reciprocals and the quotients in f64; f64: every linear form and adjugate entry as a compensated hi + lo, the quotient corrected
+ * by its remainder): their cancellation costs no digits.  1 - w is formed as exp(-a) w.  The gradients are accumulated in the type
+ * of the inputs, the score with a compensated (TwoSum) sum in it.  P <= 65535 and P M < 2^22.  No gradient for thr2 or beta.
+ *
+ *   dr_homography_soft_score       scores [P,M]: one lane per model, the points in ascending order.
+ *   dr_homography_soft_score_bwd   grad_scores [P,M] -> grad_models [P,M,9] (the forward's mapping; the two outer-product sums apart,
+ *     the adjugate's transposed Jacobian applied once per model) and, unless grad_matches is NULL, grad_matches [P,N,4] by a second
+ *     launch with the transposed mapping (one lane per point; the models in tiles of 256, every eighth of a tile summed by its own
+ *     wave, the eight partial sums added in order).  Both recompute the residuals.
+ * ------------------------------------------------------------------------------------------ */
+int dr_homography_soft_score_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep,
+                                 const float *thr2, float beta, int P, int M, int N, float *scores, void *stream);
+int dr_homography_soft_score_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                 const double *thr2, double beta, int P, int M, int N, double *scores, void *stream);
+int dr_homography_soft_score_bwd_f32(const float *matches, const uint8_t *mask, const float *models, const uint8_t *keep,
+                                     const float *thr2, float beta, const float *grad_scores, int P, int M, int N,
+                                     float *grad_models, float *grad_matches, void *stream);
+int dr_homography_soft_score_bwd_f64(const double *matches, const uint8_t *mask, const double *models, const uint8_t *keep,
+                                     const double *thr2, double beta, const double *grad_scores, int P, int M, int N,
+                                     double *grad_models, double *grad_matches, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * K5  train-mode best-of-S selection    RANSAC.__call__, ransac.py:87-96
  *   chosen[p,b] = models[p,b,argmin_s ||models[p,b,s] - gt[p]||_F]; invalid slots (valid == 0) are
  *   skipped; which [P*B] int32 (-1 when no slot is valid; chosen = eye(3) then).
