@@ -137,6 +137,18 @@ def ptr(t: Optional[torch.Tensor]) -> c_void_p:
     return c_void_p(t.data_ptr())
 
 
+def aligned(t: Optional[torch.Tensor], align: Optional[int] = None) -> Optional[torch.Tensor]:
+    """`t` itself when its first byte sits on a multiple of `align` (default: four elements, the widest vector a kernel reads
+    a row with), a fresh copy otherwise: a contiguous view may start anywhere inside a larger allocation
+    (`packed[s:e]`, `flat[1:1 + n].view(...)`), and the kernels that read an input as float4 / float2 have no scalar form.
+    Only for tensors a launch READS: a copy of a buffer that a launch writes would take the result with it."""
+    if t is None:
+        return None
+    if not t.is_contiguous() or t.data_ptr() % (align or 4 * t.element_size()) == 0:      # (ptr() refuses a strided tensor)
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def _launch_device() -> Optional[int]:
     devs = _devices()
     if len(devs) > 1:
@@ -191,5 +203,5 @@ def call(name: str, *args) -> None:
     check(status, name)
 
 
-__all__ = ["lib", "check", "ptr", "stream", "suffix", "scalar", "call", "entries", "parse_header", "c_pointer", "DransacError",
+__all__ = ["lib", "check", "ptr", "aligned", "stream", "suffix", "scalar", "call", "entries", "parse_header", "c_pointer", "DransacError",
            "LIB_PATH", "HEADER_PATH", "c_int", "c_uint64", "c_float", "c_double", "c_void_p"]

@@ -65,10 +65,11 @@ template <> __device__ __forceinline__ double gumbel_from_bits_t<double>(uint32_
 template <typename T>
 __device__ __forceinline__ void load_group(const GumbelArgs<T> &a, int p, int b, int q, T g[4], T noise[4]) {
   const int n0 = 4 * q;
-  const bool full = (n0 + 3 < a.N) && ((a.N & 3) == 0);   // 16-byte aligned, fully inside the row
+  const bool full = (n0 + 3 < a.N) && ((a.N & 3) == 0);   // fully inside the row, at a multiple of 16 bytes from the tensor's base
+  // (the base itself may sit anywhere: a caller may pass a view into a larger buffer -- then element by element)
   if (a.gumbel) {
     const T *src = a.gumbel + ((size_t)p * a.B + b) * a.N + n0;
-    if (full && sizeof(T) == 4) {
+    if (full && sizeof(T) == 4 && (reinterpret_cast<uintptr_t>(a.gumbel) & 15) == 0) {
       const float4 v = *reinterpret_cast<const float4 *>(src);
       noise[0] = v.x; noise[1] = v.y; noise[2] = v.z; noise[3] = v.w;
     } else {
@@ -85,7 +86,7 @@ __device__ __forceinline__ void load_group(const GumbelArgs<T> &a, int p, int b,
   if (!a.logits) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) l[j] = T(1);
-  } else if (full && sizeof(T) == 4) {
+  } else if (full && sizeof(T) == 4 && (reinterpret_cast<uintptr_t>(a.logits) & 15) == 0) {
     const float4 v = *reinterpret_cast<const float4 *>(a.logits + (size_t)p * a.N + n0);
     l[0] = v.x; l[1] = v.y; l[2] = v.z; l[3] = v.w;
   } else {
@@ -966,7 +967,10 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
   dim3 block(kRowsPerBlock * 64);
   const bool soft = y_sel != nullptr;   // the entry points have checked: y_sel and lse both given, or neither (then no dense outputs)
   if constexpr (sizeof(T) == 4) {
-    if (logits && !gumbel && tau == T(1) && (N & 3) == 0 && N <= 4 * 64 * kFastGroups && !y_soft && !ret && !gumbel_out) {
+    // the register and the long-row kernels read the rows as float4: N % 4 == 0 AND a 16-byte aligned base (a caller may pass a
+    // view that starts inside a larger buffer: the general kernel serves it, element by element)
+    const bool rows16 = (N & 3) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
+    if (logits && !gumbel && tau == T(1) && rows16 && N <= 4 * 64 * kFastGroups && !y_soft && !ret && !gumbel_out) {
       const char *name = "gumbel_topk_fast_kernel";
       if (race_ws && !race_ready)
         if (int rc = launch(name, gumbel_race_weights_kernel, dim3(P), 256, st, (const float *)logits, N, P, race_ws)) return rc;
@@ -979,7 +983,7 @@ int gumbel_fwd_launch(const T *logits, const T *gumbel, uint64_t seed, T tau, in
     }
     // measured against the general two-pass kernel: 50 000 x 2048 rows, k = 3: 226 -> 113 us; 4096 x 32 768 rows, k = 5: 196 -> 178 us;
     // k = 8 lists cost what the second pass costs (256 vs 250 us at N = 20 000) -> the general kernel keeps k > 5
-    if (logits && !gumbel && tau == T(1) && (N & 3) == 0 && N > 4 * 64 * kFastGroups && k <= 5 && !y_soft && !ret &&
+    if (logits && !gumbel && tau == T(1) && rows16 && N > 4 * 64 * kFastGroups && k <= 5 && !y_soft && !ret &&
         !gumbel_out) {
       const uint32_t *tb = nullptr;
       const float *Tp = nullptr;
@@ -1418,13 +1422,15 @@ int dr_gumbel_topk_gather_soft_f32(const float *logits, const float *matches, ui
                                    void *stream) {
   const float *y_soft = nullptr, *ret = nullptr;
   DR_REQUIRE(logits && matches && samples && y_sel && lse, "null pointer");
-  DR_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(samples) & 15) == 0, "16-byte alignment");
   DR_REQUIRE((reinterpret_cast<uintptr_t>(race_ws) & 15) == 0, "workspace alignment");
   DR_GUMBEL_CHECK();
+  // the fused gather moves float4: views that do not start on 16 bytes take the sampler + gather launches (the same values)
+  const bool fuse = ((reinterpret_cast<uintptr_t>(matches) | reinterpret_cast<uintptr_t>(samples)) & 15) == 0;
   bool gathered = false;
   if (int rc = dr::gumbel_fwd_launch<float>(logits, nullptr, seed, tau, P, B, N, k, idx, y_sel, lse, nullptr, nullptr, nullptr,
-                                            (hipStream_t)stream, seed_dev, reinterpret_cast<const float4 *>(matches),
-                                            reinterpret_cast<float4 *>(samples), &gathered, nullptr, dr::PairGate(), 0, race_ws, false))
+                                            (hipStream_t)stream, seed_dev, fuse ? reinterpret_cast<const float4 *>(matches) : nullptr,
+                                            fuse ? reinterpret_cast<float4 *>(samples) : nullptr, &gathered, nullptr, dr::PairGate(), 0,
+                                            race_ws, false))
     return rc;
   if (gathered) return 0;
   return dr::launch("gather_fwd_kernel", dr::gather_fwd_kernel<float>, dim3((B * k + 255) / 256, P), 256, stream, matches, idx, y_sel, N,
@@ -1461,15 +1467,17 @@ int dr_gumbel_topk_gather_f32(const float *logits, const float *matches, uint64_
   DR_REQUIRE((reinterpret_cast<uintptr_t>(race_ws) & 15) == 0, "workspace alignment");
   const float *y_sel = nullptr, *lse = nullptr, *y_soft = nullptr, *ret = nullptr;
   DR_REQUIRE(logits && matches && samples, "null pointer");
-  DR_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(samples) & 15) == 0, "16-byte alignment");
   DR_GUMBEL_CHECK();
+  // the fused gather moves float4: views that do not start on 16 bytes take the sampler + gather launches (the same values)
+  const bool fuse = ((reinterpret_cast<uintptr_t>(matches) | reinterpret_cast<uintptr_t>(samples)) & 15) == 0;
   dr::PairGate gate;
   gate.iters = gate_iters;
   gate.max_iters = gate_max_iters;
   bool gathered = false;
   if (int rc = dr::gumbel_fwd_launch<float>(logits, nullptr, seed, tau, P, B, N, k, idx, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                            (hipStream_t)stream, seed_dev, reinterpret_cast<const float4 *>(matches),
-                                            reinterpret_cast<float4 *>(samples), &gathered, nullptr, gate, sub, race_ws, race_ready != 0))
+                                            (hipStream_t)stream, seed_dev, fuse ? reinterpret_cast<const float4 *>(matches) : nullptr,
+                                            fuse ? reinterpret_cast<float4 *>(samples) : nullptr, &gathered, nullptr, gate, sub, race_ws,
+                                            race_ready != 0))
     return rc;
   if (gathered) return 0;
   return dr::launch("gather_fwd_kernel", dr::gather_fwd_kernel<float>, dim3((B * k + 255) / 256, P), 256, stream, matches, idx, nullptr,

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kRThreads) void rigid_residual_kernel(const T *__re
   const int mcount = min(kRModels, M - m0);
   const T *pt = pts + (size_t)p * N * 6;
   const T *md = models + ((size_t)p * M + m0) * 16;
-  const bool row_aligned = (N % 8) == 0;
+  const bool row_aligned = (N % 8) == 0 && (reinterpret_cast<uintptr_t>(masks) % 8) == 0;   // (a caller may pass a slice of a larger buffer)
   for (int i = tid; i < (kRThreads / 64) * kRModels; i += kRThreads) (&part[0][0])[i] = T(0);
   __syncthreads();
   const int c_begin = blockIdx.y * chunks_per_block;
@@ -314,7 +314,9 @@ int rigid_residual_launch(const T *pts, const T *models, T threshold, int P, int
                           hipStream_t st, bool sums_zeroed = false) {
   if constexpr (sizeof(T) == 4) {
     // (thresholds below 1e-12 would put `thr - d2` near the bit-6 exponent test's blind spot: general kernel)
-    if (masks && N % 16 == 0 && (reinterpret_cast<uintptr_t>(pts) & 15) == 0 && threshold > T(1e-12)) {
+    // (float4 point loads and 8-byte mask stores: both bases aligned, or the general kernel)
+    if (masks && N % 16 == 0 && (reinterpret_cast<uintptr_t>(pts) & 15) == 0 && (reinterpret_cast<uintptr_t>(masks) & 7) == 0 &&
+        threshold > T(1e-12)) {
       // One block = (pair, model tile, point chunk); every block of a launch takes the same time (tile x chunk evaluations), so
       // the launch takes ceil(blocks / resident blocks) block times: 3 200 blocks on 1 536 resident ones (138 registers: three
       // waves per SIMD, six 2-wave blocks per CU) are THREE rounds for 2.08 rounds of work.  The tile is therefore chosen per

@@ -21,6 +21,11 @@ _RACE_MIN = (32768, 32)      # (rows, pairs) from which the form is chosen autom
 FUSED_SAMPLE_GATHER = True   # False = the two-launch forward / backward of rounds 1-4
 FUSED_MATCH_LOSS = True      # False = the two-pass form of rounds 3-4
 
+# Correspondences and points are read as float4 / float2 by kernels that have no scalar form: a contiguous view that starts inside a
+# larger buffer (`packed[s:e]`, `flat[1:1 + n].view(P, N, 4)`) is copied to an aligned temporary on the way in (L.aligned: the tensor
+# itself whenever it is aligned).  Read-only arguments only; the caller's tensor stays the one autograd saves and differentiates.
+_al = L.aligned
+
 
 def _u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """an optional bool tensor as the bytes the C ABI takes"""
@@ -97,10 +102,10 @@ def msac_score(matches: torch.Tensor, models: torch.Tensor, threshold, want_mask
     if matches.dtype == torch.float32:
         # gate (a later round of a multi-round call): the blocks of terminated pairs (gate = RansacState) return at once, their
         # scores are never looked at (dr_ransac_update skips such pairs)
-        L.call("dr_msac_score_f32", ptr(matches), ptr(models), ptr(v), ptr(thr), P, M, N, ptr(scores), ptr(masks), *_gate_args(gate),
+        L.call("dr_msac_score_f32", ptr(_al(matches)), ptr(models), ptr(v), ptr(thr), P, M, N, ptr(scores), ptr(masks), *_gate_args(gate),
                stream())
         return scores, masks
-    L.call(f"dr_msac_score_{L.suffix(matches.dtype)}", ptr(matches), ptr(models), ptr(v), ptr(thr), P, M, N, ptr(scores), ptr(masks),
+    L.call(f"dr_msac_score_{L.suffix(matches.dtype)}", ptr(_al(matches)), ptr(models), ptr(v), ptr(thr), P, M, N, ptr(scores), ptr(masks),
            stream())
     return scores, masks
 
@@ -124,7 +129,7 @@ def magsac_score(matches: torch.Tensor, models: torch.Tensor, threshold, valid: 
     thr = _thr_tensor(threshold, P, matches)
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_magsac_score_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid), ptr(thr),
+    L.call(f"dr_magsac_score_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(models.contiguous()), _u8_ptr(valid), ptr(thr),
            P, M, N, ptr(scores), ptr(inliers), *_gate_args(gate), stream())
     return scores, inliers
 
@@ -149,7 +154,7 @@ def magsac_irls(state: "RansacState", matches, thr, fundamental: bool, irls_iter
     _check_counter("magsac_irls", "irls_fits", irls_fits, P)
     if weights_ws.shape != (P, N) or weights_ws.dtype != matches.dtype or not weights_ws.is_contiguous():
         raise L.DransacError("magsac_irls: weights_ws must be a contiguous [P,N] tensor of the matches' dtype")
-    L.call(f"dr_magsac_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), P, N, bool(fundamental), int(irls_iters),
+    L.call(f"dr_magsac_irls_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(thr), P, N, bool(fundamental), int(irls_iters),
            ptr(state.best_score), ptr(state.best_model), ptr(weights_ws), ptr(irls_fits), stream())
 
 
@@ -165,7 +170,7 @@ def select_best(matches: torch.Tensor, models: torch.Tensor, scores: torch.Tenso
     best_model = torch.empty((P, 3, 3), device=dev, dtype=dt)
     best_mask = torch.empty((P, N), device=dev, dtype=torch.bool)
     inliers = torch.empty((P,), device=dev, dtype=torch.int32)
-    L.call(f"dr_select_best_{L.suffix(dt)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+    L.call(f"dr_select_best_{L.suffix(dt)}", ptr(_al(matches.contiguous())), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(scores.contiguous()), ptr(thr), P, M, N, ptr(best_idx), ptr(best_score), ptr(best_model), ptr(best_mask), ptr(inliers),
            stream())
     return best_idx, best_score, best_model, best_mask, inliers
@@ -242,7 +247,7 @@ def ransac_update(state: RansacState, matches, models, valid, scores, thr, B: in
     M = models.shape[1]
     if sub_models and M > sub_models * 512:
         raise L.DransacError("ransac_update: at most 512 sub-batches per launch")
-    L.call(f"dr_ransac_update_{L.suffix(matches.dtype)}", ptr(matches), ptr(models.contiguous()), _u8_ptr(valid),
+    L.call(f"dr_ransac_update_{L.suffix(matches.dtype)}", ptr(_al(matches)), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(scores.contiguous()), ptr(thr), P, M, N, B, k, confidence, eps, state.max_iterations, ptr(state.best_score),
            ptr(state.best_model), ptr(state.best_mask), ptr(state.best_inliers), ptr(state.iters), ptr(state.max_iters),
            int(sub_models), stream())
@@ -268,7 +273,7 @@ def local_optimize(state: RansacState, matches, thr, fundamental: bool, lo: int,
     lo_seen [P,10] (matches' dtype) is the per-call snapshot, filled with NaN before the first round; lo_refits [P] int32
     (optional) accumulates the refits run per pair.  One launch, no synchronisation."""
     P, N, mi = _lo_args("local_optimize", 10, state, matches, thr, lo_seen, lo_refits, max_iterations)
-    L.call(f"dr_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr), P, N, bool(fundamental), int(lo),
+    L.call(f"dr_local_opt_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(thr), P, N, bool(fundamental), int(lo),
            int(lo_iters), int(k), confidence, eps, mi, ptr(state.best_score), ptr(state.best_model),
            ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits),
            stream())
@@ -516,6 +521,8 @@ class SampleGather(torch.autograd.Function):
             # dr_gumbel_topk_gather_bwd_f32): same index sets, weights and samples as the two-launch form, bit for bit
             matches, logits = matches.contiguous(), logits.contiguous()
             P, N = logits.shape
+            # (realigned copies for the launch only: what is saved, and what the gradient belongs to, stays the caller's view)
+            lg_in, mt_in = _al(logits), _al(matches)
             r = dict(idx=torch.empty((P, B, k), device=logits.device, dtype=torch.int32),
                      y_sel=torch.empty((P, B, k), device=logits.device, dtype=torch.float32),
                      lse=torch.empty((P, B), device=logits.device, dtype=torch.float32))
@@ -524,7 +531,7 @@ class SampleGather(torch.autograd.Function):
             # reciprocal per element), where its weights prologue pays
             rws = (torch.empty((P, N + 32), device=logits.device, dtype=torch.float32)
                    if K1_RACE_SOFT and race_form_pays(P, B, N, tau) else None)
-            L.call("dr_gumbel_topk_gather_soft_f32", ptr(logits), ptr(matches), *_seed_args(seed), tau, P, B, N, k, ptr(r["idx"]),
+            L.call("dr_gumbel_topk_gather_soft_f32", ptr(lg_in), ptr(mt_in), *_seed_args(seed), tau, P, B, N, k, ptr(r["idx"]),
                    ptr(r["y_sel"]), ptr(r["lse"]), ptr(samples), ptr(rws), stream())
         else:
             r = gumbel_topk(logits, B, k, tau, gumbel, seed)
@@ -547,7 +554,7 @@ class SampleGather(torch.autograd.Function):
         if ctx.fused and not ctx.needs_input_grad[0]:
             P, B, k = idx.shape
             gl = torch.empty_like(logits)
-            L.call("dr_gumbel_topk_gather_bwd_f32", ptr(logits), ptr(matches), *_seed_args(seed), tau, P, B, logits.shape[1], k,
+            L.call("dr_gumbel_topk_gather_bwd_f32", ptr(_al(logits)), ptr(_al(matches)), *_seed_args(seed), tau, P, B, logits.shape[1], k,
                    ptr(idx), ptr(lse), ptr(g_samples.contiguous()), ptr(None if g_w is None else g_w.contiguous()), ptr(gl), stream())
             return None, gl, None, None, None, None, None
         a_sel, gm = gather_bwd(matches, idx, y_sel, g_samples, g_w, want_grad_matches=ctx.needs_input_grad[0])
@@ -661,7 +668,7 @@ def solve_f8_uniform(matches: torch.Tensor, B: int, seed):
     idx = torch.empty((P, B, 8), device=matches.device, dtype=torch.int32)
     models = torch.empty((P, B, 3, 3), device=matches.device, dtype=torch.float32)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call("dr_solve_f8_uniform_f32", ptr(matches.contiguous()), *_seed_args(seed), P, B, N, ptr(idx), ptr(models), ptr(valid),
+    L.call("dr_solve_f8_uniform_f32", ptr(_al(matches.contiguous())), *_seed_args(seed), P, B, N, ptr(idx), ptr(models), ptr(valid),
            stream())
     return idx, models, valid
 
@@ -704,7 +711,7 @@ def solve_rigid_gather(matches: torch.Tensor, idx: torch.Tensor, flag: bool = Tr
     _, B, k = idx.shape
     model = torch.empty((P, B, 4, 4), device=matches.device, dtype=torch.float32)
     valid = torch.empty((P, B), device=matches.device, dtype=torch.bool)
-    L.call("dr_solve_rigid_gather_f32", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, k, bool(flag), ptr(model),
+    L.call("dr_solve_rigid_gather_f32", ptr(_al(matches.contiguous())), ptr(idx.contiguous()), P, B, N, k, bool(flag), ptr(model),
            ptr(None), ptr(None), ptr(None), ptr(valid), ptr(zero_sums), stream())
     return model, valid
 
@@ -719,15 +726,15 @@ def rigid_residual(pts: torch.Tensor, models: torch.Tensor, threshold: float = 0
     if res is not None:
         if pts.dtype != torch.float32 or res.shape != (P, M) or res.dtype != torch.float32:
             raise L.DransacError("rigid_residual: res must be an f32 [P,M] tensor of zeros")
-        L.call("dr_rigid_residual_f32", ptr(pts.contiguous()), ptr(models.contiguous()), threshold, P, M, N, ptr(res), ptr(masks), 1,
+        L.call("dr_rigid_residual_f32", ptr(_al(pts.contiguous(), 8)), ptr(models.contiguous()), threshold, P, M, N, ptr(res), ptr(masks), 1,
                stream())
         return res, masks
     res = torch.empty((P, M), device=pts.device, dtype=pts.dtype)
     if pts.dtype == torch.float32:
-        L.call("dr_rigid_residual_f32", ptr(pts.contiguous()), ptr(models.contiguous()), threshold, P, M, N, ptr(res), ptr(masks), 0,
+        L.call("dr_rigid_residual_f32", ptr(_al(pts.contiguous(), 8)), ptr(models.contiguous()), threshold, P, M, N, ptr(res), ptr(masks), 0,
                stream())
     else:
-        L.call(f"dr_rigid_residual_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()), threshold, P, M, N,
+        L.call(f"dr_rigid_residual_{L.suffix(pts.dtype)}", ptr(_al(pts.contiguous(), 8)), ptr(models.contiguous()), threshold, P, M, N,
                ptr(res), ptr(masks), stream())
     return res, masks
 
@@ -746,7 +753,7 @@ def ransac3d_update(pts: torch.Tensor, models: torch.Tensor, valid: Optional[tor
     out_model = torch.empty((P, 4, 4), device=pts.device, dtype=pts.dtype)
     idx = torch.empty((P,), device=pts.device, dtype=torch.int32)
     mk = None if best_mask is None else best_mask.view(torch.uint8)
-    L.call(f"dr_ransac3d_update_{L.suffix(pts.dtype)}", ptr(pts.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+    L.call(f"dr_ransac3d_update_{L.suffix(pts.dtype)}", ptr(_al(pts.contiguous(), 8)), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(res.contiguous()), threshold, P, M, N, ptr(None if best_res is None else best_res.contiguous()),
            ptr(None if best_model is None else best_model.contiguous()), ptr(out_res), ptr(out_model), ptr(mk), ptr(idx), stream())
     return out_res, out_model, idx
@@ -827,7 +834,7 @@ def _pair_sample_fit(entry: str, side: int, matches, idx, scalars=(), counters=(
     B = idx.shape[1]
     models = torch.empty((P, slots * B, side, side), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, slots * B), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(idx.contiguous()), P, B, N, *scalars, ptr(models),
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(idx.contiguous()), P, B, N, *scalars, ptr(models),
            ptr(valid), *map(ptr, counters), stream())
     return models, valid
 
@@ -839,7 +846,7 @@ def _pair_score(entry: str, matches, models, threshold, valid, want_inliers, thr
     thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
     scores = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
     inliers = torch.empty((P, M), device=matches.device, dtype=torch.int32) if want_inliers else None
-    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid), ptr(thr2), P,
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(models.contiguous()), _u8_ptr(valid), ptr(thr2), P,
            M, N, ptr(scores), ptr(inliers), *(_gate_args(gate) if gated else ()), stream())
     return scores, inliers
 
@@ -849,7 +856,7 @@ def _pair_update(entry: str, state: _PairState, matches, models, valid, scores, 
     P, N, _ = matches.shape
     M = models.shape[1]
     thr2 = thr2_tensor(threshold, P, matches) if thr2 is None else thr2
-    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models.contiguous()), _u8_ptr(valid),
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(models.contiguous()), _u8_ptr(valid),
            ptr(scores.contiguous()), ptr(thr2), P, M, N, int(B), confidence, eps, state.max_iterations, ptr(state.best_score),
            ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)), ptr(state.best_inliers), ptr(state.iters),
            ptr(state.max_iters), stream())
@@ -864,7 +871,7 @@ def _pair_refit(entry: str, side: int, matches, mask, weights):
         raise L.DransacError("the refit mask is [P,N], one flag per point")
     model = torch.empty((P, side, side), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
+    L.call(f"dr_{entry}_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), _u8_ptr(mask),
            ptr(None if weights is None else weights.to(matches.dtype).contiguous()), P, N, ptr(model), ptr(valid), stream())
     return model, valid
 
@@ -875,7 +882,7 @@ def _pair_irls(fam, state: _PairState, matches, thr2, irls_iters: int, irls_fits
     _check_matches(fam, f"{fam.entry}_irls", matches)
     P, N, _ = matches.shape
     _check_counter(f"{fam.entry}_irls", "irls_fits", irls_fits, P)
-    L.call(f"dr_{fam.entry}_irls_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(irls_iters),
+    L.call(f"dr_{fam.entry}_irls_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(thr2), P, N, int(irls_iters),
            ptr(state.best_score), ptr(state.best_model), ptr(irls_fits), stream())
 
 
@@ -920,7 +927,7 @@ def registration_local_optimize(state: RegistrationState, matches, thr2, lo: int
     last visit.  thr2 [P] = threshold^2 (thr2_tensor).  lo_seen [P,17] (matches' dtype) is the per-call snapshot, filled with NaN
     before the first round; lo_refits [P] int32 (optional) accumulates the fits run per pair.  One launch, no synchronisation."""
     P, N, mi = _lo_args("registration_local_optimize", 17, state, matches, thr2, lo_seen, lo_refits, max_iterations)
-    L.call(f"dr_registration_local_opt_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(thr2), P, N, int(lo), int(lo_iters),
+    L.call(f"dr_registration_local_opt_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(thr2), P, N, int(lo), int(lo_iters),
            confidence, eps, mi, ptr(state.best_score), ptr(state.best_model), ptr(state.best_mask.view(torch.uint8)),
            ptr(state.best_inliers), ptr(state.max_iters), ptr(lo_seen), ptr(lo_refits), stream())
 
@@ -966,7 +973,7 @@ def refit_essential(matches: torch.Tensor, mask: Optional[torch.Tensor] = None):
     P, N, _ = matches.shape
     models = torch.empty((P, 10, 3, 3), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P, 10), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_refit_essential_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask), P, N, ptr(models), ptr(valid),
+    L.call(f"dr_refit_essential_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), _u8_ptr(mask), P, N, ptr(models), ptr(valid),
            stream())
     return models, valid
 
@@ -977,7 +984,7 @@ def refit_accept(matches: torch.Tensor, cand: torch.Tensor, cand_valid: Optional
     [P,3,3] IN PLACE where a candidate scores strictly higher (ransac.py:173-185)."""
     P, N, _ = matches.shape
     S = cand.shape[1]
-    L.call(f"dr_refit_accept_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(cand.contiguous()), _u8_ptr(cand_valid),
+    L.call(f"dr_refit_accept_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(cand.contiguous()), _u8_ptr(cand_valid),
            ptr(thr), P, S, N, ptr(best_score), ptr(best_model), stream())
 
 
@@ -989,7 +996,7 @@ def refit_fundamental(matches: torch.Tensor, mask: Optional[torch.Tensor] = None
     valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
     if weights is not None and weights.shape != (P, N):
         raise L.DransacError("refit weights are [P,N], one per point")
-    L.call(f"dr_refit_fundamental_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask),
+    L.call(f"dr_refit_fundamental_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), _u8_ptr(mask),
            ptr(None if weights is None else weights.to(matches.dtype).contiguous()), P, N, ptr(models), ptr(valid), stream())
     return models, valid
 
@@ -1223,7 +1230,7 @@ def _weighted_fit_bwd(ctx, g_model, _gv):
     P, N, _ = m.shape
     gm = torch.empty_like(m) if want_m else None
     gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if want_w else None
-    L.call(f"dr_{ctx.fam.refit}_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w),
+    L.call(f"dr_{ctx.fam.refit}_bwd_{L.suffix(m.dtype)}", ptr(_al(m)), ptr(ctx.mask), ptr(w),
            ptr(g_model.to(m.dtype).reshape(P, *ctx.fam.shape).contiguous()), P, N, ptr(gm), ptr(gw), stream())
     return None, gm, None if gw is None else gw.to(ctx.wdtype), None
 
@@ -1409,7 +1416,7 @@ def refit_pnp(matches: torch.Tensor, mask: Optional[torch.Tensor], init_model: t
         raise L.DransacError(f"refit_pnp: iters must be at least 0, got {iters!r}")
     model = torch.empty((P, 4, 4), device=matches.device, dtype=matches.dtype)
     valid = torch.empty((P,), device=matches.device, dtype=torch.bool)
-    L.call(f"dr_refit_pnp_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), _u8_ptr(mask), ptr(init_model.contiguous()), P, N,
+    L.call(f"dr_refit_pnp_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), _u8_ptr(mask), ptr(init_model.contiguous()), P, N,
            int(iters), ptr(model), ptr(valid), stream())
     return model, valid
 
@@ -1437,7 +1444,7 @@ def _pnp_dlt(m, w, mask):
     P, N, _ = m.shape
     model = torch.empty((P, 4, 4), device=m.device, dtype=m.dtype)
     valid = torch.empty((P,), device=m.device, dtype=torch.bool)
-    L.call(f"dr_pnp_dlt_{L.suffix(m.dtype)}", ptr(m), _u8_ptr(mask), ptr(w), P, N, ptr(model), ptr(valid), stream())
+    L.call(f"dr_pnp_dlt_{L.suffix(m.dtype)}", ptr(_al(m)), _u8_ptr(mask), ptr(w), P, N, ptr(model), ptr(valid), stream())
     return model, valid
 
 
@@ -1465,7 +1472,7 @@ class _WeightedPnP(torch.autograd.Function):
         P, N, _ = m.shape
         model = torch.empty((P, 4, 4), device=m.device, dtype=m.dtype)
         valid = torch.empty((P,), device=m.device, dtype=torch.bool)
-        L.call(f"dr_refit_pnp_weighted_{L.suffix(m.dtype)}", ptr(m), _u8_ptr(mask), ptr(w), ptr(init_model.contiguous()), P, N,
+        L.call(f"dr_refit_pnp_weighted_{L.suffix(m.dtype)}", ptr(_al(m)), _u8_ptr(mask), ptr(w), ptr(init_model.contiguous()), P, N,
                int(iters), ptr(model), ptr(valid), stream())
         # the entry of the backward has no `valid`: a pair without a fit travels as a NaN model, which it answers with exact zeros
         saved = torch.where(valid[:, None, None], model, torch.full_like(model, float("nan")))
@@ -1486,7 +1493,7 @@ class _WeightedPnP(torch.autograd.Function):
         P, N, _ = m.shape
         gm = torch.empty_like(m) if want_m else None
         gw = torch.empty((P, N), device=m.device, dtype=m.dtype) if want_w else None
-        L.call(f"dr_refit_pnp_bwd_{L.suffix(m.dtype)}", ptr(m), ptr(ctx.mask), ptr(w), ptr(model),
+        L.call(f"dr_refit_pnp_bwd_{L.suffix(m.dtype)}", ptr(_al(m)), ptr(ctx.mask), ptr(w), ptr(model),
                ptr(g_model.to(m.dtype).reshape(P, 4, 4).contiguous()), P, N, ptr(gm), ptr(gw), stream())
         return gm, None if gw is None else gw.to(ctx.wdtype), None, None, None
 
@@ -1648,7 +1655,7 @@ class _MsacScore(torch.autograd.Function):
         P, N, _ = matches.shape
         M = models.shape[1]
         gm = torch.empty_like(models)
-        L.call("dr_msac_score_bwd_f32", ptr(matches.contiguous()), ptr(models.contiguous()), ptr(thr), ptr(g_scores.contiguous()), P,
+        L.call("dr_msac_score_bwd_f32", ptr(_al(matches.contiguous())), ptr(models.contiguous()), ptr(thr), ptr(g_scores.contiguous()), P,
                M, N, ptr(gm), stream())
         return None, gm, None, None
 
@@ -1677,7 +1684,7 @@ class _RigidResidual(torch.autograd.Function):
         P, N, _ = pts.shape
         M = models.shape[1]
         gm = torch.empty_like(models)
-        L.call("dr_rigid_residual_bwd_f32", ptr(pts.contiguous()), ptr(models.contiguous()), ptr(g_res.contiguous()), P, M, N, ptr(gm),
+        L.call("dr_rigid_residual_bwd_f32", ptr(_al(pts.contiguous(), 8)), ptr(models.contiguous()), ptr(g_res.contiguous()), P, M, N, ptr(gm),
                stream())
         return None, gm, None
 
@@ -1722,7 +1729,7 @@ def _episym_fwd(matches, mask, models, valid):
     matches, models = matches.contiguous(), models.contiguous()
     mk, v = _u8(mask), _u8(valid)
     sums = torch.empty((P, M), device=matches.device, dtype=matches.dtype)
-    L.call("dr_episym_fwd_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), P, M, N, ptr(sums), stream())
+    L.call("dr_episym_fwd_f32", ptr(_al(matches)), ptr(mk), ptr(models), ptr(v), P, M, N, ptr(sums), stream())
     return matches, models, mk, v, sums
 
 
@@ -1775,7 +1782,7 @@ class _Episym(torch.autograd.Function):
         M = models.shape[1]
         grad = red.grad(g, coef, matches.dtype)
         gm = torch.empty_like(models)   # every slot is written (invalid: 0)
-        L.call(red.bwd, ptr(matches), ptr(mk), ptr(models), ptr(v), *map(ptr, grad), P, M, N, ptr(gm), stream())
+        L.call(red.bwd, ptr(_al(matches)), ptr(mk), ptr(models), ptr(v), *map(ptr, grad), P, M, N, ptr(gm), stream())
         return None, None, None, gm, None
 
 
@@ -1808,7 +1815,7 @@ class _MatchLossFused(torch.autograd.Function):
         per_pair = torch.empty((P,), device=dev, dtype=dt)
         coef = torch.empty((P,), device=dev, dtype=dt)
         mean = torch.empty((), device=dev, dtype=dt)
-        L.call("dr_match_loss_fused_f32", ptr(matches), ptr(mk), ptr(models), ptr(v), P, M, N, ptr(sums), ptr(gun), ptr(per_pair),
+        L.call("dr_match_loss_fused_f32", ptr(_al(matches)), ptr(mk), ptr(models), ptr(v), P, M, N, ptr(sums), ptr(gun), ptr(per_pair),
                ptr(coef), ptr(mean), stream())
         ctx.save_for_backward(gun, coef)
         return mean
@@ -1891,7 +1898,7 @@ def _pair_gt_mask(fam, matches, gt_model, threshold):
         raise L.DransacError(f"{fam.entry}_gt_mask: one ground-truth {fam.gt_noun} [P,{r},{c}] per pair, in the {fam.points}' dtype")
     mask = torch.empty((P, N), device=matches.device, dtype=torch.bool)
     count = torch.empty((P,), device=matches.device, dtype=torch.int32)
-    L.call(f"dr_{fam.entry}_gt_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(gt_model.contiguous()),
+    L.call(f"dr_{fam.entry}_gt_mask_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(gt_model.contiguous()),
            ptr(thr2_tensor(threshold, P, matches)), P, N, ptr(mask.view(torch.uint8)), ptr(count), stream())
     return mask, count
 
@@ -1914,7 +1921,7 @@ def _pair_loss_fwd(fam, matches, mask, models, threshold, keep):
     dev, dt = matches.device, matches.dtype
     sums = torch.empty((P, M), device=dev, dtype=dt)
     per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-    L.call(f"dr_{fam.entry}_loss_fwd_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp),
+    L.call(f"dr_{fam.entry}_loss_fwd_{L.suffix(dt)}", ptr(_al(matches)), ptr(mk), ptr(models), ptr(kp),
            ptr(thr2_tensor(threshold, P, matches)), P, M, N, ptr(sums), ptr(per_pair), ptr(coef), ptr(mean), stream())
     return sums, per_pair, coef, mean
 
@@ -1931,7 +1938,7 @@ class _PairLossFused(torch.autograd.Function):
         sums = torch.empty((P, M), device=dev, dtype=dt)
         gun = torch.empty((P, M, *fam.shape), device=dev, dtype=dt)
         per_pair, coef, mean = torch.empty((P,), device=dev, dtype=dt), torch.empty((P,), device=dev, dtype=dt), torch.empty((), device=dev, dtype=dt)
-        L.call(f"dr_{fam.entry}_loss_fused_{L.suffix(dt)}", ptr(matches), ptr(mk), ptr(models), ptr(kp), ptr(thr2), P, M, N,
+        L.call(f"dr_{fam.entry}_loss_fused_{L.suffix(dt)}", ptr(_al(matches)), ptr(mk), ptr(models), ptr(kp), ptr(thr2), P, M, N,
                ptr(sums), ptr(gun), ptr(per_pair), ptr(coef), ptr(mean), stream())
         ctx.save_for_backward(gun, coef)
         ctx.fam = fam
@@ -2039,7 +2046,7 @@ class _SoftScore(torch.autograd.Function):
     def forward(ctx, matches, models, thr2, beta, mask, keep, entry):
         (P, N, _), M, dt = matches.shape, models.shape[1], matches.dtype
         scores = torch.empty((P, M), device=matches.device, dtype=dt)
-        L.call(f"dr_{entry}_soft_score_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2), L.scalar(dt, beta),
+        L.call(f"dr_{entry}_soft_score_{L.suffix(dt)}", ptr(_al(matches)), ptr(mask), ptr(models), ptr(keep), ptr(thr2), L.scalar(dt, beta),
                P, M, N, ptr(scores), stream())
         ctx.save_for_backward(matches, models, thr2, mask, keep)
         ctx.beta, ctx.entry = beta, entry
@@ -2052,7 +2059,7 @@ class _SoftScore(torch.autograd.Function):
         (P, N, _), M, dt = matches.shape, models.shape[1], matches.dtype
         gm = torch.empty_like(models)
         gx = torch.empty_like(matches) if ctx.needs_input_grad[0] else None
-        L.call(f"dr_{ctx.entry}_soft_score_bwd_{L.suffix(dt)}", ptr(matches), ptr(mask), ptr(models), ptr(keep), ptr(thr2),
+        L.call(f"dr_{ctx.entry}_soft_score_bwd_{L.suffix(dt)}", ptr(_al(matches)), ptr(mask), ptr(models), ptr(keep), ptr(thr2),
                L.scalar(dt, ctx.beta), ptr(g.to(dt).contiguous()), P, M, N, ptr(gm), ptr(gx), stream())
         return gx, gm, None, None, None, None, None
 
@@ -2130,7 +2137,7 @@ class _PoseError(torch.autograd.Function):
         err_t = torch.empty((P, M), device=dev, dtype=dt)
         which = torch.empty((P, M), device=dev, dtype=torch.int32)
         votes = torch.empty((P, M, 4), device=dev, dtype=torch.int32) if want_votes else None
-        L.call(f"dr_pose_error_fwd_{sfx}", ptr(matches), ptr(models), ptr(gt_R), ptr(gt_t), P, M, N, float(distance_threshold),
+        L.call(f"dr_pose_error_fwd_{sfx}", ptr(_al(matches)), ptr(models), ptr(gt_R), ptr(gt_t), P, M, N, float(distance_threshold),
                ptr(err_R), ptr(err_t), ptr(which), ptr(votes), stream())
         ctx.save_for_backward(models, gt_R, gt_t, which)
         ctx.mark_non_differentiable(which)
@@ -2192,6 +2199,6 @@ def recover_pose_mask(matches, models, distance_threshold: float = 50.0):
     M = models.shape[1]
     mask = torch.empty((P, M, N), device=matches.device, dtype=torch.bool)
     which = torch.empty((P, M), device=matches.device, dtype=torch.int32)
-    L.call(f"dr_recover_pose_mask_{L.suffix(matches.dtype)}", ptr(matches.contiguous()), ptr(models), P, M, N,
+    L.call(f"dr_recover_pose_mask_{L.suffix(matches.dtype)}", ptr(_al(matches.contiguous())), ptr(models), P, M, N,
            float(distance_threshold), ptr(which), ptr(mask), stream())
     return mask, which

@@ -776,7 +776,8 @@ class BatchedRANSAC(_SeededDriver):
 
         with torch.no_grad():
             use_K = K1 is not None and not self.fmat
-            matches = matches.contiguous()
+            # (views that start inside a larger buffer -- `packed[s:e]` of ragged pairs -- are realigned ONCE per call, not per launch)
+            matches, logits = ops.L.aligned(matches.contiguous()), ops.L.aligned(logits)
             # device rounds (see `super_hypotheses`): plan[i] batches of B hypotheses in round i, the first of them batch first[i]
             n_batches = rounds if gumbels is None else min(rounds, len(gumbels))
             plan = self.plan(n_batches, dt) if n_batches > 0 else []
@@ -983,7 +984,7 @@ class BatchedRANSAC3D(_SeededDriver):
             return dict(models=torch.cat([o[0] for o in out], 1), keep=torch.cat([o[1] for o in out], 1),
                         residuals=torch.cat([o[2] for o in out], 1), mean_residuals=torch.stack([o[3] for o in out], 1))
         with torch.no_grad():
-            matches = matches.contiguous()
+            matches, logits = ops.L.aligned(matches.contiguous()), ops.L.aligned(logits)
             best, best_model = None, None      # "no state yet": the first update writes it (no fill / copy launches per call)
             best_mask = torch.empty((P, N), device=matches.device, dtype=torch.bool) if self.keep_masks else None
             masks = None
@@ -1084,6 +1085,7 @@ class _PairStateDriver(_SeededDriver):
         if self.train:
             return self._train_rounds(matches, logits, gumbels, rounds)
         with torch.no_grad():
+            logits = ops.L.aligned(logits)      # (a view that starts inside a larger buffer: realigned once per call, as c.matches is)
             c = self._begin(matches, rounds)
             c.order = c.growth = None
             if self.sampling == "prosac":      # the ranking of this call's logits and the growth table, once for all its rounds
@@ -1116,7 +1118,7 @@ class _PairStateDriver(_SeededDriver):
         if self._device_termination and rounds > 16:      # (max_iterations / ransac_batch_size assigned after the switch)
             raise ValueError("device_termination issues every round: at most 16 rounds per call")
         P, N, _ = matches.shape
-        matches = matches.contiguous()
+        matches = ops.L.aligned(matches.contiguous())
         st = self._State(P, N, self.max_iterations, matches.device, matches.dtype)
         c = types.SimpleNamespace(matches=matches, P=P, N=N, st=st, thr2=ops.thr2_tensor(self.threshold, P, matches))
         c.lo_seen = c.lo_refits = None

@@ -118,7 +118,7 @@ int dr_prosac_sample(const int32_t *order, const int64_t *growth, uint64_t seed,
 int dr_seed_next_n(uint64_t *state, uint64_t *seeds_out, int n, void *stream);
 
 /* K1 in index-only mode + K2 in one call (test mode: `points[samples != 0]`, ransac.py:58-65, with in-kernel noise):
- * idx [P,B,k] ascending and samples [P,B,k,4] = matches[p, idx] (c = 4; 16-byte aligned buffers).  One launch when the
+ * idx [P,B,k] ascending and samples [P,B,k,4] = matches[p, idx] (c = 4; buffers not 16-byte aligned: always two launches).  One launch when the
  * register-resident sampler kernel serves the shape (N % 4 == 0, N <= 2048, tau == 1), sampler + gather launches otherwise.
  * Every argument from gate_iters on is optional (NULL / 0): */
 /* gate_iters / gate_max_iters (a round > 1 of a multi-round test-mode call): pairs with gate_iters[p] >= gate_max_iters[p] are
@@ -142,7 +142,7 @@ int dr_gumbel_topk_gather_f32(const float *logits, const float *matches, uint64_
 
 /* Train mode (round 5): K1 WITH the soft-max statistics + K2 in one call (GumbelSoftmaxSampler.sample, samplers/gumbel_sampler.py:25-42,
  * followed by `matches * ret` + the mask gather of ransac.py:58-65): idx, y_sel [P,B,k], lse [P,B] as dr_gumbel_topk_fwd_f32 and
- * samples [P,B,k,4] = matches[p, idx] * ((1 - y_sel) + y_sel) as dr_gather_fwd_f32 (c = 4; 16-byte aligned buffers).  One launch
+ * samples [P,B,k,4] = matches[p, idx] * ((1 - y_sel) + y_sel) as dr_gather_fwd_f32 (c = 4; buffers not 16-byte aligned: always two launches).  One launch
  * when the register-resident kernel serves the shape, sampler + gather launches otherwise.
  * race_ws (round 6; optional, (N + 32) * P floats, 16-byte aligned): the one-logarithm form in train mode -- keys, winners AND the
  * soft-max statistics (y_n = (1 / -key_n) / sum_m (1 / -key_m), lse = lmax + ln sum - ln ln 2) from one logarithm and one reciprocal
